@@ -20,7 +20,9 @@ Launch: `python bench.py --gpus N` starts N fresh child processes itself (one pe
 no launcher environment is present; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it
 reads RANK / LOCAL_RANK / WORLD_SIZE.  Asking for more GPUs than are visible is an error, never a silent 1-GPU run.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+the line (metric, value, unit, ms_per_step, the loop's counters); --dump-outputs DIR writes what the last timed step computed.
+Everything else is measured only with --full, after the timed region, and adds to the line
   roofline:     algorithmic HBM bytes of the dominant kernel (k_qp_ipm) / its HIP-event duration vs 8 TB/s (a probe launch over
                 the whole batch, alone on the GPU, at the state the timed loop ended in); `traffic` = measured HBM bytes per
                 instance-iteration (rocprofv3 --pmc passes, profiles/) x the probe's own iteration count; kernel_ms_in_loop =
@@ -30,6 +32,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                 the launch's load balance
   cpu_baseline: the CPU oracle (a port, not acados) timed on this host on a bounded sample of the SAME closed-loop state:
                 all-core throughput and 1-thread single-instance latency (p50 / p99, comparable to scripts/mpc.py:300-303).
+  survey_window, and on C1 latency_b1_ms / strong_proxy (see main()).
 """
 import argparse
 import json
@@ -265,6 +268,25 @@ def small_batch_latency(N=HORIZON, batches=(1,), n_steps=200, device=0, keep_sta
     return rows
 
 
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: all files of one run stay under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, named, n_inst, suffix='', cap=DUMP_BYTES):
+    """--dump-outputs: named = {name: (instance ids of the rows, array with one row per instance)}, written as
+    out_dir/<name><suffix>.npy in float64.  When they exceed cap bytes, the rows of a fixed, seeded sample of the n_inst
+    instances are written instead, with the sampled ids as instance_index."""
+    per_inst = np.full(n_inst, 8.0)                                   # (8 bytes: the instance's entry in instance_index)
+    for ids, a in named.values():
+        per_inst[ids] += a[0].size * 8
+    if per_inst.sum() - 8 * n_inst > cap:
+        keep = np.sort(np.random.default_rng(0).choice(n_inst, int(cap // per_inst.max()), replace=False))
+        named = {k: (ids[np.isin(ids, keep)], a[np.isin(ids, keep)]) for k, (ids, a) in named.items()}
+        named['instance_index'] = (keep, keep)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (_, a) in named.items():
+        np.save(os.path.join(out_dir, f'{k}{suffix}.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launch_children(args):
     """`python bench.py --gpus N` without a launcher: N fresh children, one per GPU, started before this process touches a GPU
     (device_count() only counts -- where it does go through the HIP runtime in the parent that is harmless here: the ranks are
@@ -315,6 +337,13 @@ def main():
     ap.add_argument('--qp-form', choices=['auto', 'throughput', 'latency'], default='auto',
                     help="form of the interior-point solve (smpc_set_qp_mode); auto: the latency form (a workgroup per instance) up to "
                          "1536 instances per GPU in sub-batches of at most 512, the throughput form above -- the others are for A/B runs")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure everything besides the headline: roofline probe, per-kernel times '
+                         'in the loop, CPU baseline, SURVEY 8(d) window, one-instance latency (C1); the --no-* options below '
+                         'leave single parts of it out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed, per instance of this rank, as DIR/<name>.npy (float64, '
+                         'a fixed seeded sample of the instances above DUMP_BYTES)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-latency', action='store_true', help='skip the one-instance latency measurement added to the C1 line')
     ap.add_argument('--noise', type=float, default=0.0,
@@ -330,6 +359,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.dump_outputs is not None and args.steps < 1:
+        raise SystemExit('--dump-outputs needs --steps >= 1: it writes what the last timed step computed')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_children(args))
 
@@ -594,6 +625,19 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     acc_all = sum(sb.acc.cpu().numpy().astype(np.int64) for sb in subs)
+    if args.dump_outputs is not None:
+        # what a caller of the timed path holds after its last step: the applied control (its row of the rollout log), the plant
+        # state, the step's status and IPM iterations, and the controller's guesses after the step (per horizon for C3)
+        rows = lambda get, group: (np.concatenate([np.arange(sb.off, sb.off + sb.n) for sb in group]),
+                                   torch.cat([get(sb) for sb in group]).cpu().numpy())
+        named = {'u': rows(lambda sb: u_log[args.steps - 1, sb.off:sb.off + sb.n], subs), 'x': rows(lambda sb: sb.x_sim, subs),
+                 'status': rows(lambda sb: sb.ctrl.last_status, subs), 'ipm_iterations': rows(lambda sb: sb.ctrl.qp_iter, subs)}
+        horizons = sorted({sb.N for sb in subs})
+        for Ng in horizons:
+            group, tag = [sb for sb in subs if sb.N == Ng], ('' if len(horizons) == 1 else f'_N{Ng}')
+            named['x_guess' + tag] = rows(lambda sb: sb.ctrl.x_guess, group)
+            named['u_guess' + tag] = rows(lambda sb: sb.ctrl.u_guess, group)
+        dump_outputs(args.dump_outputs, named, B, '' if world == 1 else f'_rank{rank}', DUMP_BYTES // world)
     log_check = None
     if os.environ.get('SMPC_BENCH_CHECK_LOG') == '1' and use_dist:
         # (test hook: every timed step must have left its own row in the rollout log -- with --graphs 1 the row index is the
@@ -605,7 +649,7 @@ def main():
     # Per-kernel HIP-event durations of the loop's own launches: the SAME loop continued for a few more steps with the engine's
     # event ring switched on (5 hipEventRecord per solve), outside the timed region -- `value` is measured without them.  The
     # per-solve `time_tot` of this pass is also what the reference reports per step (scripts/mpc.py:239,300-303).
-    loop_timing[0] = not args.no_loop_timing and subs[0].graph is None and world == 1
+    loop_timing[0] = args.full and not args.no_loop_timing and subs[0].graph is None and world == 1
     tt_all, t_ev = [], 0.0
     if loop_timing[0]:
         n_ev = min(max(args.steps, 8), 48)
@@ -654,7 +698,7 @@ def main():
     psubs = [sb for sb in subs if sb.N == probe_N]
     prob, net, N = psubs[0].prob, psubs[0].net, probe_N
     Bp = int(sum(sb.n for sb in psubs))
-    if rank == 0:
+    if rank == 0 and args.full:
         sv = probe_sv if probe_sv.N == probe_N else BatchedOcpSolver(prob, net, device=local)
         sv.set_qp_mode(qp_form)
         st_ = torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=dev)
@@ -729,21 +773,21 @@ def main():
                 roof['in_loop_all_groups'] = roofline_of_launches([algorithmic_bytes(sb.prob.nq, sb.N) * sb.n for sb, _ in tl], [1e3 * t_[3] for _, t_ in tl])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         nb = min(Bp, 1024)
         h = lambda a: a[:nb].cpu().numpy()
         cpu = cpu_baseline(prob, net, h(xs), h(xgf), h(ugf), h(pf))
 
     # SURVEY 8(d) / BASELINE.md section 3 quote C1 over "100 timed steps after 10 warm-up"; the closed loop gets more expensive
-    # with time (more IPM iterations per solve), so a shorter window flatters the number.  When the run's own K / W differ, the
-    # same loop is run once more over exactly that window -- from the same initial state, after everything above, outside the
-    # timed region that `value` reports -- and added to the line.
+    # with time (more IPM iterations per solve), so a shorter window flatters the number.  With --full, when the run's own K / W
+    # differ, the same loop is run once more over exactly that window -- from the same initial state, after everything above,
+    # outside the timed region that `value` reports -- and added to the line.
     survey = None
-    if (args.steps, args.warmup) == (100, 10):
+    if args.full and (args.steps, args.warmup) == (100, 10):
         survey = {'steps': 100, 'warmup': 10, 'ms_per_step': 1e3 * elapsed / 100, 'value': B_total * 100 / elapsed,
                   'mean_ipm_iterations': mean_iter, 'failed_instance_steps': fails,
                   'note': 'the window SURVEY 8(d) quotes C1 on IS this run\'s timed region (the default since round 5)'}
-    elif world == 1 and not args.no_survey_window and not args.graphs:
+    elif args.full and world == 1 and not args.no_survey_window and not args.graphs:
         for sb in subs:
             with torch.cuda.stream(sb.stream):
                 sb.ctrl.setGuess(t(np.repeat(sb.x0_h[:, None, :], sb.N + 1, axis=1)), t(np.zeros((sb.n, sb.N, nu))))
@@ -790,7 +834,7 @@ def main():
                         'MLP 14-256-256-256-1 fp32), EXT cost exact Hessian, sphere obstacle + floor rows, Halton x0')
             metric = f'RTI-MPC instance-steps/s (batch={args.batch}{" per GPU" if args.scaling == "weak" else " in total"}, 7-DoF N=40)'
         extra = {}
-        if cfg == 'c1' and world == 1 and not args.no_latency:
+        if cfg == 'c1' and world == 1 and args.full and not args.no_latency:
             # the reference's own statistic for this path: the solver time per step of ONE instance (scripts/mpc.py:300-303; budget dt = 5 ms)
             try:
                 extra['latency_b1_ms'] = small_batch_latency(N=HORIZON, batches=(1,), n_steps=100, device=local)[0]
@@ -817,8 +861,9 @@ def main():
             # host side of the loop: time this rank's Python spent enqueueing one step (all sub-batches) against
             # the step itself, and the cores it may use -- eight ranks of an 8-GPU run share one host
             'host_issue_ms_per_step': 1e3 * host_issue / max(args.steps, 1), 'usable_cores': usable_cores(),
-            'roofline': roof, 'cpu_baseline': cpu, 'survey_window': survey,
         }
+        if args.full:
+            line.update(roofline=roof, cpu_baseline=cpu, survey_window=survey)
         line.update(extra)
         if log_check is not None:
             line['log_check'] = log_check

@@ -23,8 +23,8 @@ if [ "$1" = wg ]; then
   python3 scripts/latency_scaling.py --out-dir $O --tag r06 --batches 4096,2048,1536,1024,512 > $O/latency_scaling.log 2>&1
   mv $O/r06_strong_scaling_proxy.json $O/strong_scaling_proxy.json; mv $O/r06_latency.json $O/latency.json
   cp $O/strong_scaling_proxy.json $R/profiles/r06_strong_scaling_proxy.json
-  timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
-  timeout -k 10 300 python3 bench.py --batch 512 --no-latency > $O/bench_b512.json 2>> $O/bench.err
+  timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
+  timeout -k 10 300 python3 bench.py --batch 512 --full --no-latency > $O/bench_b512.json 2>> $O/bench.err
   bash scripts/prof_bench.sh r06/benchprof512 --batch 512 --no-latency > /dev/null 2>&1
   cp $O/benchprof512/kernel_stats.csv $O/bench_b512_kernel_stats.csv; cp $O/benchprof512/kernel_summary_by_grid.txt $O/bench_b512_kernel_summary_by_grid.txt; cp $O/benchprof512/bench_under_rocprof.json $O/bench_b512_under_rocprof.json
   SMPC_B=1 python3 scripts/qp_wg_phase_profile.py > $O/wg_phase_profile_B1.txt 2>&1
@@ -43,25 +43,25 @@ cp $O/pmc_traffic.json $R/profiles/r06_pmc_traffic.json; cp $O/pmc_traffic_c4.js
 python3 scripts/latency_scaling.py --out-dir $O --tag r06 --batches 4096,2048,1536,1024,512 > $O/latency_scaling.log 2>&1
 mv $O/r06_strong_scaling_proxy.json $O/strong_scaling_proxy.json; mv $O/r06_latency.json $O/latency.json
 cp $O/strong_scaling_proxy.json $R/profiles/r06_strong_scaling_proxy.json
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 bash scripts/prof_bench.sh r06/benchprof > /dev/null 2>&1
 cp $O/benchprof/kernel_stats.csv $O/bench_kernel_stats.csv; cp $O/benchprof/kernel_summary_by_grid.txt $O/bench_kernel_summary_by_grid.txt; cp $O/benchprof/bench_under_rocprof.json $O/bench_under_rocprof.json
-timeout -k 10 300 python3 bench.py --batch 512 --no-latency > $O/bench_b512.json 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --batch 512 --full --no-latency > $O/bench_b512.json 2>> $O/bench.err
 bash scripts/prof_bench.sh r06/benchprof512 --batch 512 --no-latency > /dev/null 2>&1
 cp $O/benchprof512/kernel_stats.csv $O/bench_b512_kernel_stats.csv; cp $O/benchprof512/kernel_summary_by_grid.txt $O/bench_b512_kernel_summary_by_grid.txt; cp $O/benchprof512/bench_under_rocprof.json $O/bench_b512_under_rocprof.json
 cd /tmp
 for c in c2 c3 c4; do
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$c -- python3 $R/bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline --no-survey-window > $O/${c}_bench_under_rocprof.json 2> $O/$c.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$c -- python3 $R/bench.py --config $c --steps 10 --warmup 2 --full --no-cpu-baseline --no-survey-window > $O/${c}_bench_under_rocprof.json 2> $O/$c.err
   f=$(ls $O/$c/*/*kernel_trace.csv | head -1)
   python3 $R/scripts/trace_summary.py $f > $O/${c}_kernel_summary_by_grid.txt
   cp $(ls $O/$c/*/*kernel_stats.csv | head -1) $O/${c}_kernel_stats.csv
   rm -rf $O/$c
 done
 cd $R
-timeout -k 10 400 python3 bench.py --config c2 --steps 10 --warmup 2 --no-survey-window > $O/c2_bench.json 2>> $O/c2.err
-timeout -k 10 300 python3 bench.py --config c3 --steps 20 --warmup 3 --no-survey-window > $O/c3_bench.json 2>> $O/c3.err
-timeout -k 10 300 python3 bench.py --config c4 --steps 10 --warmup 2 --no-survey-window > $O/c4_bench.json 2>> $O/c4.err
-SMPC_BENCH_CONTROLLER=constraint_everywhere timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-latency > $O/bench_constraint_everywhere.json 2>> $O/bench.err
+timeout -k 10 400 python3 bench.py --config c2 --steps 10 --warmup 2 --full --no-survey-window > $O/c2_bench.json 2>> $O/c2.err
+timeout -k 10 300 python3 bench.py --config c3 --steps 20 --warmup 3 --full --no-survey-window > $O/c3_bench.json 2>> $O/c3.err
+timeout -k 10 300 python3 bench.py --config c4 --steps 10 --warmup 2 --full --no-survey-window > $O/c4_bench.json 2>> $O/c4.err
+SMPC_BENCH_CONTROLLER=constraint_everywhere timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-latency > $O/bench_constraint_everywhere.json 2>> $O/bench.err
 SMPC_B=1 python3 scripts/qp_wg_phase_profile.py > $O/wg_phase_profile_B1.txt 2>&1
 SMPC_B=256 python3 scripts/qp_wg_phase_profile.py > $O/wg_phase_profile_B256.txt 2>&1
 SMPC_B=256 python3 scripts/qp_phase_profile.py > $O/qp_phase_profile.txt 2>&1
