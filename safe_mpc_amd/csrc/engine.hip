@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/smpc.h"
@@ -47,7 +48,6 @@ struct smpc_handle {
     double* d_ev = nullptr;       // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
     double* d_nn = nullptr;       // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
                                   // on every node, [B][1 + nx] with the row on the end node only, not allocated without a network row
-    bool ev_new_order[64] = {};   // per slot of the event ring: the solve ran MLP -> stage builder (ev1, ev2 swap their meaning)
     double* d_ws = nullptr;
     size_t ws_bytes = 0;
     int qp_mode = -2;             // smpc_set_qp_mode: SMPC_QP_AUTO / _THROUGHPUT / _LATENCY; -2 = not set (the process default, SMPC_QP_WG)
@@ -102,7 +102,7 @@ struct smpc_handle {
     int32_t* d_pol = nullptr;   // fails / accept counters of smpc_rollout_batch, [2][pol_B]
     int pol_B = 0;
     float last_ms[4] = {0, 0, 0, 0};
-    long mlp_rows_whole = 0;    // > 0 (a worker of smpc_rollout_batch): network rows of the WHOLE call, which selects the GEMM kernel
+    long mlp_rows_whole = 0;    // > 0 (a worker of smpc_rollout_batch): network rows of the WHOLE call, which selects the network kernel
     long mlp_rows_hint = 0;     // > 0 (smpc_policy_step of the receding policies): the rows EXPECTED to be live in a compacted list -- one or
                                 // two nodes per instance, where the list's capacity is every node -- which selects the network kernel
                                 // (the count itself is only known on the device; any kernel is correct for any count)
@@ -260,7 +260,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     const int32_t* live = mode == 3 ? h->d_nn_cnt : nullptr;
     if (chained) *chained = false;
     // Few rows (the terminal row: M = B): the whole pass as ONE kernel, activations in LDS / registers (kernels_mlp.hpp).  The
-    // choice follows the rows of the whole call (mlp_rows_whole), like the tiled kernel's below.
+    // choice follows the rows of the whole call (mlp_rows_whole).
     {
         const long rows_all = h->mlp_rows_whole > 0 ? (h->mlp_rows_whole + 127) / 128 * 128
                                                     : (h->mlp_rows_hint > 0 && mode == 3 ? (h->mlp_rows_hint + 127) / 128 * 128 : (long)Mp);
@@ -301,41 +301,27 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     }
     hipLaunchKernelGGL((k_nn_features<NQ>), dim3((Mp + 63) / 64), dim3(64), 0, s, h->d_desc, M, Mp, N, mode, d_x,
                        h->d_S, idx, live);
-    // The layer-by-layer GEMMs.  Default (round 4): k_gemm_f32 as ONE-WAVE blocks -- a wavefront of it is self-contained (32 x 64
-    // tile, operands from L2, 90-130 registers, no LDS), so its blocks start on any SIMD with one free slot.  The 128 x 128
-    // LDS-tiled kernel (256-thread blocks: 200 registers per lane on all four SIMDs of one CU at once + 37 KB of LDS) is 12 % faster
-    // alone on the GPU (90 vs 79 TFLOP/s) but in C4's loop its blocks wait for CUs that QP wavefronts keep refilling: 12-14 ms per
-    // solve for 1.9 ms of work (profiles/r04_c4_kernel_summary_by_grid.txt).  SMPC_MLP_GEMM=tiled brings it back (A/B runs); the
-    // choice then follows the rows of the whole call as before (the two kernels sum K in different orders).
-    static const bool use_tiled_env = [] { const char* e = getenv("SMPC_MLP_GEMM"); return e && !strcmp(e, "tiled"); }();
-    const long rows_sel = h->mlp_rows_whole > 0 ? (h->mlp_rows_whole + 127) / 128 * 128 : (long)Mp;
-    const bool tiled = use_tiled_env && rows_sel >= 8192 && H % 128 == 0;
-    const dim3 blk(tiled ? 256 : 64), blk_t(256);
-    const dim3 grd(tiled ? Mp / 128 : Mp / 32, H / 64), grd_t(Mp / 128, H / 128);
+    // The layer-by-layer GEMMs (round 4): k_gemm_f32 as ONE-WAVE blocks -- a wavefront of it is self-contained (32 x 64 tile,
+    // operands from L2, 90-130 registers, no LDS), so its blocks start on any SIMD with one free slot.  A 128 x 128 LDS-tiled kernel
+    // (256-thread blocks: 200 registers per lane on all four SIMDs of one CU at once + 37 KB of LDS), since retired, was 12 % faster
+    // alone on the GPU (90 vs 79 TFLOP/s) but in C4's loop its blocks waited for CUs that QP wavefronts keep refilling: 12-14 ms per
+    // solve for 1.9 ms of work (profiles/r04_c4_kernel_summary_by_grid.txt).
+    const dim3 blk(64), grd(Mp / 32, H / 64);
     hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, MLP_KPAD, h->d_S, h->d_Wfwd[0], h->d_bias[0],
                        (const float*)nullptr, h->d_act[0], h->d_dg[0], live, h->act);
-    for (int l = 1; l + 1 < L; l++) {
-        if (tiled)
-            hipLaunchKernelGGL((k_gemm_f32_tiled<EPI_BIAS_GELU>), grd_t, blk_t, 0, s, Mp, H, H, h->d_act[l - 1], h->d_Wfwd[l],
-                               h->d_bias[l], (const float*)nullptr, h->d_act[l], h->d_dg[l], live, h->act);
-        else
-            hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1], h->d_Wfwd[l],
-                               h->d_bias[l], (const float*)nullptr, h->d_act[l], h->d_dg[l], live, h->act);
-    }
+    for (int l = 1; l + 1 < L; l++)
+        hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1], h->d_Wfwd[l], h->d_bias[l],
+                           (const float*)nullptr, h->d_act[l], h->d_dg[l], live, h->act);
     hipLaunchKernelGGL(k_nn_output, dim3((Mp + 3) / 4), dim3(256), 0, s, Mp, H, h->d_act[L - 2], h->d_dg[L - 2],
                        h->d_Wbwd[L - 1], h->d_bias[L - 1], h->d_y, h->d_dA, live);
     if (backward) {
         float *cur = h->d_dA, *nxt = h->d_dB;
         for (int l = L - 2; l >= 1; l--) {
-            if (tiled)
-                hipLaunchKernelGGL((k_gemm_f32_tiled<EPI_MUL>), grd_t, blk_t, 0, s, Mp, H, H, cur, h->d_Wbwd[l],
-                                   (const float*)nullptr, h->d_dg[l - 1], nxt, (float*)nullptr, live, h->act);
-            else
-                hipLaunchKernelGGL((k_gemm_f32<EPI_MUL>), grd, blk, 0, s, Mp, H, H, cur, h->d_Wbwd[l], (const float*)nullptr,
-                                   h->d_dg[l - 1], nxt, (float*)nullptr, live, h->act);
+            hipLaunchKernelGGL((k_gemm_f32<EPI_MUL>), grd, blk, 0, s, Mp, H, H, cur, h->d_Wbwd[l], (const float*)nullptr,
+                               h->d_dg[l - 1], nxt, (float*)nullptr, live, h->act);
             float* t = cur; cur = nxt; nxt = t;
         }
-        hipLaunchKernelGGL((k_gemm_f32<EPI_PLAIN>), dim3(tiled ? Mp / 128 : Mp / 32, MLP_NPAD / 64), blk, 0, s, Mp, MLP_NPAD, H, cur,
+        hipLaunchKernelGGL((k_gemm_f32<EPI_PLAIN>), dim3(Mp / 32, MLP_NPAD / 64), blk, 0, s, Mp, MLP_NPAD, H, cur,
                            h->d_Wbwd[0], (const float*)nullptr, (const float*)nullptr, h->d_GS, (float*)nullptr, live, h->act);
     }
     HIPCHK(h, hipGetLastError());
@@ -368,34 +354,21 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
     return SMPC_OK;
 }
 
+// the nodes' linearisation records by the thread-per-node kernel, the network's row included (smpc_eval_nodes, and the reference
+// set-up of smpc_debug_stage_records; not on the solve path)
 template <int NQ>
-int launch_eval(smpc_handle* h, int B, const double* d_xg, const double* d_ug, const double* d_p, double* d_ev, bool timed = false) {
-    // (timed: called from launch_solve, which owns the current slot of the event ring; smpc_eval_nodes on its own records nothing --
-    //  it would re-record two events of the last solve's slot and leave that slot's durations meaningless)
+int launch_eval(smpc_handle* h, int B, const double* d_xg, const double* d_ug, const double* d_p, double* d_ev) {
     const int N = h->N;
     hipStream_t s = h->stream;
     const long n1 = (long)B * (N + 1);
     hipLaunchKernelGGL((k_node_linearise<NQ>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
                        d_p, d_ev);
     HIPCHK(h, hipGetLastError());
-    if (timed) HIPCHK(h, hipEventRecord(h->ev_t[1], s));
     int rc;
     if ((rc = launch_nn<NQ>(h, B, d_xg, d_p, d_ev, 0))) return rc;
     // (this path has no stage builder behind the network pass to hand the row list's counter back at zero: see d_nn_cnt)
     if (h->desc.nn_mode == SMPC_NN_ALL && h->d_nn_cnt) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
-    if (timed) HIPCHK(h, hipEventRecord(h->ev_t[2], s));
     return SMPC_OK;
-}
-
-// experiment knob: extra dynamic LDS per block of k_qp_ipm limits how many wavefronts are resident per CU (the rest queue
-// behind the longest-first order and backfill)
-static size_t qp_pad_lds() {
-#ifdef SMPC_EXPERIMENTS     // (experiment builds only: make FLAGS+=-DSMPC_EXPERIMENTS; the shipped library reads no such knob on its solve path)
-    static const size_t v = [] { const char* e = getenv("SMPC_QP_PAD_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
-    return v;
-#else
-    return 0;
-#endif
 }
 
 // k_qp_ipm's non-temporal variant: -1 (default) by workspace size, 0 / 1 forced (SMPC_QP_NT, A/B runs).  The threshold sits between
@@ -406,75 +379,64 @@ static int qp_nt_mode() {
     return v;
 }
 
-// 1: the lane-cooperative stage builder (kernel_build.hpp: MLP -> k_stage_build -> k_qp_ipm), the default; 0: the thread-per-node
-// kernels of rounds 1-3 (k_node_linearise -> MLP -> k_qp_setup -> k_qp_ipm), kept for A/B runs and as what smpc_eval_nodes uses
-static int stage_build_mode() {
-    static const int v = [] { const char* e = getenv("SMPC_STAGE_BUILD"); return e ? atoi(e) : 1; }();
-    return v;
+// f(std::integral_constant<int, MR>{}) with the handle's row count as the kernels' compile-time constant: the shipped geometries
+// have 6 rows (the reference's six capsule pairs, config.yaml:205-216) or 4 (config_fr7.yaml); any other count takes the
+// runtime-row-count instantiation, MR = -1
+template <class F> int with_rows(const smpc_handle* h, F&& f) {
+    switch (h->desc.n_rows) {
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, -1>{});
+    }
 }
 
-// everything of a solve before the interior point: the stage records of the QP workspace, by either path
+// the stage bounds the set-up reads: per instance (RealReceding) when they were given for this batch size, else the shared ones
+struct StageBounds {
+    const double *lo, *hi;
+    long stride;
+};
+StageBounds stage_bounds(const smpc_handle* h, int B) {
+    if (h->inst_B == B) return {h->d_lo_b, h->d_hi_b, (long)(h->N + 1) * 2 * h->desc.nq};
+    return {h->d_lo, h->d_hi, 0L};
+}
+
+// everything of a solve before the interior point: the network pass, then the stage records of the QP workspace by the
+// lane-cooperative stage builder (kernel_build.hpp)
 template <int NQ>
-int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p, bool timed, int path) {
+int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p, bool timed) {
     int rc;
-    const bool per_inst = h->inst_B == B;
-    const double* blo = per_inst ? h->d_lo_b : h->d_lo;
-    const double* bhi = per_inst ? h->d_hi_b : h->d_hi;
-    const long bstride = per_inst ? (long)(h->N + 1) * 2 * h->desc.nq : 0L;
-    // experiment knob: the linearisation (+ network pass) and / or the set-up launched once more, to measure what
-    // a stream's chain pays for them inside the loop (bit 0: linearisation, bit 1: set-up; old path only)
-#ifdef SMPC_EXPERIMENTS
-    static const int dup = [] { const char* e = getenv("SMPC_DUP_KERNELS"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int dup = 0;
-#endif
-    if (path == 1) {
-        if ((rc = launch_nn<NQ>(h, B, xg, p, h->d_nn, h->desc.nn_mode == SMPC_NN_TERMINAL ? 2 : 1))) return rc;
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_t[1], h->stream));
-        const long nodes = (long)B * (h->N + 1);
-        const dim3 grd((unsigned)((nodes + 64 / SB_G - 1) / (64 / SB_G))), blk(64);
-        const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn : nullptr;
-        int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
-        // (experiment knob: extra dynamic LDS per block of the builder -- how much its start depends on LDS room next to QP wavefronts)
-#ifdef SMPC_EXPERIMENTS
-        static const size_t sb_pad = [] { const char* e = getenv("SMPC_SB_PAD_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
-#else
-        constexpr size_t sb_pad = 0;
-#endif
-#define SMPC_SB_LAUNCH(MR_)                                                                                                       \
-        hipLaunchKernelGGL((k_stage_build<NQ, MR_>), grd, blk, sb_pad, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, blo, bhi, h->d_zl, nn,     \
-                           h->d_ws, bstride, h->d_active, zero_cnt)
-        switch (h->desc.n_rows) {
-        case 6: SMPC_SB_LAUNCH(6); break;
-        case 4: SMPC_SB_LAUNCH(4); break;
-        default: SMPC_SB_LAUNCH(-1); break;
-        }
-#undef SMPC_SB_LAUNCH
-        HIPCHK(h, hipGetLastError());
-        if (timed) { HIPCHK(h, hipEventRecord(h->ev_t[2], h->stream)); HIPCHK(h, hipEventRecord(h->ev_t[4], h->stream)); }
+    if ((rc = launch_nn<NQ>(h, B, xg, p, h->d_nn, h->desc.nn_mode == SMPC_NN_TERMINAL ? 2 : 1))) return rc;
+    if (timed) HIPCHK(h, hipEventRecord(h->ev_t[1], h->stream));
+    const StageBounds bd = stage_bounds(h, B);
+    const long nodes = (long)B * (h->N + 1);
+    const dim3 grd((unsigned)((nodes + 64 / SB_G - 1) / (64 / SB_G))), blk(64);
+    const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn : nullptr;
+    int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
+    with_rows(h, [&](auto MR) {
+        hipLaunchKernelGGL((k_stage_build<NQ, MR>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi, h->d_zl, nn,
+                           h->d_ws, bd.stride, h->d_active, zero_cnt);
         return SMPC_OK;
-    }
-    if ((rc = launch_eval<NQ>(h, B, xg, ug, p, h->d_ev, timed))) return rc;
-    if (dup & 1) { if ((rc = launch_eval<NQ>(h, B, xg, ug, p, h->d_ev, false))) return rc; }
-    const int tiles = (int)ev_tiles((size_t)B * (h->N + 1));
-    // the row counts of the shipped geometries are compile-time constants of the kernels (6: the reference's six capsule
-    // pairs, config.yaml:205-216; 4: config_fr7.yaml); any other count takes the runtime-row-count instantiation
-#define SMPC_SETUP_LAUNCH(MR_)                                                                                                     \
-    do {                                                                                                                           \
-        hipLaunchKernelGGL((k_qp_setup<NQ, MR_>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, blo,     \
-                           bhi, h->d_zl, h->d_ev, h->d_ws, bstride, h->d_active);                                                  \
-        if (dup & 2)                                                                                                               \
-            hipLaunchKernelGGL((k_qp_setup<NQ, MR_>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, blo, \
-                               bhi, h->d_zl, h->d_ev, h->d_ws, bstride, h->d_active);                                              \
-    } while (0)
-    switch (h->desc.n_rows) {
-    case 6: SMPC_SETUP_LAUNCH(6); break;
-    case 4: SMPC_SETUP_LAUNCH(4); break;
-    default: SMPC_SETUP_LAUNCH(-1); break;
-    }
-#undef SMPC_SETUP_LAUNCH
+    });
     HIPCHK(h, hipGetLastError());
-    if (timed) HIPCHK(h, hipEventRecord(h->ev_t[4], h->stream));
+    // (ev4 ends the set-up of the QP, which the builder has done: smpc_get_qp_timing's ms2[0], the gap from ev2 to ev4, is ~0)
+    if (timed) { HIPCHK(h, hipEventRecord(h->ev_t[2], h->stream)); HIPCHK(h, hipEventRecord(h->ev_t[4], h->stream)); }
+    return SMPC_OK;
+}
+
+// The same stage records by the thread-per-node kernels of rounds 1-3 (k_node_linearise -> network pass -> k_qp_setup): not on
+// the solve path, only the independent reference that smpc_debug_stage_records (path 0) builds them with
+template <int NQ>
+int launch_stage_records_per_node(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p) {
+    int rc;
+    if ((rc = launch_eval<NQ>(h, B, xg, ug, p, h->d_ev))) return rc;
+    const StageBounds bd = stage_bounds(h, B);
+    const int tiles = (int)ev_tiles((size_t)B * (h->N + 1));
+    with_rows(h, [&](auto MR) {
+        hipLaunchKernelGGL((k_qp_setup<NQ, MR>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
+                           bd.hi, h->d_zl, h->d_ev, h->d_ws, bd.stride, h->d_active);
+        return SMPC_OK;
+    });
+    HIPCHK(h, hipGetLastError());
     return SMPC_OK;
 }
 
@@ -528,25 +490,18 @@ int launch_qp_wg(smpc_handle* h, int B, const double* x0, const double* xg, cons
         h->hrec_doubles = need;
     }
     const size_t lds = (size_t)WgLds<NQ>(h->N, h->desc.n_rows, NHW).total * sizeof(double);
-#define SMPC_WG_LAUNCH(MR_)                                                                                                        \
-    do {                                                                                                                           \
-        if (!h->wg_lds_set[NHW == 8 ? 0 : 1]) {                                                                                   \
-            /* (once per handle = per device, nq and row count: the kernel may use a whole CU's LDS -- always the same value, so a    \
-             *  handle with a short horizon never lowers the limit under one with a long horizon) */                               \
-            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qp_ipm_wg<NQ, MR_, NHW>),                               \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP_WG_LDS_LIMIT));                      \
-            h->wg_lds_set[NHW == 8 ? 0 : 1] = QP_WG_LDS_LIMIT;                                                                     \
-        }                                                                                                                          \
-        hipLaunchKernelGGL((k_qp_ipm_wg<NQ, MR_, NHW>), dim3(B), dim3(32 * NHW), lds, h->stream, h->d_desc, B, h->N, x0, xg,         \
-                           ug, h->d_ws, h->d_hrec, xo, uo, st, it, h->d_last_it, h->d_active, h->d_ord_hist);                      \
-    } while (0)
-    switch (h->desc.n_rows) {
-    case 6: SMPC_WG_LAUNCH(6); break;
-    case 4: SMPC_WG_LAUNCH(4); break;
-    default: SMPC_WG_LAUNCH(-1); break;
-    }
-#undef SMPC_WG_LAUNCH
-    return SMPC_OK;
+    return with_rows(h, [&](auto MR) {
+        if (!h->wg_lds_set[NHW == 8 ? 0 : 1]) {
+            // (once per handle = per device, nq and row count: the kernel may use a whole CU's LDS -- always the same value, so a
+            //  handle with a short horizon never lowers the limit under one with a long horizon)
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qp_ipm_wg<NQ, MR, NHW>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP_WG_LDS_LIMIT));
+            h->wg_lds_set[NHW == 8 ? 0 : 1] = QP_WG_LDS_LIMIT;
+        }
+        hipLaunchKernelGGL((k_qp_ipm_wg<NQ, MR, NHW>), dim3(B), dim3(32 * NHW), lds, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws,
+                           h->d_hrec, xo, uo, st, it, h->d_last_it, h->d_active, h->d_ord_hist);
+        return SMPC_OK;
+    });
 }
 
 template <int NQ>
@@ -561,16 +516,14 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
         h->timing_now = cs == hipStreamCaptureStatusNone;
     }
     const bool timed = h->timing_now;
-    const int path = stage_build_mode();
     if (timed) {
         h->ev_cur = (h->ev_cur + 1) % smpc_handle::EV_RING;
         h->ev_t = h->ev_sets[h->ev_cur];
         h->ev_complete[h->ev_cur] = false;      // (an error return below leaves the slot invalid, not stale)
-        h->ev_new_order[h->ev_cur] = path == 1;
         h->timed_count++;
         HIPCHK(h, hipEventRecord(h->ev_t[0], h->stream));
     }
-    if ((rc = launch_stage_records<NQ>(h, B, x0, xg, ug, p, timed, path))) return rc;
+    if ((rc = launch_stage_records<NQ>(h, B, x0, xg, ug, p, timed))) return rc;
     const int wg_nhw = qp_wg_choice<NQ>(h, B);
     const bool wg = wg_nhw > 0;
     const int32_t* order = nullptr;
@@ -593,16 +546,16 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
     if (wg) {
         if ((rc = wg_nhw == 8 ? launch_qp_wg<NQ, 8>(h, B, x0, xg, ug, xo, uo, st, it) : launch_qp_wg<NQ, 4>(h, B, x0, xg, ug, xo, uo, st, it))) return rc;
     } else {
-    const bool nt = qp_nt_mode() < 0 ? ws_doubles_per_instance(h->desc, h->N) * sizeof(double) * (size_t)B >= qp_nt_threshold : qp_nt_mode() > 0;
-#define SMPC_QP_LAUNCH(MR_, NT_)                                                                                                   \
-    hipLaunchKernelGGL((k_qp_ipm<NQ, MR_, NT_>), dim3((B + 1) / 2), dim3(64), qp_pad_lds(), h->stream, h->d_desc, B, h->N, x0, xg,  \
-                       ug, h->d_ws, xo, uo, st, it, order, h->d_last_it, wstat, h->d_active, h->d_ord_hist)
-    switch (h->desc.n_rows) {
-    case 6: if (nt) SMPC_QP_LAUNCH(6, true); else SMPC_QP_LAUNCH(6, false); break;
-    case 4: if (nt) SMPC_QP_LAUNCH(4, true); else SMPC_QP_LAUNCH(4, false); break;
-    default: SMPC_QP_LAUNCH(-1, false); break;      // (the runtime-row-count instantiation is not built twice)
-    }
-#undef SMPC_QP_LAUNCH
+        const bool nt = qp_nt_mode() < 0 ? ws_doubles_per_instance(h->desc, h->N) * sizeof(double) * (size_t)B >= qp_nt_threshold : qp_nt_mode() > 0;
+        with_rows(h, [&](auto MR) {
+            const auto launch = [&](auto NT) {
+                hipLaunchKernelGGL((k_qp_ipm<NQ, MR, NT>), dim3((B + 1) / 2), dim3(64), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws,
+                                   xo, uo, st, it, order, h->d_last_it, wstat, h->d_active, h->d_ord_hist);
+                return SMPC_OK;
+            };
+            if constexpr (MR < 0) return launch(std::false_type{});      // (the runtime-row-count instantiation is not built twice)
+            else return nt ? launch(std::true_type{}) : launch(std::false_type{});
+        });
     }
     h->order_B = B;
     HIPCHK(h, hipGetLastError());
@@ -1466,10 +1419,9 @@ int smpc_get_timing(smpc_handle* h, float* ms4) {
     if (!h->timed || !h->ev_complete[h->ev_cur]) return fail(h, SMPC_ESTATE, "no solve has been timed since smpc_enable_timing");
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipEventSynchronize(h->ev_t[3]));
-    // (stage-builder path: the network pass comes first, ev0 -> ev1, then linearisation + set-up in one kernel, ev1 -> ev2)
-    const bool nw = h->ev_new_order[h->ev_cur];
-    HIPCHK(h, hipEventElapsedTime(&ms4[nw ? 1 : 0], h->ev_t[0], h->ev_t[1]));
-    HIPCHK(h, hipEventElapsedTime(&ms4[nw ? 0 : 1], h->ev_t[1], h->ev_t[2]));
+    // (the network pass comes first, ev0 -> ev1, then the stage builder -- linearisation + set-up in one kernel -- ev1 -> ev2)
+    HIPCHK(h, hipEventElapsedTime(&ms4[1], h->ev_t[0], h->ev_t[1]));
+    HIPCHK(h, hipEventElapsedTime(&ms4[0], h->ev_t[1], h->ev_t[2]));
     HIPCHK(h, hipEventElapsedTime(&ms4[2], h->ev_t[2], h->ev_t[3]));
     HIPCHK(h, hipEventElapsedTime(&ms4[3], h->ev_t[0], h->ev_t[3]));
     return SMPC_OK;
@@ -1495,9 +1447,8 @@ int smpc_get_timing_history(smpc_handle* h, int back, float* ms6) {
     if (!h->ev_complete[slot]) return SMPC_OK;     // the solve that owns the slot returned early: valid stays 0
     hipEvent_t* ev = h->ev_sets[slot];
     if (hipEventQuery(ev[3]) != hipSuccess) { (void)hipGetLastError(); return SMPC_OK; }   // not finished yet: valid stays 0
-    const bool nw = h->ev_new_order[slot];
-    HIPCHK(h, hipEventElapsedTime(&ms6[nw ? 1 : 0], ev[0], ev[1]));
-    HIPCHK(h, hipEventElapsedTime(&ms6[nw ? 0 : 1], ev[1], ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&ms6[1], ev[0], ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&ms6[0], ev[1], ev[2]));
     HIPCHK(h, hipEventElapsedTime(&ms6[2], ev[2], ev[4]));
     HIPCHK(h, hipEventElapsedTime(&ms6[3], ev[4], ev[3]));
     HIPCHK(h, hipEventElapsedTime(&ms6[4], ev[0], ev[3]));
@@ -1531,10 +1482,11 @@ int smpc_get_qp_wave_stats(smpc_handle* h, double* out3) {
 
 }  // extern "C"
 
-// Test hook (not part of include/smpc.h): the stage records of the QP workspace as either path builds them (path 1: MLP ->
-// k_stage_build; path 0: k_node_linearise -> MLP -> k_qp_setup), copied to the host, and the layout's offsets -- so that
-// tests/test_gpu_parity.py can compare the two builders block by block.  Host pointers.  layout[24] = {stride, nIMG, oIMG, oSL,
-// nF, oR0, oR1, oR2, oCZA, oCZN, oZ, oZN, NRT, nJ, doubles per instance, record version, iTT, iGT, iGN, iB, iSC, iHQQ, iGZ, 0}.
+// Test hook (not part of include/smpc.h): the stage records of the QP workspace as the solve path builds them (path 1: MLP ->
+// k_stage_build) or as the thread-per-node kernels of rounds 1-3 do (path 0: k_node_linearise -> MLP -> k_qp_setup, off the solve
+// path and kept as this independent reference), copied to the host, and the layout's offsets -- so that tests/test_gpu_parity.py
+// can compare the two builders block by block.  Host pointers.  layout[24] = {stride, nIMG, oIMG, oSL, nF, oR0, oR1, oR2, oCZA,
+// oCZN, oZ, oZN, NRT, nJ, doubles per instance, record version, iTT, iGT, iGN, iB, iSC, iHQQ, iGZ, 0}.
 extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p,
                                         int path, double* ws_out, int32_t* layout) {
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
@@ -1549,7 +1501,8 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     HIPCHK(h, hipMemcpyAsync(h->d_p, p, sizeof(double) * B * (N + 1) * SMPC_NP, hipMemcpyHostToDevice, s));
     const size_t per = ws_doubles_per_instance(h->desc, N);
     HIPCHK(h, hipMemsetAsync(h->d_ws, 0, per * (size_t)B * sizeof(double), s));
-    DISPATCH_NQ(h, (launch_stage_records<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p, false, path)));
+    DISPATCH_NQ(h, (path == 1 ? launch_stage_records<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p, false)
+                              : launch_stage_records_per_node<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p)));
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(ws_out, h->d_ws, per * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));

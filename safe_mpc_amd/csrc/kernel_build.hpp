@@ -347,10 +347,10 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
                         hv += rd::dot(rd::v3(dx, dy, dz), rd::cross(rd::v3(zl[0], zl[1], zl[2]), Jhi));
                     }
                 }
-                if (valid) stnt_su((reach ? cs * (Q2 * hv) : 0.0) + (g == j ? lm : 0.0), hq + j);
+                if (valid) hq[j] = (reach ? cs * (Q2 * hv) : 0.0) + (g == j ? lm : 0.0);
             }
         }
-        if (NQ * NQ < qp_even_c(NQ * NQ) && g == SB_G - 1 && valid) stnt_su(0.0, w + Ly.oIMG + Ly.iHQQ + NQ * NQ);
+        if (NQ * NQ < qp_even_c(NQ * NQ) && g == SB_G - 1 && valid) *(w + Ly.oIMG + Ly.iHQQ + NQ * NQ) = 0.0;
     }
     // Collision rows (env_model.py:263-316): row g + 8 s ON LANE g, value forward, gradient in reverse mode: the row's adjoints
     // w.r.t. its (up to four) moving points, then d row / d q_j = z_j . sum over the points riding on links >= j of
@@ -480,7 +480,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
     for (int i = g; i < NX; i += SB_G) {
         const double bb = defect(i);
         bmax = fmax(bmax, fabs(bb));
-        if (valid) stnt_su(bb, w + Ly.oIMG + Ly.iB + i);
+        if (valid) *(w + Ly.oIMG + Ly.iB + i) = bb;
     }
     bmax = grp_max(bmax);
     const double bflag = bmax > 0.0 ? 1.0 : 0.0;
@@ -488,15 +488,15 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
     auto gz_u = [&](int c) -> double { return (reach && !last) ? cs * 2.0 * D->R * uk[c] : 0.0; };
     for (int hz = g; hz < NZP; hz += SB_G) {
         if (hz >= NU && hz < NU + NQ) continue;
-        if (valid) stnt_su(hz < NU ? gz_u(hz) : 0.0, w + Ly.oIMG + Ly.iGZ + hz);
+        if (valid) *(w + Ly.oIMG + Ly.iGZ + hz) = hz < NU ? gz_u(hz) : 0.0;
     }
-    if (jl && valid) stnt_su(gz_q, w + Ly.oIMG + Ly.iGZ + NU + g);
+    if (jl && valid) *(w + Ly.oIMG + Ly.iGZ + NU + g) = gz_q;
     if (g < 4 && valid) {
         const double huu = (reach && !last ? cs * 2.0 * D->R : 0.0) + lm;
-        stnt_su(g == 0 ? huu : (g == 1 ? lm : (g == 2 ? wsoft : bflag)), w + Ly.oIMG + Ly.iSC + g);
-        stnt_su(g == 0 ? wsoft : (g == 1 ? bflag : 0.0), w + Ly.oSL + g);
+        *(w + Ly.oIMG + Ly.iSC + g) = g == 0 ? huu : (g == 1 ? lm : (g == 2 ? wsoft : bflag));
+        *(w + Ly.oSL + g) = g == 0 ? wsoft : (g == 1 ? bflag : 0.0);
     }
-    if (valid) stnt_su(0.0, w + Ly.oWC + g);
+    if (valid) *(w + Ly.oWC + g) = 0.0;
 
     double r0_loc = 0.0, mu_acc = 0.0, inf0 = 0.0;
     int cnt = 0;
@@ -526,9 +526,9 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
                 mu_acc += lu * tu;
             }
             if (valid) {
-                stnt_su(dbl2{lo, hi}, reinterpret_cast<dbl2*>(w + Ly.oR0) + r);
-                stnt_su(dbl2{tl, tu}, reinterpret_cast<dbl2*>(w + Ly.oR1) + r);
-                stnt_su(dbl2{ll, lu}, reinterpret_cast<dbl2*>(w + Ly.oR2) + r);
+                reinterpret_cast<dbl2*>(w + Ly.oR0)[r] = dbl2{lo, hi};
+                reinterpret_cast<dbl2*>(w + Ly.oR1)[r] = dbl2{tl, tu};
+                reinterpret_cast<dbl2*>(w + Ly.oR2)[r] = dbl2{ll, lu};
             }
         }
         return -(ll - lu);
@@ -594,10 +594,10 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
         if (!mine) eN = 0.0;
     }
     for (int r = g; r < 32; r += SB_G)
-        if (valid) { stnt_su(0.0, w + Ly.oCZA + r); stnt_su(0.0, w + Ly.oCZN + r); }
+        if (valid) { *(w + Ly.oCZA + r) = 0.0; *(w + Ly.oCZN + r) = 0.0; }
     for (int hz = g; hz < NZ; hz += SB_G) {
         const double z0 = hz >= NU ? sZ0[hz - NU] : 0.0;
-        if (valid) { stnt_su(z0, w + Ly.oZ + hz); stnt_su(z0, w + Ly.oZN + hz); }
+        if (valid) { *(w + Ly.oZ + hz) = z0; *(w + Ly.oZN + hz) = z0; }
     }
     lds_fence();
     // stationarity residual at the initial point (pi = 0): g + C^T e; dx_0 does not enter.  This lane's share of C^T e, summed
@@ -638,18 +638,18 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
         double* img = w + Ly.oIMG;
         if (g < NQP) {
 #pragma unroll
-            for (int c = 0; c < NZ; c++) stnt_su(rowT[c], img + Ly.iTT + c * NQP + g);      // (lanes NQ.. hold zeros: the pad rows)
+            for (int c = 0; c < NZ; c++) *(img + Ly.iTT + c * NQP + g) = rowT[c];      // (lanes NQ.. hold zeros: the pad rows)
         }
 #pragma unroll
         for (int sl = 0; sl < NSLOT; sl++) {
             const int r = g + SB_G * sl;
             if (r < MRP) {
 #pragma unroll
-                for (int j = 0; j < NQ; j++) stnt_su(grow[sl][j], img + Ly.iGT + j * MRP + r);   // (zeros in the pad row)
+                for (int j = 0; j < NQ; j++) *(img + Ly.iGT + j * MRP + r) = grow[sl][j];   // (zeros in the pad row)
             }
         }
         if (g == NNL)
-            for (int i = 0; i < NX; i++) stnt_su(nn_on ? nnk[1 + i] : 0.0, img + Ly.iGN + i);
+            for (int i = 0; i < NX; i++) *(img + Ly.iGN + i) = nn_on ? nnk[1 + i] : 0.0;
     }
     lds_fence();     // (the next node of this group reuses the block)
 }

@@ -4,7 +4,9 @@
 //
 // Two kernels:
 //   k_qp_setup : one half-wavefront per (instance, stage): builds the stage's constraint rows, bounds, cost blocks and the
-//                initial interior point from the linearisation records (embarrassingly parallel, no horizon loop)
+//                initial interior point from the linearisation records (embarrassingly parallel, no horizon loop).  Off the
+//                solve path since round 4 (kernel_build.hpp does the same in one pass): kept as the independent reference of
+//                smpc_debug_stage_records
 //   k_qp_ipm   : ONE WAVEFRONT PER PAIR OF OCP INSTANCES -- lanes 0-31 own one instance, lanes 32-63 another, each with its
 //                own LDS region, workspace and iteration state.  The halves never exchange data, so every branch is
 //                half-uniform and the SIMT exec mask does the rest (a converged half idles until its twin is done;
@@ -137,28 +139,8 @@ typedef double dbl2 __attribute__((ext_vector_type(2)));
 // wavefront and comes round again a millisecond later, long after the 4 MB L2 of its XCD has turned over.  Whether non-temporal
 // (`nt`) accesses pay depends on the workspace's size against the 256 MB Infinity Cache, so k_qp_ipm is built both ways
 // (template parameter NT: nt on its wide loads and on the factorisation sweep's wide stores) and the engine picks PER LAUNCH
-// (engine.hip: qp_nt_threshold; measurements at the kernel, below).  SMPC_NT_MASK is the build-time override of rounds 2-3, kept
-// for experiments on the remaining access classes (narrow 8-byte nt loads measured +6 %, k_qp_setup's stores no gain); its
-// default 0 leaves everything but the NT template's accesses plain.
-#ifndef SMPC_NT_MASK
-#define SMPC_NT_MASK 0x0
-#endif
-template <int BIT, class T> __device__ __forceinline__ T ld_ws(const T* p) {
-    if constexpr ((SMPC_NT_MASK >> BIT) & 1) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <int BIT, class T> __device__ __forceinline__ void st_ws(T v, T* p) {
-    if constexpr ((SMPC_NT_MASK >> BIT) & 1) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-// bit 0: wide loads of k_qp_ipm (pieces, row pairs)   bit 1: wide stores of the factorisation sweep (t, lambda, factor block)
-// bit 2: narrow loads of k_qp_ipm                     bit 3: narrow stores of k_qp_ipm      bit 4: k_qp_setup (record load, stores)
-template <class T> __device__ __forceinline__ T ldnt(const T* p) { return ld_ws<0>(p); }
-template <class T> __device__ __forceinline__ void stnt_b1(T v, T* p) { st_ws<1>(v, p); }
-template <class T> __device__ __forceinline__ T ldnt_s(const T* p) { return ld_ws<2>(p); }
-template <class T> __device__ __forceinline__ void stnt_s(T v, T* p) { st_ws<3>(v, p); }
-template <class T> __device__ __forceinline__ T ldnt_su(const T* p) { return ld_ws<4>(p); }
-template <class T> __device__ __forceinline__ void stnt_su(T v, T* p) { st_ws<4>(v, p); }
+// (engine.hip: qp_nt_threshold; measurements at the kernel, below).  Every other workspace access is plain (rounds 2-3 measured
+// the rest with a build-time mask since retired: narrow 8-byte nt loads +6 %, k_qp_setup's stores no gain).
 
 // wave-local hand-off through LDS: LDS operations of one wave execute in issue order, so all that is needed is that the
 // compiler neither reorders nor caches them across this point
@@ -366,7 +348,7 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
         // the tile: EV_TILE * EV_D doubles, contiguous; piece p holds element (2p) / EV_TILE of nodes (2p) % EV_TILE and the next one
         const dbl2* s2 = reinterpret_cast<const dbl2*>(ev + (size_t)blockIdx.x * (EV_TILE * EV_D));
         for (int p2 = threadIdx.x; p2 < EV_TILE * EV_D / 2; p2 += 32 * EV_TILE) {
-            const dbl2 v = ldnt_su(s2 + p2);
+            const dbl2 v = s2[p2];
             const int f = (2 * p2) / EV_TILE, n = (2 * p2) % EV_TILE;
             smem[n * HALF_D + f] = v.x;
             smem[(n + 1) * HALF_D + f] = v.y;
@@ -472,26 +454,26 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
     const double bflag = bmax > 0.0 ? 1.0 : 0.0;
 
     // ---- static blocks out ---------------------------------------------------------------------------------------------
-    if (hl < NRT) stnt_su(dbl2{sLO[hl], sHI[hl]}, reinterpret_cast<dbl2*>(w + Ly.oR0) + hl);
+    if (hl < NRT) reinterpret_cast<dbl2*>(w + Ly.oR0)[hl] = dbl2{sLO[hl], sHI[hl]};
     double* img = w + Ly.oIMG;
     for (int el = hl; el < NZ * NQP; el += 32) {
         const int c = el / NQP, r = el - c * NQP;
-        stnt_su(r < NQ ? sC[r * NZP + c] : 0.0, img + Ly.iTT + el);
+        *(img + Ly.iTT + el) = r < NQ ? sC[r * NZP + c] : 0.0;
     }
     for (int el = hl; el < NQ * MRP; el += 32) {
         const int ix = el / MRP, r = el - ix * MRP;
-        stnt_su(r < MR ? sC[(NQ + r) * NZP + NU + ix] : 0.0, img + Ly.iGT + el);
+        *(img + Ly.iGT + el) = r < MR ? sC[(NQ + r) * NZP + NU + ix] : 0.0;
     }
-    if (hl < NX) stnt_su(sC[(NQ + MR) * NZP + NU + hl], img + Ly.iGN + hl);
+    if (hl < NX) *(img + Ly.iGN + hl) = sC[(NQ + MR) * NZP + NU + hl];
     for (int el = hl; el < qp_even_c(NQ * NQ); el += 32) {
         const int i = el / NQ, j = el - i * NQ;
-        stnt_su(el < NQ * NQ ? (reach ? cs * e.cost_hess_qq[el] : 0.0) + (i == j ? lm : 0.0) : 0.0, img + Ly.iHQQ + el);
+        *(img + Ly.iHQQ + el) = el < NQ * NQ ? (reach ? cs * e.cost_hess_qq[el] : 0.0) + (i == j ? lm : 0.0) : 0.0;
     }
-    if (hl < NZP) stnt_su(sGZ[hl], img + Ly.iGZ + hl);
-    if (hl < NX) stnt_su(sB[hl], img + Ly.iB + hl);
+    if (hl < NZP) *(img + Ly.iGZ + hl) = sGZ[hl];
+    if (hl < NX) *(img + Ly.iB + hl) = sB[hl];
     if (hl < 4) {
         const double huu = (reach && !last ? cs * 2.0 * D->R : 0.0) + lm;
-        stnt_su(hl == 0 ? huu : (hl == 1 ? lm : (hl == 2 ? wsoft : bflag)), img + Ly.iSC + hl);
+        *(img + Ly.iSC + hl) = hl == 0 ? huu : (hl == 1 ? lm : (hl == 2 ? wsoft : bflag));
     }
 
     // ---- initial slacks / multipliers ----------------------------------------------------------------------------------
@@ -538,16 +520,16 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
             }
         }
         if (r < NRT) {
-            stnt_su(dbl2{tl, tu}, reinterpret_cast<dbl2*>(w + Ly.oR1) + r);
-            stnt_su(dbl2{ll, lu}, reinterpret_cast<dbl2*>(w + Ly.oR2) + r);
+            reinterpret_cast<dbl2*>(w + Ly.oR1)[r] = dbl2{tl, tu};
+            reinterpret_cast<dbl2*>(w + Ly.oR2)[r] = dbl2{ll, lu};
         }
-        stnt_su(0.0, w + Ly.oCZA + hl);   // (32 entries each: one per lane)
-        stnt_su(0.0, w + Ly.oCZN + hl);
+        *(w + Ly.oCZA + hl) = 0.0;   // (32 entries each: one per lane)
+        *(w + Ly.oCZN + hl) = 0.0;
         sE[r] = -(ll - lu);
     }
-    if (hl < 4) stnt_su(hl == 0 ? wsoft : (hl == 1 ? bflag : 0.0), w + Ly.oSL + hl);
-    if (hl < 8) stnt_su(0.0, w + Ly.oWC + hl);
-    if (hl < NZ) { stnt_su(sZ0[hl], w + Ly.oZ + hl); stnt_su(sZ0[hl], w + Ly.oZN + hl); }
+    if (hl < 4) *(w + Ly.oSL + hl) = hl == 0 ? wsoft : (hl == 1 ? bflag : 0.0);
+    if (hl < 8) *(w + Ly.oWC + hl) = 0.0;
+    if (hl < NZ) { *(w + Ly.oZ + hl) = sZ0[hl]; *(w + Ly.oZN + hl) = sZ0[hl]; }
     lds_fence();
     // stationarity residual at the initial point (pi = 0): g - C^T (ll - lu); dx_0 does not enter (no cost cross term)
     if (hl < NZ && !(k == 0 && hl >= NU) && !(last && hl < NU)) {
@@ -598,13 +580,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     using LyT = QpLayout<NQ>;
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NZP = LyT::NZP, NQP = LyT::NQP, WS2 = LyT::WS2, NL = 32,
                   LC0 = LyT::LC0, KS = LyT::KS, NWP = LyT::NWP;
-    // (the wide workspace accesses of this kernel: these two shadow the build-time-selectable helpers of the same names)
+    // (the wide workspace accesses of this kernel)
     auto ldnt = [](auto* p) {
-        if constexpr (NT || (SMPC_NT_MASK & 1)) return __builtin_nontemporal_load(p);
+        if constexpr (NT) return __builtin_nontemporal_load(p);
         else return *p;
     };
     auto stnt_b1 = [](auto v, auto* p) {
-        if constexpr (NT || (SMPC_NT_MASK & 2)) __builtin_nontemporal_store(v, p);
+        if constexpr (NT) __builtin_nontemporal_store(v, p);
         else *p = v;
     };
     // load-balance probe (smpc_get_qp_wave_stats): two reads of the constant 100 MHz clock per half-wave; the first one is
@@ -615,13 +597,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     constexpr int NRC_MAX = NQ + MR_MAX + 1;
     static_assert(MRT < 0 || NX + NRC_MAX <= NL, "one lane per constraint row");
     static_assert(KS <= NL, "one lane per column of [G | rho | I]");
-#ifndef QP_P_INPLACE
-#define QP_P_INPLACE 0      // (measured, round 6: the eighth 7-DoF wavefront it buys makes C4 SLOWER, 20.82 -> 21.31 ms per step)
-#endif
-    constexpr bool P_INPLACE = QP_P_INPLACE != 0;
     constexpr int NTRI_U = NQ * (NQ + 1) / 2, NTRI_X = NX * (NX + 1) / 2;
-    // first index of the q-q corner's elements in the x-x index table (below): they need the cost Hessian and the collision rows
-    constexpr int TRI_Q0 = P_INPLACE ? NTRI_X - NTRI_U : 0;
     constexpr int IMG_MAX = NZ * NQP + NQ * MRP_MAX + NX + qp_even_c(NQ * NQ) + NZP + NX + 4;
     constexpr int IMG_PF = (IMG_MAX / 2 + 31) / 32;
     constexpr int CST_MAX = NRC_MAX * NZP;                                       // row-major image of the general rows in LDS
@@ -661,7 +637,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     // [image | D | E | -- buffers of the factorisation sweep only: TD GD Lambda G Wt P P -- | vectors]
     constexpr int O_D = IMG_MAX, O_E = O_D + NL, O_TD = O_E + NL, O_GD = O_TD + NZ * NQP, O_LAM = O_GD + NQ * MRP_MAX,
                   O_G = O_LAM + qp_even_c(NQ * NQ), O_WT = O_G + NQ * WS2, O_PA = O_WT + (NX + 1) * NQP,
-                  O_PB2 = O_PA + (P_INPLACE ? 0 : NX * NX),      // (P_k is built over P_{k+1}: see the index table below)
+                  O_PB2 = O_PA + NX * NX,
                   O_PEND = O_PB2 + NX * NX, O_STG = O_TD + CST_MAX + 2 * NWP,   // (the forward sweeps stage their blocks over the B1-only buffers)
                   O_PVA = O_PEND > O_STG ? O_PEND : O_STG, O_PVB = O_PVA + NX, O_PB = O_PVB + NX,
                   O_ZU = O_PB + NX, O_XB = O_ZU + NQP, O_RHO = O_XB + 2 * NX, O_WV = O_RHO + NQP, HALF_D = O_WV + NQP;
@@ -702,33 +678,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         triUi[e] = (unsigned char)i;
         triUj[e] = (unsigned char)(i + rem);
     }
-    // Upper triangle of the x-x block.  Default (QP_P_INPLACE=0): the q-q corner first, P ping-ponged between two buffers.  With
-    // -DQP_P_INPLACE=1 the table is ordered so that P_k can be built OVER P_{k+1} (one P buffer instead of two: 1.5 KB of LDS per
-    // half-wave at 7-DoF, 18.4 instead of 21.6 KB per block, i.e. the eighth wavefront per CU -- built and measured in round 6, parity
-    // green, and slower in C4's loop, so not the default): element (i, j) of P_k reads entries (i, j), (i, j - NQ), (i - NQ, j),
-    // (i - NQ, j - NQ) of P_{k+1} (A^T P A in closed form), i.e. its own and entries of blocks "below" its own in the order
-    // v-v > q-v > q-q.  With the v-v block first, then q-v, then the q-q corner, a pass only ever overwrites entries that no later pass
-    // reads; inside a pass every read is issued and waited for before the first write (hold_rows4).  The corner's elements -- the only
-    // ones that need the cost Hessian and the collision rows -- are the table's last NTRI_U.
-    static_assert(NTRI_U <= 32, "the v-v block (same size as the q-q corner) fits the first pass");
+    // Upper triangle of the x-x block, the q-q corner first; P ping-pongs between two buffers (in place was slower: DESIGN.md section 8)
     for (int e = hl; e < NTRI_X; e += 32) {
         int i = 0, j;
-        if (P_INPLACE) {
-            if (e < NTRI_U) {                       // v-v, rows NQ .. NX-1
-                int rem = e;
-                while (rem >= NQ - i) { rem -= NQ - i; i++; }
-                j = NQ + i + rem;
-                i += NQ;
-            } else if (e < NTRI_U + NQ * NQ) {      // q-v: the full NQ x NQ block
-                const int t = e - NTRI_U;
-                i = t / NQ;
-                j = NQ + t - i * NQ;
-            } else {                                // q-q corner
-                int rem = e - NTRI_U - NQ * NQ;
-                while (rem >= NQ - i) { rem -= NQ - i; i++; }
-                j = i + rem;
-            }
-        } else if (e < NTRI_U) {
+        if (e < NTRI_U) {
             int rem = e;
             while (rem >= NQ - i) { rem -= NQ - i; i++; }
             j = i + rem;
@@ -863,11 +816,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 const dbl2 r0 = ldnt(reinterpret_cast<const dbl2*>(w + Ly.oR0) + hr), r1 = ldnt(reinterpret_cast<const dbl2*>(w + Ly.oR1) + hr),
                            r2 = ldnt(reinterpret_cast<const dbl2*>(w + Ly.oR2) + hr);
                 rs.lo = r0.x; rs.hi = r0.y; rs.tl = r1.x; rs.tu = r1.y; rs.ll = r2.x; rs.lu = r2.y;
-                czar = ldnt_s(w + Ly.oCZA + hr);
-                cznr = ldnt_s(w + Ly.oCZN + hr);
-                slb = ldnt_s(reinterpret_cast<const dbl2*>(w + Ly.oSL));
-                zc = ldnt_s(w + Ly.oZ + hz);
-                znc = ldnt_s(w + Ly.oZN + hz);
+                czar = *(w + Ly.oCZA + hr);
+                cznr = *(w + Ly.oCZN + hr);
+                slb = *reinterpret_cast<const dbl2*>(w + Ly.oSL);
+                zc = *(w + Ly.oZ + hz);
+                znc = *(w + Ly.oZN + hz);
             };
             auto stage_b1 = [&](int k, auto last_tag) {
                 constexpr bool last = decltype(last_tag)::value;
@@ -896,7 +849,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                     mu_new += row_live ? qp_row_comp(rs, soft, wsoft) : 0.0;
                 }
                 zc += alpha * (znc - zc);
-                stnt_s(zc, w + Ly.oZ + hz);
+                *(w + Ly.oZ + hz) = zc;
                 lds_fence();
                 QPT(0);
                 load_b1(k > 0 ? k - 1 : 0);
@@ -1030,7 +983,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                     for (int t = 0; t < (NTRI_X + 31) / 32; t++) {
                         const int el = min(hl + 32 * t, NTRI_X - 1);
                         const int ix = triXi[el], jx = triXj[el];
-                        const double a = hxx_elem(ix, jx, 32 * (t + 1) > TRI_Q0 && 32 * t < TRI_Q0 + NTRI_U);
+                        const double a = hxx_elem(ix, jx, 32 * t < NTRI_U);
                         Pn[ix * NX + jx] = a;
                         Pn[jx * NX + ix] = a;
                     }
@@ -1146,7 +1099,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                                 a = (s0 + s1) - (w0 + w1);
                             }
                             a = fma(sc[0] * sc[2], sc[1], a);
-                            if (32 * (t + 1) > TRI_Q0 && 32 * t < TRI_Q0 + NTRI_U) {   // (the passes that hold elements of the q-q corner, see the index table)
+                            if (32 * t < NTRI_U) {   // (the passes that hold elements of the q-q corner, see the index table)
                                 const int iq = min(i, NQ - 1), jq = min(j, NQ - 1);
                                 const double qq = sHQQ[iq * NQ + jq] + pdot(sGT + iq * MRP, sGD + jq * MRP, MRP >> 1);
                                 a += j < NQ ? qq : 0.0;
@@ -1172,7 +1125,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 QPT(4);
                 lds_fence();
                 if (last || k > 0) {
-                    if (!P_INPLACE) { double* t1 = Pc; Pc = Pn; Pn = t1; }
+                    double* t1 = Pc; Pc = Pn; Pn = t1;
                     double* t2 = pvc; pvc = pvn; pvn = t2;
                 }
                 QPT(5);
@@ -1269,8 +1222,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 R.r1 = ldnt(reinterpret_cast<const dbl2*>(w + Ly.oR1) + hr);
                 R.r2 = ldnt(reinterpret_cast<const dbl2*>(w + Ly.oR2) + hr);
                 if (CORR) {
-                    R.cza = ldnt_s(w + Ly.oCZA + hr);
-                    R.wc = ldnt_s(w + Ly.oWC + hl_u);   // the corrector's w (B2)
+                    R.cza = *(w + Ly.oCZA + hr);
+                    R.wc = *(w + Ly.oWC + hl_u);   // the corrector's w (B2)
                 }
             };
             if (hl < NX) sIMG[o_xb + hl] = dx0_reg;
@@ -1350,13 +1303,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                     if (!CORR) {
                         double e1, e2;
                         qp_row_dir<true>(rs, soft, wsoft, cz, 0.0, 0.0, cz, &rr, &s1_, &s2_, &e1, &e2);
-                        stnt_s(cz, w + Ly.oCZA + hr);
+                        *(w + Ly.oCZA + hr) = cz;
                         sD[hr] = e1;     // (B1's D / E arrays are free during the forward sweeps)
                         sE[hr] = e2;
                     } else {
                         qp_row_dir<false>(rs, soft, wsoft, cz, sigmu, corr_w, cur.cza, &rr, &s1_, &s2_, nullptr, nullptr);
-                        stnt_s(cz, w + Ly.oCZN + hr);
-                        stnt_s(hz < NU ? sZU[hl_u] : xb[hl_px], w + Ly.oZN + hz);
+                        *(w + Ly.oCZN + hr) = cz;
+                        *(w + Ly.oZN + hz) = hz < NU ? sZU[hl_u] : xb[hl_px];
                     }
                     S1 += row_live ? s1_ : 0.0;
                     S2 += row_live ? s2_ : 0.0;
@@ -1391,7 +1344,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                     a1 += b1;
                     a2 += b2;
                     if (hz >= NU) { a1 += sD[hz - NU]; a2 += sE[hz - NU]; }
-                    stnt_s(dbl2{a1, a2}, reinterpret_cast<dbl2*>(w + Ly.oA12) + hz);
+                    reinterpret_cast<dbl2*>(w + Ly.oA12)[hz] = dbl2{a1, a2};
                     lds_fence();   // (the next stage overwrites the staged rows)
                 }
                 { const int t = o_xb; o_xb = o_xn; o_xn = t; }
@@ -1489,7 +1442,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                         if (hl < NQ) sWv[hl] = v;
                         // the corrector's w: one 64-byte sector of its own (inside the factor block it was NQ separate
                         // read-modify-writes); lanes NQ.. hold the last entry again and fill the sector
-                        stnt_s(v, w + Ly.oWC + (hl < 8 ? hl : NQ - 1));
+                        *(w + Ly.oWC + (hl < 8 ? hl : NQ - 1)) = v;
                     }
                     lds_fence();
                     if (k > 0 && hz >= NU) {
@@ -1563,8 +1516,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         for (int j = 0; j < EP_CH; j++) {
             const int k = k0 + j <= N ? k0 + j : N;
             const double* w = ws + (size_t)k * Ly.stride;
-            zz[j] = ldnt_s(w + Ly.oZ + hz);
-            zzn[j] = ldnt_s(w + Ly.oZN + hz);
+            zz[j] = *(w + Ly.oZ + hz);
+            zzn[j] = *(w + Ly.oZN + hz);
             const int ku = k < N ? k : N - 1;
             bb[j] = hl < NU ? ub0[(size_t)ku * NU + hl_u] : xb0[(size_t)k * NX + hl_px];
         }

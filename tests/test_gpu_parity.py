@@ -665,20 +665,19 @@ def test_eval_nodes_device_path_matches_host_path():
 
 def test_mlp_layer_by_layer_gemm_kernels_in_child_processes():
     """From 8 192 network rows on the default is the one-wave fused kernel (k_mlp_wave, round 5); the layer-by-layer GEMM chain of
-    rounds 1-4 stays selectable (SMPC_MLP_LARGE=chain: one-wave blocks of k_gemm_f32; with SMPC_MLP_GEMM=tiled on top the 128 x 128
-    LDS-tiled kernel) for A/B runs and for networks that are not 256 wide with three hidden layers.  The knobs are read once per
-    process, so both chains are exercised in child processes running the large-row tests of this file."""
+    rounds 1-4 stays selectable (SMPC_MLP_LARGE=chain: one-wave blocks of k_gemm_f32) for A/B runs and for networks that are not
+    256 wide with three hidden layers.  The knob is read once per process, so the chain is exercised in a child process running the
+    large-row tests of this file."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for extra in ({'SMPC_MLP_LARGE': 'chain'}, {'SMPC_MLP_LARGE': 'chain', 'SMPC_MLP_GEMM': 'tiled'}):
-        env = dict(os.environ, **extra)
-        r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_gpu_parity.py'), '-m', 'gpu', '-q', '-x', '-k',
-                            'test_mlp_large_row_counts or test_mlp_activations_fused_and_large_paths'], env=env, cwd=root, capture_output=True,
-                           text=True, timeout=900)
-        assert r.returncode == 0, (extra, r.stdout[-2000:] + r.stderr[-2000:])
-        assert '7 passed' in r.stdout, (extra, r.stdout[-500:])
+    env = dict(os.environ, SMPC_MLP_LARGE='chain')
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_gpu_parity.py'), '-m', 'gpu', '-q', '-x', '-k',
+                        'test_mlp_large_row_counts or test_mlp_activations_fused_and_large_paths'], env=env, cwd=root, capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert '7 passed' in r.stdout, r.stdout[-500:]
 
 
 @pytest.mark.parametrize('switched', [False, True])
