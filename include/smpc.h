@@ -288,7 +288,8 @@ enum {
     SMPC_POLICY_STATE_CHECK = 1,    /* ControllerSafeSetEverywhere: success also needs checkStateConstraints       :651-661 */
     SMPC_POLICY_STWA = 2,           /* STWAController / HTWAController: viable state, abort after N - 1 failures   :375-388 */
     SMPC_POLICY_RECEDING = 3,       /* RecedingController: receding index r, row switched on at node r             :448-498 */
-    SMPC_POLICY_REAL_RECEDING = 4   /* RealReceding: node r boxed to the planned state +- tube                     :524-565 */
+    SMPC_POLICY_REAL_RECEDING = 4,  /* RealReceding: node r boxed to the planned state +- tube                     :524-565 */
+    SMPC_POLICY_PARALLEL = 5        /* ParallelController: N candidate OCPs, row on at node n = N..1, best kept    :567-644 */
 };
 
 typedef struct {
@@ -325,6 +326,13 @@ typedef struct {                    /* what a controller object holds per instan
  * left untouched and skipped by the QP kernels.  u_out[b] = the policy's control, u_guess[b][0] for an instance that raises
  * abort, u_other[b] for one that did not step (u_other may be NULL when stepping is).  abort_out[b] = the step's second return
  * value; *any_abort (one int32) is set to 1 if any instance aborted, 0 otherwise. */
+/* SMPC_POLICY_PARALLEL needs st->r and a network with the row on every node (SMPC_NN_ALL), like the receding kinds need r.  Its
+ * step solves candidate n = N for every stepping instance, then candidates N - 1 .. 1 for the instances whose first candidate did
+ * not reach node N, as one launch over a dense list of candidate slots (which slots are live is only known on the device).  That
+ * second launch runs on candidate scratch of up to B * (N - 1) extra instances, allocated on the first parallel step of a batch
+ * size and reused: the QP workspace of B * (N - 1) instances, the network pass's per-row buffers for their B * (N - 1) * N nodes,
+ * and the candidates' inputs and outputs.  For nq = 6, 6 rows, N = 30, B = 4096 (computed from the layouts, not measured):
+ * 19.8 GB + 10.9 GB + 1.6 GB.  When it cannot be allocated the call returns SMPC_ENOMEM and says how much it asked for. */
 int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const smpc_policy_state* st, const double* x,
                      const uint8_t* stepping, const double* u_other, double* u_out, uint8_t* abort_out, int32_t* any_abort);
 

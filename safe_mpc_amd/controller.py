@@ -403,6 +403,77 @@ class RealReceding(RecedingController):
         return self._post_solve(x, status, u_abort)
 
 
+class ParallelController(RecedingController):
+    """controller.py:567-644: every step solves N candidate OCPs from the same corrected guess -- candidate n (n = N .. 1) with the
+    hard safe-set row switched on at node n alone (constrain_n, :578-587: all other nodes of 1..N off, the terminal node included
+    unless n = N) -- and keeps the one whose trajectory reaches the furthest safe node (sing_step / check_safe_n, :589-612).  The
+    reference solves them one after another; here they are one batch of B * N instances (numpy path) or, on the device, candidate
+    N for every instance followed by the other N - 1 for the instances it did not settle (smpc_policy_step, kernels_policy.hpp).
+    acados is assumed to keep no state between the candidate solves (exact_hess_constr = 0, :110; reset() in solve, :141)
+    [EXT-UNVERIFIED].  The reference's get_controller table (utils.py:64-75) does not list this class: get_controller finds it in
+    UNREGISTERED_CONTROLLERS."""
+    cont_name = 'parallel'
+    policy_kind = 5
+    can_abort = True
+
+    def candidate_flags(self):
+        """[N, N+1] p[4] of candidate n = N, N-1, .., 1 (row c is candidate N - c); node 0 keeps the instance's own flag"""
+        N = self.N
+        k, n = np.arange(N + 1)[None, :], np.arange(N, 0, -1)[:, None]
+        return np.where(k == n, 1.0, -1.0)
+
+    def step(self, x):
+        """controller.py:614-640 with every candidate evaluated: the choice is the one the reference's loop (order N .. 1, break at
+        the first result N) makes; status / qp_iter (and x_temp / u_temp on failure) are those of the last candidate it solves"""
+        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
+            return self.step_on_device(x)
+        B, N, nx, nu = self.B, self.N, self.nx, self.nu
+        self.guessCorrection()
+        xg, ug = np.asarray(self.x_guess), np.asarray(self.u_guess)
+        u_abort, xg1 = ug[:, 0].copy(), xg[:, 1].copy()          # (taken after guessCorrection, :615-616, 636)
+        # what solve() writes into the instance's own parameters (controller.py:153-156); the flags stay the instance's
+        self.p[:, :, 3] = self.params.alpha
+        self._apply_traj()
+        # the B * N candidates, instance-major: candidate c of instance b is row b * N + c, c = N - n
+        P = np.repeat(np.asarray(self.p)[:, None], N, axis=1)                      # [B, N, N+1, 5]
+        P[:, :, 1:, 4] = self.candidate_flags()[None, :, 1:]
+        rep = lambda a: np.ascontiguousarray(np.repeat(a[:, None], N, axis=1).reshape((B * N,) + a.shape[1:]))
+        xs, us, st, it = self.ocp_solver.solve(rep(np.asarray(x, float)), rep(xg), rep(ug), P.reshape(B * N, N + 1, 5))
+        xs, us = np.asarray(xs).reshape(B, N, N + 1, nx), np.asarray(us).reshape(B, N, N, nu)
+        st, it = np.asarray(st).reshape(B, N), np.asarray(it).reshape(B, N)
+        state_ok = np.asarray(self.checkStateConstraints(xs.reshape(B * N, N + 1, nx))).reshape(B, N)
+        safe = np.asarray(self.checkSafeConstraints(xs.reshape(B * N, N + 1, nx))).reshape(B, N, N + 1)
+        # sing_step / check_safe_n (:589-612) with r at the start of the step
+        r = np.asarray(self.r)[:, None]                                               # [B, 1]
+        i = np.arange(N + 1)
+        in_range = safe & (i[None, None, :] >= r[:, :, None])
+        checked = np.where(in_range.any(axis=2), N - np.argmax(in_range[:, :, ::-1], axis=2), 0)    # last safe node of r..N, else 0
+        ns = np.arange(N, 0, -1)[None, :]
+        constr_ver = np.where(checked >= r, checked, np.minimum(ns, r))
+        result = np.where((st == 0) & (constr_ver >= r) & state_ok, constr_ver, 0)   # [B, N], candidates in the order N .. 1
+        self.candidate_results = result            # (kept for diagnostics: result[:, 0] == N is what the device schedule settles first)
+        # selection (:614-624): the largest result, ties to the first candidate in that order (the largest n)
+        best = result.max(axis=1)
+        chosen = np.argmax(result, axis=1)
+        last = np.where(best == N, chosen, N - 1)        # the loop broke at the chosen candidate, or ran down to candidate 1
+        success = best > 1
+        pick = np.where(success, chosen, last)
+        rows = np.arange(B)
+        self.x_temp, self.u_temp = xs[rows, pick].copy(), us[rows, pick].copy()
+        self.last_status = st[rows, last].astype(np.int32)
+        self.qp_iter = it[rows, last].astype(np.int32)
+        # automaton (:625-640); the abort returns before r -= 1, the step count and provideControl
+        r = r[:, 0]
+        abort = ~success & (r == 1)
+        self.x_viable = np.where(abort[:, None], xg1, self.x_viable)
+        self.fails = np.where(success, 0, self.fails + 1).astype(np.int64)
+        self.r = np.where(success, best - 1, np.where(abort, N, r - 1)).astype(np.int64)
+        active = ~abort
+        self.current_step = self.current_step + active.astype(np.int64)
+        u, _ = self.provideControl(active)
+        return np.where(abort[:, None], u_abort, u), abort
+
+
 class ControllerSafeSetEverywhere(STController):
     cont_name = 'constraint_everywhere'
     policy_kind = 1
@@ -433,8 +504,13 @@ CONTROLLERS = {'naive': NaiveController, 'zerovel': TerminalZeroVelocity, 'st': 
                'constraint_everywhere': ControllerSafeSetEverywhere}
 
 
+# complete in the reference's controller.py but missing from its get_controller table (utils.py:64-75); scripts/run_all_mpc.sh:12 runs it
+UNREGISTERED_CONTROLLERS = {'parallel': ParallelController}
+
+
 def get_controller(cont_name, params, batch, **kw):
-    """utils.py:64-75"""
-    if cont_name not in CONTROLLERS:
+    """utils.py:64-75, and the classes of UNREGISTERED_CONTROLLERS"""
+    cls = CONTROLLERS.get(cont_name, UNREGISTERED_CONTROLLERS.get(cont_name))
+    if cls is None:
         raise ValueError(f'Controller {cont_name} not available')
-    return CONTROLLERS[cont_name](params, batch, **kw)
+    return cls(params, batch, **kw)

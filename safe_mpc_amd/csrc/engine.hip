@@ -45,6 +45,7 @@ struct smpc_handle {
     float* d_bias[SMPC_MAX_LAYERS] = {nullptr};
     // per-batch scratch, grown on demand
     int capB = 0;
+    int capEV = 0;                // instances d_ev is sized for (ensure_batch)
     double* d_ev = nullptr;       // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
     double* d_nn = nullptr;       // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
                                   // on every node, [B][1 + nx] with the row on the end node only, not allocated without a network row
@@ -62,7 +63,8 @@ struct smpc_handle {
     double *d_x0 = nullptr, *d_xg = nullptr, *d_ug = nullptr, *d_p = nullptr, *d_xo = nullptr, *d_uo = nullptr;
     int32_t *d_st = nullptr, *d_it = nullptr;
     // MLP activations
-    size_t capM = 0;
+    size_t capM = 0;            // rows every buffer below is sized for (the layer-by-layer GEMM chain)
+    size_t capY = 0, capDG = 0; // rows d_y / d_dg are sized for (>= capM): the fused and one-wave passes need no more than these
     float *d_S = nullptr, *d_y = nullptr, *d_GS = nullptr, *d_dA = nullptr, *d_dB = nullptr;
     int32_t *d_nn_idx = nullptr, *d_nn_cnt = nullptr;   // compacted list of the nodes whose safe-set row is on + its length
                                 // INVARIANT: *d_nn_cnt is zero whenever no chain of kernels is using it.  Every chain that fills it ends in
@@ -106,6 +108,11 @@ struct smpc_handle {
     long mlp_rows_hint = 0;     // > 0 (smpc_policy_step of the receding policies): the rows EXPECTED to be live in a compacted list -- one or
                                 // two nodes per instance, where the list's capacity is every node -- which selects the network kernel
                                 // (the count itself is only known on the device; any kernel is correct for any count)
+    // SMPC_POLICY_PARALLEL's candidate buffers (smpc_policy_step): one block, laid out by ParScratch for par_B instances of horizon
+    // par_N, zeroed when allocated
+    char* d_par = nullptr;
+    size_t par_bytes = 0;
+    int par_B = 0, par_N = 0;
     char err[256] = "";
 };
 
@@ -161,13 +168,18 @@ int upload_bounds(smpc_handle* h, const double* lo, const double* hi) {
     return SMPC_OK;
 }
 
-int ensure_batch(smpc_handle* h, int B) {
+// with_ev = false: the solve path only (SMPC_POLICY_PARALLEL's candidate batch), which never reads the linearisation records d_ev --
+// 2.6 KB per node, 10 GB for the candidates of 4096 instances at N = 30 -- so they are not grown for it
+int ensure_batch(smpc_handle* h, int B, bool with_ev = true) {
     const size_t per = ws_doubles_per_instance(h->desc, h->N);
     const size_t need = per * (size_t)B * sizeof(double);
+    int rc;
     if (B > h->capB || need > h->ws_bytes) {
-        int rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = dev_alloc(h, &h->d_ev, ev_tiles((size_t)B * (h->N + 1)) * EV_TILE * EV_D))) return rc;
+        if (with_ev) {
+            if ((rc = dev_alloc(h, &h->d_ev, ev_tiles((size_t)B * (h->N + 1)) * EV_TILE * EV_D))) return rc;
+            h->capEV = B;
+        }
         if ((rc = dev_alloc(h, &h->d_ws, per * (size_t)B))) return rc;
         {
             const size_t nn_nodes = h->desc.nn_mode == SMPC_NN_NONE ? 0 : (h->desc.nn_mode == SMPC_NN_TERMINAL ? (size_t)B : (size_t)B * (h->N + 1));
@@ -183,6 +195,11 @@ int ensure_batch(smpc_handle* h, int B) {
         h->ws_bytes = need;
         h->capB = B;
         h->capIO = 0;
+    }
+    if (with_ev && B > h->capEV) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = dev_alloc(h, &h->d_ev, ev_tiles((size_t)B * (h->N + 1)) * EV_TILE * EV_D))) return rc;
+        h->capEV = B;
     }
     return SMPC_OK;
 }
@@ -214,10 +231,26 @@ int ensure_tmp(smpc_handle* h, size_t bytes) {
     return SMPC_OK;
 }
 
-int ensure_mlp(smpc_handle* h, size_t M) {
+// the network pass's buffers for M rows: level 0 the output alone (k_mlp_fused), 1 also the hidden layers' activation derivatives
+// (k_mlp_wave), 2 every buffer of the layer-by-layer GEMM chain
+int ensure_mlp(smpc_handle* h, size_t M, int level = 2) {
     const size_t Mp = (M + 127) / 128 * 128;
     if (Mp <= h->capM) return SMPC_OK;
     int rc;
+    if (level < 2) {
+        if (Mp <= h->capY && (level == 0 || Mp <= h->capDG)) return SMPC_OK;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (Mp > h->capY) {
+            if ((rc = dev_alloc(h, &h->d_y, Mp))) { h->capY = h->capM = 0; return rc; }
+            h->capY = Mp;
+        }
+        if (level == 1 && Mp > h->capDG) {
+            for (int l = 0; l + 1 < h->nlayers; l++)
+                if ((rc = dev_alloc(h, &h->d_dg[l], Mp * h->H))) { h->capDG = h->capM = 0; return rc; }
+            h->capDG = Mp;
+        }
+        return SMPC_OK;
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t H = h->H;
     if ((rc = dev_alloc(h, &h->d_S, Mp * MLP_KPAD))) return rc;
@@ -229,7 +262,7 @@ int ensure_mlp(smpc_handle* h, size_t M) {
         if ((rc = dev_alloc(h, &h->d_act[l], Mp * H))) return rc;
         if ((rc = dev_alloc(h, &h->d_dg[l], Mp * H))) return rc;
     }
-    h->capM = Mp;
+    h->capM = h->capY = h->capDG = Mp;
     return SMPC_OK;
 }
 
@@ -253,7 +286,6 @@ int ensure_nn_idx(smpc_handle* h, size_t M) {
 template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const double* d_x, bool backward, const double* d_p = nullptr,
                               double* d_ev = nullptr, bool* chained = nullptr, int compact = 0) {
     int rc;
-    if ((rc = ensure_mlp(h, (size_t)M))) return rc;
     const int Mp = (M + 127) / 128 * 128, H = h->H, L = h->nlayers;
     hipStream_t s = h->stream;
     const int32_t* idx = mode == 3 ? h->d_nn_idx : nullptr;
@@ -267,6 +299,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         static const bool no_fused = getenv("SMPC_MLP_UNFUSED") != nullptr;     // (A/B knob)
         static const long fused_max = [] { const char* e = getenv("SMPC_MLP_FUSED_MAX"); return e ? atol(e) : 8192L; }();   // (A/B knob)
         if (!no_fused && rows_all < fused_max && H == MLPF_H && L == 4 && (!backward || (d_p && d_ev))) {
+            if ((rc = ensure_mlp(h, (size_t)M, 0))) return rc;
             MlpWeights Wt;
             for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(256);
@@ -285,6 +318,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         // GEMMs back (A/B runs; they also serve any network that is not 256 wide with three hidden layers).
         static const bool large_chain = [] { const char* e = getenv("SMPC_MLP_LARGE"); return e && !strcmp(e, "chain"); }();
         if (!no_fused && !large_chain && rows_all >= fused_max && H == MLPF_H && L == 4 && (!backward || (d_p && d_ev))) {
+            if ((rc = ensure_mlp(h, (size_t)M, backward ? 1 : 0))) return rc;
             MlpWeights Wt;
             for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(64);
@@ -299,6 +333,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
             return SMPC_OK;
         }
     }
+    if ((rc = ensure_mlp(h, (size_t)M))) return rc;
     hipLaunchKernelGGL((k_nn_features<NQ>), dim3((Mp + 63) / 64), dim3(64), 0, s, h->d_desc, M, Mp, N, mode, d_x,
                        h->d_S, idx, live);
     // The layer-by-layer GEMMs (round 4): k_gemm_f32 as ONE-WAVE blocks -- a wavefront of it is self-contained (32 x 64 tile,
@@ -685,6 +720,166 @@ int rollout_workers(smpc_handle* h, int n) {
     return SMPC_OK;
 }
 
+// ---- SMPC_POLICY_PARALLEL (kernels_policy.hpp, k_par_*) ------------------------------------------------------------------------
+// the candidate block for B instances at horizon N (K = N - 1 candidates per instance in phase 2, S = B * K slots)
+struct ParScratch {
+    double *p1, *x0, *xg, *ug, *p, *xo, *uo;
+    int32_t *st, *it, *ok, *safe, *list, *pos, *n_open;
+    uint8_t* active;
+    size_t bytes;
+};
+ParScratch par_layout(char* base, int B, int N, int nq) {
+    const size_t S = (size_t)B * (N - 1), nx = 2 * (size_t)nq;
+    ParScratch c{};
+    size_t off = 0;
+    const auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+    c.p1 = (double*)take(sizeof(double) * B * (N + 1) * SMPC_NP);
+    c.x0 = (double*)take(sizeof(double) * S * nx);
+    c.xg = (double*)take(sizeof(double) * S * (N + 1) * nx);
+    c.ug = (double*)take(sizeof(double) * S * N * nq);
+    c.p = (double*)take(sizeof(double) * S * (N + 1) * SMPC_NP);
+    c.xo = (double*)take(sizeof(double) * S * (N + 1) * nx);
+    c.uo = (double*)take(sizeof(double) * S * N * nq);
+    c.st = (int32_t*)take(sizeof(int32_t) * S);
+    c.it = (int32_t*)take(sizeof(int32_t) * S);
+    c.ok = (int32_t*)take(sizeof(int32_t) * S);
+    c.safe = (int32_t*)take(sizeof(int32_t) * S * (N + 1));
+    c.list = (int32_t*)take(sizeof(int32_t) * B);
+    c.pos = (int32_t*)take(sizeof(int32_t) * B);
+    c.n_open = (int32_t*)take(sizeof(int32_t));
+    c.active = (uint8_t*)take(S);
+    c.bytes = off;
+    return c;
+}
+
+// everything a parallel step needs beyond what every policy step has: the candidate block, the solve path's scratch (QP workspace,
+// network-row records) for max(B, S) instances, the network lists for S * (N + 1) nodes.  Grown on the first step of a batch size,
+// never inside a graph capture (as every ensure_*).
+int ensure_parallel(smpc_handle* h, int B) {
+    const int N = h->N;
+    const long S = (long)B * (N - 1);
+    const ParScratch need = par_layout(nullptr, B, N, h->desc.nq);
+    const size_t ws = ws_doubles_per_instance(h->desc, N) * sizeof(double) * (size_t)(S > B ? S : B);
+    int rc = SMPC_OK;
+    if (S > INT32_MAX / (N + 1)) rc = SMPC_EINVAL;
+    if (!rc && (h->par_N != N || h->par_B < B || h->par_bytes < need.bytes)) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->d_par) { (void)hipFree(h->d_par); h->d_par = nullptr; }
+        h->par_bytes = 0;
+        h->par_B = h->par_N = 0;
+        if (hipMalloc((void**)&h->d_par, need.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            h->d_par = nullptr;
+            rc = SMPC_ENOMEM;
+        } else {
+            HIPCHK(h, hipMemsetAsync(h->d_par, 0, need.bytes, h->stream));
+            h->par_bytes = need.bytes;
+            h->par_B = B;
+            h->par_N = N;
+        }
+    }
+    if (!rc && S > 0) rc = ensure_batch(h, (int)(S > B ? S : B), false);
+    if (!rc && S > 0) rc = ensure_nn_idx(h, (size_t)S * (N + 1));
+    if (rc) {
+        // (a failed allocation may have freed the old buffers: make the next call allocate afresh)
+        h->capB = 0;
+        h->ws_bytes = 0;
+        h->capEV = 0;
+        return fail(h, rc == SMPC_EINVAL ? SMPC_EINVAL : SMPC_ENOMEM,
+                    "parallel policy: candidate scratch for B * (N - 1) = %ld instances could not be allocated: %.2f GB of QP workspace "
+                    "+ %.2f GB of candidate buffers (B = %d, N = %d)", S, ws / 1e9, need.bytes / 1e9, B, N);
+    }
+    return SMPC_OK;
+}
+
+// ParallelController.step (controller.py:567-644) for the stepping instances, enqueue-only.  Phase 1: candidate N of every stepping
+// instance -- the htwa OCP under per-node switching -- into the instance's own x_temp / u_temp / status / qp_iter, its state test and
+// its safe-set test at nodes r..N.  Phase 2: candidates N-1 .. 1 of the instances phase 1 left open, as one launch over the dense
+// candidate list (dead slots skipped), tested the same way.  Then k_par_select (selection and automaton) and provideControl.
+int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, const smpc_policy_state* st, const double* x,
+                         const uint8_t* stepping, const double* u_other, double* u_out, uint8_t* abort_out, int32_t* any_abort,
+                         int32_t* d_ok, int32_t* d_safe, int32_t* d_acc, uint8_t* d_act) {
+    const int N = h->N, nq = h->desc.nq, nx = 2 * nq, K = N - 1;
+    const long S = (long)B * K;
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = ensure_parallel(h, B))) return rc;
+    if ((rc = ensure_nn_idx(h, (size_t)B * (N + 1)))) return rc;
+    const ParScratch c = par_layout(h->d_par, B, N, nq);
+    const dim3 blk(64);
+    const auto grid = [](long n) { return dim3((unsigned)((n + 63) / 64)); };
+    // guessCorrection; also resets *any_abort and presets the state-test verdicts of phase 1
+    hipLaunchKernelGGL(k_guess_correction, grid((long)B * nq), blk, 0, s, B, N, nq, h->desc.dt, st->x_guess, st->u_guess, stepping,
+                       any_abort, d_ok);
+    if (st->traj) {      // controller.py:153-156, into the instance's own p (what solve() writes there)
+        if (st->traj_len < 1) return fail(h, SMPC_EINVAL, "traj_len must be >= 1");
+        hipLaunchKernelGGL(k_policy_traj, grid((long)B * (N + 1)), blk, 0, s, B, N, stepping, st->current_step, st->traj,
+                           (long)st->traj_len, st->p);
+    }
+    hipLaunchKernelGGL(k_par_fanout1, grid((long)B * (N + 1)), blk, 0, s, B, N, stepping, st->p, c.p1, c.n_open);
+    HIPCHK(h, hipGetLastError());
+    const int coll = par->collision_first_node ? 1 : N + 1;
+    // The network kernel (run_mlp) is chosen by the rows of the statement that solves all B * N candidates at once -- B * N * N in the
+    // solve, B * N * (N + 1) in the safe-set test -- so that both schedules take the same kernel and give the same numbers
+    const long rows_solve = (long)B * N * N, rows_test = (long)B * N * (N + 1);
+    h->d_active = stepping;
+    h->mlp_rows_hint = rows_solve;
+    DISPATCH_NQ(h, (launch_solve<NQ_>(h, B, x, st->x_guess, st->u_guess, c.p1, st->x_temp, st->u_temp, st->status, st->qp_iter)));
+    h->d_active = nullptr;
+    if (rc) { h->mlp_rows_hint = 0; return rc; }
+    h->mlp_rows_hint = rows_test;
+    hipLaunchKernelGGL(k_par_safe_list, grid((long)B * (N + 1)), blk, 0, s, B, N, K, stepping, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, st->r, st->status, h->d_nn_idx, h->d_nn_cnt);
+    if ((rc = check_nodes_dev(h, B, N + 1, st->x_temp, par->tol_x, coll, par->alpha, par->tol_safe, d_ok, d_safe, true, true))) {
+        h->mlp_rows_hint = 0;
+        return rc;
+    }
+    hipLaunchKernelGGL(k_par_compact, grid(B), blk, 0, s, B, N, stepping, st->r, st->status, d_ok, d_safe, c.list, c.pos, c.n_open,
+                       h->d_nn_cnt);
+    if (K > 0) {
+        // phase 2 over the candidate capacity S: the live slots are the first *n_open * K.  The QP form follows S (or the pinned mode),
+        // never the live count, which the host does not see.
+        hipLaunchKernelGGL(k_par_fanout2, grid(S * (N + 1)), blk, 0, s, (int)S, N, nq, c.list, c.n_open, x, st->x_guess, st->u_guess,
+                           st->p, c.x0, c.xg, c.ug, c.p, c.active, c.ok);
+        HIPCHK(h, hipGetLastError());
+        h->d_active = c.active;
+        h->mlp_rows_hint = rows_solve;
+        DISPATCH_NQ(h, (launch_solve<NQ_>(h, (int)S, c.x0, c.xg, c.ug, c.p, c.xo, c.uo, c.st, c.it)));
+        h->d_active = nullptr;
+        if (rc) { h->mlp_rows_hint = 0; return rc; }
+        h->mlp_rows_hint = rows_test;
+        hipLaunchKernelGGL(k_par_safe_list, grid(S * (N + 1)), blk, 0, s, (int)S, N, K, stepping, c.list, c.n_open, st->r, c.st,
+                           h->d_nn_idx, h->d_nn_cnt);
+        const double* d_min = h->d_chk;
+        const double* d_max = d_min + nx;
+        const double* d_rlb = d_max + nx;
+        const double* d_rub = d_rlb + SMPC_MAX_ROWS;
+        const long M = S * (N + 1);
+        switch (nq) {
+        case 5: hipLaunchKernelGGL((k_par_check_state<5>), grid(M), blk, 0, s, h->d_desc, (int)S, N, c.n_open, c.xo, d_min, d_max, par->tol_x, d_rlb, d_rub, c.st, c.ok, coll); break;
+        case 6: hipLaunchKernelGGL((k_par_check_state<6>), grid(M), blk, 0, s, h->d_desc, (int)S, N, c.n_open, c.xo, d_min, d_max, par->tol_x, d_rlb, d_rub, c.st, c.ok, coll); break;
+        default: hipLaunchKernelGGL((k_par_check_state<7>), grid(M), blk, 0, s, h->d_desc, (int)S, N, c.n_open, c.xo, d_min, d_max, par->tol_x, d_rlb, d_rub, c.st, c.ok, coll); break;
+        }
+        HIPCHK(h, hipGetLastError());
+        DISPATCH_NQ(h, (run_mlp<NQ_>(h, (int)M, 3, 0, c.xo, false)));
+        if (rc) { h->mlp_rows_hint = 0; return rc; }
+        switch (nq) {
+        case 5: hipLaunchKernelGGL((k_check_nn<5>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
+        case 6: hipLaunchKernelGGL((k_check_nn<6>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
+        default: hipLaunchKernelGGL((k_check_nn<7>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    h->mlp_rows_hint = 0;
+    hipLaunchKernelGGL(k_par_select, grid(B), blk, 0, s, B, N, nq, stepping, d_ok, d_safe, c.pos, c.st, c.it, c.ok, c.safe, c.xo, c.uo,
+                       st->x_temp, st->u_temp, st->status, st->qp_iter, st->x_guess, st->fails, st->current_step, st->r, st->x_viable,
+                       d_acc, d_act, abort_out, any_abort, h->d_nn_cnt);
+    hipLaunchKernelGGL(k_provide_control, grid((long)B * (nx + nq)), blk, 0, s, B, N, nq, d_acc, st->x_temp, st->u_temp, st->x_guess,
+                       st->u_guess, u_out, stepping, d_act, u_other);
+    HIPCHK(h, hipGetLastError());
+    return SMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -762,6 +957,7 @@ void smpc_destroy(smpc_handle* h) {
     }
     for (auto& set : h->ev_sets) for (auto& e : set) if (e) (void)hipEventDestroy(e);
     if (h->d_pol) (void)hipFree(h->d_pol);
+    if (h->d_par) (void)hipFree(h->d_par);
     if (h->d_polw) (void)hipFree(h->d_polw);
     if (h->d_nn_idx) (void)hipFree(h->d_nn_idx);
     if (h->d_roll) (void)hipFree(h->d_roll);
@@ -784,7 +980,7 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers borrow the weight buffers replaced below)
     h->kids.clear();
-    h->capM = 0;
+    h->capM = h->capY = h->capDG = 0;
     for (int l = 0; l < nlayers; l++) {
         const int ni = dims[l], no = dims[l + 1];
         std::vector<float> w((size_t)ni * no), bb(no);
@@ -836,6 +1032,7 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     h->inst_B = 0;
     if (h->d_zl) { (void)hipFree(h->d_zl); h->d_zl = nullptr; }   // per-node weights belong to the old horizon
     h->ws_bytes = 0;  // workspace layout, linearisation records and IO staging are sized by N
+    h->capEV = 0;
     h->capIO = 0;
     return upload_bounds(h, nullptr, nullptr);
 }
@@ -1237,14 +1434,16 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
         !st->current_step || !st->status || !st->qp_iter)
         return fail(h, SMPC_EINVAL, "policy state incomplete");
     const int kind = par->kind;
-    if (kind < SMPC_POLICY_NAIVE || kind > SMPC_POLICY_REAL_RECEDING) return fail(h, SMPC_EINVAL, "unknown policy kind %d", kind);
+    if (kind < SMPC_POLICY_NAIVE || kind > SMPC_POLICY_PARALLEL) return fail(h, SMPC_EINVAL, "unknown policy kind %d", kind);
     const bool receding = kind == SMPC_POLICY_RECEDING || kind == SMPC_POLICY_REAL_RECEDING;
-    if (receding && !st->r) return fail(h, SMPC_EINVAL, "receding policy without r");
+    const bool parallel = kind == SMPC_POLICY_PARALLEL;
+    if ((receding || parallel) && !st->r) return fail(h, SMPC_EINVAL, "receding policy without r");
+    if (parallel && h->desc.nn_mode != SMPC_NN_ALL) return fail(h, SMPC_EINVAL, "parallel policy needs the safe-set row on every node (SMPC_NN_ALL)");
     if (kind == SMPC_POLICY_REAL_RECEDING && (!par->stage_lo || !par->stage_hi)) return fail(h, SMPC_EINVAL, "stage_lo / stage_hi missing");
     if (stepping && !u_other) return fail(h, SMPC_EINVAL, "u_other missing");
     if (kind != SMPC_POLICY_NAIVE && (!par->x_min || !par->x_max || (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk))))
         return fail(h, SMPC_EINVAL, "check bounds missing");
-    if (receding && h->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
+    if ((receding || parallel) && h->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
@@ -1258,6 +1457,7 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     int32_t* d_acc = d_safe + (size_t)B * (N + 1);
     uint8_t* d_act = (uint8_t*)(d_acc + B);
     if (kind != SMPC_POLICY_NAIVE && (rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
+    if (parallel) return policy_step_parallel(h, B, par, st, x, stepping, u_other, u_out, abort_out, any_abort, d_ok, d_safe, d_acc, d_act);
     // guessCorrection (not RealReceding, controller.py:524-565); the launch also resets *any_abort.  Every kind launches exactly
     // one of the two kernels that do so -- k_guess_correction here, k_policy_pre (RealReceding) below -- and both grids are
     // non-empty (B > 0, nq > 0), so thread 0 of block 0 always exists.

@@ -70,6 +70,64 @@ __global__ void k_provide_control(int B, int N, int nq, const int32_t* __restric
     }
 }
 
+// checkStateConstraints of one node (env_model.py:170-173, 236-243), in two parts: the state within the model bounds widened by
+// tol_x, and (node_rows_ok, starting from that verdict) the collision rows within their check bounds.  The same test as
+// k_check_nodes below, for kernels that test a device-counted subset of nodes (k_par_check_state).  (k_check_nodes keeps its own
+// copy: written through these two functions its gfx950 code changed, and the existing kernels' code is kept as it is.)
+template <int NQ>
+__device__ __forceinline__ bool node_box_ok(const double* __restrict__ xk, const double* __restrict__ x_min, const double* __restrict__ x_max,
+                                            double tol_x) {
+    constexpr int NX = 2 * NQ;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < NX; i++) ok = ok && (xk[i] >= x_min[i] - tol_x) && (xk[i] <= x_max[i] + tol_x);
+    return ok;
+}
+template <int NQ>
+__device__ __forceinline__ bool node_rows_ok(const smpc_problem_desc* __restrict__ D, const double* __restrict__ xk, bool ok,
+                                             const double* __restrict__ row_lb, const double* __restrict__ row_ub) {
+    double q[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; i++) q[i] = xk[i];
+    Mat3<double> Rw[NQ];
+    Vec3<double> pw[NQ], zw[NQ];
+    fk_world<NQ>(D->joints, q, Rw, pw, zw);
+    for (int r = 0; r < D->n_rows; r++) {
+        const smpc_row& row = D->rows[r];
+        double v;
+        switch (row.kind) {
+        case SMPC_ROW_SEG_FIXEDSEG:
+            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
+                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(row.C),
+                                  dv_const<NQ>(row.D)).v;
+            break;
+        case SMPC_ROW_SEG_SEG:
+            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
+                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw),
+                                  point_with_jacobian<NQ>(D->points[row.pc], Rw, pw, zw),
+                                  point_with_jacobian<NQ>(D->points[row.pd], Rw, pw, zw)).v;
+            break;
+        case SMPC_ROW_SEG_POINT:
+            v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
+                                       point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
+                                       dv_const<NQ>(row.C)).v;
+            break;
+        case SMPC_ROW_POINT_POINT: {
+            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(row.C);
+            v = dot(w, w).v;
+            break;
+        }
+        default: {
+            DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
+            v = (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - row.offset;
+            break;
+        }
+        }
+        ok = ok && (row_lb[r] <= v) && (v <= row_ub[r]);
+    }
+    return ok;
+}
+
 // checkStateConstraints over trajectories (env_model.py:170-173, 236-243): bounds with tolerance + collision rows within
 // the check bounds.  One thread per (instance, node); instance verdicts are AND-ed with an atomic.
 template <int NQ>

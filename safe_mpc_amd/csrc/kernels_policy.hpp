@@ -4,6 +4,7 @@
 // numpy path of safe_mpc_amd/controller.py and closed_loop.py, which the GPU tests run side by side with these kernels.
 #pragma once
 #include "device_model.hpp"
+#include "kernels_callers.hpp"
 
 namespace smpc {
 
@@ -130,6 +131,205 @@ __global__ void k_policy_post(int B, int N, int nx, int kind, int abort_flag, co
         r_all[b] = r;
         f = abort ? f : (ok ? 0 : f + 1);
     }
+    fails[b] = f;
+    current_step[b] += abort ? 0 : 1;
+    accept[b] = f == 0;
+    active[b] = !abort;
+    abort_out[b] = abort;
+    if (abort) atomicOr(any_abort, 1);
+}
+
+// ---- ParallelController (controller.py:567-644): N candidate OCPs per instance and step ------------------------------------------
+// Candidate n (n = N, N-1, .., 1) is the same OCP from the same corrected guess with the safe-set row switched on at node n alone
+// (constrain_n, :578-587: every other node of 1..N off, the terminal node included unless n = N; node 0 untouched).  The engine
+// solves candidate N for every stepping instance first (phase 1, on the instance's own x_temp / u_temp / status), then candidates
+// N-1 .. 1 of the instances whose candidate N did not reach node N (phase 2), in a dense list of slots: instance list[j] owns
+// slots j*K .. j*K + K - 1 (K = N - 1), slot j*K + i holding candidate n = N - 1 - i.  Which slots are live is known on the device
+// only (*n_open * K of them); the dead ones are skipped by the stage builder, the network pass and the QP kernels (active mask).
+
+// the flag of node k in candidate n (constrain_n, :578-587); node 0 keeps the instance's own
+__device__ __forceinline__ double par_flag(int k, int n, double own0) { return k == 0 ? own0 : (k == n ? 1.0 : -1.0); }
+
+// sing_step + check_safe_n (:589-612): the result of candidate n for an instance whose receding index is r at the start of the step.
+// checked_r = the last node of r..N that passes the safe-set test (0 if none); the verdicts are read only when the QP succeeded
+// (only those nodes are listed for the network, k_par_safe_list)
+__device__ __forceinline__ int par_result(int n, int N, int r, int status, int state_ok, const int32_t* __restrict__ safe) {
+    if (status != 0 || !state_ok) return 0;
+    int checked = 0;
+    for (int i = r > 0 ? r : 0; i <= N; i++)        // (r is in 1..N; the clamp only keeps a corrupted r from reading out of bounds)
+        if (safe[i]) checked = i;
+    const int cv = checked >= r ? checked : (n < r ? n : r);
+    return cv >= r ? cv : 0;
+}
+
+// phase 1: the parameters of candidate N of every instance -- p[0:4] as solve() left them in the instance's p (alpha, the
+// trajectory's columns), the flags of constrain_n(N).  Instances that do not step get every row off (the network's compacted list
+// must not carry them).  Also resets the count of open instances.  One thread per (instance, node).
+__global__ void k_par_fanout1(int B, int N, const uint8_t* __restrict__ stepping, const double* __restrict__ p,
+                              double* __restrict__ p1, int32_t* __restrict__ n_open) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) *n_open = 0;
+    if (t >= (long)B * (N + 1)) return;
+    const long b = t / (N + 1);
+    const int k = (int)(t - b * (N + 1));
+    const double* src = p + t * SMPC_NP;
+    double* dst = p1 + t * SMPC_NP;
+    for (int i = 0; i < 4; i++) dst[i] = src[i];
+    const bool stp = !stepping || stepping[b];
+    dst[4] = stp ? par_flag(k, N, p[b * (N + 1) * SMPC_NP + 4]) : (k == 0 ? src[4] : -1.0);
+}
+
+// The nodes whose safe-set verdict par_result can read: nodes r..N of every candidate whose QP succeeded.  Phase 1 (list == null):
+// slot = instance, S = B.  Phase 2: slot s < *n_open * K of the candidate list, instance list[s / K].  One thread per (slot, node);
+// idx holds slot * (N + 1) + node.
+__global__ void k_par_safe_list(int S, int N, int K, const uint8_t* __restrict__ stepping, const int32_t* __restrict__ list,
+                                const int32_t* __restrict__ n_open, const int64_t* __restrict__ r_all, const int32_t* __restrict__ status,
+                                int32_t* __restrict__ idx, int32_t* __restrict__ count) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)S * (N + 1)) return;
+    const long s = t / (N + 1);
+    const int k = (int)(t - s * (N + 1));
+    long b = s;
+    if (list) {
+        if (s >= (long)(*n_open) * K) return;
+        b = list[s / K];
+    } else if (stepping && !stepping[b]) {
+        return;
+    }
+    if (status[s] != 0) return;
+    if (k >= r_all[b]) idx[atomicAdd(count, 1)] = (int32_t)t;
+}
+
+// After phase 1: the instances whose candidate N did not reach node N get a place in the candidate list (list[j] = b, pos[b] = j).
+// Hands the network list's counter back at zero (the phase-1 safe-set test has read it).  One thread per instance.
+__global__ void k_par_compact(int B, int N, const uint8_t* __restrict__ stepping, const int64_t* __restrict__ r_all,
+                              const int32_t* __restrict__ status, const int32_t* __restrict__ state_ok, const int32_t* __restrict__ safe,
+                              int32_t* __restrict__ list, int32_t* __restrict__ pos, int32_t* __restrict__ n_open,
+                              int32_t* __restrict__ zero_cnt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) *zero_cnt = 0;
+    if (b >= B || (stepping && !stepping[b])) return;
+    if (par_result(N, N, (int)r_all[b], status[b], state_ok[b], safe + (size_t)b * (N + 1)) == N) return;
+    const int j = atomicAdd(n_open, 1);
+    list[j] = b;
+    pos[b] = j;
+}
+
+// phase 2: the inputs of every live slot (x0, the corrected guess, p with the flags of its candidate), its active flag and its
+// state-test verdict preset to "ok".  A dead slot only switches its one row off (node n is the only one a slot ever has on) and
+// is marked inactive.  One thread per (slot, node).
+__global__ void k_par_fanout2(int S, int N, int nq, const int32_t* __restrict__ list, const int32_t* __restrict__ n_open,
+                              const double* __restrict__ x, const double* __restrict__ xg, const double* __restrict__ ug,
+                              const double* __restrict__ p, double* __restrict__ c_x0, double* __restrict__ c_xg,
+                              double* __restrict__ c_ug, double* __restrict__ c_p, uint8_t* __restrict__ c_active,
+                              int32_t* __restrict__ c_ok) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)S * (N + 1)) return;
+    const int K = N - 1, nx = 2 * nq;
+    const long s = t / (N + 1);
+    const int k = (int)(t - s * (N + 1));
+    const int n = N - 1 - (int)(s % K);
+    if (s >= (long)(*n_open) * K) {
+        if (k == 0) c_active[s] = 0;
+        if (k == n) c_p[t * SMPC_NP + 4] = -1.0;
+        return;
+    }
+    const long b = list[s / K];
+    if (k == 0) {
+        c_active[s] = 1;
+        c_ok[s] = 1;
+        for (int i = 0; i < nx; i++) c_x0[s * nx + i] = x[b * nx + i];
+    }
+    const long src = b * (N + 1) + k;
+    for (int i = 0; i < nx; i++) c_xg[t * nx + i] = xg[src * nx + i];
+    if (k < N)
+        for (int i = 0; i < nq; i++) c_ug[(s * N + k) * nq + i] = ug[(b * N + k) * nq + i];
+    for (int i = 0; i < 4; i++) c_p[t * SMPC_NP + i] = p[src * SMPC_NP + i];
+    c_p[t * SMPC_NP + 4] = par_flag(k, n, p[b * (N + 1) * SMPC_NP + 4]);
+}
+
+// phase 2: checkStateConstraints of the live candidates whose QP succeeded (k_check_nodes' test); verdicts were
+// preset by k_par_fanout2.  One thread per (slot, node).
+template <int NQ>
+__global__ void k_par_check_state(const smpc_problem_desc* __restrict__ D, int S, int N, const int32_t* __restrict__ n_open,
+                                  const double* __restrict__ x, const double* __restrict__ x_min, const double* __restrict__ x_max,
+                                  double tol_x, const double* __restrict__ row_lb, const double* __restrict__ row_ub,
+                                  const int32_t* __restrict__ status, int32_t* __restrict__ state_ok, int coll_nodes) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)S * (N + 1)) return;
+    const long s = t / (N + 1);
+    if (s >= (long)(*n_open) * (N - 1) || status[s] != 0) return;
+    const int k = (int)(t - s * (N + 1));
+    const double* xk = x + t * 2 * NQ;
+    bool ok = node_box_ok<NQ>(xk, x_min, x_max, tol_x);
+    if (ok && k < coll_nodes) ok = node_rows_ok<NQ>(D, xk, ok, row_lb, row_ub);
+    if (!ok) atomicAnd(&state_ok[s], 0);
+}
+
+// The selection and automaton of ParallelController.step (:614-640), one thread per instance.  Candidates in the reference's order
+// N, N-1, .., 1, stopping at the first result N; node_success = the largest result, ties to the first (largest n).
+//   success (node_success > 1): x_temp / u_temp <- the chosen candidate; fails = 0; r = node_success - 1; the step counts
+//   failure, r == 1: fails + 1; x_viable = x_guess[1]; r = N; abort (guess not shifted, step not counted)
+//   failure, r > 1: fails + 1; r - 1; the step counts, provideControl rejects
+// status / qp_iter (and on failure x_temp / u_temp) are those of the last candidate the reference would have solved: the one that
+// broke the loop, else candidate 1.  Phase 1 wrote candidate N's into the instance's own buffers, so only a phase-2 pick is copied.
+// accept / active / abort_out / *any_abort as k_policy_post; hands the network list's counter back at zero.
+__global__ void k_par_select(int B, int N, int nq, const uint8_t* __restrict__ stepping, const int32_t* __restrict__ state_ok,
+                             const int32_t* __restrict__ safe, const int32_t* __restrict__ pos, const int32_t* __restrict__ c_st,
+                             const int32_t* __restrict__ c_it, const int32_t* __restrict__ c_ok, const int32_t* __restrict__ c_safe,
+                             const double* __restrict__ c_xo, const double* __restrict__ c_uo, double* __restrict__ x_temp,
+                             double* __restrict__ u_temp, int32_t* __restrict__ status, int32_t* __restrict__ qp_iter,
+                             const double* __restrict__ xg, int64_t* __restrict__ fails, int64_t* __restrict__ current_step,
+                             int64_t* __restrict__ r_all, double* __restrict__ x_viable, int32_t* __restrict__ accept,
+                             uint8_t* __restrict__ active, uint8_t* __restrict__ abort_out, int32_t* __restrict__ any_abort,
+                             int32_t* __restrict__ zero_cnt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) *zero_cnt = 0;
+    if (b >= B) return;
+    if (stepping && !stepping[b]) {
+        accept[b] = 0;
+        active[b] = 0;
+        abort_out[b] = 0;
+        return;
+    }
+    const int K = N - 1, nx = 2 * nq;
+    const int r = (int)r_all[b];
+    int best = par_result(N, N, r, status[b], state_ok[b], safe + (size_t)b * (N + 1));
+    long chosen = -1, last = -1;               // -1: candidate N (phase 1); otherwise a phase-2 slot
+    if (best != N && K > 0) {
+        const long s0 = (long)pos[b] * K;
+        for (int i = 0; i < K; i++) {
+            const long s = s0 + i;
+            const int res = par_result(N - 1 - i, N, r, c_st[s], c_ok[s], c_safe + s * (N + 1));
+            last = s;
+            if (res > best) {
+                best = res;
+                chosen = s;
+                if (res == N) break;
+            }
+        }
+    }
+    const bool success = best > 1;
+    const long pick = success ? chosen : last;
+    if (pick >= 0) {
+        for (int i = 0; i < (N + 1) * nx; i++) x_temp[(size_t)b * (N + 1) * nx + i] = c_xo[(size_t)pick * (N + 1) * nx + i];
+        for (int i = 0; i < N * nq; i++) u_temp[(size_t)b * N * nq + i] = c_uo[(size_t)pick * N * nq + i];
+    }
+    if (last >= 0) {
+        status[b] = c_st[last];
+        qp_iter[b] = c_it[last];
+    }
+    const bool abort = !success && r == 1;
+    int64_t f = fails[b];
+    if (success) {
+        f = 0;
+        r_all[b] = best - 1;
+    } else {
+        f += 1;
+        r_all[b] = abort ? N : r - 1;
+    }
+    if (abort)
+        for (int i = 0; i < nx; i++) x_viable[(size_t)b * nx + i] = xg[((size_t)b * (N + 1) + 1) * nx + i];
     fails[b] = f;
     current_step[b] += abort ? 0 : 1;
     accept[b] = f == 0;

@@ -97,6 +97,7 @@ CONTROLLER_KINDS = {
     'receding':        (NN_ALL,      'ws_t',    None,     False),
     'real_receding':   (NN_TERMINAL, None,      None,     False),
     'constraint_everywhere': (NN_ALL, None,     None,     False),
+    'parallel':        (NN_ALL,      None,      None,     False),     # both rows hard (controller.py:573-576)
     'backup':          (NN_NONE,     None,      None,     True),
 }
 
@@ -264,7 +265,10 @@ class OcpProblem:
         # the stall exit (include/smpc.h) is on where infeasible QPs are part of normal operation: RealReceding's tubes, and the backup
         # OCP (terminal zero velocity from the viable state of an aborting instance: in RealReceding's loop 27 of 29 such solves
         # are infeasible and used to run 34 iterations on average, 52 at worst, until the step length underflowed; feasible ones take 5)
-        d.qp_stall_iters = int(getattr(params, 'qp_stall_iters', 24 if controller in ('real_receding', 'backup') else 0))
+        # ... and ParallelController's low-n candidates, whose hard row at a single early node is often infeasible: without the exit each
+        # would run 40-90 iterations until its step underflows.  A QP given up on yields candidate result 0 -- which can drop a slow but
+        # feasible candidate that acados would have solved, the trade RealReceding already makes
+        d.qp_stall_iters = int(getattr(params, 'qp_stall_iters', 24 if controller in ('real_receding', 'parallel', 'backup') else 0))
         d.qp_tol_res = float(getattr(params, 'qp_tol_res', 0.0))     # 0: same as qp_tol
         self.desc = d
 
