@@ -15,7 +15,8 @@
  *   - every entry point returns 0 on success and a negative SMPC_E* code on API misuse / HIP failure.
  *     The numerical outcome of each instance is reported only through status[B], using the acados codes the
  *     reference tests against (0 ok, 1 NaN, 2 max-iter, 3 min-step, 4 QP failure; controller.py:125,158).
- *   - a handle is bound to one device and one stream, owns all device scratch, and is not thread-safe.
+ *   - a handle is bound to one device and one stream, owns all device scratch, and is not thread-safe.  Scratch grows in
+ *     eager calls: a call that would grow it while the handle's stream is being captured into a hipGraph returns SMPC_ESTATE.
  */
 #ifndef SMPC_H_
 #define SMPC_H_
@@ -281,8 +282,9 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
 /* The reference walks its instances one at a time through <Controller>.step (controller.py:274-284, 375-388, 448-498,
  * 524-565, 651-661) and the safe-abort loop of scripts/mpc.py:125-264.  These three entry points are those two pieces of code
  * for B instances at once, state resident on the device, enqueue-only on the handle's stream (no host synchronisation, so a
- * caller can capture a whole closed-loop step in a hipGraph).  All pointers inside the structs and all array arguments are
- * DEVICE pointers unless stated otherwise; flags are one byte per instance (0 / 1). */
+ * caller can capture a whole closed-loop step in a hipGraph once an eager step of the same batch size has grown the handle's
+ * buffers; a call that would grow one while the stream is being captured returns SMPC_ESTATE).  All pointers inside the structs
+ * and all array arguments are DEVICE pointers unless stated otherwise; flags are one byte per instance (0 / 1). */
 enum {
     SMPC_POLICY_NAIVE = 0,          /* NaiveController / TerminalZeroVelocity / STController                      :274-284 */
     SMPC_POLICY_STATE_CHECK = 1,    /* ControllerSafeSetEverywhere: success also needs checkStateConstraints       :651-661 */

@@ -24,63 +24,71 @@ namespace {
 thread_local char g_create_err[256] = "";
 }
 
+// A device buffer owned by a handle: grown on demand, never shrunk, freed with the handle.  reserve() (below the handle) is the
+// engine's one place that synchronises the stream, frees and allocates for growth.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;     // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    int reserve(smpc_handle* h, const char* what, size_t bytes, bool zero = false);
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 struct smpc_handle {
     smpc_problem_desc desc;
     int device = 0;
     int N = 0;
     hipStream_t stream = nullptr;
     smpc_problem_desc* d_desc = nullptr;
-    double *d_lo = nullptr, *d_hi = nullptr;  // [N+1][nx] stage bounds
-    double* d_zl = nullptr;                   // [N+1] run-time slack weights of the soft safe-set rows (cost_set), or null
-    double *d_lo_b = nullptr, *d_hi_b = nullptr;  // [B][N+1][nx] per-instance bounds (RealReceding), valid for inst_B
+    DevBuf<double> d_lo, d_hi;      // [N+1][nx] stage bounds
+    DevBuf<double> d_zl;            // [N+1] run-time slack weights of the soft safe-set rows (cost_set); empty: the formulation's
+    DevBuf<double> d_lo_b, d_hi_b;  // [B][N+1][nx] per-instance bounds (RealReceding), valid for inst_B
     int inst_B = 0;
-    size_t inst_cap = 0;   // doubles allocated in d_lo_b / d_hi_b
     // network
     int nlayers = 0;
     int act = SMPC_ACT_GELU_TANH;
     int dims[SMPC_MAX_LAYERS + 1] = {0};
     int H = 0;
+    DevBuf<char> d_weights;         // one block for the three arrays below, 256-byte aligned (empty in a worker of smpc_rollout_batch:
+                                    // it borrows its parent's)
     float* d_Wfwd[SMPC_MAX_LAYERS] = {nullptr};  // [K][N] = W^T (layer 0 padded to MLP_KPAD rows)
     float* d_Wbwd[SMPC_MAX_LAYERS] = {nullptr};  // [out][in] as given (layer 0 padded to MLP_NPAD columns)
     float* d_bias[SMPC_MAX_LAYERS] = {nullptr};
-    // per-batch scratch, grown on demand
-    int capB = 0;
-    int capEV = 0;                // instances d_ev is sized for (ensure_batch)
-    double* d_ev = nullptr;       // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
-    double* d_nn = nullptr;       // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
-                                  // on every node, [B][1 + nx] with the row on the end node only, not allocated without a network row
-    double* d_ws = nullptr;
-    size_t ws_bytes = 0;
-    int qp_mode = -2;             // smpc_set_qp_mode: SMPC_QP_AUTO / _THROUGHPUT / _LATENCY; -2 = not set (the process default, SMPC_QP_WG)
-    double* d_hrec = nullptr;     // k_qp_ipm_wg only: the stages' P-independent blocks, [B][N+1][HRecLayout::SIZE] (allocated on first use)
-    size_t hrec_doubles = 0;
-    size_t wg_lds_set[2] = {0, 0};    // dynamic-LDS limit already raised for this handle's instantiation of k_qp_ipm_wg (8 / 4 half-waves)
-    int32_t *d_order = nullptr, *d_last_it = nullptr;  // longest-first dispatch order from the previous call's iterations
-    int order_B = 0;                                   // batch size d_last_it is valid for (0 = none yet)
-    int32_t* d_ord_hist = nullptr;                     // [256] histogram of d_last_it (k_qp_ipm) | [256] bin cursors | ticket (k_order_by_iters)
-    // staging for host-pointer calls
-    int capIO = 0;
-    double *d_x0 = nullptr, *d_xg = nullptr, *d_ug = nullptr, *d_p = nullptr, *d_xo = nullptr, *d_uo = nullptr;
-    int32_t *d_st = nullptr, *d_it = nullptr;
-    // MLP activations
-    size_t capM = 0;            // rows every buffer below is sized for (the layer-by-layer GEMM chain)
-    size_t capY = 0, capDG = 0; // rows d_y / d_dg are sized for (>= capM): the fused and one-wave passes need no more than these
-    float *d_S = nullptr, *d_y = nullptr, *d_GS = nullptr, *d_dA = nullptr, *d_dB = nullptr;
-    int32_t *d_nn_idx = nullptr, *d_nn_cnt = nullptr;   // compacted list of the nodes whose safe-set row is on + its length
+    // per-batch scratch of the solve path (ensure_batch)
+    DevBuf<double> d_ev;    // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
+    DevBuf<double> d_nn;    // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
+                            // on every node, [B][1 + nx] with the row on the end node only, empty without a network row; zeroed
+                            // when allocated
+    DevBuf<double> d_ws;
+    int qp_mode = -2;       // smpc_set_qp_mode: SMPC_QP_AUTO / _THROUGHPUT / _LATENCY; -2 = not set (the process default, SMPC_QP_WG)
+    DevBuf<double> d_hrec;  // k_qp_ipm_wg only: the stages' P-independent blocks, [B][N+1][HRecLayout::SIZE] (grown for a batch that
+                            // takes the latency form only)
+    bool wg_lds_raised[2] = {false, false};   // dynamic-LDS limit raised for this handle's instantiation of k_qp_ipm_wg (8 / 4 half-waves)
+    DevBuf<int32_t> d_order, d_last_it;       // longest-first dispatch order from the previous call's iterations
+    int order_B = 0;                          // batch size d_last_it is valid for (0 = none yet)
+    DevBuf<int32_t> d_ord_hist;   // [256] histogram of d_last_it (k_qp_ipm) | [256] bin cursors | ticket (k_order_by_iters); zeroed
+                                  // when allocated
+    // MLP activations (ensure_mlp)
+    DevBuf<float> d_S, d_y, d_GS, d_dA, d_dB;
+    DevBuf<int32_t> d_nn_idx;     // compacted list of the nodes whose safe-set row is on, followed by its length d_nn_cnt
+    int32_t* d_nn_cnt = nullptr;
                                 // INVARIANT: *d_nn_cnt is zero whenever no chain of kernels is using it.  Every chain that fills it ends in
                                 // something that hands it back at zero -- on the solve path a kernel that runs anyway (k_stage_build after the
                                 // network pass, k_policy_post after the safe-set test), elsewhere a memset -- so the hot path has no memset
                                 // launch of its own, and a captured step can be replayed whatever ran in between
-    size_t nn_idx_cap = 0;
-    float* d_act[SMPC_MAX_LAYERS] = {nullptr};
-    float* d_dg[SMPC_MAX_LAYERS] = {nullptr};
-    // generic scratch for the caller entry points
-    void* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    double* d_chk = nullptr;    // check bounds of smpc_check_trajectory [x_min | x_max | row_lb | row_ub], uploaded on change
+    DevBuf<float> d_act[SMPC_MAX_LAYERS];
+    DevBuf<float> d_dg[SMPC_MAX_LAYERS];
+    DevBuf<char> d_stage;       // staging of the host-pointer calls (Stage)
+    DevBuf<double> d_chk;       // check bounds of smpc_check_trajectory [x_min | x_max | row_lb | row_ub], uploaded on change
     std::vector<double> chk_cache;
-    char* d_roll = nullptr;     // staging of smpc_rollout_batch's host-pointer path, grown on demand
-    size_t roll_bytes = 0;
+    DevBuf<char> d_roll;        // smpc_rollout_batch's scratch of the sub-batch this handle steps (RollScratch)
     // timing
     int timing = 0;
     int timed = 0;              // a solve has been timed since timing was enabled
@@ -95,24 +103,16 @@ struct smpc_handle {
     long timed_count = 0;       // solves timed since timing was enabled
     // sub-batch workers of smpc_rollout_batch: full handles on their own streams that borrow this handle's network weights
     std::vector<smpc_handle*> kids;
-    bool borrowed_mlp = false;            // (a worker: the weight buffers belong to its parent)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned long long* d_wstat = nullptr;   // [4] load-balance probe of k_qp_ipm (timing builds of a call only)
+    DevBuf<unsigned long long> d_wstat;   // [4] load-balance probe of k_qp_ipm (timing mode 1)
     const uint8_t* d_active = nullptr;   // smpc_policy_step only: instances the QP kernels skip (borrowed for the call)
-    int32_t* d_polw = nullptr;  // scratch of the policy entry points: verdicts, masks, the next state of the plant
-    size_t polw_bytes = 0;
-    int32_t* d_pol = nullptr;   // fails / accept counters of smpc_rollout_batch, [2][pol_B]
-    int pol_B = 0;
+    DevBuf<char> d_polw;        // scratch of the policy entry points (PolScratch)
     float last_ms[4] = {0, 0, 0, 0};
     long mlp_rows_whole = 0;    // > 0 (a worker of smpc_rollout_batch): network rows of the WHOLE call, which selects the network kernel
     long mlp_rows_hint = 0;     // > 0 (smpc_policy_step of the receding policies): the rows EXPECTED to be live in a compacted list -- one or
                                 // two nodes per instance, where the list's capacity is every node -- which selects the network kernel
                                 // (the count itself is only known on the device; any kernel is correct for any count)
-    // SMPC_POLICY_PARALLEL's candidate buffers (smpc_policy_step): one block, laid out by ParScratch for par_B instances of horizon
-    // par_N, zeroed when allocated
-    char* d_par = nullptr;
-    size_t par_bytes = 0;
-    int par_B = 0, par_N = 0;
+    DevBuf<char> d_par;         // SMPC_POLICY_PARALLEL's candidate buffers (ParScratch), zeroed when allocated
     char err[256] = "";
 };
 
@@ -132,16 +132,93 @@ int fail(smpc_handle* h, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(h, SMPC_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
     } while (0)
 
-template <class T> int dev_alloc(smpc_handle* h, T** p, size_t count) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (count == 0) return SMPC_OK;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
+// the handle's stream is being captured into a hipGraph (directly or by joining a capture through an event)
+bool capturing(const smpc_handle* h) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+}  // namespace
+
+// Growth is refused while the stream is being captured: synchronising it would invalidate the capture.  A failed allocation
+// leaves the buffer empty.
+template <class T> int DevBuf<T>::reserve(smpc_handle* h, const char* what, size_t bytes, bool zero) {
+    if (bytes <= cap) return SMPC_OK;
+    if (capturing(h))
+        return fail(h, SMPC_ESTATE, "the %s must grow from %zu to %zu bytes while the stream is being captured: run one eager call "
+                    "of this size first", what, cap, bytes);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    release();
+    const hipError_t e = hipMalloc((void**)&p, bytes);
     if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(h, SMPC_ENOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+        (void)hipGetLastError();
+        p = nullptr;
+        return fail(h, SMPC_ENOMEM, "hipMalloc(%zu bytes) for the %s failed: %s", bytes, what, hipGetErrorString(e));
     }
+    if (zero) HIPCHK(h, hipMemsetAsync(p, 0, bytes, h->stream));
+    cap = bytes;
     return SMPC_OK;
 }
+
+namespace {
+
+// Bump allocator with 256-byte alignment: with a null base it only sizes a layout (off), with a buffer's base it places it.
+struct Carve {
+    char* base;
+    size_t off = 0;
+    template <class T> T* take(size_t n) {
+        T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (sizeof(T) * n + 255) & ~(size_t)255;
+        return q;
+    }
+};
+
+// Device views of an entry point's array arguments.  Host pointers (on_device == 0): in() uploads an input into the handle's
+// staging buffer, out() is a staged array that finish() copies back (a null host pointer: scratch only), inout() both, and
+// finish() waits for the copies.  place() runs the caller's `views` twice, to size the staging buffer (null base) and then on
+// it.  Device pointers: every view is the caller's own pointer, the staging buffer is not touched and finish() does nothing.
+struct Stage {
+    smpc_handle* h;
+    bool dev;
+    Carve c{nullptr};
+    hipError_t e = hipSuccess;
+    struct Back {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    };
+    std::vector<Back> back;
+
+    template <class T> T* view(T* host, size_t n, bool up, bool down) {
+        if (dev || (up && !host)) return host;       // (a null input is an absent optional one)
+        auto* d = c.take<std::remove_const_t<T>>(n);
+        if (!d) return nullptr;                       // (sizing pass)
+        if (up && e == hipSuccess) e = hipMemcpyAsync(d, host, sizeof(T) * n, hipMemcpyHostToDevice, h->stream);
+        if (down && host) back.push_back({(void*)host, d, sizeof(T) * n});
+        return d;
+    }
+    template <class T> const T* in(const T* host, size_t n) { return view(host, n, true, false); }
+    template <class T> T* out(T* host, size_t n) { return view(host, n, false, true); }
+    template <class T> T* inout(T* host, size_t n) { return view(host, n, true, true); }
+
+    template <class F> int place(F&& views) {
+        views(*this);
+        if (dev) return SMPC_OK;
+        int rc;
+        if ((rc = h->d_stage.reserve(h, "staging buffer", c.off))) return rc;
+        c = Carve{h->d_stage.p};
+        views(*this);
+        if (e != hipSuccess) return fail(h, SMPC_EHIP, "staging copy failed: %s", hipGetErrorString(e));
+        return SMPC_OK;
+    }
+    int finish() {
+        if (dev) return SMPC_OK;
+        for (const Back& b : back) HIPCHK(h, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return SMPC_OK;
+    }
+};
 
 size_t ws_doubles_per_instance(const smpc_problem_desc& d, int N) {
     switch (d.nq) {
@@ -160,120 +237,40 @@ int upload_bounds(smpc_handle* h, const double* lo, const double* hi) {
             u[(size_t)k * nx + i] = hi ? hi[(size_t)k * nx + i] : (k == h->N ? h->desc.x_hi_e[i] : h->desc.x_hi[i]);
         }
     int rc;
-    if ((rc = dev_alloc(h, &h->d_lo, l.size()))) return rc;
-    if ((rc = dev_alloc(h, &h->d_hi, u.size()))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_lo, l.data(), l.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_hi, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = h->d_lo.reserve(h, "stage bounds", l.size() * sizeof(double))) ||
+        (rc = h->d_hi.reserve(h, "stage bounds", u.size() * sizeof(double))))
+        return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_lo.p, l.data(), l.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_hi.p, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    return SMPC_OK;
-}
-
-// with_ev = false: the solve path only (SMPC_POLICY_PARALLEL's candidate batch), which never reads the linearisation records d_ev --
-// 2.6 KB per node, 10 GB for the candidates of 4096 instances at N = 30 -- so they are not grown for it
-int ensure_batch(smpc_handle* h, int B, bool with_ev = true) {
-    const size_t per = ws_doubles_per_instance(h->desc, h->N);
-    const size_t need = per * (size_t)B * sizeof(double);
-    int rc;
-    if (B > h->capB || need > h->ws_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (with_ev) {
-            if ((rc = dev_alloc(h, &h->d_ev, ev_tiles((size_t)B * (h->N + 1)) * EV_TILE * EV_D))) return rc;
-            h->capEV = B;
-        }
-        if ((rc = dev_alloc(h, &h->d_ws, per * (size_t)B))) return rc;
-        {
-            const size_t nn_nodes = h->desc.nn_mode == SMPC_NN_NONE ? 0 : (h->desc.nn_mode == SMPC_NN_TERMINAL ? (size_t)B : (size_t)B * (h->N + 1));
-            if ((rc = dev_alloc(h, &h->d_nn, nn_nodes * (1 + 2 * h->desc.nq)))) return rc;
-            // (entries beyond n_dof_safe_set are never written and must read as zero)
-            if (nn_nodes) HIPCHK(h, hipMemsetAsync(h->d_nn, 0, sizeof(double) * nn_nodes * (1 + 2 * h->desc.nq), h->stream));
-        }
-        if ((rc = dev_alloc(h, &h->d_order, (size_t)B))) return rc;
-        if ((rc = dev_alloc(h, &h->d_last_it, (size_t)B))) return rc;
-        if ((rc = dev_alloc(h, &h->d_ord_hist, (size_t)520))) return rc;
-        HIPCHK(h, hipMemsetAsync(h->d_ord_hist, 0, 520 * sizeof(int32_t), h->stream));
-        h->order_B = 0;
-        h->ws_bytes = need;
-        h->capB = B;
-        h->capIO = 0;
-    }
-    if (with_ev && B > h->capEV) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = dev_alloc(h, &h->d_ev, ev_tiles((size_t)B * (h->N + 1)) * EV_TILE * EV_D))) return rc;
-        h->capEV = B;
-    }
-    return SMPC_OK;
-}
-
-int ensure_io(smpc_handle* h, int B) {
-    if (B <= h->capIO) return SMPC_OK;
-    const int nx = 2 * h->desc.nq, nu = h->desc.nq, NN = h->N;   // (smpc_set_horizon resets capIO)
-    int rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = dev_alloc(h, &h->d_x0, (size_t)B * nx))) return rc;
-    if ((rc = dev_alloc(h, &h->d_xg, (size_t)B * (NN + 1) * nx))) return rc;
-    if ((rc = dev_alloc(h, &h->d_ug, (size_t)B * NN * nu))) return rc;
-    if ((rc = dev_alloc(h, &h->d_p, (size_t)B * (NN + 1) * SMPC_NP))) return rc;
-    if ((rc = dev_alloc(h, &h->d_xo, (size_t)B * (NN + 1) * nx))) return rc;
-    if ((rc = dev_alloc(h, &h->d_uo, (size_t)B * NN * nu))) return rc;
-    if ((rc = dev_alloc(h, &h->d_st, (size_t)B))) return rc;
-    if ((rc = dev_alloc(h, &h->d_it, (size_t)B))) return rc;
-    h->capIO = B;
-    return SMPC_OK;
-}
-
-int ensure_tmp(smpc_handle* h, size_t bytes) {
-    if (bytes <= h->tmp_bytes) return SMPC_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_tmp) { (void)hipFree(h->d_tmp); h->d_tmp = nullptr; }
-    hipError_t e = hipMalloc(&h->d_tmp, bytes);
-    if (e != hipSuccess) return fail(h, SMPC_ENOMEM, "hipMalloc(%zu) failed", bytes);
-    h->tmp_bytes = bytes;
     return SMPC_OK;
 }
 
 // the network pass's buffers for M rows: level 0 the output alone (k_mlp_fused), 1 also the hidden layers' activation derivatives
 // (k_mlp_wave), 2 every buffer of the layer-by-layer GEMM chain
 int ensure_mlp(smpc_handle* h, size_t M, int level = 2) {
-    const size_t Mp = (M + 127) / 128 * 128;
-    if (Mp <= h->capM) return SMPC_OK;
+    const size_t Mp = (M + 127) / 128 * 128, row = sizeof(float) * Mp, H = h->H;
     int rc;
-    if (level < 2) {
-        if (Mp <= h->capY && (level == 0 || Mp <= h->capDG)) return SMPC_OK;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (Mp > h->capY) {
-            if ((rc = dev_alloc(h, &h->d_y, Mp))) { h->capY = h->capM = 0; return rc; }
-            h->capY = Mp;
-        }
-        if (level == 1 && Mp > h->capDG) {
-            for (int l = 0; l + 1 < h->nlayers; l++)
-                if ((rc = dev_alloc(h, &h->d_dg[l], Mp * h->H))) { h->capDG = h->capM = 0; return rc; }
-            h->capDG = Mp;
-        }
-        return SMPC_OK;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t H = h->H;
-    if ((rc = dev_alloc(h, &h->d_S, Mp * MLP_KPAD))) return rc;
-    if ((rc = dev_alloc(h, &h->d_y, Mp))) return rc;
-    if ((rc = dev_alloc(h, &h->d_GS, Mp * MLP_NPAD))) return rc;
-    if ((rc = dev_alloc(h, &h->d_dA, Mp * H))) return rc;
-    if ((rc = dev_alloc(h, &h->d_dB, Mp * H))) return rc;
-    for (int l = 0; l + 1 < h->nlayers; l++) {
-        if ((rc = dev_alloc(h, &h->d_act[l], Mp * H))) return rc;
-        if ((rc = dev_alloc(h, &h->d_dg[l], Mp * H))) return rc;
-    }
-    h->capM = h->capY = h->capDG = Mp;
+    if ((rc = h->d_y.reserve(h, "network output", row))) return rc;
+    for (int l = 0; level >= 1 && l + 1 < h->nlayers; l++)
+        if ((rc = h->d_dg[l].reserve(h, "network activation derivatives", row * H))) return rc;
+    if (level < 2) return SMPC_OK;
+    if ((rc = h->d_S.reserve(h, "network features", row * MLP_KPAD)) || (rc = h->d_GS.reserve(h, "network gradients", row * MLP_NPAD)) ||
+        (rc = h->d_dA.reserve(h, "network backward pass", row * H)) || (rc = h->d_dB.reserve(h, "network backward pass", row * H)))
+        return rc;
+    for (int l = 0; l + 1 < h->nlayers; l++)
+        if ((rc = h->d_act[l].reserve(h, "network activations", row * H))) return rc;
     return SMPC_OK;
 }
 
-// list of live network rows (mode 3 of run_mlp) and its device-side length
+// list of live network rows (mode 3 of run_mlp) and its device-side length d_nn_cnt, the buffer's last entry, zeroed when allocated
 int ensure_nn_idx(smpc_handle* h, size_t M) {
-    if (M <= h->nn_idx_cap) return SMPC_OK;
-    int rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = dev_alloc(h, &h->d_nn_idx, M + 1))) return rc;
-    h->nn_idx_cap = M;
-    h->d_nn_cnt = h->d_nn_idx + M;
+    if (sizeof(int32_t) * (M + 1) <= h->d_nn_idx.cap) return SMPC_OK;
+    const int rc = h->d_nn_idx.reserve(h, "network row list", sizeof(int32_t) * (M + 1));
+    // (the counter follows the buffer whatever the outcome: a refused growth keeps the old list and its counter, a failed one
+    //  leaves neither)
+    h->d_nn_cnt = h->d_nn_idx.cap ? h->d_nn_idx.p + h->d_nn_idx.cap / sizeof(int32_t) - 1 : nullptr;
+    if (rc) return rc;
     HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), h->stream));
     return SMPC_OK;
 }
@@ -288,7 +285,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     int rc;
     const int Mp = (M + 127) / 128 * 128, H = h->H, L = h->nlayers;
     hipStream_t s = h->stream;
-    const int32_t* idx = mode == 3 ? h->d_nn_idx : nullptr;
+    const int32_t* idx = mode == 3 ? h->d_nn_idx.p : nullptr;
     const int32_t* live = mode == 3 ? h->d_nn_cnt : nullptr;
     if (chained) *chained = false;
     // Few rows (the terminal row: M = B): the whole pass as ONE kernel, activations in LDS / registers (kernels_mlp.hpp).  The
@@ -304,10 +301,10 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
             for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(256);
             if (backward)
-                hipLaunchKernelGGL((k_mlp_fused<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y, d_ev,
+                hipLaunchKernelGGL((k_mlp_fused<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
                                    compact);
             else
-                hipLaunchKernelGGL((k_mlp_fused<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y,
+                hipLaunchKernelGGL((k_mlp_fused<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
                                    (double*)nullptr, 0);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
@@ -323,10 +320,10 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
             for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(64);
             if (backward)
-                hipLaunchKernelGGL((k_mlp_wave<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y, d_ev,
-                                   compact, h->d_dg[0], h->d_dg[1], h->d_dg[2]);
+                hipLaunchKernelGGL((k_mlp_wave<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
+                                   compact, h->d_dg[0].p, h->d_dg[1].p, h->d_dg[2].p);
             else
-                hipLaunchKernelGGL((k_mlp_wave<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y,
+                hipLaunchKernelGGL((k_mlp_wave<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
                                    (double*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
@@ -335,29 +332,29 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     }
     if ((rc = ensure_mlp(h, (size_t)M))) return rc;
     hipLaunchKernelGGL((k_nn_features<NQ>), dim3((Mp + 63) / 64), dim3(64), 0, s, h->d_desc, M, Mp, N, mode, d_x,
-                       h->d_S, idx, live);
+                       h->d_S.p, idx, live);
     // The layer-by-layer GEMMs (round 4): k_gemm_f32 as ONE-WAVE blocks -- a wavefront of it is self-contained (32 x 64 tile,
     // operands from L2, 90-130 registers, no LDS), so its blocks start on any SIMD with one free slot.  A 128 x 128 LDS-tiled kernel
     // (256-thread blocks: 200 registers per lane on all four SIMDs of one CU at once + 37 KB of LDS), since retired, was 12 % faster
     // alone on the GPU (90 vs 79 TFLOP/s) but in C4's loop its blocks waited for CUs that QP wavefronts keep refilling: 12-14 ms per
     // solve for 1.9 ms of work (profiles/r04_c4_kernel_summary_by_grid.txt).
     const dim3 blk(64), grd(Mp / 32, H / 64);
-    hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, MLP_KPAD, h->d_S, h->d_Wfwd[0], h->d_bias[0],
-                       (const float*)nullptr, h->d_act[0], h->d_dg[0], live, h->act);
+    hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, MLP_KPAD, h->d_S.p, h->d_Wfwd[0], h->d_bias[0],
+                       (const float*)nullptr, h->d_act[0].p, h->d_dg[0].p, live, h->act);
     for (int l = 1; l + 1 < L; l++)
-        hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1], h->d_Wfwd[l], h->d_bias[l],
-                           (const float*)nullptr, h->d_act[l], h->d_dg[l], live, h->act);
-    hipLaunchKernelGGL(k_nn_output, dim3((Mp + 3) / 4), dim3(256), 0, s, Mp, H, h->d_act[L - 2], h->d_dg[L - 2],
-                       h->d_Wbwd[L - 1], h->d_bias[L - 1], h->d_y, h->d_dA, live);
+        hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1].p, h->d_Wfwd[l], h->d_bias[l],
+                           (const float*)nullptr, h->d_act[l].p, h->d_dg[l].p, live, h->act);
+    hipLaunchKernelGGL(k_nn_output, dim3((Mp + 3) / 4), dim3(256), 0, s, Mp, H, h->d_act[L - 2].p, h->d_dg[L - 2].p,
+                       h->d_Wbwd[L - 1], h->d_bias[L - 1], h->d_y.p, h->d_dA.p, live);
     if (backward) {
-        float *cur = h->d_dA, *nxt = h->d_dB;
+        float *cur = h->d_dA.p, *nxt = h->d_dB.p;
         for (int l = L - 2; l >= 1; l--) {
             hipLaunchKernelGGL((k_gemm_f32<EPI_MUL>), grd, blk, 0, s, Mp, H, H, cur, h->d_Wbwd[l], (const float*)nullptr,
-                               h->d_dg[l - 1], nxt, (float*)nullptr, live, h->act);
+                               h->d_dg[l - 1].p, nxt, (float*)nullptr, live, h->act);
             float* t = cur; cur = nxt; nxt = t;
         }
         hipLaunchKernelGGL((k_gemm_f32<EPI_PLAIN>), dim3(Mp / 32, MLP_NPAD / 64), blk, 0, s, Mp, MLP_NPAD, H, cur,
-                           h->d_Wbwd[0], (const float*)nullptr, (const float*)nullptr, h->d_GS, (float*)nullptr, live, h->act);
+                           h->d_Wbwd[0], (const float*)nullptr, (const float*)nullptr, h->d_GS.p, (float*)nullptr, live, h->act);
     }
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
@@ -377,13 +374,13 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
     int rc;
     if (mode == 3) {
         if ((rc = ensure_nn_idx(h, (size_t)M))) return rc;
-        hipLaunchKernelGGL(k_nn_compact, dim3((M + 63) / 64), dim3(64), 0, s, M, N, d_p, h->d_nn_idx, h->d_nn_cnt);
+        hipLaunchKernelGGL(k_nn_compact, dim3((M + 63) / 64), dim3(64), 0, s, M, N, d_p, h->d_nn_idx.p, h->d_nn_cnt);
     }
     bool chained = false;
     if ((rc = run_mlp<NQ>(h, M, mode, N, d_xg, true, d_p, d_out, &chained, compact))) return rc;
     if (!chained)
         hipLaunchKernelGGL((k_nn_chain<NQ>), dim3((M + 63) / 64), dim3(64), 0, s, h->d_desc, M, N, mode, d_xg, d_p,
-                           h->d_y, h->d_GS, d_out, mode == 3 ? h->d_nn_idx : (const int32_t*)nullptr,
+                           h->d_y.p, h->d_GS.p, d_out, mode == 3 ? h->d_nn_idx.p : (const int32_t*)nullptr,
                            mode == 3 ? h->d_nn_cnt : (const int32_t*)nullptr, compact);
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
@@ -431,8 +428,19 @@ struct StageBounds {
     long stride;
 };
 StageBounds stage_bounds(const smpc_handle* h, int B) {
-    if (h->inst_B == B) return {h->d_lo_b, h->d_hi_b, (long)(h->N + 1) * 2 * h->desc.nq};
-    return {h->d_lo, h->d_hi, 0L};
+    if (h->inst_B == B) return {h->d_lo_b.p, h->d_hi_b.p, (long)(h->N + 1) * 2 * h->desc.nq};
+    return {h->d_lo.p, h->d_hi.p, 0L};
+}
+
+// RealReceding's per-instance bounds for B instances, zeroed when grown if asked.  A failure that freed or replaced either array
+// leaves no per-instance bounds (inst_B = 0); a refused growth keeps the old ones.
+int ensure_instance_bounds(smpc_handle* h, int B, bool zero) {
+    const size_t bytes = sizeof(double) * B * (h->N + 1) * 2 * h->desc.nq;
+    int rc;
+    if ((rc = h->d_lo_b.reserve(h, "per-instance bounds", bytes, zero)) || (rc = h->d_hi_b.reserve(h, "per-instance bounds", bytes, zero))) {
+        if (!h->d_lo_b.p || h->d_lo_b.cap != h->d_hi_b.cap) h->inst_B = 0;
+    }
+    return rc;
 }
 
 // everything of a solve before the interior point: the network pass, then the stage records of the QP workspace by the
@@ -440,16 +448,16 @@ StageBounds stage_bounds(const smpc_handle* h, int B) {
 template <int NQ>
 int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p, bool timed) {
     int rc;
-    if ((rc = launch_nn<NQ>(h, B, xg, p, h->d_nn, h->desc.nn_mode == SMPC_NN_TERMINAL ? 2 : 1))) return rc;
+    if ((rc = launch_nn<NQ>(h, B, xg, p, h->d_nn.p, h->desc.nn_mode == SMPC_NN_TERMINAL ? 2 : 1))) return rc;
     if (timed) HIPCHK(h, hipEventRecord(h->ev_t[1], h->stream));
     const StageBounds bd = stage_bounds(h, B);
     const long nodes = (long)B * (h->N + 1);
     const dim3 grd((unsigned)((nodes + 64 / SB_G - 1) / (64 / SB_G))), blk(64);
-    const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn : nullptr;
+    const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn.p : nullptr;
     int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
     with_rows(h, [&](auto MR) {
-        hipLaunchKernelGGL((k_stage_build<NQ, MR>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi, h->d_zl, nn,
-                           h->d_ws, bd.stride, h->d_active, zero_cnt);
+        hipLaunchKernelGGL((k_stage_build<NQ, MR>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi, h->d_zl.p, nn,
+                           h->d_ws.p, bd.stride, h->d_active, zero_cnt);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -463,12 +471,12 @@ int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* 
 template <int NQ>
 int launch_stage_records_per_node(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p) {
     int rc;
-    if ((rc = launch_eval<NQ>(h, B, xg, ug, p, h->d_ev))) return rc;
+    if ((rc = launch_eval<NQ>(h, B, xg, ug, p, h->d_ev.p))) return rc;
     const StageBounds bd = stage_bounds(h, B);
     const int tiles = (int)ev_tiles((size_t)B * (h->N + 1));
     with_rows(h, [&](auto MR) {
         hipLaunchKernelGGL((k_qp_setup<NQ, MR>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
-                           bd.hi, h->d_zl, h->d_ev, h->d_ws, bd.stride, h->d_active);
+                           bd.hi, h->d_zl.p, h->d_ev.p, h->d_ws.p, bd.stride, h->d_active);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -514,29 +522,40 @@ template <int NQ> int qp_wg_choice(const smpc_handle* h, int B) {
     return fits(4) ? 4 : 0;
 }
 
+// (the records and the LDS limit were set up by ensure_batch)
 template <int NQ, int NHW>
 int launch_qp_wg(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, double* xo, double* uo, int32_t* st,
                  int32_t* it) {
-    const size_t need = (size_t)B * (h->N + 1) * HRecLayout<NQ>::SIZE;
-    if (need > h->hrec_doubles) {
-        int rc;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = dev_alloc(h, &h->d_hrec, need))) return rc;
-        h->hrec_doubles = need;
-    }
+    if (h->d_hrec.cap < sizeof(double) * B * (h->N + 1) * HRecLayout<NQ>::SIZE)
+        return fail(h, SMPC_ESTATE, "latency-form records not grown for %d instances", B);
     const size_t lds = (size_t)WgLds<NQ>(h->N, h->desc.n_rows, NHW).total * sizeof(double);
     return with_rows(h, [&](auto MR) {
-        if (!h->wg_lds_set[NHW == 8 ? 0 : 1]) {
-            // (once per handle = per device, nq and row count: the kernel may use a whole CU's LDS -- always the same value, so a
-            //  handle with a short horizon never lowers the limit under one with a long horizon)
-            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qp_ipm_wg<NQ, MR, NHW>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP_WG_LDS_LIMIT));
-            h->wg_lds_set[NHW == 8 ? 0 : 1] = QP_WG_LDS_LIMIT;
-        }
-        hipLaunchKernelGGL((k_qp_ipm_wg<NQ, MR, NHW>), dim3(B), dim3(32 * NHW), lds, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws,
-                           h->d_hrec, xo, uo, st, it, h->d_last_it, h->d_active, h->d_ord_hist);
+        hipLaunchKernelGGL((k_qp_ipm_wg<NQ, MR, NHW>), dim3(B), dim3(32 * NHW), lds, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws.p,
+                           h->d_hrec.p, xo, uo, st, it, h->d_last_it.p, h->d_active, h->d_ord_hist.p);
         return SMPC_OK;
     });
+}
+
+// raises k_qp_ipm_wg's dynamic-LDS limit: once per handle = per device, nq and row count, and half-wave count.  The kernel may use a
+// whole CU's LDS -- always the same value, so a handle with a short horizon never lowers the limit under one with a long horizon.
+template <int NQ, int NHW> int raise_qp_wg_lds_limit(smpc_handle* h) {
+    if (h->wg_lds_raised[NHW == 8 ? 0 : 1]) return SMPC_OK;
+    const int rc = with_rows(h, [&](auto MR) {
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qp_ipm_wg<NQ, MR, NHW>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)QP_WG_LDS_LIMIT));
+        return SMPC_OK;
+    });
+    h->wg_lds_raised[NHW == 8 ? 0 : 1] = rc == SMPC_OK;
+    return rc;
+}
+
+// the latency form's records and LDS limit, for a launch of B instances that takes it (ensure_batch)
+template <int NQ> int ensure_qp_wg(smpc_handle* h, int B) {
+    const int nhw = qp_wg_choice<NQ>(h, B);
+    if (nhw == 0) return SMPC_OK;
+    int rc;
+    if ((rc = h->d_hrec.reserve(h, "latency-form records", sizeof(double) * B * (h->N + 1) * HRecLayout<NQ>::SIZE))) return rc;
+    return nhw == 8 ? raise_qp_wg_lds_limit<NQ, 8>(h) : raise_qp_wg_lds_limit<NQ, 4>(h);
 }
 
 template <int NQ>
@@ -546,9 +565,7 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
     h->timing_now = false;
     if (h->timing) {
         // a solve that is being captured into a hipGraph records nothing: every replay would re-record the one slot it captured
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-        h->timing_now = cs == hipStreamCaptureStatusNone;
+        h->timing_now = !capturing(h);
     }
     const bool timed = h->timing_now;
     if (timed) {
@@ -563,19 +580,18 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
     const bool wg = wg_nhw > 0;
     const int32_t* order = nullptr;
     if (h->order_B == B && B > 1 && !wg) {
-        hipLaunchKernelGGL(k_order_by_iters, dim3((B + ORD_PER_BLOCK - 1) / ORD_PER_BLOCK), dim3(64), 0, h->stream, B, h->d_last_it,
-                           h->d_order, h->d_ord_hist, h->d_ord_hist + 256, h->d_ord_hist + 512);
-        order = h->d_order;
+        hipLaunchKernelGGL(k_order_by_iters, dim3((B + ORD_PER_BLOCK - 1) / ORD_PER_BLOCK), dim3(64), 0, h->stream, B, h->d_last_it.p,
+                           h->d_order.p, h->d_ord_hist.p, h->d_ord_hist.p + 256, h->d_ord_hist.p + 512);
+        order = h->d_order.p;
     } else {
         // (no order this time: the histogram k_qp_ipm adds to must hold this solve alone when the next one sorts by it)
-        HIPCHK(h, hipMemsetAsync(h->d_ord_hist, 0, 520 * sizeof(int32_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_ord_hist.p, 0, 520 * sizeof(int32_t), h->stream));
     }
     unsigned long long* wstat = nullptr;
     if (timed && h->timing == 1) {      // (timing mode 2: events only, no in-kernel load-balance probe)
-        if (!h->d_wstat) HIPCHK(h, hipMalloc((void**)&h->d_wstat, 4 * sizeof(unsigned long long)));
-        const unsigned long long init[4] = {0ull, ~0ull, 0ull, 0ull};
-        HIPCHK(h, hipMemcpyAsync(h->d_wstat, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-        wstat = h->d_wstat;
+        const unsigned long long init[4] = {0ull, ~0ull, 0ull, 0ull};     // (d_wstat: smpc_enable_timing)
+        HIPCHK(h, hipMemcpyAsync(h->d_wstat.p, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+        wstat = h->d_wstat.p;
     }
     // non-temporal workspace accesses once this launch's workspace is well beyond the Infinity Cache (kernel_qp.hpp, k_qp_ipm)
     if (wg) {
@@ -584,8 +600,8 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
         const bool nt = qp_nt_mode() < 0 ? ws_doubles_per_instance(h->desc, h->N) * sizeof(double) * (size_t)B >= qp_nt_threshold : qp_nt_mode() > 0;
         with_rows(h, [&](auto MR) {
             const auto launch = [&](auto NT) {
-                hipLaunchKernelGGL((k_qp_ipm<NQ, MR, NT>), dim3((B + 1) / 2), dim3(64), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws,
-                                   xo, uo, st, it, order, h->d_last_it, wstat, h->d_active, h->d_ord_hist);
+                hipLaunchKernelGGL((k_qp_ipm<NQ, MR, NT>), dim3((B + 1) / 2), dim3(64), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws.p,
+                                   xo, uo, st, it, order, h->d_last_it.p, wstat, h->d_active, h->d_ord_hist.p);
                 return SMPC_OK;
             };
             if constexpr (MR < 0) return launch(std::false_type{});      // (the runtime-row-count instantiation is not built twice)
@@ -624,10 +640,11 @@ int upload_check_bounds(smpc_handle* h, const double* x_min, const double* x_max
         memcpy(cur.data() + 2 * nx, row_lb_chk, sizeof(double) * nr);
         memcpy(cur.data() + 2 * nx + SMPC_MAX_ROWS, row_ub_chk, sizeof(double) * nr);
     }
-    if (!h->d_chk) HIPCHK(h, hipMalloc((void**)&h->d_chk, cur.size() * sizeof(double)));
+    int rc;
+    if ((rc = h->d_chk.reserve(h, "check bounds", cur.size() * sizeof(double)))) return rc;
     if (cur != h->chk_cache) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(h->d_chk, cur.data(), cur.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->d_chk.p, cur.data(), cur.size() * sizeof(double), hipMemcpyHostToDevice));
         h->chk_cache.swap(cur);
     }
     return SMPC_OK;
@@ -640,7 +657,7 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
     const int nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     const size_t M = (size_t)B * n_nodes;
-    double* d_min = h->d_chk;
+    double* d_min = h->d_chk.p;
     double* d_max = d_min + nx;
     double* d_rlb = d_max + nx;
     double* d_rub = d_rlb + SMPC_MAX_ROWS;
@@ -663,26 +680,64 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
         DISPATCH_NQ(h, (run_mlp<NQ_>(h, (int)M, nn_listed ? 3 : 0, 0, d_x, false)));
         if (rc) return rc;
         const dim3 g2((unsigned)((M + 63) / 64)), b2(64);
-        const int32_t* li = nn_listed ? h->d_nn_idx : nullptr;
+        const int32_t* li = nn_listed ? h->d_nn_idx.p : nullptr;
         const int32_t* lc = nn_listed ? h->d_nn_cnt : nullptr;
         switch (nq) {
-        case 5: hipLaunchKernelGGL((k_check_nn<5>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y, d_nn, li, lc); break;
-        case 6: hipLaunchKernelGGL((k_check_nn<6>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y, d_nn, li, lc); break;
-        default: hipLaunchKernelGGL((k_check_nn<7>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y, d_nn, li, lc); break;
+        case 5: hipLaunchKernelGGL((k_check_nn<5>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y.p, d_nn, li, lc); break;
+        case 6: hipLaunchKernelGGL((k_check_nn<6>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y.p, d_nn, li, lc); break;
+        default: hipLaunchKernelGGL((k_check_nn<7>), g2, b2, 0, s, h->d_desc, (int)M, d_x, alpha, tol_safe, h->d_y.p, d_nn, li, lc); break;
         }
         HIPCHK(h, hipGetLastError());
     }
     return SMPC_OK;
 }
 
-// scratch of the policy entry points (grown on demand: the first, eager steps of a loop; never inside a graph capture)
-int ensure_polw(smpc_handle* h, size_t bytes) {
-    if (bytes <= h->polw_bytes) return SMPC_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_polw) { (void)hipFree(h->d_polw); h->d_polw = nullptr; h->polw_bytes = 0; }
-    if (hipMalloc((void**)&h->d_polw, bytes) != hipSuccess) return fail(h, SMPC_ENOMEM, "hipMalloc(%zu) failed", bytes);
-    h->polw_bytes = bytes;
+// scratch of the policy entry points: smpc_policy_step's verdicts and masks, then smpc_loop_post's next state of the plant and its
+// verdicts (one layout for both: the two are enqueued one after the other on the handle's stream)
+struct PolScratch {
+    int32_t *ok, *safe, *acc;   // state_ok [B] | safe [B][N+1] | accept [B]
+    uint8_t* act;               // [B]
+    double* xn;                 // [B][nx]
+    int32_t* okn;               // [B]
+    size_t bytes;
+};
+PolScratch pol_layout(char* base, int B, int N, int nx) {
+    Carve m{base};
+    PolScratch w{};
+    w.ok = m.take<int32_t>(B);
+    w.safe = m.take<int32_t>((size_t)B * (N + 1));
+    w.acc = m.take<int32_t>(B);
+    w.act = m.take<uint8_t>(B);
+    w.xn = m.take<double>((size_t)B * nx);
+    w.okn = m.take<int32_t>(B);
+    w.bytes = m.off;
+    return w;
+}
+int policy_scratch(smpc_handle* h, int B, PolScratch* w) {
+    const int nx = 2 * h->desc.nq;
+    int rc;
+    if ((rc = h->d_polw.reserve(h, "policy scratch", pol_layout(nullptr, B, h->N, nx).bytes))) return rc;
+    *w = pol_layout(h->d_polw.p, B, h->N, nx);
     return SMPC_OK;
+}
+
+// scratch of smpc_rollout_batch for the n instances one handle steps: the policy's fails / accept counters (kept in the handle: the
+// device path does not synchronise) and the solve's outputs
+struct RollScratch {
+    int32_t *fails, *accept, *it;
+    double *xo, *uo;
+    size_t bytes;
+};
+RollScratch roll_layout(char* base, int n, int N, int nq) {
+    Carve m{base};
+    RollScratch r{};
+    r.fails = m.take<int32_t>(n);
+    r.accept = m.take<int32_t>(n);
+    r.xo = m.take<double>((size_t)n * (N + 1) * 2 * nq);
+    r.uo = m.take<double>((size_t)n * N * nq);
+    r.it = m.take<int32_t>(n);
+    r.bytes = m.off;
+    return r;
 }
 
 // Worker handles of smpc_rollout_batch: same problem, own stream and workspaces, the parent's network weights (borrowed).
@@ -691,7 +746,6 @@ int rollout_workers(smpc_handle* h, int n) {
         smpc_handle* k = nullptr;
         int rc = smpc_create(&h->desc, h->device, &k);
         if (rc) return fail(h, rc, "rollout worker: %s", smpc_last_error(nullptr));
-        k->borrowed_mlp = true;
         h->kids.push_back(k);
     }
     for (int i = 0; i < n; i++) {
@@ -706,15 +760,14 @@ int rollout_workers(smpc_handle* h, int n) {
         for (int l = 0; l < SMPC_MAX_LAYERS; l++) { k->d_Wfwd[l] = h->d_Wfwd[l]; k->d_Wbwd[l] = h->d_Wbwd[l]; k->d_bias[l] = h->d_bias[l]; }
         // stage bounds and slack weights follow the parent (small; stream-ordered on the worker's stream)
         const size_t nb = (size_t)(h->N + 1) * 2 * h->desc.nq;
-        HIPCHK(h, hipMemcpyAsync(k->d_lo, h->d_lo, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
-        HIPCHK(h, hipMemcpyAsync(k->d_hi, h->d_hi, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
-        if (h->d_zl) {
-            if (!k->d_zl && (rc = dev_alloc(h, &k->d_zl, (size_t)h->N + 1))) return rc;
-            HIPCHK(h, hipMemcpyAsync(k->d_zl, h->d_zl, sizeof(double) * (h->N + 1), hipMemcpyDeviceToDevice, k->stream));
-        } else if (k->d_zl) {
+        HIPCHK(h, hipMemcpyAsync(k->d_lo.p, h->d_lo.p, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
+        HIPCHK(h, hipMemcpyAsync(k->d_hi.p, h->d_hi.p, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
+        if (h->d_zl.p) {
+            if ((rc = k->d_zl.reserve(k, "slack weights", sizeof(double) * (h->N + 1)))) return fail(h, rc, "rollout worker: %s", k->err);
+            HIPCHK(h, hipMemcpyAsync(k->d_zl.p, h->d_zl.p, sizeof(double) * (h->N + 1), hipMemcpyDeviceToDevice, k->stream));
+        } else if (k->d_zl.p) {
             HIPCHK(h, hipStreamSynchronize(k->stream));
-            (void)hipFree(k->d_zl);
-            k->d_zl = nullptr;
+            k->d_zl.release();
         }
     }
     return SMPC_OK;
@@ -730,66 +783,44 @@ struct ParScratch {
 };
 ParScratch par_layout(char* base, int B, int N, int nq) {
     const size_t S = (size_t)B * (N - 1), nx = 2 * (size_t)nq;
+    Carve m{base};
     ParScratch c{};
-    size_t off = 0;
-    const auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-    c.p1 = (double*)take(sizeof(double) * B * (N + 1) * SMPC_NP);
-    c.x0 = (double*)take(sizeof(double) * S * nx);
-    c.xg = (double*)take(sizeof(double) * S * (N + 1) * nx);
-    c.ug = (double*)take(sizeof(double) * S * N * nq);
-    c.p = (double*)take(sizeof(double) * S * (N + 1) * SMPC_NP);
-    c.xo = (double*)take(sizeof(double) * S * (N + 1) * nx);
-    c.uo = (double*)take(sizeof(double) * S * N * nq);
-    c.st = (int32_t*)take(sizeof(int32_t) * S);
-    c.it = (int32_t*)take(sizeof(int32_t) * S);
-    c.ok = (int32_t*)take(sizeof(int32_t) * S);
-    c.safe = (int32_t*)take(sizeof(int32_t) * S * (N + 1));
-    c.list = (int32_t*)take(sizeof(int32_t) * B);
-    c.pos = (int32_t*)take(sizeof(int32_t) * B);
-    c.n_open = (int32_t*)take(sizeof(int32_t));
-    c.active = (uint8_t*)take(S);
-    c.bytes = off;
+    c.p1 = m.take<double>((size_t)B * (N + 1) * SMPC_NP);
+    c.x0 = m.take<double>(S * nx);
+    c.xg = m.take<double>(S * (N + 1) * nx);
+    c.ug = m.take<double>(S * N * nq);
+    c.p = m.take<double>(S * (N + 1) * SMPC_NP);
+    c.xo = m.take<double>(S * (N + 1) * nx);
+    c.uo = m.take<double>(S * N * nq);
+    c.st = m.take<int32_t>(S);
+    c.it = m.take<int32_t>(S);
+    c.ok = m.take<int32_t>(S);
+    c.safe = m.take<int32_t>(S * (N + 1));
+    c.list = m.take<int32_t>(B);
+    c.pos = m.take<int32_t>(B);
+    c.n_open = m.take<int32_t>(1);
+    c.active = m.take<uint8_t>(S);
+    c.bytes = m.off;
     return c;
 }
 
+int ensure_batch(smpc_handle* h, int B, bool with_ev = true);
+
 // everything a parallel step needs beyond what every policy step has: the candidate block, the solve path's scratch (QP workspace,
-// network-row records) for max(B, S) instances, the network lists for S * (N + 1) nodes.  Grown on the first step of a batch size,
-// never inside a graph capture (as every ensure_*).
+// network-row records) for max(B, S) instances, the network lists for S * (N + 1) nodes.  Grown on the first step of a batch size.
 int ensure_parallel(smpc_handle* h, int B) {
     const int N = h->N;
     const long S = (long)B * (N - 1);
     const ParScratch need = par_layout(nullptr, B, N, h->desc.nq);
     const size_t ws = ws_doubles_per_instance(h->desc, N) * sizeof(double) * (size_t)(S > B ? S : B);
-    int rc = SMPC_OK;
-    if (S > INT32_MAX / (N + 1)) rc = SMPC_EINVAL;
-    if (!rc && (h->par_N != N || h->par_B < B || h->par_bytes < need.bytes)) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->d_par) { (void)hipFree(h->d_par); h->d_par = nullptr; }
-        h->par_bytes = 0;
-        h->par_B = h->par_N = 0;
-        if (hipMalloc((void**)&h->d_par, need.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            h->d_par = nullptr;
-            rc = SMPC_ENOMEM;
-        } else {
-            HIPCHK(h, hipMemsetAsync(h->d_par, 0, need.bytes, h->stream));
-            h->par_bytes = need.bytes;
-            h->par_B = B;
-            h->par_N = N;
-        }
-    }
+    int rc = S > INT32_MAX / (N + 1) ? SMPC_EINVAL : SMPC_OK;
+    if (!rc) rc = h->d_par.reserve(h, "parallel candidate buffers", need.bytes, true);
     if (!rc && S > 0) rc = ensure_batch(h, (int)(S > B ? S : B), false);
     if (!rc && S > 0) rc = ensure_nn_idx(h, (size_t)S * (N + 1));
-    if (rc) {
-        // (a failed allocation may have freed the old buffers: make the next call allocate afresh)
-        h->capB = 0;
-        h->ws_bytes = 0;
-        h->capEV = 0;
-        return fail(h, rc == SMPC_EINVAL ? SMPC_EINVAL : SMPC_ENOMEM,
-                    "parallel policy: candidate scratch for B * (N - 1) = %ld instances could not be allocated: %.2f GB of QP workspace "
-                    "+ %.2f GB of candidate buffers (B = %d, N = %d)", S, ws / 1e9, need.bytes / 1e9, B, N);
-    }
-    return SMPC_OK;
+    if (rc == SMPC_EINVAL || rc == SMPC_ENOMEM)
+        return fail(h, rc, "parallel policy: candidate scratch for B * (N - 1) = %ld instances could not be allocated: %.2f GB of QP "
+                    "workspace + %.2f GB of candidate buffers (B = %d, N = %d)", S, ws / 1e9, need.bytes / 1e9, B, N);
+    return rc;
 }
 
 // ParallelController.step (controller.py:567-644) for the stepping instances, enqueue-only.  Phase 1: candidate N of every stepping
@@ -805,7 +836,7 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
     int rc;
     if ((rc = ensure_parallel(h, B))) return rc;
     if ((rc = ensure_nn_idx(h, (size_t)B * (N + 1)))) return rc;
-    const ParScratch c = par_layout(h->d_par, B, N, nq);
+    const ParScratch c = par_layout(h->d_par.p, B, N, nq);
     const dim3 blk(64);
     const auto grid = [](long n) { return dim3((unsigned)((n + 63) / 64)); };
     // guessCorrection; also resets *any_abort and presets the state-test verdicts of phase 1
@@ -829,7 +860,7 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
     if (rc) { h->mlp_rows_hint = 0; return rc; }
     h->mlp_rows_hint = rows_test;
     hipLaunchKernelGGL(k_par_safe_list, grid((long)B * (N + 1)), blk, 0, s, B, N, K, stepping, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, st->r, st->status, h->d_nn_idx, h->d_nn_cnt);
+                       (const int32_t*)nullptr, st->r, st->status, h->d_nn_idx.p, h->d_nn_cnt);
     if ((rc = check_nodes_dev(h, B, N + 1, st->x_temp, par->tol_x, coll, par->alpha, par->tol_safe, d_ok, d_safe, true, true))) {
         h->mlp_rows_hint = 0;
         return rc;
@@ -849,8 +880,8 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
         if (rc) { h->mlp_rows_hint = 0; return rc; }
         h->mlp_rows_hint = rows_test;
         hipLaunchKernelGGL(k_par_safe_list, grid(S * (N + 1)), blk, 0, s, (int)S, N, K, stepping, c.list, c.n_open, st->r, c.st,
-                           h->d_nn_idx, h->d_nn_cnt);
-        const double* d_min = h->d_chk;
+                           h->d_nn_idx.p, h->d_nn_cnt);
+        const double* d_min = h->d_chk.p;
         const double* d_max = d_min + nx;
         const double* d_rlb = d_max + nx;
         const double* d_rub = d_rlb + SMPC_MAX_ROWS;
@@ -864,9 +895,9 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
         DISPATCH_NQ(h, (run_mlp<NQ_>(h, (int)M, 3, 0, c.xo, false)));
         if (rc) { h->mlp_rows_hint = 0; return rc; }
         switch (nq) {
-        case 5: hipLaunchKernelGGL((k_check_nn<5>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
-        case 6: hipLaunchKernelGGL((k_check_nn<6>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
-        default: hipLaunchKernelGGL((k_check_nn<7>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y, c.safe, h->d_nn_idx, h->d_nn_cnt); break;
+        case 5: hipLaunchKernelGGL((k_check_nn<5>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y.p, c.safe, h->d_nn_idx.p, h->d_nn_cnt); break;
+        case 6: hipLaunchKernelGGL((k_check_nn<6>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y.p, c.safe, h->d_nn_idx.p, h->d_nn_cnt); break;
+        default: hipLaunchKernelGGL((k_check_nn<7>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y.p, c.safe, h->d_nn_idx.p, h->d_nn_cnt); break;
         }
         HIPCHK(h, hipGetLastError());
     }
@@ -878,6 +909,28 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
                        st->u_guess, u_out, stepping, d_act, u_other);
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
+}
+
+// The solve path's per-batch buffers for B instances.  with_ev = false: the solve path only (SMPC_POLICY_PARALLEL's candidate batch),
+// which never reads the linearisation records d_ev -- 2.6 KB per node, 10 GB for the candidates of 4096 instances at N = 30 -- so
+// they are not grown for it.  (Defined after the solve path on purpose: a kernel's place in the code object follows the first
+// mention of it in this file, and ensure_qp_wg must not be the first to name k_qp_ipm_wg.)
+int ensure_batch(smpc_handle* h, int B, bool with_ev) {
+    const size_t nodes = (size_t)B * (h->N + 1);
+    const size_t nn_nodes = h->desc.nn_mode == SMPC_NN_NONE ? 0 : (h->desc.nn_mode == SMPC_NN_TERMINAL ? (size_t)B : nodes);
+    int rc;
+    if ((with_ev && (rc = h->d_ev.reserve(h, "linearisation records", sizeof(double) * ev_tiles(nodes) * EV_TILE * EV_D))) ||
+        (rc = h->d_ws.reserve(h, "QP workspace", sizeof(double) * ws_doubles_per_instance(h->desc, h->N) * B)) ||
+        // (entries beyond n_dof_safe_set are never written and must read as zero)
+        (rc = h->d_nn.reserve(h, "network rows", sizeof(double) * nn_nodes * (1 + 2 * h->desc.nq), true)) ||
+        (rc = h->d_order.reserve(h, "dispatch order", sizeof(int32_t) * B)))
+        return rc;
+    const size_t had = h->d_last_it.cap;
+    rc = h->d_last_it.reserve(h, "iteration counts", sizeof(int32_t) * B);
+    if (h->d_last_it.cap != had) h->order_B = 0;     // (a new or freed d_last_it holds no iterations; a refused growth keeps them)
+    if (rc || (rc = h->d_ord_hist.reserve(h, "iteration histogram", sizeof(int32_t) * 520, true))) return rc;
+    DISPATCH_NQ(h, ensure_qp_wg<NQ_>(h, B));
+    return rc;
 }
 
 }  // namespace
@@ -941,30 +994,13 @@ void smpc_destroy(smpc_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     for (smpc_handle* k : h->kids) smpc_destroy(k);
-    h->kids.clear();
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    void* ptrs[] = {h->d_desc, h->d_zl, h->d_lo, h->d_hi, h->d_lo_b, h->d_hi_b, h->d_ev, h->d_nn, h->d_ws, h->d_hrec, h->d_order, h->d_last_it, h->d_ord_hist, h->d_x0, h->d_xg, h->d_ug, h->d_p, h->d_xo, h->d_uo,
-                    h->d_st, h->d_it, h->d_S, h->d_y, h->d_GS, h->d_dA, h->d_dB, h->d_tmp};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int l = 0; l < SMPC_MAX_LAYERS; l++) {
-        if (h->d_Wfwd[l] && !h->borrowed_mlp) (void)hipFree(h->d_Wfwd[l]);
-        if (h->d_Wbwd[l] && !h->borrowed_mlp) (void)hipFree(h->d_Wbwd[l]);
-        if (h->d_bias[l] && !h->borrowed_mlp) (void)hipFree(h->d_bias[l]);
-        if (h->d_act[l]) (void)hipFree(h->d_act[l]);
-        if (h->d_dg[l]) (void)hipFree(h->d_dg[l]);
-    }
     for (auto& set : h->ev_sets) for (auto& e : set) if (e) (void)hipEventDestroy(e);
-    if (h->d_pol) (void)hipFree(h->d_pol);
-    if (h->d_par) (void)hipFree(h->d_par);
-    if (h->d_polw) (void)hipFree(h->d_polw);
-    if (h->d_nn_idx) (void)hipFree(h->d_nn_idx);
-    if (h->d_roll) (void)hipFree(h->d_roll);
-    if (h->d_chk) (void)hipFree(h->d_chk);
-    if (h->d_wstat) (void)hipFree(h->d_wstat);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    if (h->d_desc) (void)hipFree(h->d_desc);
+    delete h;       // (and with it every buffer the handle owns)
 }
 
 int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* const* W, const float* const* b,
@@ -978,9 +1014,22 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
         if (dims[l] != H) return fail(h, SMPC_EINVAL, "hidden layers must share one width");
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers borrow the weight buffers replaced below)
+    for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers borrow the weight buffers rewritten below)
     h->kids.clear();
-    h->capM = h->capY = h->capDG = 0;
+    h->nlayers = 0;     // (no network until every layer is in place)
+    // one block for every layer's W^T (layer 0 padded to MLP_KPAD rows), W (layer 0 padded to MLP_NPAD columns) and b
+    const auto layout = [&](char* base) {
+        Carve m{base};
+        for (int l = 0; l < nlayers; l++) {
+            h->d_Wfwd[l] = m.take<float>((size_t)(l == 0 ? MLP_KPAD : dims[l]) * dims[l + 1]);
+            h->d_Wbwd[l] = m.take<float>((size_t)dims[l + 1] * (l == 0 ? MLP_NPAD : dims[l]));
+            h->d_bias[l] = m.take<float>(dims[l + 1]);
+        }
+        return m.off;
+    };
+    int rc;
+    if ((rc = h->d_weights.reserve(h, "network weights", layout(nullptr)))) return rc;
+    layout(h->d_weights.p);
     for (int l = 0; l < nlayers; l++) {
         const int ni = dims[l], no = dims[l + 1];
         std::vector<float> w((size_t)ni * no), bb(no);
@@ -994,10 +1043,6 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
                 wf[(size_t)i * no + o] = w[(size_t)o * ni + i];
                 wb[(size_t)o * nb + i] = w[(size_t)o * ni + i];
             }
-        int rc;
-        if ((rc = dev_alloc(h, &h->d_Wfwd[l], wf.size()))) return rc;
-        if ((rc = dev_alloc(h, &h->d_Wbwd[l], wb.size()))) return rc;
-        if ((rc = dev_alloc(h, &h->d_bias[l], bb.size()))) return rc;
         HIPCHK(h, hipMemcpy(h->d_Wfwd[l], wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(h->d_Wbwd[l], wb.data(), wb.size() * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(h->d_bias[l], bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1028,12 +1073,13 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     if (!h) return SMPC_EINVAL;
     if (N < 1 || N > SMPC_MAX_N) return fail(h, SMPC_EINVAL, "N=%d outside 1..%d", N, SMPC_MAX_N);
     (void)hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->N = N;
     h->inst_B = 0;
-    if (h->d_zl) { (void)hipFree(h->d_zl); h->d_zl = nullptr; }   // per-node weights belong to the old horizon
-    h->ws_bytes = 0;  // workspace layout, linearisation records and IO staging are sized by N
-    h->capEV = 0;
-    h->capIO = 0;
+    h->order_B = 0;
+    // every buffer laid out by the horizon starts afresh (zeroed where that is its contract) in the next call that needs it
+    for (DevBuf<double>* buf : {&h->d_zl, &h->d_lo_b, &h->d_hi_b, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
+    h->d_par.release();
     return upload_bounds(h, nullptr, nullptr);
 }
 
@@ -1049,14 +1095,14 @@ int smpc_set_slack_weights(smpc_handle* h, const double* zl) {
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!zl) {
-        if (h->d_zl) { (void)hipFree(h->d_zl); h->d_zl = nullptr; }
+        h->d_zl.release();
         return SMPC_OK;
     }
     for (int k = 1; k <= h->N; k++)
         if (!(zl[k] >= 0.0)) return fail(h, SMPC_EINVAL, "slack weight of node %d is negative or NaN", k);
     int rc;
-    if ((rc = dev_alloc(h, &h->d_zl, (size_t)h->N + 1))) return rc;
-    HIPCHK(h, hipMemcpy(h->d_zl, zl, sizeof(double) * (h->N + 1), hipMemcpyHostToDevice));
+    if ((rc = h->d_zl.reserve(h, "slack weights", sizeof(double) * (h->N + 1)))) return rc;
+    HIPCHK(h, hipMemcpy(h->d_zl.p, zl, sizeof(double) * (h->N + 1), hipMemcpyHostToDevice));
     return SMPC_OK;
 }
 
@@ -1068,15 +1114,11 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
     const size_t n = (size_t)B * (h->N + 1) * 2 * h->desc.nq;
     int rc;
-    if (n > h->inst_cap) {   // (re)allocate only when the tube grows: a per-step caller pays two stream-ordered copies
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = dev_alloc(h, &h->d_lo_b, n))) return rc;
-        if ((rc = dev_alloc(h, &h->d_hi_b, n))) return rc;
-        h->inst_cap = n;
-    }
+    // (grown only when the tube grows: a per-step caller pays two stream-ordered copies)
+    if ((rc = ensure_instance_bounds(h, B, false))) return rc;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIPCHK(h, hipMemcpyAsync(h->d_lo_b, lo, n * sizeof(double), kind, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_hi_b, hi, n * sizeof(double), kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_lo_b.p, lo, n * sizeof(double), kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_hi_b.p, hi, n * sizeof(double), kind, h->stream));
     if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
     h->inst_B = B;
     return SMPC_OK;
@@ -1089,25 +1131,25 @@ int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, 
     (void)hipSetDevice(h->device);
     int rc;
     if ((rc = ensure_batch(h, B))) return rc;
-    const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
-    if (on_device) {
-        DISPATCH_NQ(h, (launch_solve<NQ_>(h, B, x0, xg, ug, p, x_out, u_out, status, qp_iter)));
+    const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
+    Stage io{h, on_device != 0};
+    const double *dx0, *dxg, *dug, *dp;
+    double *dxo, *duo;
+    int32_t *dst, *dit;
+    if ((rc = io.place([&](Stage& v) {
+             dx0 = v.in(x0, (size_t)B * 2 * h->desc.nq);
+             dxg = v.in(xg, nX);
+             dug = v.in(ug, nU);
+             dp = v.in(p, (size_t)B * (h->N + 1) * SMPC_NP);
+             dxo = v.out(x_out, nX);
+             duo = v.out(u_out, nU);
+             dst = v.out(status, (size_t)B);
+             dit = v.out(qp_iter, (size_t)B);
+         })))
         return rc;
-    }
-    if ((rc = ensure_io(h, B))) return rc;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_x0, x0, sizeof(double) * B * nx, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_xg, xg, sizeof(double) * B * (N + 1) * nx, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_ug, ug, sizeof(double) * B * N * nu, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_p, p, sizeof(double) * B * (N + 1) * SMPC_NP, hipMemcpyHostToDevice, s));
-    DISPATCH_NQ(h, (launch_solve<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p, h->d_xo, h->d_uo, h->d_st, h->d_it)));
+    DISPATCH_NQ(h, (launch_solve<NQ_>(h, B, dx0, dxg, dug, dp, dxo, duo, dst, dit)));
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(x_out, h->d_xo, sizeof(double) * B * (N + 1) * nx, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(u_out, h->d_uo, sizeof(double) * B * N * nu, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(status, h->d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    if (qp_iter) HIPCHK(h, hipMemcpyAsync(qp_iter, h->d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return SMPC_OK;
+    return io.finish();
 }
 
 int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, const double* p, smpc_node_eval* out,
@@ -1120,28 +1162,24 @@ int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, c
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     hipStream_t s = h->stream;
     const long nodes = (long)B * (N + 1);
-    const double *dxg = xg, *dug = ug, *dp = p;
-    double* dout = reinterpret_cast<double*>(out);
-    if (!on_device) {
-        if ((rc = ensure_io(h, B))) return rc;
-        if ((rc = ensure_tmp(h, sizeof(smpc_node_eval) * (size_t)nodes))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->d_xg, xg, sizeof(double) * B * (N + 1) * nx, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->d_ug, ug, sizeof(double) * B * N * nu, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->d_p, p, sizeof(double) * B * (N + 1) * SMPC_NP, hipMemcpyHostToDevice, s));
-        dxg = h->d_xg; dug = h->d_ug; dp = h->d_p;
-        dout = (double*)h->d_tmp;
-    }
+    Stage io{h, on_device != 0};
+    const double *dxg, *dug, *dp;
+    smpc_node_eval* dout;
+    if ((rc = io.place([&](Stage& v) {
+             dxg = v.in(xg, (size_t)nodes * nx);
+             dug = v.in(ug, (size_t)B * N * nu);
+             dp = v.in(p, (size_t)nodes * SMPC_NP);
+             dout = v.out(out, (size_t)nodes);
+         })))
+        return rc;
     // (entries no kernel writes -- the unused tails of the MAX_NQ / MAX_ROWS arrays -- read as zero)
-    HIPCHK(h, hipMemsetAsync(h->d_ev, 0, sizeof(double) * ev_tiles((size_t)nodes) * EV_TILE * EV_D, s));
-    DISPATCH_NQ(h, (launch_eval<NQ_>(h, B, dxg, dug, dp, h->d_ev)));
+    HIPCHK(h, hipMemsetAsync(h->d_ev.p, 0, sizeof(double) * ev_tiles((size_t)nodes) * EV_TILE * EV_D, s));
+    DISPATCH_NQ(h, (launch_eval<NQ_>(h, B, dxg, dug, dp, h->d_ev.p)));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ev_untile, dim3((unsigned)((nodes * EV_D + 255) / 256)), dim3(256), 0, s, nodes, h->d_ev, dout);
+    hipLaunchKernelGGL(k_ev_untile, dim3((unsigned)((nodes * EV_D + 255) / 256)), dim3(256), 0, s, nodes, h->d_ev.p,
+                       reinterpret_cast<double*>(dout));
     HIPCHK(h, hipGetLastError());
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(out, dout, sizeof(smpc_node_eval) * (size_t)nodes, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    return SMPC_OK;
+    return io.finish();
 }
 
 int smpc_guess_correction(smpc_handle* h, int B, double* xg, const double* ug, int on_device) {
@@ -1149,26 +1187,19 @@ int smpc_guess_correction(smpc_handle* h, int B, double* xg, const double* ug, i
     if (B <= 0 || !xg || !ug) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
-    hipStream_t s = h->stream;
-    double *dx = xg;
-    const double* du = ug;
-    if (!on_device) {
-        int rc;
-        if ((rc = ensure_tmp(h, sizeof(double) * B * ((size_t)(N + 1) * nx + (size_t)N * nq)))) return rc;
-        dx = (double*)h->d_tmp;
-        double* duw = dx + (size_t)B * (N + 1) * nx;
-        HIPCHK(h, hipMemcpyAsync(dx, xg, sizeof(double) * B * (N + 1) * nx, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(duw, ug, sizeof(double) * B * N * nq, hipMemcpyHostToDevice, s));
-        du = duw;
-    }
-    hipLaunchKernelGGL(k_guess_correction, dim3((B * nq + 63) / 64), dim3(64), 0, s, B, N, nq, h->desc.dt, dx, du, (const uint8_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr);
+    Stage io{h, on_device != 0};
+    double* dx;
+    const double* du;
+    int rc;
+    if ((rc = io.place([&](Stage& v) {
+             dx = v.inout(xg, (size_t)B * (N + 1) * nx);
+             du = v.in(ug, (size_t)B * N * nq);
+         })))
+        return rc;
+    hipLaunchKernelGGL(k_guess_correction, dim3((B * nq + 63) / 64), dim3(64), 0, h->stream, B, N, nq, h->desc.dt, dx, du,
+                       (const uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
     HIPCHK(h, hipGetLastError());
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(xg, dx, sizeof(double) * B * (N + 1) * nx, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    return SMPC_OK;
+    return io.finish();
 }
 
 int smpc_provide_control(smpc_handle* h, int B, const int32_t* accept, const double* x_temp, const double* u_temp,
@@ -1177,35 +1208,25 @@ int smpc_provide_control(smpc_handle* h, int B, const int32_t* accept, const dou
     if (B <= 0 || !accept || !x_temp || !u_temp || !xg || !ug || !u_apply) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
-    hipStream_t s = h->stream;
     const size_t nX = (size_t)B * (N + 1) * nx, nU = (size_t)B * N * nq;
-    if (on_device) {
-        hipLaunchKernelGGL(k_provide_control, dim3((B * (nx + nq) + 63) / 64), dim3(64), 0, s, B, N, nq, accept, x_temp,
-                           u_temp, xg, ug, u_apply, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const double*)nullptr);
-        HIPCHK(h, hipGetLastError());
-        return SMPC_OK;
-    }
+    Stage io{h, on_device != 0};
+    const int32_t* dacc;
+    const double *dxt, *dut;
+    double *dxg, *dug, *dua;
     int rc;
-    if ((rc = ensure_tmp(h, sizeof(double) * (2 * nX + 2 * nU + (size_t)B * nq) + sizeof(int32_t) * B + 64))) return rc;
-    double* d_xt = (double*)h->d_tmp;
-    double* d_ut = d_xt + nX;
-    double* d_xg = d_ut + nU;
-    double* d_ug = d_xg + nX;
-    double* d_ua = d_ug + nU;
-    int32_t* d_acc = (int32_t*)(d_ua + (size_t)B * nq);
-    HIPCHK(h, hipMemcpyAsync(d_xt, x_temp, sizeof(double) * nX, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_ut, u_temp, sizeof(double) * nU, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_xg, xg, sizeof(double) * nX, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_ug, ug, sizeof(double) * nU, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_acc, accept, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_provide_control, dim3((B * (nx + nq) + 63) / 64), dim3(64), 0, s, B, N, nq, d_acc, d_xt, d_ut,
-                       d_xg, d_ug, d_ua, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const double*)nullptr);
+    if ((rc = io.place([&](Stage& v) {
+             dxt = v.in(x_temp, nX);
+             dut = v.in(u_temp, nU);
+             dxg = v.inout(xg, nX);
+             dug = v.inout(ug, nU);
+             dua = v.out(u_apply, (size_t)B * nq);
+             dacc = v.in(accept, (size_t)B);
+         })))
+        return rc;
+    hipLaunchKernelGGL(k_provide_control, dim3((B * (nx + nq) + 63) / 64), dim3(64), 0, h->stream, B, N, nq, dacc, dxt, dut, dxg, dug,
+                       dua, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(xg, d_xg, sizeof(double) * nX, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(ug, d_ug, sizeof(double) * nU, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(u_apply, d_ua, sizeof(double) * B * nq, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return SMPC_OK;
+    return io.finish();
 }
 
 int smpc_check_trajectory(smpc_handle* h, int B, int n_nodes, const double* x, const double* x_min, const double* x_max,
@@ -1216,30 +1237,21 @@ int smpc_check_trajectory(smpc_handle* h, int B, int n_nodes, const double* x, c
     if (h->desc.n_rows > 0 && (!row_lb_chk || !row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
     if (nn_ok && h->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_ok requested but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
-    const int nq = h->desc.nq, nx = 2 * nq;
-    hipStream_t s = h->stream;
     const size_t M = (size_t)B * n_nodes;
     // (x_min / x_max / row bounds are host pointers on both paths: small, constant per caller)
     int rc;
-    const size_t big = on_device ? 0 : sizeof(double) * M * nx + sizeof(int32_t) * (B + M) + 64;
-    if ((rc = ensure_tmp(h, big))) return rc;
     if ((rc = upload_check_bounds(h, x_min, x_max, row_lb_chk, row_ub_chk))) return rc;
-    const double* d_x = x;
-    int32_t *d_ok = state_ok, *d_nn = nn_ok;
-    if (!on_device) {
-        double* dx = (double*)h->d_tmp;
-        HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * M * nx, hipMemcpyHostToDevice, s));
-        d_x = dx;
-        d_ok = (int32_t*)(dx + M * nx);
-        d_nn = d_ok + B;
-    }
-    if ((rc = check_nodes_dev(h, B, n_nodes, d_x, tol_x, n_nodes, alpha, tol_safe, d_ok, nn_ok ? d_nn : nullptr))) return rc;
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(state_ok, d_ok, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-        if (nn_ok) HIPCHK(h, hipMemcpyAsync(nn_ok, d_nn, sizeof(int32_t) * M, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    return SMPC_OK;
+    Stage io{h, on_device != 0};
+    const double* dx;
+    int32_t *dok, *dnn;
+    if ((rc = io.place([&](Stage& v) {
+             dx = v.in(x, M * 2 * h->desc.nq);
+             dok = v.out(state_ok, (size_t)B);
+             dnn = v.out(nn_ok, M);
+         })))
+        return rc;
+    if ((rc = check_nodes_dev(h, B, n_nodes, dx, tol_x, n_nodes, alpha, tol_safe, dok, nn_ok ? dnn : nullptr))) return rc;
+    return io.finish();
 }
 
 int smpc_plant_step(smpc_handle* h, int B, const double* x, const double* u, const smpc_joint* joints_noisy,
@@ -1249,38 +1261,27 @@ int smpc_plant_step(smpc_handle* h, int B, const double* x, const double* u, con
     (void)hipSetDevice(h->device);
     const int nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
-    const double *dx = x, *du = u, *dn = tau_noise;
-    const smpc_joint* dj = joints_noisy;
-    double *dxn = x_next, *due = u_eff;
-    if (!on_device) {
-        int rc;
-        const size_t bytes = sizeof(double) * B * (2 * (size_t)nx + 3 * (size_t)nq) + sizeof(smpc_joint) * (size_t)B * nq + 64;
-        if ((rc = ensure_tmp(h, bytes))) return rc;
-        double* w = (double*)h->d_tmp;
-        double* wx = w; w += (size_t)B * nx;
-        double* wu = w; w += (size_t)B * nq;
-        double* wn = w; w += (size_t)B * nq;
-        dxn = w; w += (size_t)B * nx;
-        due = w; w += (size_t)B * nq;
-        smpc_joint* wj = (smpc_joint*)w;
-        HIPCHK(h, hipMemcpyAsync(wx, x, sizeof(double) * B * nx, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(wu, u, sizeof(double) * B * nq, hipMemcpyHostToDevice, s));
-        dx = wx; du = wu;
-        if (tau_noise) { HIPCHK(h, hipMemcpyAsync(wn, tau_noise, sizeof(double) * B * nq, hipMemcpyHostToDevice, s)); dn = wn; }
-        if (joints_noisy) { HIPCHK(h, hipMemcpyAsync(wj, joints_noisy, sizeof(smpc_joint) * (size_t)B * nq, hipMemcpyHostToDevice, s)); dj = wj; }
-    }
+    Stage io{h, on_device != 0};
+    const double *dx, *du, *dn;
+    const smpc_joint* dj;
+    double *dxn, *due;
+    int rc;
+    if ((rc = io.place([&](Stage& v) {
+             dx = v.in(x, (size_t)B * nx);
+             du = v.in(u, (size_t)B * nq);
+             dn = v.in(tau_noise, (size_t)B * nq);
+             dj = v.in(joints_noisy, (size_t)B * nq);
+             dxn = v.out(x_next, (size_t)B * nx);
+             due = v.out(u_eff, (size_t)B * nq);
+         })))
+        return rc;
     switch (nq) {
     case 5: hipLaunchKernelGGL((k_plant_step<5>), dim3((B + 8) / 9), dim3(64), 0, s, h->d_desc, B, dx, du, dj, dn, dxn, due); break;
     case 6: hipLaunchKernelGGL((k_plant_step<6>), dim3((B + 7) / 8), dim3(64), 0, s, h->d_desc, B, dx, du, dj, dn, dxn, due); break;
     default: hipLaunchKernelGGL((k_plant_step<7>), dim3((B + 6) / 7), dim3(64), 0, s, h->d_desc, B, dx, du, dj, dn, dxn, due); break;
     }
     HIPCHK(h, hipGetLastError());
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(x_next, dxn, sizeof(double) * B * nx, hipMemcpyDeviceToHost, s));
-        if (u_eff) HIPCHK(h, hipMemcpyAsync(u_eff, due, sizeof(double) * B * nq, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    return SMPC_OK;
+    return io.finish();
 }
 
 int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, double* x_guess, double* u_guess,
@@ -1295,49 +1296,24 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     int rc;
     const size_t nX = (size_t)B * (N + 1) * nx, nU = (size_t)B * N * nq, nP = (size_t)B * (N + 1) * SMPC_NP;
     const size_t sx = (size_t)B * nx, su = (size_t)B * nq;
-    // device views of the arguments (host pointers: one staging allocation for the call)
-    char* stage = nullptr;
-    const double *dx0 = x0, *dp = p, *dnoise = tau_noise;
-    const smpc_joint* dj = joints_noisy;
-    double *dxg = x_guess, *dug = u_guess, *dxt = x_traj, *dut = u_traj;
-    int32_t *dst = status_traj, *dit = iter_traj;
-    size_t o_x0 = 0, o_xg, o_ug, o_p, o_xt, o_ut, o_j, o_n, o_st, o_it, o_end;
-    if (!on_device) {
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        o_xg = al(o_x0 + sizeof(double) * sx);
-        o_ug = al(o_xg + sizeof(double) * nX);
-        o_p = al(o_ug + sizeof(double) * nU);
-        o_xt = al(o_p + sizeof(double) * nP);
-        o_ut = al(o_xt + sizeof(double) * sx * (n_steps + 1));
-        o_j = al(o_ut + sizeof(double) * su * n_steps);
-        o_n = al(o_j + (joints_noisy ? sizeof(smpc_joint) * (size_t)B * nq : 0));
-        o_st = al(o_n + (tau_noise ? sizeof(double) * su * n_steps : 0));
-        o_it = al(o_st + sizeof(int32_t) * (size_t)B * n_steps);
-        o_end = al(o_it + sizeof(int32_t) * (size_t)B * n_steps);
-        if (o_end > h->roll_bytes) {
-            HIPCHK(h, hipStreamSynchronize(s));
-            if (h->d_roll) { (void)hipFree(h->d_roll); h->d_roll = nullptr; h->roll_bytes = 0; }
-            if (hipMalloc((void**)&h->d_roll, o_end) != hipSuccess) return fail(h, SMPC_ENOMEM, "hipMalloc(%zu) failed", o_end);
-            h->roll_bytes = o_end;
-        }
-        stage = h->d_roll;
-        dxg = (double*)(stage + o_xg); dug = (double*)(stage + o_ug); dxt = (double*)(stage + o_xt); dut = (double*)(stage + o_ut);
-        dst = (int32_t*)(stage + o_st); dit = (int32_t*)(stage + o_it);
-        hipError_t e = hipMemcpyAsync(stage + o_x0, x0, sizeof(double) * sx, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(dxg, x_guess, sizeof(double) * nX, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(dug, u_guess, sizeof(double) * nU, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(stage + o_p, p, sizeof(double) * nP, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && joints_noisy)
-            e = hipMemcpyAsync(stage + o_j, joints_noisy, sizeof(smpc_joint) * (size_t)B * nq, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && tau_noise)
-            e = hipMemcpyAsync(stage + o_n, tau_noise, sizeof(double) * su * n_steps, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail(h, SMPC_EHIP, "staging copy failed: %s", hipGetErrorString(e));
-        dx0 = (const double*)(stage + o_x0); dp = (const double*)(stage + o_p);
-        dj = joints_noisy ? (const smpc_joint*)(stage + o_j) : nullptr;
-        dnoise = tau_noise ? (const double*)(stage + o_n) : nullptr;
-    } else if (!dit) {
-        dit = h->d_it;
-    }
+    Stage io{h, on_device != 0};
+    const double *dx0, *dp, *dnoise;
+    const smpc_joint* dj;
+    double *dxg, *dug, *dxt, *dut;
+    int32_t *dst, *dit;
+    if ((rc = io.place([&](Stage& v) {
+             dx0 = v.in(x0, sx);
+             dxg = v.inout(x_guess, nX);
+             dug = v.inout(u_guess, nU);
+             dp = v.in(p, nP);
+             dxt = v.out(x_traj, sx * (n_steps + 1));
+             dut = v.out(u_traj, su * n_steps);
+             dj = v.in(joints_noisy, (size_t)B * nq);
+             dnoise = v.in(tau_noise, su * n_steps);
+             dst = v.out(status_traj, (size_t)B * n_steps);
+             dit = v.out(iter_traj, (size_t)B * n_steps);
+         })))
+        return rc;
     // ---- the steps.  Instances are independent, so a large batch is split into sub-batches that advance on their own
     // streams (worker handles): while one sub-batch's QP launch waits for its slowest instances the others' kernels fill the
     // chip (scripts/rollout_bench.py, B = 4096, round 4: 3.53 / 3.06 / 3.04 / 3.07 ms per step with 1 / 2 / 3 / 4 sub-batches,
@@ -1359,7 +1335,7 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
         if (!h->ev_fork) HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         HIPCHK(h, hipEventRecord(h->ev_fork, s));        // inputs (staging copies, x_traj[0]) are ordered before the workers
     }
-    struct Slice { smpc_handle* w; int lo, n; };
+    struct Slice { smpc_handle* w; int lo, n; RollScratch r; };
     std::vector<Slice> slices;
     for (int k = 0; k < n_sub; k++) {
         const int base = B / n_sub, rem = B % n_sub;
@@ -1369,17 +1345,11 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
         const int nn_mode = h->desc.nn_mode;
         w->mlp_rows_whole = n_sub > 1 ? (nn_mode == SMPC_NN_TERMINAL ? (long)B : (long)B * N) : 0;
         int rw;
-        if ((rw = ensure_batch(w, n)) || (rw = ensure_io(w, n))) return fail(h, rw, "worker %d: %s", k, w->err);
-        if (w->pol_B < n) {     // fails / accept counters of the policy (kept in the handle: the device path does not synchronise)
-            (void)hipStreamSynchronize(w->stream);
-            if (w->d_pol) (void)hipFree(w->d_pol);
-            w->d_pol = nullptr;
-            w->pol_B = 0;
-            if (hipMalloc((void**)&w->d_pol, sizeof(int32_t) * 2 * (size_t)n) != hipSuccess) return fail(h, SMPC_ENOMEM, "hipMalloc failed");
-            w->pol_B = n;
-        }
-        if (hipMemsetAsync(w->d_pol, 0, sizeof(int32_t) * n, w->stream) != hipSuccess) return fail(h, SMPC_EHIP, "rollout init failed");
-        slices.push_back({w, lo, n});
+        if ((rw = ensure_batch(w, n)) || (rw = w->d_roll.reserve(w, "rollout scratch", roll_layout(nullptr, n, N, nq).bytes)))
+            return fail(h, rw, "worker %d: %s", k, w->err);
+        const RollScratch r = roll_layout(w->d_roll.p, n, N, nq);
+        if (hipMemsetAsync(r.fails, 0, sizeof(int32_t) * n, w->stream) != hipSuccess) return fail(h, SMPC_EHIP, "rollout init failed");
+        slices.push_back({w, lo, n, r});
     }
     for (int t = 0; t < n_steps && rc == SMPC_OK; t++) {
         for (const Slice& sl : slices) {
@@ -1391,12 +1361,11 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
             double* ug_w = dug + (size_t)lo * N * nq;
             const double* p_w = dp + (size_t)lo * (N + 1) * SMPC_NP;
             int32_t* st_w = dst + (size_t)t * B + lo;
-            int32_t* it_w = (on_device && !iter_traj) ? w->d_it : dit + (size_t)t * B + lo;
-            int32_t *d_fails = w->d_pol, *d_accept = w->d_pol + n;
+            int32_t* it_w = dit ? dit + (size_t)t * B + lo : sl.r.it;
             if ((rc = smpc_guess_correction(w, n, xg_w, ug_w, 1))) break;
-            if ((rc = smpc_solve_batch(w, n, xt, xg_w, ug_w, p_w, w->d_xo, w->d_uo, st_w, it_w, 1))) break;
-            hipLaunchKernelGGL(k_accept, dim3((n + 63) / 64), dim3(64), 0, w->stream, n, st_w, d_fails, d_accept);
-            if ((rc = smpc_provide_control(w, n, d_accept, w->d_xo, w->d_uo, xg_w, ug_w, ut, 1))) break;
+            if ((rc = smpc_solve_batch(w, n, xt, xg_w, ug_w, p_w, sl.r.xo, sl.r.uo, st_w, it_w, 1))) break;
+            hipLaunchKernelGGL(k_accept, dim3((n + 63) / 64), dim3(64), 0, w->stream, n, st_w, sl.r.fails, sl.r.accept);
+            if ((rc = smpc_provide_control(w, n, sl.r.accept, sl.r.xo, sl.r.uo, xg_w, ug_w, ut, 1))) break;
             rc = smpc_plant_step(w, n, xt, ut, dj ? dj + (size_t)lo * nq : nullptr,
                                  dnoise ? dnoise + (size_t)t * su + (size_t)lo * nq : nullptr, xt + sx, nullptr, 1);
             if (rc) break;
@@ -1410,19 +1379,11 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
             HIPCHK(h, hipStreamWaitEvent(s, h->ev_join, 0));
         }
     }
-    if (rc == SMPC_OK && !on_device) {
-        e = hipMemcpyAsync(x_traj, dxt, sizeof(double) * sx * (n_steps + 1), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(u_traj, dut, sizeof(double) * su * n_steps, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_traj, dst, sizeof(int32_t) * (size_t)B * n_steps, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && iter_traj) e = hipMemcpyAsync(iter_traj, dit, sizeof(int32_t) * (size_t)B * n_steps, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(x_guess, dxg, sizeof(double) * nX, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(u_guess, dug, sizeof(double) * nU, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) rc = fail(h, SMPC_EHIP, "copy back failed: %s", hipGetErrorString(e));
+    if (rc) {
+        if (!on_device) (void)hipStreamSynchronize(s);      // (host path: nothing of the call is in flight on return)
+        return rc;
     }
-    if (stage) {   // host path: results are on the host when the call returns
-        if (hipStreamSynchronize(s) != hipSuccess && rc == SMPC_OK) rc = fail(h, SMPC_EHIP, "stream synchronisation failed");
-    }
-    return rc;
+    return io.finish();
 }
 
 // ---- the policy layer on the device ------------------------------------------------------------------------------------------
@@ -1449,13 +1410,10 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     hipStream_t s = h->stream;
     int rc;
     if ((rc = ensure_batch(h, B))) return rc;
-    // scratch: state_ok [B] | safe [B][N+1] | accept [B] | active [B] bytes
-    const size_t nI = (size_t)B * (N + 3);
-    if ((rc = ensure_polw(h, sizeof(int32_t) * nI + (size_t)B + 64))) return rc;
-    int32_t* d_ok = h->d_polw;
-    int32_t* d_safe = d_ok + B;
-    int32_t* d_acc = d_safe + (size_t)B * (N + 1);
-    uint8_t* d_act = (uint8_t*)(d_acc + B);
+    PolScratch w;
+    if ((rc = policy_scratch(h, B, &w))) return rc;
+    int32_t *d_ok = w.ok, *d_safe = w.safe, *d_acc = w.acc;
+    uint8_t* d_act = w.act;
     if (kind != SMPC_POLICY_NAIVE && (rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
     if (parallel) return policy_step_parallel(h, B, par, st, x, stepping, u_other, u_out, abort_out, any_abort, d_ok, d_safe, d_acc, d_act);
     // guessCorrection (not RealReceding, controller.py:524-565); the launch also resets *any_abort.  Every kind launches exactly
@@ -1466,20 +1424,12 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
                            st->u_guess, stepping, any_abort, d_ok);
     if (receding) {
         if (kind == SMPC_POLICY_REAL_RECEDING) {
-            const size_t n = (size_t)B * (N + 1) * nx;
-            if (n > h->inst_cap) {
-                HIPCHK(h, hipStreamSynchronize(s));
-                if ((rc = dev_alloc(h, &h->d_lo_b, n))) return rc;
-                if ((rc = dev_alloc(h, &h->d_hi_b, n))) return rc;
-                h->inst_cap = n;
-                // (instances that never step keep valid bounds)
-                HIPCHK(h, hipMemsetAsync(h->d_lo_b, 0, n * sizeof(double), s));
-                HIPCHK(h, hipMemsetAsync(h->d_hi_b, 0, n * sizeof(double), s));
-            }
+            // (zeroed when grown: instances that never step keep valid bounds)
+            if ((rc = ensure_instance_bounds(h, B, true))) return rc;
             h->inst_B = B;
         }
         hipLaunchKernelGGL(k_policy_pre, dim3((unsigned)(((size_t)B * (N + 1) + 63) / 64)), dim3(64), 0, s, B, N, nx, kind,
-                           stepping, st->r, st->p, st->x_guess, par->stage_lo, par->stage_hi, par->tube, h->d_lo_b, h->d_hi_b,
+                           stepping, st->r, st->p, st->x_guess, par->stage_lo, par->stage_hi, par->tube, h->d_lo_b.p, h->d_hi_b.p,
                            kind == SMPC_POLICY_REAL_RECEDING ? any_abort : (int32_t*)nullptr,
                            kind == SMPC_POLICY_REAL_RECEDING ? d_ok : (int32_t*)nullptr);
     }
@@ -1504,7 +1454,7 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
             const size_t M = (size_t)B * (N + 1);
             if ((rc = ensure_nn_idx(h, M))) return rc;
             hipLaunchKernelGGL(k_policy_safe_list, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, B, N, par->abort_flag, stepping, st->r,
-                               h->d_nn_idx, h->d_nn_cnt);
+                               h->d_nn_idx.p, h->d_nn_cnt);
         }
         if ((rc = check_nodes_dev(h, B, N + 1, st->x_temp, par->tol_x, coll, par->alpha, par->tol_safe, d_ok, receding ? d_safe : nullptr,
                                   receding, true))) {
@@ -1576,19 +1526,16 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     if (!par->x_min || !par->x_max || (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)))
         return fail(h, SMPC_EINVAL, "check bounds missing");
     (void)hipSetDevice(h->device);
-    const int nq = h->desc.nq, nx = 2 * nq;
+    const int nq = h->desc.nq;
     hipStream_t s = h->stream;
     int rc;
-    // scratch behind smpc_policy_step's (same handle, stream-ordered): x_next [B][nx] | ok [B]
-    const size_t off = (sizeof(int32_t) * (size_t)B * (h->N + 3) + (size_t)B + 64 + 15) & ~(size_t)15;
-    if ((rc = ensure_polw(h, off + sizeof(double) * (size_t)B * nx + sizeof(int32_t) * (size_t)B))) return rc;
-    double* d_xn = (double*)((char*)h->d_polw + off);
-    int32_t* d_okn = (int32_t*)(d_xn + (size_t)B * nx);
+    PolScratch w;       // (its x_next [B][nx] and ok [B] lie behind smpc_policy_step's part)
+    if ((rc = policy_scratch(h, B, &w))) return rc;
     if ((rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
-    if ((rc = smpc_plant_step(h, B, ls->x_cur, u, joints_noisy, tau_noise, d_xn, nullptr, 1))) return rc;
+    if ((rc = smpc_plant_step(h, B, ls->x_cur, u, joints_noisy, tau_noise, w.xn, nullptr, 1))) return rc;
     // one node per instance: the model bounds widened by tol_x and the rows against their check bounds = checkStateConstraints
-    if ((rc = check_nodes_dev(h, B, 1, d_xn, par->tol_x, 1, 0.0, 0.0, d_okn, nullptr))) return rc;
-    hipLaunchKernelGGL(k_loop_post, dim3((B + 63) / 64), dim3(64), 0, s, B, nq, u, d_xn, d_okn, ls->step, ls->x_log, ls->u_log,
+    if ((rc = check_nodes_dev(h, B, 1, w.xn, par->tol_x, 1, 0.0, 0.0, w.okn, nullptr))) return rc;
+    hipLaunchKernelGGL(k_loop_post, dim3((B + 63) / 64), dim3(64), 0, s, B, nq, u, w.xn, w.okn, ls->step, ls->x_log, ls->u_log,
                        ls->alive, ls->collided, ls->last_x, ls->last_u, ls->x_cur);
     hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(1), 0, s, ls->step);
     HIPCHK(h, hipGetLastError());
@@ -1610,7 +1557,9 @@ int smpc_enable_timing(smpc_handle* h, int on) {
     h->timed = 0;
     h->timed_count = 0;
     for (bool& c : h->ev_complete) c = false;
-    return SMPC_OK;
+    if (h->timing != 1) return SMPC_OK;
+    (void)hipSetDevice(h->device);
+    return h->d_wstat.reserve(h, "load-balance probe", 4 * sizeof(unsigned long long));
 }
 
 int smpc_get_timing(smpc_handle* h, float* ms4) {
@@ -1668,11 +1617,11 @@ int smpc_accumulate_stats(smpc_handle* h, int B, const int32_t* status, const in
 
 int smpc_get_qp_wave_stats(smpc_handle* h, double* out3) {
     if (!h || !out3) return SMPC_EINVAL;
-    if (h->timing != 1 || !h->timed || !h->d_wstat) return fail(h, SMPC_ESTATE, "no solve has been timed since smpc_enable_timing(1)");
+    if (h->timing != 1 || !h->timed || !h->d_wstat.p) return fail(h, SMPC_ESTATE, "no solve has been timed since smpc_enable_timing(1)");
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     unsigned long long w[4];
-    HIPCHK(h, hipMemcpy(w, h->d_wstat, sizeof(w), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(w, h->d_wstat.p, sizeof(w), hipMemcpyDeviceToHost));
     const double tick_us = 1e-2;   // s_memrealtime: constant 100 MHz
     out3[0] = w[3] ? (double)w[0] / (double)w[3] * tick_us : 0.0;   // mean busy time of a half-wave (one instance), us
     out3[1] = w[3] ? (double)(w[2] - w[1]) * tick_us : 0.0;          // first start -> last end, us
@@ -1692,20 +1641,24 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = ensure_batch(h, B)) || (rc = ensure_io(h, B))) return rc;
+    if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_x0, x0, sizeof(double) * B * nx, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_xg, xg, sizeof(double) * B * (N + 1) * nx, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_ug, ug, sizeof(double) * B * N * nu, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_p, p, sizeof(double) * B * (N + 1) * SMPC_NP, hipMemcpyHostToDevice, s));
+    Stage io{h, false};
+    const double *dx0, *dxg, *dug, *dp;
+    if ((rc = io.place([&](Stage& v) {
+             dx0 = v.in(x0, (size_t)B * nx);
+             dxg = v.in(xg, (size_t)B * (N + 1) * nx);
+             dug = v.in(ug, (size_t)B * N * nu);
+             dp = v.in(p, (size_t)B * (N + 1) * SMPC_NP);
+         })))
+        return rc;
     const size_t per = ws_doubles_per_instance(h->desc, N);
-    HIPCHK(h, hipMemsetAsync(h->d_ws, 0, per * (size_t)B * sizeof(double), s));
-    DISPATCH_NQ(h, (path == 1 ? launch_stage_records<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p, false)
-                              : launch_stage_records_per_node<NQ_>(h, B, h->d_x0, h->d_xg, h->d_ug, h->d_p)));
+    HIPCHK(h, hipMemsetAsync(h->d_ws.p, 0, per * (size_t)B * sizeof(double), h->stream));
+    DISPATCH_NQ(h, (path == 1 ? launch_stage_records<NQ_>(h, B, dx0, dxg, dug, dp, false)
+                              : launch_stage_records_per_node<NQ_>(h, B, dx0, dxg, dug, dp)));
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(ws_out, h->d_ws, per * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipMemcpyAsync(ws_out, h->d_ws.p, per * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = io.finish())) return rc;
     auto fill = [&](auto Ly) {
         const int v[24] = {Ly.stride, Ly.nIMG, Ly.oIMG, Ly.oSL, Ly.nF, Ly.oR0, Ly.oR1, Ly.oR2, Ly.oCZA, Ly.oCZN, Ly.oZ, Ly.oZN, Ly.NRT, Ly.nJ,
                            (int)per, 12, Ly.iTT, Ly.iGT, Ly.iGN, Ly.iB, Ly.iSC, Ly.iHQQ, Ly.iGZ, 0};

@@ -198,6 +198,45 @@ def test_device_pointer_path_matches_host_path():
     assert np.array_equal(sd.cpu().numpy(), sh)
 
 
+def test_buffer_growth_inside_a_graph_capture_is_a_state_error():
+    """A handle's buffers grow in eager calls only.  The engine's stream joins a capture through BatchedOcpSolver._ordered, as in
+    closed_loop._Group._run_half: a captured solve of a warmed-up batch size replays what the eager solve computed, and a captured
+    solve that would have to grow a buffer fails with SMPC_ESTATE instead of synchronising the capturing stream -- the capture still
+    ends cleanly, and the next eager call grows the buffers."""
+    import warnings
+    import torch
+    from safe_mpc_amd._lib import EngineError
+    par, prob, net = make_problem('st', N=20)
+    s, o = _solver(prob, net), _oracle(prob, net)
+    B = 128
+    x0 = sample_instances(prob, B, seed=7, vel_scale=0.1)
+    xg, ug, p = constant_guess(prob, x0)
+    big = [torch.tensor(a, dtype=torch.float64, device='cuda:0') for a in (x0, xg, ug, p)]
+    small = [a[:B // 2] for a in big]
+    eager = s.solve(*small)                      # (grows every buffer of B / 2 instances)
+    out = tuple(torch.empty_like(a) for a in eager)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        s.solve(*small, out=out)
+    g.replay()
+    torch.cuda.synchronize()
+    for a, b in zip(out, eager):
+        assert torch.equal(a, b)
+    with pytest.raises(EngineError, match='engine error -4: .* while the stream is being captured'), warnings.catch_warnings():
+        warnings.filterwarnings('ignore', 'The CUDA Graph is empty')       # (the refused solve captured nothing)
+        with torch.cuda.graph(torch.cuda.CUDAGraph()):
+            s.solve(*big)
+    torch.cuda.synchronize()
+    xa, ua, sa, ia = (a.cpu().numpy() for a in s.solve(*big))
+    xb, ub, sb, ib = o.solve_batch(x0, xg, ug, p)
+    assert np.array_equal(sa, sb)
+    ok = sb == 0
+    assert ok.sum() >= B - 2
+    assert np.abs(ia[ok] - ib[ok]).max() <= 2
+    assert np.abs(ua[ok] - ub[ok]).max() < 1e-4 * (1 + np.abs(ub[ok]).max())
+    assert np.abs(xa[ok] - xb[ok]).max() < 1e-4
+
+
 def test_policy_layer_and_scripts_on_engine(tmp_path):
     """The batched controllers + run_mpc on the real engine agree with the same code on the CPU test double."""
     from fake_solver import OracleSolver
