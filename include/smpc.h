@@ -242,6 +242,58 @@ int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, 
 int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, const double* p, smpc_node_eval* out,
                     int on_device);
 
+/* ---- full SQP with merit backtracking (the warm starts of scripts/guess_acados.py) ------------ */
+/* The two terms of the l1 merit function  f + mu |c|_1  of B trajectories, evaluated forward-only at the trial points
+ * (x + alpha[b] dx, u + alpha[b] du):  out[B][3] = {f, viol, gd}.
+ *   f     the cost as acados sums it: cost_scale_stage / cost_scale_term times Q |ee - p[0:3]|^2 (+ R |u|^2 on nodes 0..N-1);
+ *         0 for SMPC_COST_ZERO
+ *   viol  the l1 norm of every constraint's violation: |x_0 - x0|, the defects of the double integrator, the state box of nodes
+ *         1..N, max(|tau| - tau_max, 0) on nodes 0..N-1, the collision rows on nodes 1..N (a bound with |value| >= SMPC_INF is
+ *         absent), the safe-set row max(-g, 0) on the nodes where the formulation has it and p[4] > 0 (never on node 0)
+ *   gd    grad f . (dx, du), for the instances with alpha[b] == 0 (or alpha == NULL) when dx / du are given; 0 otherwise
+ * dx / du / alpha may be NULL (the point is (x, u), gd = 0).  mask[B] (bytes, may be NULL): instances with mask[b] == 0 are
+ * skipped and their out[b] left as it is (so out is read as well as written on the host path).  Sums are formed in a fixed order:
+ * two calls give the same bits.  Pointers follow on_device like smpc_solve_batch. */
+int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, const double* u, const double* p, const double* dx,
+                     const double* du, const double* alpha, const uint8_t* mask, double* out, int on_device);
+
+typedef struct {
+    int32_t max_iter;        /* SQP iterations of this call at most (nlp_solver_max_iter, parser.py:139) */
+    int32_t reserved0;
+    double tol;              /* an instance is done once alpha * |step|_inf < tol (1e-6) */
+    double armijo;           /* sufficient-decrease factor of the line search (1e-4) */
+    double alpha_reduction;  /* step-length factor per rejected trial (0.7) */
+    double alpha_min;        /* floor at which the step is taken regardless (0.05) */
+    double mu0;              /* start value of the penalty (10): the caller fills the state's mu[B] with it before the first call;
+                              * the call itself reads and writes mu[B] only */
+    double mu_max;           /* cap of the penalty (1e8) */
+} smpc_sqp_opts;
+
+typedef struct {             /* per-instance arrays [B], read AND written: a call resumes where the previous one stopped */
+    double* mu;              /* penalty of the l1 merit function */
+    uint8_t* done;           /* converged (or failed): skipped by every kernel of later iterations */
+    int32_t* status;         /* acados status of the last QP the instance took part in */
+    double* alpha;           /* last iteration the instance took part in: accepted step length (0: step not taken) */
+    double* merit_before;    /* ... merit at the iterate before the step */
+    double* merit;           /* ... merit after it (= merit_before where the step was not taken) */
+    double* violation;       /* ... l1 violation after it */
+    uint8_t* updated;        /* ... the iterate moved */
+    int32_t* iters;          /* SQP iterations the instance took part in (accumulates) */
+    int32_t* qp_iter_total;  /* interior-point iterations of those solves (accumulates) */
+} smpc_sqp_state;
+
+/* SQP with l1-merit backtracking for B instances, in place on (x_guess, u_guess): replaces ocp_solver.solve() with
+ * nlp_solver_type 'SQP' and globalization 'MERIT_BACKTRACKING' (parser.py:115-117, guess_acados.py:115).  Per iteration: the
+ * stage QP at the iterate (instances that are done are masked out of the stage builder and the QP), penalty update so that the QP
+ * step is a descent direction of the merit, backtracking over the step lengths 1, r, r^2, .. down to alpha_min with the Armijo test
+ *   merit(alpha) <= merit(0) + armijo alpha min(grad f . d - mu |c|_1, 0) + 1e-12 (1 + |merit(0)|),
+ * commit of the accepted point, done |= alpha |step|_inf < tol or status != 0.  max_iter = 1 called k times equals one call with
+ * max_iter = k, bit for bit.  The call stops early once no instance is open; that 4-byte count is the only per-iteration host read
+ * (skipped while the stream is being captured).  on_device != 0: every array, the state's included, is a device pointer; 0: host
+ * pointers, copied in and out. */
+int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const double* x0, double* x_guess, double* u_guess,
+                   const double* p, const smpc_sqp_state* state, int on_device);
+
 /* ---- callers on either side of the solve ------------------------------------------- */
 /* guessCorrection (controller.py:226-231): x_guess[k+1] = f(x_guess[k], u_guess[k]) in place. */
 int smpc_guess_correction(smpc_handle* h, int B, double* xg, const double* ug, int on_device);

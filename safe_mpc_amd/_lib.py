@@ -19,7 +19,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_provide_control', 'smpc_check_trajectory', 'smpc_plant_step', 'smpc_rollout_batch', 'smpc_sync', 'smpc_stream',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
-           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode']
+           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch']
 
 
 class EngineError(RuntimeError):
@@ -46,6 +46,22 @@ class LoopState(C.Structure):
     """smpc_loop_state"""
     _fields_ = [(k, _vp) for k in ('x_cur', 'alive', 'sa', 'collided', 'ja', 'last_x', 'last_u', 'x_abort', 'u_abort', 'step',
                                    'x_log', 'u_log', 'r_log', 'resumed')]
+
+
+class SqpOpts(C.Structure):
+    """smpc_sqp_opts; the defaults are those of closed_loop.generate_guess"""
+    _fields_ = [('max_iter', C.c_int32), ('reserved0', C.c_int32), ('tol', C.c_double), ('armijo', C.c_double),
+                ('alpha_reduction', C.c_double), ('alpha_min', C.c_double), ('mu0', C.c_double), ('mu_max', C.c_double)]
+
+    def __init__(self, max_iter=1, tol=1e-6, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, mu0=10.0, mu_max=1e8):
+        super().__init__(int(max_iter), 0, float(tol), float(armijo), float(alpha_reduction), float(alpha_min), float(mu0), float(mu_max))
+
+
+class SqpState(C.Structure):
+    """smpc_sqp_state: per-instance arrays [B]"""
+    FIELDS = (('mu', 'f8'), ('done', 'u1'), ('status', 'i4'), ('alpha', 'f8'), ('merit_before', 'f8'), ('merit', 'f8'),
+              ('violation', 'f8'), ('updated', 'u1'), ('iters', 'i4'), ('qp_iter_total', 'i4'))
+    _fields_ = [(k, _vp) for k, _ in FIELDS]
 
 
 def build(force=False):
@@ -104,5 +120,7 @@ def lib():
     L.smpc_accumulate_stats.argtypes = [vp, C.c_int, dp, dp, dp]
     L.smpc_set_mlp_activation.argtypes = [vp, C.c_int]
     L.smpc_set_qp_mode.argtypes = [vp, C.c_int]
+    L.smpc_merit_terms.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    L.smpc_sqp_batch.argtypes = [vp, C.c_int, C.POINTER(SqpOpts), dp, dp, dp, dp, C.POINTER(SqpState), C.c_int]
     _lib = L
     return L

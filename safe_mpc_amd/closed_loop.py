@@ -226,8 +226,41 @@ def merit_terms(ctrl, x0, x, u):
     return f, gq, gu, viol
 
 
+def _sqp_on_device(ctrl, x0, max_iter, history, verbose, opts):
+    """The SQP loop of :func:`generate_guess` through the engine (smpc_sqp_batch) on device tensors: one call for all iterations,
+    or one call per iteration when ``history`` is wanted.  Leaves the iterate in ctrl.x_guess / u_guess (numpy); returns status."""
+    import torch
+    sv = ctrl.ocp_solver
+    ctrl.p[:, :, 3] = ctrl.params.alpha                     # what ctrl.solve does before every solve
+    ctrl._apply_traj()
+    dev = torch.device('cuda', sv.device)
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), np.float64), device=dev)
+    x0_d, xg, ug, p_d = to(x0), to(ctrl.x_guess), to(ctrl.u_guess), to(ctrl.p)
+    B = x0_d.shape[0]
+    state = sv.new_sqp_state(B, x0_d)
+    if history is None:
+        sv.sqp(x0_d, xg, ug, p_d, dict(max_iter=max_iter, **opts), state)
+    else:
+        for it in range(max_iter):
+            was_done = state['done'].cpu().numpy().astype(bool)
+            sv.sqp(x0_d, xg, ug, p_d, dict(max_iter=1, **opts), state)
+            h = {k: state[k].cpu().numpy() for k in ('merit', 'merit_before', 'alpha', 'mu', 'violation', 'updated', 'done')}
+            # (an instance that was done before this iteration took no part in it: its entries are those of its last iteration,
+            #  reported the way the host loop reports an instance it does not move)
+            upd = h['updated'].astype(bool) & ~was_done
+            history.append({'merit': h['merit'], 'merit_before': np.where(was_done, h['merit'], h['merit_before']),
+                            'alpha': np.where(upd, h['alpha'], 0.0), 'mu': h['mu'], 'violation': h['violation'], 'updated': upd})
+            if verbose:
+                print(f'SQP iteration {it}: {int(h["done"].sum())}/{B} done')
+            if h['done'].all():
+                break
+    sv.sync()
+    ctrl.x_guess, ctrl.u_guess = xg.cpu().numpy(), ug.cpu().numpy()
+    return state['status'].cpu().numpy()
+
+
 def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7,
-                   alpha_min=0.05, history=None):
+                   alpha_min=0.05, history=None, on_device=False):
     """guess_acados.py:98-158: Halton q0 in the joint box, collision filter, constant guess, SQP to convergence, checkGuess.
 
     SQP with merit backtracking (the reference runs acados with nlp_solver_type SQP, globalization MERIT_BACKTRACKING,
@@ -238,9 +271,16 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     alpha_reduction / alpha_min from config.yaml but never hands them to acados, parser.py:119-120).  The penalty mu grows
     so that the QP step is a descent direction of the merit.  All instances advance together; one batched linearisation per
     trial step length.  Returns (dict(xg [m,N+1,nx], ug [m,N,nu]) of the accepted instances in sampling order, good mask);
-    ``history`` (a list) receives the per-iteration merit values [B] for inspection."""
+    ``history`` (a list) receives the per-iteration merit values [B] for inspection.
+
+    ``on_device=True``: the same sampling, filter and checkGuess, with the SQP iterations run by the engine on device-resident
+    arrays (``solver.sqp``, smpc_sqp_batch) instead of the numpy loop below, which stays the statement the engine's iteration is
+    tested against.  With ``history`` the engine advances one iteration per call and the same keys are appended."""
     make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
     ctrl = make_controller(cont_name, n)
+    if on_device and not hasattr(ctrl.ocp_solver, 'sqp'):
+        raise ValueError(f'generate_guess(on_device=True) needs a solver with a device SQP (BatchedOcpSolver.sqp); '
+                         f'{type(ctrl.ocp_solver).__name__} has none')
     pr = ctrl.problem
     nq = pr.nq
     q = pr.x_min[:nq] + halton(4 * n + 16, nq) * (pr.x_max[:nq] - pr.x_min[:nq])        # guess_acados.py:100
@@ -251,6 +291,12 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
         ctrl = make_controller(cont_name, len(x0))
     B = len(x0)
     ctrl.setGuess(np.repeat(x0[:, None, :], ctrl.N + 1, axis=1), np.zeros((B, ctrl.N, ctrl.nu)))
+    if on_device:
+        status = _sqp_on_device(ctrl, x0, int(params.nlp_max_iter), history, verbose,
+                                dict(tol=sqp_tol, armijo=armijo, alpha_reduction=alpha_reduction, alpha_min=alpha_min))
+        ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
+        good = ((status == 0) | (status == 2)) & ctrl.checkGuess()
+        return {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}, good
     done = np.zeros(B, bool)
     status = np.zeros(B, np.int32)
     mu = np.full(B, 10.0)

@@ -17,6 +17,7 @@
 #include "kernels_policy.hpp"
 #include "kernels_mlp.hpp"
 #include "kernels_nodes.hpp"
+#include "kernels_sqp.hpp"
 
 using namespace smpc;
 
@@ -113,6 +114,7 @@ struct smpc_handle {
                                 // two nodes per instance, where the list's capacity is every node -- which selects the network kernel
                                 // (the count itself is only known on the device; any kernel is correct for any count)
     DevBuf<char> d_par;         // SMPC_POLICY_PARALLEL's candidate buffers (ParScratch), zeroed when allocated
+    DevBuf<char> d_sqp;         // scratch of smpc_sqp_batch / smpc_merit_terms (SqpScratch)
     char err[256] = "";
 };
 
@@ -933,6 +935,83 @@ int ensure_batch(smpc_handle* h, int B, bool with_ev) {
     return rc;
 }
 
+// ---- SQP with merit backtracking (kernels_sqp.hpp) -----------------------------------------------------------------------------
+// scratch of smpc_sqp_batch and smpc_merit_terms for B instances: the QP's solution and the step, the trial points' states (what
+// the network pass reads), the line search's per-instance state
+struct SqpScratch {
+    double *xs, *us, *dx, *du, *xt, *step, *m0t, *mt, *alpha, *m0, *Dd;
+    int32_t *st, *it, *pos, *n_open;
+    uint8_t *act, *settled, *trial;
+    size_t bytes;
+};
+SqpScratch sqp_layout(char* base, int B, int N, int nq, bool full) {
+    const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
+    Carve m{base};
+    SqpScratch w{};
+    w.xt = m.take<double>(nX);
+    w.pos = m.take<int32_t>((size_t)B * (N + 1));
+    if (full) {
+        w.xs = m.take<double>(nX);
+        w.us = m.take<double>(nU);
+        w.dx = m.take<double>(nX);
+        w.du = m.take<double>(nU);
+        w.step = m.take<double>(B);
+        w.m0t = m.take<double>((size_t)3 * B);
+        w.mt = m.take<double>((size_t)3 * B);
+        w.alpha = m.take<double>(B);
+        w.m0 = m.take<double>(B);
+        w.Dd = m.take<double>(B);
+        w.st = m.take<int32_t>(B);
+        w.it = m.take<int32_t>(B);
+        w.n_open = m.take<int32_t>(1);
+        w.act = m.take<uint8_t>(B);
+        w.settled = m.take<uint8_t>(B);
+        w.trial = m.take<uint8_t>(B);
+    }
+    w.bytes = m.off;
+    return w;
+}
+int sqp_scratch(smpc_handle* h, int B, bool full, SqpScratch* w) {
+    int rc;
+    if ((rc = h->d_sqp.reserve(h, "SQP scratch", sqp_layout(nullptr, B, h->N, h->desc.nq, full).bytes))) return rc;
+    *w = sqp_layout(h->d_sqp.p, B, h->N, h->desc.nq, full);
+    return SMPC_OK;
+}
+
+// {f, viol, gd} of the instances whose mask byte is set, at (x + alpha dx, u + alpha du): the forward-only network pass on the
+// nodes that carry the safe-set row (listed by k_sqp_nn_list, so that masked-out instances cost no network rows), then k_merit.
+// The list's counter goes back to zero behind the chain (see d_nn_cnt).
+template <int NQ>
+int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, const double* x, const double* u, const double* p,
+                 const double* dx, const double* du, const double* alpha, const uint8_t* mask, double* out) {
+    const int N = h->N;
+    hipStream_t s = h->stream;
+    const long nodes = (long)B * (N + 1);
+    const float* y = nullptr;
+    if (h->desc.nn_mode != SMPC_NN_NONE) {
+        if (h->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_mode != NONE but smpc_set_mlp was not called");
+        const int terminal = h->desc.nn_mode == SMPC_NN_TERMINAL;
+        const int M = terminal ? B : B * N;          // the list's capacity
+        int rc;
+        if ((rc = ensure_nn_idx(h, (size_t)M))) return rc;
+        const double* xn = x;
+        if (dx && alpha) {
+            hipLaunchKernelGGL(k_sqp_trial_states, dim3((unsigned)((nodes * 2 * NQ + 63) / 64)), dim3(64), 0, s, B, (N + 1) * 2 * NQ, x, dx,
+                               alpha, mask, w.xt);
+            xn = w.xt;
+        }
+        hipLaunchKernelGGL(k_sqp_nn_list, dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, s, B, N, terminal, p, mask, h->d_nn_idx.p, w.pos,
+                           h->d_nn_cnt);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = run_mlp<NQ>(h, M, 3, N, xn, false))) return rc;
+        y = h->d_y.p;
+    }
+    hipLaunchKernelGGL((k_merit<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out);
+    HIPCHK(h, hipGetLastError());
+    if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
+    return SMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1080,6 +1159,7 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     // every buffer laid out by the horizon starts afresh (zeroed where that is its contract) in the next call that needs it
     for (DevBuf<double>* buf : {&h->d_zl, &h->d_lo_b, &h->d_hi_b, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
     h->d_par.release();
+    h->d_sqp.release();
     return upload_bounds(h, nullptr, nullptr);
 }
 
@@ -1540,6 +1620,124 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(1), 0, s, ls->step);
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
+}
+
+// ---- SQP with merit backtracking ---------------------------------------------------------------------------------------------------
+int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, const double* u, const double* p, const double* dx,
+                     const double* du, const double* alpha, const uint8_t* mask, double* out, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (B <= 0 || !x0 || !x || !u || !p || !out) return fail(h, SMPC_EINVAL, "bad argument");
+    if ((dx == nullptr) != (du == nullptr)) return fail(h, SMPC_EINVAL, "dx and du must both be given or both be NULL");
+    if (alpha && !dx) return fail(h, SMPC_EINVAL, "alpha without a step");
+    (void)hipSetDevice(h->device);
+    const int N = h->N, nq = h->desc.nq;
+    const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
+    int rc;
+    SqpScratch w;
+    if ((rc = sqp_scratch(h, B, false, &w))) return rc;
+    Stage io{h, on_device != 0};
+    const double *dx0, *dxg, *dug, *dp, *ddx, *ddu, *dal;
+    const uint8_t* dmask;
+    double* dout;
+    if ((rc = io.place([&](Stage& v) {
+             dx0 = v.in(x0, (size_t)B * 2 * nq);
+             dxg = v.in(x, nX);
+             dug = v.in(u, nU);
+             dp = v.in(p, (size_t)B * (N + 1) * SMPC_NP);
+             ddx = v.in(dx, nX);
+             ddu = v.in(du, nU);
+             dal = v.in(alpha, (size_t)B);
+             dmask = v.in(mask, (size_t)B);
+             dout = v.inout(out, (size_t)3 * B);
+         })))
+        return rc;
+    DISPATCH_NQ(h, (launch_merit<NQ_>(h, B, w, dx0, dxg, dug, dp, ddx, ddu, dal, dmask, dout)));
+    if (rc) return rc;
+    return io.finish();
+}
+
+int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const double* x0, double* x_guess, double* u_guess,
+                   const double* p, const smpc_sqp_state* state, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (B <= 0 || !opts || !x0 || !x_guess || !u_guess || !p || !state) return fail(h, SMPC_EINVAL, "bad argument");
+    if (!state->mu || !state->done || !state->status || !state->alpha || !state->merit_before || !state->merit || !state->violation ||
+        !state->updated || !state->iters || !state->qp_iter_total)
+        return fail(h, SMPC_EINVAL, "SQP state incomplete");
+    if (opts->max_iter < 0 || !(opts->alpha_reduction > 0.0 && opts->alpha_reduction < 1.0) || !(opts->alpha_min > 0.0 && opts->alpha_min <= 1.0))
+        return fail(h, SMPC_EINVAL, "SQP options: max_iter >= 0, 0 < alpha_reduction < 1, 0 < alpha_min <= 1");
+    (void)hipSetDevice(h->device);
+    const int N = h->N, nq = h->desc.nq;
+    const int nX1 = (N + 1) * 2 * nq, nU1 = N * nq;
+    const size_t nX = (size_t)B * nX1, nU = (size_t)B * nU1;
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = ensure_batch(h, B, false))) return rc;
+    SqpScratch w;
+    if ((rc = sqp_scratch(h, B, true, &w))) return rc;
+    Stage io{h, on_device != 0};
+    const double *dx0, *dp;
+    double *dxg, *dug, *d_mu, *d_alpha, *d_before, *d_merit, *d_viol;
+    uint8_t *d_done, *d_upd;
+    int32_t *d_status, *d_iters, *d_qpit;
+    if ((rc = io.place([&](Stage& v) {
+             dx0 = v.in(x0, (size_t)B * 2 * nq);
+             dp = v.in(p, (size_t)B * (N + 1) * SMPC_NP);
+             dxg = v.inout(x_guess, nX);
+             dug = v.inout(u_guess, nU);
+             d_mu = v.inout(state->mu, (size_t)B);
+             d_alpha = v.inout(state->alpha, (size_t)B);
+             d_before = v.inout(state->merit_before, (size_t)B);
+             d_merit = v.inout(state->merit, (size_t)B);
+             d_viol = v.inout(state->violation, (size_t)B);
+             d_done = v.inout(state->done, (size_t)B);
+             d_upd = v.inout(state->updated, (size_t)B);
+             d_status = v.inout(state->status, (size_t)B);
+             d_iters = v.inout(state->iters, (size_t)B);
+             d_qpit = v.inout(state->qp_iter_total, (size_t)B);
+         })))
+        return rc;
+    const bool captured = capturing(h);
+    const dim3 blk(64), per_inst((B + 63) / 64);
+    // step lengths an instance can try: 1, r, r^2, .. while above alpha_min, then alpha_min itself
+    int n_trials = 1;
+    for (double a = 1.0; a > opts->alpha_min && n_trials < 64; n_trials++) a = a * opts->alpha_reduction > opts->alpha_min ? a * opts->alpha_reduction : opts->alpha_min;
+    for (int iter = 0; iter < opts->max_iter; iter++) {
+        hipLaunchKernelGGL(k_sqp_begin, per_inst, blk, 0, s, B, d_done, w.act, w.n_open);
+        HIPCHK(h, hipGetLastError());
+        h->d_active = w.act;
+        DISPATCH_NQ(h, (launch_solve<NQ_>(h, B, dx0, dxg, dug, dp, w.xs, w.us, w.st, w.it)));
+        h->d_active = nullptr;
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_sqp_direction, dim3(B), blk, 0, s, B, nX1, nU1, w.act, dxg, dug, w.xs, w.us, w.dx, w.du, w.step);
+        HIPCHK(h, hipGetLastError());
+        // merit terms and grad f . d at the iterate
+        DISPATCH_NQ(h, (launch_merit<NQ_>(h, B, w, dx0, dxg, dug, dp, w.dx, w.du, nullptr, w.act, w.m0t)));
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_sqp_penalty, per_inst, blk, 0, s, B, opts->mu_max, w.act, w.st, w.it, w.m0t, d_mu, w.m0, w.Dd, w.alpha, w.settled,
+                           w.trial, d_status, d_iters, d_qpit);
+        HIPCHK(h, hipGetLastError());
+        // the line search: every pass evaluates the instances not yet settled at their own step length (a pass over none costs its
+        // launches only; how many instances are still searching is not read back)
+        for (int t = 0; t < n_trials; t++) {
+            DISPATCH_NQ(h, (launch_merit<NQ_>(h, B, w, dx0, dxg, dug, dp, w.dx, w.du, w.alpha, w.trial, w.mt)));
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_sqp_armijo, per_inst, blk, 0, s, B, opts->armijo, opts->alpha_reduction, opts->alpha_min, w.mt, d_mu, w.m0,
+                               w.Dd, w.alpha, w.settled, w.trial);
+            HIPCHK(h, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_sqp_finish, per_inst, blk, 0, s, B, opts->tol, w.act, w.st, w.step, w.alpha, d_mu, w.m0, w.m0t, w.mt, d_done, d_upd,
+                           d_alpha, d_before, d_merit, d_viol, w.n_open);
+        hipLaunchKernelGGL(k_sqp_commit, dim3((unsigned)(((size_t)B * (nX1 + nU1) + 63) / 64)), blk, 0, s, B, nX1, nU1, w.act, d_upd, d_alpha,
+                           w.dx, w.du, dxg, dug);
+        HIPCHK(h, hipGetLastError());
+        if (!captured && iter + 1 < opts->max_iter) {
+            int32_t open = 0;
+            HIPCHK(h, hipMemcpyAsync(&open, w.n_open, sizeof(open), hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+            if (open == 0) break;
+        }
+    }
+    return io.finish();
 }
 
 int smpc_sync(smpc_handle* h) {

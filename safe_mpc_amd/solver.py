@@ -243,6 +243,79 @@ class BatchedOcpSolver:
         self._chk(self.L.smpc_eval_nodes(self.h, B, *ptrs, out.ctypes.data, 0))
         return out
 
+    # -- SQP with merit backtracking (a11) ---------------------------------------------------------------------------------
+    def merit_terms(self, x0, x, u, p, dx=None, du=None, alpha=None, mask=None, out=None):
+        """[B, 3] = (f, viol, gd) of the l1 merit function at (x + alpha dx, u + alpha du), forward-only on the device
+        (smpc_merit_terms; the numpy statement is closed_loop.merit_terms).  gd = grad f . (dx, du) where alpha is 0 / None.
+        ``mask`` (uint8 [B]): instances with 0 are skipped and keep their row of ``out``."""
+        B = x.shape[0]
+        N, nx, nu = self.N, self.nx, self.nu
+        arrs = [x0, x, u, p, dx, du, alpha, mask]
+        shapes = [(B, nx), (B, N + 1, nx), (B, N, nu), (B, N + 1, 5), (B, N + 1, nx), (B, N, nu), (B,), (B,)]
+        ptrs, dev, keep = self._prep(arrs, shapes, [np.float64] * 7 + [np.uint8])
+        if dev:
+            import torch
+            if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError('mask must be uint8 or bool')
+            if out is None:
+                out = torch.zeros((B, 3), dtype=torch.float64, device=x.device)
+            op = out.data_ptr()
+        else:
+            out = np.zeros((B, 3)) if out is None else out
+            assert out.dtype == np.float64 and out.shape == (B, 3) and out.flags.c_contiguous
+            op = out.ctypes.data
+        with self._ordered(dev):
+            self._chk(self.L.smpc_merit_terms(self.h, B, *ptrs, op, dev))
+        return out
+
+    def new_sqp_state(self, B, like=None, mu0=10.0):
+        """the per-instance in/out arrays of :meth:`sqp` (smpc_sqp_state) at their start values, numpy or on ``like``'s device"""
+        if like is not None and _is_torch(like):
+            import torch
+            tdt = {'f8': torch.float64, 'u1': torch.uint8, 'i4': torch.int32}
+            st = {k: torch.zeros((B,), dtype=tdt[dt], device=like.device) for k, dt in _lib.SqpState.FIELDS}
+            st['mu'].fill_(float(mu0))
+        else:
+            st = {k: np.zeros(B, dt) for k, dt in _lib.SqpState.FIELDS}
+            st['mu'][:] = float(mu0)
+        return st
+
+    def sqp(self, x0, x_guess, u_guess, p, opts=None, state=None):
+        """SQP with l1-merit backtracking for B instances on the device (smpc_sqp_batch): up to ``opts.max_iter`` iterations from
+        (x_guess, u_guess), resuming from ``state`` (a dict from :meth:`new_sqp_state`, updated in place) when given.  ``opts``: an
+        _lib.SqpOpts, a dict of its fields, or None for generate_guess' defaults with max_iter = 1.  Torch tensors are updated in
+        place; numpy arrays are copied.  Returns (x_guess, u_guess, state)."""
+        B = x0.shape[0]
+        N, nx, nu = self.N, self.nx, self.nu
+        if opts is None or isinstance(opts, dict):
+            opts = _lib.SqpOpts(**(opts or {}))
+        dev = _is_torch(x0)
+        if not dev:
+            x_guess = np.array(x_guess, np.float64, order='C', copy=True)
+            u_guess = np.array(u_guess, np.float64, order='C', copy=True)
+        if state is None:
+            state = self.new_sqp_state(B, x0, opts.mu0)
+        ptrs, dev, keep = self._prep([x0, x_guess, u_guess, p], [(B, nx), (B, N + 1, nx), (B, N, nu), (B, N + 1, 5)])
+        if not dev:
+            ptrs[1], ptrs[2] = x_guess.ctypes.data, u_guess.ctypes.data
+        sp = []
+        for k, dt in _lib.SqpState.FIELDS:
+            a = state[k]
+            if _is_torch(a) != bool(dev):
+                raise TypeError('mix of torch and numpy arguments')
+            if dev:
+                if not a.is_cuda or not a.is_contiguous() or tuple(a.shape) != (B,) or a.element_size() != np.dtype(dt).itemsize:
+                    raise ValueError(f'SQP state {k}: expected a contiguous [{B}] device tensor of {dt}')
+                sp.append(a.data_ptr())
+            else:
+                if a.dtype != np.dtype(dt) or a.shape != (B,) or not a.flags.c_contiguous:
+                    raise ValueError(f'SQP state {k}: expected a contiguous [{B}] array of {dt}')
+                sp.append(a.ctypes.data)
+        cst = _lib.SqpState(*sp)
+        with self._ordered(dev):
+            self._chk(self.L.smpc_sqp_batch(self.h, B, C.byref(opts), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(cst), dev))
+        return x_guess, u_guess, state
+
     # -- callers around the solve (a13, a15, a16) ------------------------------------------------------------------------
     def guess_correction(self, x_guess, u_guess):
         """In place on torch tensors; returns a corrected copy for numpy."""

@@ -6,7 +6,9 @@ workload size (B = 4096, Z1, N = 30), next to the plain-policy number bench.py r
     python scripts/policy_bench.py [controller ...]      (default: st htwa receding)
 SMPC_WARM=1: start from generate_guess warm starts (full SQP with merit backtracking on the hard-terminal OCP, as the reference's
 guess_acados.py writes them for every safe-set controller, utils.py:46-58, and scripts/mpc.py:79-84 loads them) instead of the
-constant guess -- what the reference times; the share of infeasible QPs is then the policy's, not the cold start's."""
+constant guess -- what the reference times; the share of infeasible QPs is then the policy's, not the cold start's.
+SMPC_WARM_DEVICE=1: generate them with the engine's device-resident SQP (generate_guess(on_device=True), smpc_sqp_batch) instead of
+the host loop; SMPC_WARM_STATS=1 runs the generation a second time with a history, to report SQP iterations and trial passes."""
 import os
 import sys
 import time
@@ -34,12 +36,23 @@ def main():
         import copy
         pg = copy.copy(par)
         pg.nlp_max_iter = int(os.environ.get('SMPC_SQP_ITERS', '60'))
+        on_dev = os.environ.get('SMPC_WARM_DEVICE', '0') == '1'
         t0 = time.perf_counter()
-        guess, good = cl.generate_guess(pg, 'htwa', B)
+        guess, good = cl.generate_guess(pg, 'htwa', B, on_device=on_dev)
         xg, ug = guess['xg'], guess['ug']
         B = len(xg)
-        print(f'warm starts: {good.sum()} of {len(good)} Halton starts accepted by checkGuess after <= {pg.nlp_max_iter} SQP iterations '
-              f'({time.perf_counter() - t0:.1f} s); running {B} instances', flush=True)
+        print(f'warm starts ({"device" if on_dev else "host"} SQP): {good.sum()} of {len(good)} Halton starts accepted by checkGuess after '
+              f'<= {pg.nlp_max_iter} SQP iterations ({time.perf_counter() - t0:.2f} s); running {B} instances', flush=True)
+        if os.environ.get('SMPC_WARM_STATS', '0') == '1':
+            hist = []
+            t0 = time.perf_counter()
+            cl.generate_guess(pg, 'htwa', len(good), on_device=on_dev, history=hist)
+            dt = time.perf_counter() - t0
+            # trial passes of an iteration: the position of the smallest accepted step length on the ladder 1, 0.7, .., 0.05
+            passes = [1 + int(np.ceil(np.log(h['alpha'][h['updated']].min()) / np.log(0.7) - 1e-9)) if h['updated'].any() else 1 for h in hist]
+            print(f'  with a history: {len(hist)} SQP iterations in {dt:.2f} s = {1e3 * dt / len(hist):.2f} ms per iteration, '
+                  f'mean trial passes per iteration {np.mean(np.minimum(passes, 10)):.2f}, '
+                  f'instances updated per iteration {np.mean([h["updated"].sum() for h in hist]):.0f}', flush=True)
     for name in names:
         for dev in (True, False):
             if not dev and os.environ.get('SMPC_HOST', '0') != '1':

@@ -1,0 +1,333 @@
+"""The device-resident SQP (smpc_merit_terms, smpc_sqp_batch) against the host statement the package ships: numpy
+``closed_loop.merit_terms`` and the loop body of ``closed_loop.generate_guess``.  -m gpu only.
+
+Tolerances: 1e-9 (1 + |.|) for everything that is FP64 end to end (the tolerance of the linearisation parity tests), 2e-5 (1 + |.|)
+for the part of the violation that passes through the fp32 network (test_gpu_parity's tolerance for the network's value)."""
+import types
+
+import numpy as np
+import pytest
+
+from conftest import constant_guess, make_problem, make_problem_fr7, sample_instances
+
+pytestmark = pytest.mark.gpu
+
+
+def _solver(prob, net):
+    from safe_mpc_amd.solver import BatchedOcpSolver
+    return BatchedOcpSolver(prob, net)
+
+
+def _host_ctrl(par, prob, s, p):
+    """what closed_loop.merit_terms reads of a controller"""
+    return types.SimpleNamespace(problem=prob, ocp_solver=s, p=p, N=prob.N, nq=prob.nq, params=par)
+
+
+def _violation_classes(par, prob, s, x0, x, u, p):
+    """the classes of the l1 violation of closed_loop.merit_terms, separately, per instance (numpy, from smpc_eval_nodes)"""
+    d, nq, N, dt = prob.desc, prob.nq, prob.N, par.dt
+    ev = s.eval_nodes(x, u, p)
+    pos = lambda a: np.maximum(a, 0.0)
+    xn = np.empty_like(x[:, 1:])
+    xn[:, :, :nq] = x[:, :-1, :nq] + dt * x[:, :-1, nq:] + 0.5 * dt * dt * u
+    xn[:, :, nq:] = x[:, :-1, nq:] + dt * u
+    lo = np.tile(prob.lbx, (N + 1, 1)); hi = np.tile(prob.ubx, (N + 1, 1))
+    lo[N], hi[N] = prob.lbx_e, prob.ubx_e
+    out = {'defect': np.abs(x[:, 1:] - xn).sum(axis=(1, 2)),
+           'box': (pos(lo[1:] - x[:, 1:]) + pos(x[:, 1:] - hi[1:])).sum(axis=(1, 2)),
+           'torque': pos(np.abs(np.asarray(ev['tau'])[:, :N, :nq]) - prob.tau_max).sum(axis=(1, 2))}
+    if d.n_rows:
+        rv = np.asarray(ev['row_val'])[:, 1:, :d.n_rows]
+        lb = np.where(np.abs(prob.row_lb) < 1e5, prob.row_lb, -np.inf)
+        ub = np.where(np.abs(prob.row_ub) < 1e5, prob.row_ub, np.inf)
+        out['rows'] = (pos(lb - rv) + pos(rv - ub)).sum(axis=(1, 2))
+    if d.nn_mode != 0:
+        on = p[:, :, 4] > 0
+        on[:, 0] = False
+        if d.nn_mode == 1:
+            on[:, :N] = False
+        out['safe'] = (pos(-np.asarray(ev['nn_val'])) * on).sum(1)
+    return out
+
+
+@pytest.mark.parametrize('case', ['naive', 'htwa', 'receding', 'fr7'])
+def test_merit_terms_match_the_numpy_statement(case):
+    """smpc_merit_terms at trial points x + a dx ((dx, du) a solved RTI step, a random in [0.05, 1]) against numpy merit_terms on
+    the same handle: f, gd and the network-free part of viol within 1e-9 (1 + |.|), the safe-set part within 2e-5 (1 + |.|); every
+    violation class the case has is non-zero somewhere; two calls give the same bits; masked-out instances keep a sentinel."""
+    from safe_mpc_amd import closed_loop as cl
+    if case == 'fr7':
+        par, prob, net = make_problem_fr7()
+    else:
+        par, prob, net = make_problem(case, 'ext', N=20)
+    s = _solver(prob, net)
+    B, N, nq = 64, prob.N, prob.nq
+    rng = np.random.default_rng(11)
+    x0 = sample_instances(prob, B, seed=3, vel_scale=0.3)
+    xg, ug, p = constant_guess(prob, x0, alpha=par.alpha)
+    xg[:, 1:] += 0.05 * rng.standard_normal(xg[:, 1:].shape)
+    ug += rng.uniform(-2, 2, ug.shape)
+    if case == 'receding':
+        p[:, :, 4] = np.where(rng.uniform(size=(B, N + 1)) < 0.5, 1.0, 0.0)      # some switches off
+        assert (p[:, 1:, 4] <= 0).any() and (p[:, 1:, 4] > 0).any()
+    xs, us, st, it = s.solve(x0, xg, ug, p)
+    dx, du = np.asarray(xs) - xg, np.asarray(us) - ug
+    fin = np.isfinite(dx).reshape(B, -1).all(1) & np.isfinite(du).reshape(B, -1).all(1)
+    dx[~fin], du[~fin] = 0.0, 0.0
+    a = rng.uniform(0.05, 1.0, B)
+    want = ['defect', 'box', 'torque'] + (['rows'] if prob.desc.n_rows else []) + (['safe'] if prob.desc.nn_mode != 0 else [])
+    for scale in (1.0, 2.0, 4.0, 8.0, 16.0, 32.0):
+        xt, ut = xg + a[:, None, None] * (scale * dx), ug + a[:, None, None] * (scale * du)
+        cls = _violation_classes(par, prob, s, x0, xt, ut, p)
+        if all((cls[k] > 0).any() for k in want):
+            break
+    assert all((cls[k] > 0).any() for k in want), {k: float(cls[k].max()) for k in want}
+    dx, du = scale * dx, scale * du
+    xt, ut = xg + a[:, None, None] * dx, ug + a[:, None, None] * du
+
+    ctrl = _host_ctrl(par, prob, s, p)
+    p_off = p.copy()
+    p_off[:, :, 4] = 0.0                                                       # the same problem without its safe-set rows
+    ctrl_off = _host_ctrl(par, prob, s, p_off)
+    close = lambda got, ref, tol: np.all(np.abs(got - ref) <= tol * (1.0 + np.abs(ref)))
+    # at the trial points
+    f_h, _, _, c_h = cl.merit_terms(ctrl, x0, xt, ut)
+    _, _, _, cfree_h = cl.merit_terms(ctrl_off, x0, xt, ut)
+    got = s.merit_terms(x0, xg, ug, p, dx, du, a)
+    got_off = s.merit_terms(x0, xg, ug, p_off, dx, du, a)
+    print(case, 'f', np.abs(got[:, 0] - f_h).max(), 'free', np.abs(got_off[:, 1] - cfree_h).max(), 'safe',
+          np.abs((got[:, 1] - got_off[:, 1]) - (c_h - cfree_h)).max())
+    assert close(got[:, 0], f_h, 1e-9)
+    assert close(got_off[:, 1], cfree_h, 1e-9)
+    assert close(got[:, 1] - got_off[:, 1], c_h - cfree_h, 2e-5)
+    assert np.all(got[:, 2] == 0.0)
+    # at the iterate, with the directional derivative of the cost
+    f0, gq, gu, c0 = cl.merit_terms(ctrl, x0, xg, ug)
+    _, _, _, c0free = cl.merit_terms(ctrl_off, x0, xg, ug)
+    gd_h = (gq * dx[:, :, :nq]).sum(axis=(1, 2)) + (gu * du).sum(axis=(1, 2))
+    g0 = s.merit_terms(x0, xg, ug, p, dx, du)
+    g0_off = s.merit_terms(x0, xg, ug, p_off, dx, du)
+    print(case, 'gd', np.abs(g0[:, 2] - gd_h).max(), np.abs(gd_h).max())
+    assert close(g0[:, 0], f0, 1e-9) and close(g0[:, 2], gd_h, 1e-9)
+    assert close(g0_off[:, 1], c0free, 1e-9) and close(g0[:, 1] - g0_off[:, 1], c0 - c0free, 2e-5)
+    plain = s.merit_terms(x0, xg, ug, p)                                      # no step at all: the point is (x, u), gd = 0
+    assert np.array_equal(plain[:, :2], g0[:, :2]) and np.all(plain[:, 2] == 0.0)
+    # the same bits twice; masked-out instances keep what was there
+    assert np.array_equal(got, s.merit_terms(x0, xg, ug, p, dx, du, a))
+    mask = (rng.uniform(size=B) < 0.5).astype(np.uint8)
+    out = np.full((B, 3), -7.5)
+    s.merit_terms(x0, xg, ug, p, dx, du, a, mask=mask, out=out)
+    assert np.all(out[mask == 0] == -7.5) and np.array_equal(out[mask != 0], got[mask != 0])
+
+
+# ---- the iteration --------------------------------------------------------------------------------------------------------------
+def _guess_problem():
+    """the set-up of the existing guess tests: htwa, N = 20, 48 Halton starts, constant guess (generate_guess' first lines)"""
+    from safe_mpc_amd import controller as C
+    from safe_mpc_amd.closed_loop import halton
+    from safe_mpc_amd.parser import Parameters
+    par = Parameters({}, 'z1')
+    par.nq, par.n_dof_safe_set, par.net_size, par.N, par.nlp_max_iter = 6, 6, [12, 256, 1], 20, 200
+    n = 48
+    ctrl = C.get_controller('htwa', par, n)
+    pr, nq = ctrl.problem, ctrl.problem.nq
+    q = pr.x_min[:nq] + halton(4 * n + 16, nq) * (pr.x_max[:nq] - pr.x_min[:nq])
+    x_all = np.hstack([q, np.zeros_like(q)])
+    free = np.asarray(ctrl.ocp_solver.check_trajectory(x_all[:, None, :], tol_x=0.0))
+    x0 = x_all[free][:n]
+    assert len(x0) == n
+    ctrl.setGuess(np.repeat(x0[:, None, :], ctrl.N + 1, axis=1), np.zeros((n, ctrl.N, ctrl.nu)))
+    return par, ctrl, x0
+
+
+def _host_iteration(ctrl, x0, mu, done, status, sqp_tol=1e-6, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05):
+    """one pass of generate_guess' loop body (closed_loop.py), statement by statement, on ``ctrl``; also the smallest distance of
+    an instance's Armijo inequality from equality over the trials it took part in, relative to 1 + |m0|"""
+    from safe_mpc_amd.closed_loop import merit_terms
+    B, nq = len(x0), ctrl.nq
+    st = ctrl.solve(x0)
+    dx, du = ctrl.x_temp - ctrl.x_guess, ctrl.u_temp - ctrl.u_guess
+    step = np.maximum(np.abs(dx).reshape(B, -1).max(1), np.abs(du).reshape(B, -1).max(1))
+    f0, gq, gu, c0 = merit_terms(ctrl, x0, ctrl.x_guess, ctrl.u_guess)
+    gd = (gq * dx[:, :, :nq]).sum(axis=(1, 2)) + (gu * du).sum(axis=(1, 2))
+    need = np.where(c0 > 1e-12, 2.0 * np.maximum(gd, 0.0) / np.maximum(c0, 1e-12), 0.0)
+    mu = np.minimum(np.maximum(mu, need), 1e8)
+    m0 = f0 + mu * c0
+    D = gd - mu * c0
+    alpha = np.ones(B)
+    settled = done | (st != 0)
+    margin = np.full(B, np.inf)
+    while True:
+        xt = ctrl.x_guess + alpha[:, None, None] * dx
+        ut = ctrl.u_guess + alpha[:, None, None] * du
+        ft, _, _, ct = merit_terms(ctrl, x0, xt, ut)
+        lhs, rhs = ft + mu * ct, m0 + armijo * alpha * np.minimum(D, 0.0) + 1e-12 * (1.0 + np.abs(m0))
+        ok = lhs <= rhs
+        margin = np.where(settled, margin, np.minimum(margin, np.abs(lhs - rhs) / (1.0 + np.abs(m0))))
+        settled = settled | ok | (alpha <= alpha_min)
+        if settled.all():
+            break
+        alpha = np.where(settled, alpha, np.maximum(alpha * alpha_reduction, alpha_min))
+    upd = ~done & (st == 0)
+    ctrl.x_guess = np.where(upd[:, None, None], xt, ctrl.x_guess)
+    ctrl.u_guess = np.where(upd[:, None, None], ut, ctrl.u_guess)
+    status = np.where(~done, st, status)
+    done = done | (alpha * step < sqp_tol) | (st != 0)
+    return dict(mu=mu, done=done, status=status, alpha=np.where(upd, alpha, 0.0), updated=upd, margin=margin)
+
+
+def _state_from(s, B, mu, done, status):
+    state = s.new_sqp_state(B)
+    state['mu'][:], state['done'][:], state['status'][:] = mu, done, status
+    return state
+
+
+def test_one_sqp_iteration_matches_the_host_loop_body():
+    """From the constant guess, and again from the iterate after five (host) iterations: one smpc_sqp_batch(max_iter = 1) against one
+    pass of the host loop body.  An instance is decidable if at every trial step length the host's Armijo inequality holds or fails
+    by more than 1e-9 (1 + |m0|); for those: same updated, alpha, mu, new iterate within 1e-9 (1 + |.|inf).  At most 2 of 48 may be
+    undecidable.  An instance that is done when the iteration starts takes no part in it on the device -- no solve, no merit pass,
+    its state left as it is -- while the host loop still evaluates it (and may raise its mu, which nothing reads afterwards): such
+    an instance is held to "not updated, iterate untouched" instead."""
+    par, ctrl, x0 = _guess_problem()
+    s, B = ctrl.ocp_solver, len(x0)
+    mu, done, status = np.full(B, 10.0), np.zeros(B, bool), np.zeros(B, np.int32)
+    for start in (0, 5):
+        while start:                                  # advance the host statement to the second point of comparison
+            r = _host_iteration(ctrl, x0, mu, done, status)
+            mu, done, status = r['mu'], r['done'], r['status']
+            start -= 1
+        xg0, ug0 = ctrl.x_guess.copy(), ctrl.u_guess.copy()
+        r = _host_iteration(ctrl, x0, mu, done, status)
+        xd, ud, state = s.sqp(x0, xg0, ug0, ctrl.p, dict(max_iter=1), _state_from(s, B, mu, done, status))
+        open_ = ~done
+        dec = open_ & (r['margin'] > 1e-9)
+        print('done at entry', int(done.sum()), 'undecidable', int((open_ & ~dec).sum()), 'min margin', r['margin'][open_].min())
+        assert (open_ & ~dec).sum() <= 2
+        assert np.array_equal(state['updated'][dec].astype(bool), r['updated'][dec])
+        assert np.array_equal(state['alpha'][dec], r['alpha'][dec])
+        assert np.all(np.abs(state['mu'][dec] - r['mu'][dec]) <= 1e-9 * (1.0 + np.abs(r['mu'][dec])))
+        assert np.array_equal(state['done'][dec].astype(bool), r['done'][dec]) and np.array_equal(state['status'][dec], r['status'][dec])
+        ex = np.abs(xd - ctrl.x_guess).reshape(B, -1).max(1) / (1.0 + np.abs(ctrl.x_guess).reshape(B, -1).max(1))
+        eu = np.abs(ud - ctrl.u_guess).reshape(B, -1).max(1) / (1.0 + np.abs(ctrl.u_guess).reshape(B, -1).max(1))
+        print('iterate', ex[dec].max(), eu[dec].max())
+        assert np.all(ex[dec] <= 1e-9) and np.all(eu[dec] <= 1e-9)
+        assert np.array_equal(xd[done], xg0[done]) and np.array_equal(ud[done], ug0[done])
+        mu, done, status = r['mu'], r['done'], r['status']
+
+
+def _run(s, x0, xg, ug, p, calls, max_iter, state=None):
+    for _ in range(calls):
+        xg, ug, state = s.sqp(x0, xg, ug, p, dict(max_iter=max_iter), state)
+    return xg, ug, state
+
+
+def test_sqp_is_resumable_bit_for_bit():
+    """twelve calls with max_iter = 1 and one call with max_iter = 12 end in identical bits"""
+    par, ctrl, x0 = _guess_problem()
+    s = ctrl.ocp_solver
+    ctrl.p[:, :, 3] = par.alpha
+    xa, ua, sa = _run(s, x0, ctrl.x_guess, ctrl.u_guess, ctrl.p, 12, 1)
+    xb, ub, sb = _run(s, x0, ctrl.x_guess, ctrl.u_guess, ctrl.p, 1, 12)
+    assert np.array_equal(xa, xb) and np.array_equal(ua, ub)
+    for k in ('mu', 'done', 'status'):
+        assert np.array_equal(sa[k], sb[k]), k
+    assert np.array_equal(sa['iters'], sb['iters']) and np.array_equal(sa['qp_iter_total'], sb['qp_iter_total'])
+    assert sa['iters'].max() == 12 and not np.array_equal(xa, ctrl.x_guess)
+
+
+def test_converged_instances_cost_nothing():
+    """An instance that is done takes no part in later iterations: its iterate, its state and its qp_iter_total stay bit-identical
+    while the others go on; and once all 48 are done a further call changes no array at all.
+
+    Measured on this problem (htwa, N = 20, 48 Halton starts): the Gauss-Newton SQP converges linearly, no instance meets
+    alpha |step| < 1e-6 within 600 iterations, 29 of 48 do within 1000 and 42 within 3000 -- the remaining ones keep taking
+    alpha_min steps of about 1e-5.  So "all 48 done" is not reached by iterating alone; the second half of the test gets there by
+    marking the open instances done through the state's own in/out array, which is what a caller that gives up on them does."""
+    par, ctrl, x0 = _guess_problem()
+    s = ctrl.ocp_solver
+    ctrl.p[:, :, 3] = par.alpha
+    xg, ug, state = _run(s, x0, ctrl.x_guess, ctrl.u_guess, ctrl.p, 1, 1000)
+    done = state['done'].astype(bool)
+    print('done after 1000 iterations', int(done.sum()), 'iters', state['iters'].min(), state['iters'].max())
+    assert done.sum() >= 12 and not done.all()
+    assert np.all(state['iters'][done] < 1000) and np.all(state['iters'][~done] == 1000)
+    before = {k: v.copy() for k, v in state.items()}
+    x2, u2, state = s.sqp(x0, xg, ug, ctrl.p, dict(max_iter=3), state)
+    assert np.array_equal(x2[done], xg[done]) and np.array_equal(u2[done], ug[done])
+    for k, v in before.items():
+        assert np.array_equal(state[k][done], v[done]), k
+    assert np.all(state['iters'][~done] > 1000) and np.all(state['qp_iter_total'][~done] > before['qp_iter_total'][~done])
+    # all 48 done
+    state['done'][:] = 1
+    before = {k: v.copy() for k, v in state.items()}
+    x3, u3, state = s.sqp(x0, x2, u2, ctrl.p, dict(max_iter=3), state)
+    assert np.array_equal(x3, x2) and np.array_equal(u3, u2)
+    for k, v in before.items():
+        assert np.array_equal(state[k], v), k
+
+
+def test_sqp_device_pointers_equal_host_pointers():
+    """the same run on torch device tensors (on_device = 1) and on numpy arrays: identical bits"""
+    import torch
+    par, ctrl, x0 = _guess_problem()
+    s = ctrl.ocp_solver
+    ctrl.p[:, :, 3] = par.alpha
+    xh, uh, sh = _run(s, x0, ctrl.x_guess, ctrl.u_guess, ctrl.p, 2, 4)
+    dev = torch.device('cuda', s.device)
+    t = lambda a: torch.tensor(a, dtype=torch.float64, device=dev)
+    xd, ud, x0d, pd = t(ctrl.x_guess), t(ctrl.u_guess), t(x0), t(ctrl.p)
+    sd = None
+    for _ in range(2):
+        _, _, sd = s.sqp(x0d, xd, ud, pd, dict(max_iter=4), sd)
+    s.sync()
+    assert np.array_equal(xh, xd.cpu().numpy()) and np.array_equal(uh, ud.cpu().numpy())
+    for k in sh:
+        assert np.array_equal(sh[k], sd[k].cpu().numpy()), k
+    # and the merit terms through device pointers
+    xs, us, _, _ = s.solve(x0, ctrl.x_guess, ctrl.u_guess, ctrl.p)
+    dx, du = np.asarray(xs) - ctrl.x_guess, np.asarray(us) - ctrl.u_guess
+    a = np.linspace(0.05, 1.0, len(x0))
+    mh = s.merit_terms(x0, ctrl.x_guess, ctrl.u_guess, ctrl.p, dx, du, a)
+    md = s.merit_terms(x0d, t(ctrl.x_guess), t(ctrl.u_guess), pd, t(dx), t(du), t(a))
+    s.sync()
+    assert np.array_equal(mh, md.cpu().numpy())
+
+
+def test_generate_guess_on_device_matches_the_host_path():
+    """generate_guess(on_device=True) against generate_guess on the host path, on the criteria of
+    test_generate_guess_merit_backtracking_on_engine and test_generate_guess_engine_matches_oracle_double: the same accepted set,
+    at least 24 accepted, per accepted instance either the warm start within 1e-4 (1 + |.|inf) (for at least 90 %) or the same final
+    merit within 1e-6 relative, final violation < 1e-5, merit non-increasing along accepted steps with alpha > 0.05, checkGuess on a
+    fresh controller."""
+    from safe_mpc_amd import closed_loop as cl
+    from safe_mpc_amd import controller as C
+    from safe_mpc_amd.parser import Parameters
+    par = Parameters({}, 'z1')
+    par.nq, par.n_dof_safe_set, par.net_size, par.N, par.nlp_max_iter = 6, 6, [12, 256, 1], 20, 200
+    h0, h1 = [], []
+    g0, good0 = cl.generate_guess(par, 'htwa', 48, history=h0)
+    g1, good1 = cl.generate_guess(par, 'htwa', 48, on_device=True, history=h1)
+    print('accepted', int(good0.sum()), int(good1.sum()), 'iterations', len(h0), len(h1))
+    assert np.array_equal(good0, good1), (np.where(good0)[0], np.where(good1)[0])
+    assert good1.sum() >= 24 and g1['xg'].shape == (good1.sum(), 21, 12)
+    x0_, u0_, x1_, u1_ = g0['xg'], g0['ug'], g1['xg'], g1['ug']
+    ex = np.abs(x1_ - x0_).reshape(len(x0_), -1).max(1) / (1.0 + np.abs(x0_).reshape(len(x0_), -1).max(1))
+    eu = np.abs(u1_ - u0_).reshape(len(u0_), -1).max(1) / (1.0 + np.abs(u0_).reshape(len(u0_), -1).max(1))
+    close = (ex < 1e-4) & (eu < 1e-4)
+    m0, m1 = h0[-1]['merit'][good0], h1[-1]['merit'][good1]
+    same_merit = np.abs(m1 - m0) <= 1e-6 * (1.0 + np.abs(m0))
+    print('close', close.mean(), 'ex', ex.max(), 'eu', eu.max(), 'merit', np.abs(m1 - m0).max())
+    assert np.all(close | same_merit), (ex.max(), eu.max(), np.abs(m1 - m0).max())
+    assert close.mean() >= 0.9, close.mean()
+    assert np.all(h1[-1]['violation'][good1] < 1e-5)
+    assert set(h1[0]) == set(h0[0])
+    for h in h1:
+        up = h['updated'] & (h['alpha'] > 0.05)
+        assert np.all(h['merit'][up] <= h['merit_before'][up] + 1e-9 * (1 + np.abs(h['merit_before'][up])))
+    ctrl = C.get_controller('htwa', par, int(good1.sum()))
+    ctrl.x_temp, ctrl.u_temp = g1['xg'].copy(), g1['ug'].copy()
+    assert np.all(ctrl.checkGuess())
+    # without a history the engine runs every iteration in one call: the same guesses, bit for bit
+    g2, good2 = cl.generate_guess(par, 'htwa', 48, on_device=True)
+    assert np.array_equal(good2, good1) and np.array_equal(g2['xg'], g1['xg']) and np.array_equal(g2['ug'], g1['ug'])
