@@ -30,6 +30,7 @@
  * derivatives of the recursion (no dual numbers) and wave-cooperative LDS tiles.
  */
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -803,6 +804,8 @@ int qp_ipm(std::vector<Stage>& S, int N, int nx, int nu, double dt, const double
 
     double mu = mu_now();
     int stall = 0, stall_total = 0;
+    static thread_local std::vector<std::array<double, MAXZ>> z_before;   /* the iterate before the last step */
+    z_before.resize(N + 1);
     for (it = 0; it < o.max_iter; it++) {
         if (mu <= o.tol && rho * R0 <= o.tol_res) { status = 0; break; }
         if (!factorize()) { status = 4; break; }
@@ -845,7 +848,7 @@ int qp_ipm(std::vector<Stage>& S, int N, int nx, int nu, double dt, const double
         for (int k = 0; k <= N; k++) {
             Stage& s = S[k];
             int nz = s.nu + nx;
-            for (int i = 0; i < nz; i++) s.z[i] += alpha * (s.zn[i] - s.z[i]);
+            for (int i = 0; i < nz; i++) { z_before[k][i] = s.z[i]; s.z[i] += alpha * (s.zn[i] - s.z[i]); }
             for (int r = 0; r < s.nr; r++) {
                 if (s.has_lo[r]) {
                     s.tl[r] += alpha * s.dtl[r];
@@ -870,7 +873,14 @@ int qp_ipm(std::vector<Stage>& S, int N, int nx, int nu, double dt, const double
         if (std::getenv("SMPC_ORACLE_TRACE"))
             std::fprintf(stderr, "it %3d a_aff %.3e sigma %.3e alpha %.3e mu %.3e rho*R0 %.3e  blocked by stage %d row %d (tl %.2e ll %.2e tu %.2e lu %.2e)\n",
                          it, a_aff, sigma, alpha, mu, rho * R0, blk_k, blk_r, S[blk_k].tl[blk_r], S[blk_k].ll[blk_r], S[blk_k].tu[blk_r], S[blk_k].lu[blk_r]);
-        if (!(mu == mu)) { status = 4; break; }
+        if (!(mu == mu)) {
+            /* a step that leaves no number behind is not part of the returned iterate (the engine knows the new complementarity
+             * before it applies the step, and drops it) */
+            for (int k = 0; k <= N; k++)
+                for (int i = 0; i < S[k].nu + nx; i++) S[k].z[i] = z_before[k][i];
+            status = 4;
+            break;
+        }
     }
     if (it == o.max_iter && status == 2 && mu <= o.tol && rho * R0 <= o.tol_res) status = 0;
     *iters = it;

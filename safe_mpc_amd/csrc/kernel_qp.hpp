@@ -1490,7 +1490,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         // sum(lambda t) is a quadratic in the step length: the new complementarity is known before the step is applied
         const double mu_before = mu;
         mu = (mu * (double)m_comp + alpha * S1c + alpha * alpha * S2c) * inv_m;
-        if (!(mu == mu)) { st_code = 4; pending = false; break; }
+        if (!(mu == mu)) { st_code = 4; pending = false; break; }    // (a step that leaves no number behind is dropped: oracle, mu_now)
         // a stalled iteration: a short step that did not halve the complementarity either (a degenerate but feasible QP
         // crawls with short steps while mu still falls); an iterate that meets the exit test is never reported as stalled
         // ... stall_max of them in a row, or 7/6 of that in total (an infeasible QP whose complementarity falls in bursts resets the run
@@ -1524,7 +1524,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
 #pragma unroll
         for (int j = 0; j < EP_CH; j++) {
             const int k = k0 + j;
-            const double v = bb[j] + zz[j] + a_fin * (zzn[j] - zz[j]);
+            // (nothing pending: z+ may hold anything, also from a sweep that met no number -- 0 x that is not 0)
+            const double v = pending ? bb[j] + zz[j] + a_fin * (zzn[j] - zz[j]) : bb[j] + zz[j];
             if (k <= N) {
                 if (hl < NU) {
                     if (k < N) { u_out[((size_t)b * N + k) * NU + hl] = v; bad |= !(v == v); }

@@ -1088,19 +1088,19 @@ __global__ __launch_bounds__(32 * NHW) __attribute__((amdgpu_waves_per_eu(QP_WG_
     // ---- full SQP step, applying the last IPM step if it is still pending (stage-parallel) --------------------------------
     __syncthreads();
     double bad = 0.0;
-    const double a_fin = pending ? alpha : 0.0;
+    const double a_fin = pending ? alpha : 0.0;    // (nothing pending: z+ may hold anything -- 0 x that is not 0, so it is not read into v)
     for (int idx = tid; idx < (N + 1) * NZ; idx += NT) {
         const int k = idx / NZ, c = idx - k * NZ;
         const double* w = ws + (size_t)k * Ly.stride;
         const double zz = w[Ly.oZ + c], zzn = w[Ly.oZN + c];
         if (c < NU) {
             if (k < N) {
-                const double v = ub0[(size_t)k * NU + c] + zz + a_fin * (zzn - zz);
+                const double v = pending ? ub0[(size_t)k * NU + c] + zz + a_fin * (zzn - zz) : ub0[(size_t)k * NU + c] + zz;
                 u_out[((size_t)b * N + k) * NU + c] = v;
                 bad = !(v == v) ? 1.0 : bad;
             }
         } else {
-            const double v = xb0[(size_t)k * NX + c - NU] + zz + a_fin * (zzn - zz);
+            const double v = pending ? xb0[(size_t)k * NX + c - NU] + zz + a_fin * (zzn - zz) : xb0[(size_t)k * NX + c - NU] + zz;
             x_out[((size_t)b * (N + 1) + k) * NX + c - NU] = v;
             bad = !(v == v) ? 1.0 : bad;
         }
