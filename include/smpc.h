@@ -294,6 +294,35 @@ typedef struct {             /* per-instance arrays [B], read AND written: a cal
 int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const double* x0, double* x_guess, double* u_guess,
                    const double* p, const smpc_sqp_state* state, int on_device);
 
+/* The acceptance test of a warm start, AbstractController.checkGuess (guess_acados.py:118: `status in (0, 2) and checkGuess()`),
+ * per instance and forward-only, so that a device-resident SQP batch can be asked between two smpc_sqp_batch calls which of its
+ * instances are acceptable.  flags[B]: bit i set = predicate i FAILS (a NaN fails); worst[B][5]: the value each predicate tests.
+ *   0  state box on nodes 0..N (env_model.py:170-172): max over nodes, components of max(x_min - x, x - x_max)   passes: <= tol_x
+ *   1  collision rows (env_model.py:236-243), on node 0 only when collision_first_node != 0, on every node otherwise: max over the
+ *      tested nodes and rows of max(row_lb_chk - v, v - row_ub_chk); -inf without rows                            passes: <= 0
+ *   2  torque on nodes 0..N-1 (env_model.py:179-182): max of max(tau_min - tau, tau - tau_max)                    passes: <= tol_tau
+ *   3  dynamics (env_model.py:226-234, the controller's own model: what smpc_guess_correction rolls out from node 0):
+ *      |x - x_sim|_2 over the whole trajectory                                                     passes: < tol_dyn sqrt(N + 1)
+ *   4  safe set at node safe_node (safe_set.py:61-68): -g(x, alpha); safe_node < 0: not tested, bit clear, -inf
+ *                                                                         passes: g >= -tol_safe && g <= 1e6 + tol_safe */
+typedef struct {
+    double tol_x, tol_tau, tol_dyn, tol_safe, alpha;
+    int32_t collision_first_node;   /* as smpc_policy_params */
+    int32_t safe_node;              /* node of the safe-set test (N for the terminal-set controllers), < 0: none */
+    const double *x_min, *x_max;            /* HOST [nx]   */
+    const double *tau_min, *tau_max;        /* HOST [nq]   */
+    const double *row_lb_chk, *row_ub_chk;  /* HOST [n_rows] */
+} smpc_guess_check;
+
+/* x [B][N+1][nx], u [B][N][nu]; mask[B] (bytes, may be NULL): instances with mask[b] == 0 are skipped and their flags[b] /
+ * worst[b] left as they are (so both are read as well as written on the host path).  Sums are formed in a fixed order: two calls
+ * give the same bits.  x, u, mask, flags, worst follow on_device like smpc_merit_terms; with device pointers the call only
+ * enqueues.  The small host arrays of `par` are kept in a device block of the handle and uploaded only when they change.
+ * SMPC_ESTATE: safe_node >= 0 without a network, or scratch / the bounds block would have to change while the stream is being
+ * captured.  SMPC_EINVAL: safe_node > N.  (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, const smpc_guess_check* par,
+                     const uint8_t* mask, int32_t* flags, double* worst, int on_device);
+
 /* ---- callers on either side of the solve ------------------------------------------- */
 /* guessCorrection (controller.py:226-231): x_guess[k+1] = f(x_guess[k], u_guess[k]) in place. */
 int smpc_guess_correction(smpc_handle* h, int B, double* xg, const double* ug, int on_device);

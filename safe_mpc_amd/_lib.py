@@ -19,7 +19,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_provide_control', 'smpc_check_trajectory', 'smpc_plant_step', 'smpc_rollout_batch', 'smpc_sync', 'smpc_stream',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
-           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch']
+           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess']
 
 
 class EngineError(RuntimeError):
@@ -62,6 +62,13 @@ class SqpState(C.Structure):
     FIELDS = (('mu', 'f8'), ('done', 'u1'), ('status', 'i4'), ('alpha', 'f8'), ('merit_before', 'f8'), ('merit', 'f8'),
               ('violation', 'f8'), ('updated', 'u1'), ('iters', 'i4'), ('qp_iter_total', 'i4'))
     _fields_ = [(k, _vp) for k, _ in FIELDS]
+
+
+class GuessCheck(C.Structure):
+    """smpc_guess_check: tolerances, the two node choices and HOST pointers to the bounds of smpc_check_guess"""
+    _fields_ = [('tol_x', C.c_double), ('tol_tau', C.c_double), ('tol_dyn', C.c_double), ('tol_safe', C.c_double), ('alpha', C.c_double),
+                ('collision_first_node', C.c_int32), ('safe_node', C.c_int32),
+                ('x_min', _vp), ('x_max', _vp), ('tau_min', _vp), ('tau_max', _vp), ('row_lb_chk', _vp), ('row_ub_chk', _vp)]
 
 
 def build(force=False):
@@ -122,5 +129,6 @@ def lib():
     L.smpc_set_qp_mode.argtypes = [vp, C.c_int]
     L.smpc_merit_terms.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_sqp_batch.argtypes = [vp, C.c_int, C.POINTER(SqpOpts), dp, dp, dp, dp, C.POINTER(SqpState), C.c_int]
+    L.smpc_check_guess.argtypes = [vp, C.c_int, dp, dp, C.POINTER(GuessCheck), dp, dp, dp, C.c_int]
     _lib = L
     return L

@@ -1,6 +1,7 @@
 """Batched versions of the reference's two live entry points, as library functions:
 
 * :func:`generate_guess`  -- scripts/guess_acados.py:72-158,235-244 (warm starts by SQP to convergence)
+* :func:`generate_guess_until` -- the same with the reference's ``while succ < num_ics``: on the device, until n are accepted
 * :func:`run_mpc`         -- scripts/mpc.py:102-317 (closed loop with safe abort, failure taxonomy, result dict)
 
 Every instance of the reference's outer loop (mpc.py:102) is one row of the arrays handled here; the inner loop over MPC
@@ -10,6 +11,7 @@ steps stays a Python loop, each iteration being a handful of batched engine call
 from __future__ import annotations
 
 import copy
+import heapq
 import os
 import pickle
 
@@ -338,6 +340,214 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
     good = ((status == 0) | (status == 2)) & ctrl.checkGuess()              # guess_acados.py:115 accepts status 0 or 2
     return {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}, good
+
+
+class GuessSlots:
+    """Bookkeeping of :func:`generate_guess_until`: which sample of the stream sits in which of ``batch`` slots, who was accepted,
+    who failed.  No arrays, no engine: samples are numbers 0, 1, 2, .. in sampling order.
+
+    :meth:`issue` hands out the next samples to free slots, but only while ``accepted + in_flight < n`` -- so never more are in
+    flight than could still be needed.  :meth:`resolve` records a slot's fate and frees it.  When nothing is in flight and nothing
+    can be issued, the issued samples are a prefix of the stream, all resolved, with exactly ``n`` accepted (fewer only when
+    ``max_samples`` ran out): the first ``n`` accepted in sampling order, whatever ``batch`` was."""
+
+    def __init__(self, n, batch=None, max_samples=None):
+        self.n = int(n)
+        self.batch = max(1, min(int(batch) if batch else self.n, self.n)) if self.n > 0 else 0
+        self.max_samples = None if max_samples is None else int(max_samples)
+        self.slot_sample = [None] * self.batch      # sample in each slot, None = free
+        self._free = list(range(self.batch))        # free slots as a min-heap: the lowest free slot is filled first
+        self.in_flight = 0                          # slots that hold a sample (kept as a count: issue() asks for it per slot)
+        self.issued = 0                             # samples handed out so far = index of the next one
+        self.accepted, self.failed = [], []         # sample indices, in the order they were resolved
+
+    @property
+    def exhausted(self):
+        """max_samples ran out before n samples were accepted"""
+        return (self.max_samples is not None and self.issued >= self.max_samples and self.in_flight == 0
+                and len(self.accepted) < self.n)
+
+    def live(self):
+        """[(slot, sample)] of the slots in flight, by slot"""
+        return [(k, s) for k, s in enumerate(self.slot_sample) if s is not None]
+
+    def issue(self):
+        """fill free slots with the next samples while accepted + in_flight < n; returns [(slot, sample)] issued now"""
+        out = []
+        while self._free and len(self.accepted) + self.in_flight < self.n:
+            if self.max_samples is not None and self.issued >= self.max_samples:
+                break
+            k = heapq.heappop(self._free)
+            self.slot_sample[k] = self.issued
+            self.in_flight += 1
+            out.append((k, self.issued))
+            self.issued += 1
+        return out
+
+    def resolve(self, slot, accepted):
+        s = self.slot_sample[slot]
+        if s is None:
+            raise ValueError(f'slot {slot} is free')
+        (self.accepted if accepted else self.failed).append(s)
+        self.slot_sample[slot] = None
+        heapq.heappush(self._free, slot)
+        self.in_flight -= 1
+        return s
+
+    def finished(self):
+        return self.in_flight == 0 and (len(self.accepted) >= self.n or
+                                        (self.max_samples is not None and self.issued >= self.max_samples))
+
+    def result_order(self):
+        """accepted samples in sampling order: the order of the returned guesses"""
+        return sorted(self.accepted)
+
+
+class _FreeStarts:
+    """The sample stream of generate_guess in chunks: Halton q0 in the joint box at rest (guess_acados.py:100), collision filter
+    (:109).  ``take(j)`` = the j-th free start, whatever the chunking.  A filter that lets nothing through (check bounds that no
+    configuration meets, a fully obstructed box) would draw for ever: after ``max_barren`` chunks in a row without one free start
+    ``take`` raises."""
+
+    def __init__(self, solver, problem, chunk=256, max_barren=64):
+        self.sv, self.pr, self.chunk, self.max_barren = solver, problem, int(chunk), int(max_barren)
+        self.drawn = 0
+        self.x = np.zeros((0, problem.nx))
+
+    def take(self, j):
+        pr, nq = self.pr, self.pr.nq
+        barren = 0
+        while j >= len(self.x):
+            q = pr.x_min[:nq] + halton(self.chunk, nq, skip=1 + self.drawn) * (pr.x_max[:nq] - pr.x_min[:nq])
+            self.drawn += self.chunk
+            x_all = np.hstack([q, np.zeros_like(q)])
+            free = np.asarray(self.sv.check_trajectory(x_all[:, None, :], tol_x=0.0)).astype(bool)
+            barren = 0 if free.any() else barren + 1
+            if barren >= self.max_barren:
+                raise RuntimeError(f'the collision filter rejected {barren * self.chunk} Halton starts in a row ({self.drawn} drawn, '
+                                   f'{len(self.x)} free so far): no collision-free start to sample')
+            self.x = np.vstack([self.x, x_all[free]])
+        return self.x[j]
+
+
+def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accept='final', max_samples=None, make_controller=None,
+                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05):
+    """guess_acados.py:98-158 with its ``while succ < num_ics``: sample, solve and test warm starts until ``n`` are ACCEPTED, on
+    the device.  Returns ``(guess, info)``: ``guess['xg'] [n, N+1, nx]``, ``guess['ug'] [n, N, nu]`` in sampling order.
+
+    The sample stream is :func:`generate_guess`'s (sample j = its j-th collision-free Halton start, constant guess, mu = mu0).
+    ``B = min(batch or n, n)`` slots live on the device.  A round is ``solver.sqp(max_iter=check_every)`` on all slots followed by
+    one ``solver.check_guess`` (smpc_check_guess) on the live ones; the host then reads flags, status, done and iters -- a few
+    bytes per slot -- and decides each live sample's fate:
+
+    * ``accept='final'`` (the reference's rule, what generate_guess applies): once the sample is done or has used its budget, it
+      is accepted if ``status in (0, 2)`` and ``flags == 0`` and fails otherwise.
+    * ``accept='first'``: accepted at the first round where ``status == 0`` and ``flags == 0``; it fails when it is done
+      otherwise or has used its budget.
+
+    The budget is ``params.nlp_max_iter`` ROUNDED UP to a multiple of ``check_every``: samples are only looked at between rounds.
+    Resolved slots get ``done = 1`` in the SQP state, so they cost nothing until they are refilled, which happens only between
+    rounds and only while ``accepted + in_flight < n`` (:class:`GuessSlots`).  The result is therefore the first ``n`` accepted
+    samples of the stream in sampling order, whatever ``batch`` is.  WHICH samples those are, and their bits, do not depend on
+    ``batch`` only if a sample's SQP does not: the engine picks the form of the QP solve and the network kernel by the width of the
+    launch (smpc_set_qp_mode 'auto'), the forms agree to rounding, and over hundreds of iterations rounding can move an iteration
+    count.  Pin the form through ``make_controller`` (``ctrl.ocp_solver.set_qp_mode('throughput')``) where bit-identical results
+    across batch sizes are wanted; the tests do.  With ``max_samples`` the stream stops after that many
+    samples and ``info['exhausted']`` says whether that cut the result short.
+
+    ``info``: 'accepted' / 'failed' (sample indices, sampling order), 'iters' (SQP iterations of every issued sample),
+    'status', 'flags' (at the sample's resolution), 'issued', 'rounds', 'instance_iterations', 'exhausted'."""
+    if accept not in ('final', 'first'):
+        raise ValueError("accept must be 'final' or 'first'")
+    check_every = int(check_every)
+    if check_every < 1:
+        raise ValueError('check_every must be >= 1')
+    make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
+    book = GuessSlots(n, batch, max_samples)
+    B = max(book.batch, 1)
+    ctrl = make_controller(cont_name, B)
+    sv = ctrl.ocp_solver
+    if not hasattr(sv, 'sqp') or not hasattr(sv, 'check_guess'):
+        raise ValueError(f'generate_guess(on_device=True) needs a solver with a device SQP (BatchedOcpSolver.sqp); '
+                         f'{type(sv).__name__} has none')
+    N, nx, nu = ctrl.N, ctrl.nx, ctrl.nu
+    info = {'accepted': [], 'failed': [], 'iters': {}, 'status': {}, 'flags': {}, 'issued': 0, 'rounds': 0, 'instance_iterations': 0,
+            'exhausted': False}
+    if n <= 0:
+        return {'xg': np.zeros((0, N + 1, nx)), 'ug': np.zeros((0, N, nu))}, info
+    import torch
+    dev = torch.device('cuda', sv.device)
+    ctrl.p[:, :, 3] = ctrl.params.alpha                     # what ctrl.solve does before every solve
+    ctrl._apply_traj()
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), np.float64), device=dev)
+    p_d = to(ctrl.p)
+    x0_d = torch.zeros((B, nx), dtype=torch.float64, device=dev)
+    xg = torch.zeros((B, N + 1, nx), dtype=torch.float64, device=dev)
+    ug = torch.zeros((B, N, nu), dtype=torch.float64, device=dev)
+    opts = dict(tol=sqp_tol, armijo=armijo, alpha_reduction=alpha_reduction, alpha_min=alpha_min)
+    from ._lib import SqpOpts, SqpState
+    mu0 = SqpOpts().mu0                                     # generate_guess' start value of the penalty
+    state = sv.new_sqp_state(B, x0_d, mu0)
+    state['done'].fill_(1)                                  # a free slot is a finished instance: every kernel skips it
+    flags_d = torch.zeros((B,), dtype=torch.int32, device=dev)
+    worst_d = torch.zeros((B, 5), dtype=torch.float64, device=dev)
+    mask_d = torch.zeros((B,), dtype=torch.uint8, device=dev)
+    safe_node = N if getattr(ctrl, 'guess_safe_node', False) else None
+    budget = -(-int(params.nlp_max_iter) // check_every) * check_every
+    stream = _FreeStarts(sv, ctrl.problem)
+    got_x, got_u = {}, {}
+    while True:
+        new = book.issue()
+        if new:
+            slots = torch.as_tensor([k for k, _ in new], dtype=torch.long, device=dev)
+            xs = to(np.stack([stream.take(j) for _, j in new]))
+            x0_d[slots] = xs
+            xg[slots] = xs[:, None, :].expand(-1, N + 1, -1)
+            ug[slots] = 0.0
+            for key, _ in SqpState.FIELDS:                      # a fresh sample: the state new_sqp_state would give it
+                state[key][slots] = mu0 if key == 'mu' else 0
+        live = book.live()
+        if not live:
+            break
+        sv.sqp(x0_d, xg, ug, p_d, dict(max_iter=check_every, **opts), state)
+        mask_d.zero_()
+        live_slots = torch.as_tensor([k for k, _ in live], dtype=torch.long, device=dev)
+        mask_d[live_slots] = 1
+        sv.check_guess(xg, ug, safe_node=safe_node, mask=mask_d, flags=flags_d, worst=worst_d)
+        small = torch.stack([flags_d, state['status'], state['done'].to(torch.int32), state['iters']]).cpu().numpy()
+        fl, st, dn, it = small
+        info['rounds'] += 1
+        take, resolved = [], []
+        for k, j in live:
+            ended = bool(dn[k]) or it[k] >= budget
+            if accept == 'final':
+                ok = ended and st[k] in (0, 2) and fl[k] == 0
+            else:
+                ok = st[k] == 0 and fl[k] == 0
+            if not (ok or ended):
+                continue
+            book.resolve(k, ok)
+            resolved.append(k)
+            info['iters'][j], info['status'][j], info['flags'][j] = int(it[k]), int(st[k]), int(fl[k])
+            if ok:
+                take.append((k, j))
+        if resolved:
+            state['done'][torch.as_tensor(resolved, dtype=torch.long, device=dev)] = 1
+        if take:
+            ts = torch.as_tensor([k for k, _ in take], dtype=torch.long, device=dev)
+            hx, hu = xg[ts].cpu().numpy(), ug[ts].cpu().numpy()
+            for i, (_, j) in enumerate(take):
+                got_x[j], got_u[j] = hx[i], hu[i]
+        if verbose:
+            print(f'round {info["rounds"]}: {len(book.accepted)}/{n} accepted, {len(book.failed)} failed, {book.in_flight} in flight, '
+                  f'{book.issued} issued')
+    sv.sync()
+    order = book.result_order()
+    info.update(accepted=order, failed=sorted(book.failed), issued=book.issued, exhausted=book.exhausted,
+                instance_iterations=int(sum(info['iters'].values())))
+    xg_out = np.stack([got_x[j] for j in order]) if order else np.zeros((0, N + 1, nx))
+    ug_out = np.stack([got_u[j] for j in order]) if order else np.zeros((0, N, nu))
+    return {'xg': xg_out, 'ug': ug_out}, info
 
 
 # ---- closed loop -----------------------------------------------------------------------------------------------------------------

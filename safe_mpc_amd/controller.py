@@ -26,6 +26,7 @@ class AbstractController(InPlaceState):
     cont_name = 'naive'
     can_abort = False            # policies whose step() may return abort=True (the driver then needs one flag per step)
     policy_kind = 0              # SMPC_POLICY_* of include/smpc.h: which automaton smpc_policy_step runs for this class
+    guess_safe_node = False      # checkGuess includes checkSafeConstraints on the last node (STWA and below)
 
     def __init__(self, params, batch, cost='ext', N=None, solver=None, net=None, device=0, device_state=False):
         self.params = params
@@ -232,6 +233,12 @@ class AbstractController(InPlaceState):
         return (self.checkStateConstraints(self.x_temp) & self.checkTorqueConstraints(self.x_temp, self.u_temp) &
                 self.checkDynamicsConstraints(self.x_temp, self.u_temp))
 
+    def guess_report(self, mask=None, flags=None, worst=None):
+        """``checkGuess`` on x_temp / u_temp as ONE engine call (smpc_check_guess): ``(flags [B], worst [B, 5])``, where
+        ``flags == 0`` is checkGuess' verdict and the bits say which predicate failed (BatchedOcpSolver.check_guess)."""
+        return self.ocp_solver.check_guess(self.x_temp, self.u_temp, safe_node=self.N if self.guess_safe_node else None,
+                                           mask=mask, flags=flags, worst=worst)
+
     def initialize(self, x0, u0=None):
         """controller.py:260-272: trivial guess, one solve, keep it where it checks out.  Returns 1/0 per instance."""
         xp = self.xp
@@ -280,6 +287,7 @@ class STWAController(STController):
     cont_name = 'stwa'
     can_abort = True
     policy_kind = 2
+    guess_safe_node = True
 
     def setGuess(self, x_guess, u_guess):
         super().setGuess(x_guess, u_guess)

@@ -18,6 +18,7 @@
 #include "kernels_mlp.hpp"
 #include "kernels_nodes.hpp"
 #include "kernels_sqp.hpp"
+#include "kernels_guess.hpp"
 
 using namespace smpc;
 
@@ -115,6 +116,9 @@ struct smpc_handle {
                                 // (the count itself is only known on the device; any kernel is correct for any count)
     DevBuf<char> d_par;         // SMPC_POLICY_PARALLEL's candidate buffers (ParScratch), zeroed when allocated
     DevBuf<char> d_sqp;         // scratch of smpc_sqp_batch / smpc_merit_terms (SqpScratch)
+    DevBuf<int32_t> d_guess;    // scratch of smpc_check_guess: pos[B], where an instance's safe-set row sits in the network pass's list
+    DevBuf<double> d_gchk;      // bounds of smpc_check_guess [x_min | x_max | tau_min | tau_max | row_lb | row_ub], uploaded on change
+    std::vector<double> gchk_cache;
     char err[256] = "";
 };
 
@@ -1012,6 +1016,64 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
     return SMPC_OK;
 }
 
+// The bounds smpc_check_guess tests against, in a small device block of their own like upload_check_bounds' (whose block the
+// policy entry points keep warm with another layout): uploaded only when they change, so an unchanged call does not synchronise.
+int upload_guess_bounds(smpc_handle* h, const smpc_guess_check* par) {
+    const int nq = h->desc.nq, nx = 2 * nq, nr = h->desc.n_rows;
+    std::vector<double> cur((size_t)2 * nx + 2 * nq + 2 * SMPC_MAX_ROWS, 0.0);
+    memcpy(cur.data(), par->x_min, sizeof(double) * nx);
+    memcpy(cur.data() + nx, par->x_max, sizeof(double) * nx);
+    memcpy(cur.data() + 2 * nx, par->tau_min, sizeof(double) * nq);
+    memcpy(cur.data() + 2 * nx + nq, par->tau_max, sizeof(double) * nq);
+    if (nr > 0) {
+        memcpy(cur.data() + 2 * nx + 2 * nq, par->row_lb_chk, sizeof(double) * nr);
+        memcpy(cur.data() + 2 * nx + 2 * nq + SMPC_MAX_ROWS, par->row_ub_chk, sizeof(double) * nr);
+    }
+    int rc;
+    if ((rc = h->d_gchk.reserve(h, "guess check bounds", cur.size() * sizeof(double)))) return rc;
+    if (cur != h->gchk_cache) {
+        if (capturing(h))
+            return fail(h, SMPC_ESTATE, "the guess check bounds changed while the stream is being captured: run one eager call with "
+                        "these bounds first");
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(h->d_gchk.p, cur.data(), cur.size() * sizeof(double), hipMemcpyHostToDevice));
+        h->gchk_cache.swap(cur);
+    }
+    return SMPC_OK;
+}
+
+// flags / worst of the instances whose mask byte is set: the forward-only network pass on their safe-set node (listed by
+// k_guess_nn_list, so that masked-out instances cost no network rows), then k_check_guess.  The list's counter goes back to zero
+// behind the chain (see d_nn_cnt).
+template <int NQ>
+int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, const smpc_guess_check* par, const uint8_t* mask,
+                       int32_t* flags, double* worst) {
+    const int N = h->N, nx = 2 * NQ;
+    hipStream_t s = h->stream;
+    int rc;
+    const float* y = nullptr;
+    if (par->safe_node >= 0) {
+        if ((rc = h->d_guess.reserve(h, "guess check scratch", sizeof(int32_t) * (size_t)B)) || (rc = ensure_nn_idx(h, (size_t)B))) return rc;
+        hipLaunchKernelGGL(k_guess_nn_list, dim3((B + 63) / 64), dim3(64), 0, s, B, N, (int)par->safe_node, mask, h->d_nn_idx.p, h->d_guess.p,
+                           h->d_nn_cnt);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = run_mlp<NQ>(h, B, 3, N, x, false))) return rc;
+        y = h->d_y.p;
+    }
+    const double* d_min = h->d_gchk.p;
+    const double* d_max = d_min + nx;
+    const double* d_tlo = d_max + nx;
+    const double* d_thi = d_tlo + NQ;
+    const double* d_rlb = d_thi + NQ;
+    const double* d_rub = d_rlb + SMPC_MAX_ROWS;
+    hipLaunchKernelGGL((k_check_guess<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
+                       par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, d_min, d_max, d_tlo, d_thi, d_rlb,
+                       d_rub, mask, y, (const int32_t*)h->d_guess.p, flags, worst);
+    HIPCHK(h, hipGetLastError());
+    if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
+    return SMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1160,6 +1222,7 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     for (DevBuf<double>* buf : {&h->d_zl, &h->d_lo_b, &h->d_hi_b, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
     h->d_par.release();
     h->d_sqp.release();
+    h->d_guess.release();
     return upload_bounds(h, nullptr, nullptr);
 }
 
@@ -1737,6 +1800,36 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
             if (open == 0) break;
         }
     }
+    return io.finish();
+}
+
+int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, const smpc_guess_check* par, const uint8_t* mask,
+                     int32_t* flags, double* worst, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (B <= 0 || !x || !u || !par || !flags || !worst) return fail(h, SMPC_EINVAL, "bad argument");
+    if (!par->x_min || !par->x_max || !par->tau_min || !par->tau_max) return fail(h, SMPC_EINVAL, "state or torque bounds missing");
+    if (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
+    if (par->safe_node > h->N) return fail(h, SMPC_EINVAL, "safe_node=%d beyond the horizon N=%d", (int)par->safe_node, h->N);
+    if (par->safe_node >= 0 && h->nlayers == 0) return fail(h, SMPC_ESTATE, "safe_node given but smpc_set_mlp was not called");
+    (void)hipSetDevice(h->device);
+    const int N = h->N, nq = h->desc.nq;
+    int rc;
+    if ((rc = upload_guess_bounds(h, par))) return rc;
+    Stage io{h, on_device != 0};
+    const double *dx, *du;
+    const uint8_t* dmask;
+    int32_t* dflags;
+    double* dworst;
+    if ((rc = io.place([&](Stage& v) {
+             dx = v.in(x, (size_t)B * (N + 1) * 2 * nq);
+             du = v.in(u, (size_t)B * N * nq);
+             dmask = v.in(mask, (size_t)B);
+             dflags = v.inout(flags, (size_t)B);
+             dworst = v.inout(worst, (size_t)B * GUESS_N_WORST);
+         })))
+        return rc;
+    DISPATCH_NQ(h, (launch_check_guess<NQ_>(h, B, dx, du, par, dmask, dflags, dworst)));
+    if (rc) return rc;
     return io.finish();
 }
 

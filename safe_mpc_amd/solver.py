@@ -316,6 +316,55 @@ class BatchedOcpSolver:
             self._chk(self.L.smpc_sqp_batch(self.h, B, C.byref(opts), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(cst), dev))
         return x_guess, u_guess, state
 
+    def check_guess(self, x, u, safe_node=None, collision_first_node=None, mask=None, flags=None, worst=None, **tol):
+        """The acceptance test of a warm start per instance, forward-only on the device (smpc_check_guess; the statement is
+        AbstractController.checkGuess).  Returns ``(flags [B] int32, worst [B, 5])``: bit i of ``flags`` is set when predicate i
+        fails -- 0 state box, 1 collision rows, 2 torque, 3 dynamics, 4 safe set at node ``safe_node`` (None: not tested) -- and
+        ``worst[:, i]`` is the value the predicate tests (include/smpc.h).  ``mask`` (uint8 [B]): instances with 0 are skipped and
+        keep their rows of ``flags`` / ``worst``.  ``collision_first_node`` defaults to ``params.reference_quirks``; ``tol`` may
+        override tol_x, tol_tau, tol_dyn, tol_safe, alpha, x_min, x_max, tau_min, tau_max, row_lb, row_ub (defaults from the
+        problem and its params, as in :meth:`check_trajectory`)."""
+        pr, par = self.problem, self.problem.params
+        unknown = set(tol) - {'tol_x', 'tol_tau', 'tol_dyn', 'tol_safe', 'alpha', 'x_min', 'x_max', 'tau_min', 'tau_max', 'row_lb', 'row_ub'}
+        if unknown:
+            raise TypeError(f'check_guess: unknown argument(s) {sorted(unknown)}')
+        if collision_first_node is None:
+            collision_first_node = bool(getattr(par, 'reference_quirks', True))
+        small = [np.ascontiguousarray(tol.get(k, d), np.float64)
+                 for k, d in (('x_min', pr.x_min), ('x_max', pr.x_max), ('tau_min', pr.tau_min), ('tau_max', pr.tau_max),
+                              ('row_lb', pr.row_check[:, 0]), ('row_ub', pr.row_check[:, 1]))]
+        for a, n in zip(small, (self.nx, self.nx, self.nq, self.nq, len(pr.row_check), len(pr.row_check))):
+            if a.shape != (n,):
+                raise ValueError(f'check_guess: a bound has shape {a.shape}, expected ({n},)')
+        gc = _lib.GuessCheck(float(tol.get('tol_x', par.tol_x)), float(tol.get('tol_tau', par.tol_tau)),
+                             float(tol.get('tol_dyn', par.tol_dyn)), float(tol.get('tol_safe', par.tol_safe_set)),
+                             float(tol.get('alpha', par.alpha)), int(bool(collision_first_node)),
+                             -1 if safe_node is None else int(safe_node), *[a.ctypes.data for a in small])
+        B = x.shape[0]
+        N, nx, nu = self.N, self.nx, self.nu
+        ptrs, dev, keep = self._prep([x, u, mask, flags, worst], [(B, N + 1, nx), (B, N, nu), (B,), (B,), (B, 5)],
+                                     [np.float64, np.float64, np.uint8, np.int32, np.float64])
+        if dev:
+            import torch
+            if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError('mask must be uint8 or bool')
+            if flags is None:
+                flags = torch.zeros((B,), dtype=torch.int32, device=x.device)
+            if worst is None:
+                worst = torch.zeros((B, 5), dtype=torch.float64, device=x.device)
+            if flags.dtype != torch.int32 or worst.dtype != torch.float64:
+                raise ValueError('flags must be int32 and worst float64')
+            fp, wp = flags.data_ptr(), worst.data_ptr()
+        else:
+            flags = np.zeros(B, np.int32) if flags is None else flags
+            worst = np.zeros((B, 5)) if worst is None else worst
+            assert flags.dtype == np.int32 and flags.shape == (B,) and flags.flags.c_contiguous
+            assert worst.dtype == np.float64 and worst.shape == (B, 5) and worst.flags.c_contiguous
+            fp, wp = flags.ctypes.data, worst.ctypes.data
+        with self._ordered(dev):
+            self._chk(self.L.smpc_check_guess(self.h, B, ptrs[0], ptrs[1], C.byref(gc), ptrs[2], fp, wp, dev))
+        return flags, worst
+
     # -- callers around the solve (a13, a15, a16) ------------------------------------------------------------------------
     def guess_correction(self, x_guess, u_guess):
         """In place on torch tensors; returns a corrected copy for numpy."""

@@ -5,6 +5,8 @@
     python scripts/guess_acados.py -c st --horizon 30 --alpha 10 [--on-device]
 
 --on-device: the SQP iterations run inside the engine on device-resident arrays (smpc_sqp_batch) instead of the host loop.
+--until-accepted [--accept first|final] [--batch B] [--check-every K]: the reference's `while succ < num_ics` -- samples are drawn,
+solved and tested on the device until exactly test_num guesses are accepted (closed_loop.generate_guess_until); implies --on-device.
 """
 import os
 import sys
@@ -17,7 +19,12 @@ from safe_mpc_amd.parser import Parameters, parse_args          # noqa: E402
 
 def main(argv=None):
     args = parse_args(argv)
-    on_device = '--on-device' in (sys.argv[1:] if argv is None else argv)
+    raw = list(sys.argv[1:] if argv is None else argv)
+    on_device = '--on-device' in raw
+    until = '--until-accepted' in raw
+
+    def opt(flag, default, cast):
+        return cast(raw[raw.index(flag) + 1]) if flag in raw and raw.index(flag) + 1 < len(raw) else default
     model_name = args['system']
     params = Parameters(args, model_name, rti=False)            # full SQP (parser.py:115-117)
     params.act, params.alpha, params.N = args['activation'], args['alpha'], args['horizon']
@@ -25,8 +32,16 @@ def main(argv=None):
     # every safe-set controller name is generated with the hard-terminal OCP (utils.py:46-58)
     gen_name = cont_name if cont_name in ('naive', 'zerovel') else 'htwa'
     t0 = time.time()
-    guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device)
-    print(f'{good.sum()}/{len(good)} guesses accepted in {time.time() - t0:.1f} s')
+    if until:
+        guess, info = cl.generate_guess_until(params, gen_name, params.test_num, batch=opt('--batch', None, int),
+                                              check_every=opt('--check-every', 50, int), accept=opt('--accept', 'final', str),
+                                              verbose=True)
+        print(f'{len(info["accepted"])}/{params.test_num} guesses accepted from {info["issued"]} samples in {info["rounds"]} rounds, '
+              f'{info["instance_iterations"]} instance-iterations, {time.time() - t0:.1f} s'
+              + (' (sample stream exhausted)' if info['exhausted'] else ''))
+    else:
+        guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device)
+        print(f'{good.sum()}/{len(good)} guesses accepted in {time.time() - t0:.1f} s')
     use_net = None if cont_name in ('naive', 'zerovel') else True
     out = cl.guess_file(params, model_name, cont_name, params.N, use_net)
     cl.save_pickle(out, guess)

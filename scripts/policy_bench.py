@@ -8,7 +8,10 @@ SMPC_WARM=1: start from generate_guess warm starts (full SQP with merit backtrac
 guess_acados.py writes them for every safe-set controller, utils.py:46-58, and scripts/mpc.py:79-84 loads them) instead of the
 constant guess -- what the reference times; the share of infeasible QPs is then the policy's, not the cold start's.
 SMPC_WARM_DEVICE=1: generate them with the engine's device-resident SQP (generate_guess(on_device=True), smpc_sqp_batch) instead of
-the host loop; SMPC_WARM_STATS=1 runs the generation a second time with a history, to report SQP iterations and trial passes."""
+the host loop; SMPC_WARM_UNTIL=1: generate them until SMPC_B are accepted (generate_guess_until; SMPC_WARM_ACCEPT = final | first,
+SMPC_WARM_EVERY = iterations per round, SMPC_WARM_BATCH = device slots), so the loop runs on as many instances as were asked for;
+SMPC_WARM_STATS=1 runs the generation a second time with a history, to report SQP iterations and trial passes (with SMPC_WARM_UNTIL=1
+it prints the loop's own iteration counts instead)."""
 import os
 import sys
 import time
@@ -38,12 +41,28 @@ def main():
         pg.nlp_max_iter = int(os.environ.get('SMPC_SQP_ITERS', '60'))
         on_dev = os.environ.get('SMPC_WARM_DEVICE', '0') == '1'
         t0 = time.perf_counter()
-        guess, good = cl.generate_guess(pg, 'htwa', B, on_device=on_dev)
-        xg, ug = guess['xg'], guess['ug']
-        B = len(xg)
-        print(f'warm starts ({"device" if on_dev else "host"} SQP): {good.sum()} of {len(good)} Halton starts accepted by checkGuess after '
-              f'<= {pg.nlp_max_iter} SQP iterations ({time.perf_counter() - t0:.2f} s); running {B} instances', flush=True)
-        if os.environ.get('SMPC_WARM_STATS', '0') == '1':
+        until = os.environ.get('SMPC_WARM_UNTIL', '0') == '1'
+        if until:
+            guess, info = cl.generate_guess_until(pg, 'htwa', B, batch=int(os.environ['SMPC_WARM_BATCH']) if 'SMPC_WARM_BATCH' in os.environ else None,
+                                                  check_every=int(os.environ.get('SMPC_WARM_EVERY', '50')),
+                                                  accept=os.environ.get('SMPC_WARM_ACCEPT', 'final'))
+            xg, ug = guess['xg'], guess['ug']
+            B = len(xg)
+            print(f'warm starts (device SQP until accepted): {B} of {info["issued"]} samples accepted in {info["rounds"]} rounds, '
+                  f'{info["instance_iterations"]} instance-iterations, budget {pg.nlp_max_iter} ({time.perf_counter() - t0:.2f} s); '
+                  f'running {B} instances', flush=True)
+            if os.environ.get('SMPC_WARM_STATS', '0') == '1':          # (no second run here: the loop keeps its own counts)
+                it = np.array(list(info['iters'].values()))
+                print(f'  SQP iterations per sample min / median / max {it.min()} / {int(np.median(it))} / {it.max()}, '
+                      f'{len(info["failed"])} samples failed, {info["instance_iterations"] / max(info["rounds"], 1):.0f} instance-iterations per round',
+                      flush=True)
+        else:
+            guess, good = cl.generate_guess(pg, 'htwa', B, on_device=on_dev)
+            xg, ug = guess['xg'], guess['ug']
+            B = len(xg)
+            print(f'warm starts ({"device" if on_dev else "host"} SQP): {good.sum()} of {len(good)} Halton starts accepted by checkGuess after '
+                  f'<= {pg.nlp_max_iter} SQP iterations ({time.perf_counter() - t0:.2f} s); running {B} instances', flush=True)
+        if not until and os.environ.get('SMPC_WARM_STATS', '0') == '1':
             hist = []
             t0 = time.perf_counter()
             cl.generate_guess(pg, 'htwa', len(good), on_device=on_dev, history=hist)
