@@ -323,6 +323,50 @@ typedef struct {
 int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, const smpc_guess_check* par,
                      const uint8_t* mask, int32_t* flags, double* worst, int on_device);
 
+/* ---- scoring a closed-loop run where its logs are ------------------------------------------------------------------ */
+/* The last step of the experiment: the closed-loop cost of every instance (metrics_count_fails.py:19-28), the distance the
+ * convergence test compares with tol_conv (mpc.py:273) and how close the run came to the obstacles, the state box
+ * (env_model.py:170-172,236-243) and the learned safe set (safe_set.py:61-68), from the step-major logs of smpc_loop_state, per
+ * instance and forward-only.  out[B][SMPC_SCORE_ND] doubles and outi[B][SMPC_SCORE_NI] int32:
+ *   d0  cost = Q d1 + R d2 with the descriptor's Q and R (no cost_scale_*, no dt): for a complete log the reference's metric
+ *   d1  sum over j <= last_x of |ee(x_j) - ref_j|^2; ref_j = ee_ref, or column min(j, traj_len - 1) of traj (the convention of
+ *       smpc_policy_state.traj)
+ *   d2  sum over j <= last_u of |u_j|^2
+ *   d3  |ee(x_j) - ref_j|_2 at j = last_x
+ *   d4  worst collision margin: max over j <= last_x and the rows of max(row_lb_chk - v, v - row_ub_chk), v as smpc_merit_terms forms
+ *       the rows; <= 0 means free; -inf without rows.                                        i0, i1: its step and row (-1, -1)
+ *   d5  worst state-box margin: max over j <= last_x and components of max(x_min - x, x - x_max)           i2: its step
+ *   d6  least safe-set value: min over j <= last_x of g(x_j, alpha), g as smpc_check_guess forms it (fp32-accurate: it passes
+ *       through the network); +inf when want_safe == 0                                                 i3: its step (-1)
+ * last_x[B] / last_u[B]: last valid row of each log, inclusive (last_u = -1: no valid control; last_x >= max(last_u, 0)); NULL: the
+ * logs are complete.  Rows past them may hold anything, NaN included, and affect nothing.  Ties go to the earliest step, then the
+ * lowest row; a maximum or minimum that has seen a NaN in a valid row stays NaN (placed at the first one), and so do the sums. */
+#define SMPC_SCORE_ND 7
+#define SMPC_SCORE_NI 4
+typedef struct {
+    double alpha, tol_safe;         /* as smpc_guess_check; tol_safe is carried for the caller's own test of d6 and read by no kernel */
+    int32_t want_safe;              /* != 0: fill d6 / i3 (needs smpc_set_mlp) */
+    int32_t reserved0;
+    const double *x_min, *x_max;            /* HOST [nx] */
+    const double *row_lb_chk, *row_ub_chk;  /* HOST [n_rows] */
+    const double *ee_ref;                   /* HOST [3], used when traj == NULL */
+    const double *traj; int64_t traj_len;   /* [3][traj_len], follows on_device; or NULL */
+} smpc_score_params;
+
+/* x_log [n_steps+1][B][nx], u_log [n_steps][B][nu]; mask[B] (bytes, may be NULL): instances with mask[b] == 0 are skipped and their
+ * out[b] / outi[b] left as they are (so both are read as well as written on the host path).  Sums are formed in a fixed order and
+ * without floating-point atomics: steps ascending inside segments of 32 steps cut by absolute step index, then the segments
+ * ascending -- two calls give the same bits, and d0..d5 / i0..i2 of an instance do not depend on B or on the rest of the batch (d6
+ * may: the row count selects the network kernel).  The network runs over the log in passes of a bounded row count, so scratch does
+ * not grow with n_steps * B beyond 64 bytes per instance and 32 steps.  x_log, u_log, last_x, last_u, traj, mask, out, outi follow
+ * on_device like smpc_check_guess; with device pointers the call only enqueues.  The small host arrays of `par` are kept in a device
+ * block of the handle and uploaded only when they change.  SMPC_ESTATE: want_safe without a network, or scratch / the bounds block
+ * would have to change while the stream is being captured.  SMPC_EINVAL: n_steps < 1, missing bounds, traj with traj_len < 1.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, const double* u_log,
+                       const int64_t* last_x, const int64_t* last_u, const smpc_score_params* par,
+                       const uint8_t* mask, double* out, int32_t* outi, int on_device);
+
 /* ---- callers on either side of the solve ------------------------------------------- */
 /* guessCorrection (controller.py:226-231): x_guess[k+1] = f(x_guess[k], u_guess[k]) in place. */
 int smpc_guess_correction(smpc_handle* h, int B, double* xg, const double* ug, int on_device);

@@ -19,7 +19,8 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_provide_control', 'smpc_check_trajectory', 'smpc_plant_step', 'smpc_rollout_batch', 'smpc_sync', 'smpc_stream',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
-           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess']
+           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
+           'smpc_score_rollout']
 
 
 class EngineError(RuntimeError):
@@ -69,6 +70,13 @@ class GuessCheck(C.Structure):
     _fields_ = [('tol_x', C.c_double), ('tol_tau', C.c_double), ('tol_dyn', C.c_double), ('tol_safe', C.c_double), ('alpha', C.c_double),
                 ('collision_first_node', C.c_int32), ('safe_node', C.c_int32),
                 ('x_min', _vp), ('x_max', _vp), ('tau_min', _vp), ('tau_max', _vp), ('row_lb_chk', _vp), ('row_ub_chk', _vp)]
+
+
+class ScoreParams(C.Structure):
+    """smpc_score_params: what smpc_score_rollout scores against; the small arrays are HOST pointers, traj follows on_device"""
+    _fields_ = [('alpha', C.c_double), ('tol_safe', C.c_double), ('want_safe', C.c_int32), ('reserved0', C.c_int32),
+                ('x_min', _vp), ('x_max', _vp), ('row_lb_chk', _vp), ('row_ub_chk', _vp), ('ee_ref', _vp), ('traj', _vp),
+                ('traj_len', C.c_int64)]
 
 
 def build(force=False):
@@ -130,5 +138,6 @@ def lib():
     L.smpc_merit_terms.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_sqp_batch.argtypes = [vp, C.c_int, C.POINTER(SqpOpts), dp, dp, dp, dp, C.POINTER(SqpState), C.c_int]
     L.smpc_check_guess.argtypes = [vp, C.c_int, dp, dp, C.POINTER(GuessCheck), dp, dp, dp, C.c_int]
+    L.smpc_score_rollout.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(ScoreParams), dp, dp, dp, C.c_int]
     _lib = L
     return L

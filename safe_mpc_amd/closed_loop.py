@@ -554,6 +554,107 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
 _STATE = ('x_guess', 'u_guess', 'fails', 'current_step', 'x_viable', 'r')
 
 
+# ---- scores of a closed-loop run ------------------------------------------------------------------------------------------
+def _score_eval_chunks(solver, problem, states, alpha, chunk, safe):
+    """ee [M, 3] and row_val [M, n_rows] of M states (``safe`` false), or g [M] (``safe`` true), through ``solver.eval_nodes``, at
+    most ``chunk`` states per call.  The states are packed into the nodes of evaluated trajectories: all N + 1 nodes for ee /
+    row_val, the nodes that carry the safe-set row for g (1..N with the row on every node, node N alone otherwise)."""
+    N, nx, nr = solver.N, problem.nx, int(problem.desc.n_rows)
+    M = states.shape[0]
+    ee, rows, g = np.zeros((M, 3)), np.zeros((M, nr)), np.zeros(M)
+    nodes = slice(0, N + 1) if not safe else (slice(1, N + 1) if int(problem.desc.nn_mode) == 2 else slice(N, N + 1))
+    per = nodes.stop - nodes.start
+    for lo in range(0, M, chunk):
+        s = states[lo:lo + chunk]
+        m = s.shape[0]
+        packed = np.zeros((-(-m // per) * per, nx))
+        packed[:m] = s
+        xg = np.zeros((packed.shape[0] // per, N + 1, nx))
+        xg[:, nodes] = packed.reshape(-1, per, nx)
+        p = np.zeros((xg.shape[0], N + 1, 5))
+        p[:, :, 3], p[:, :, 4] = alpha, 1.0
+        ev = solver.eval_nodes(xg, np.zeros((xg.shape[0], N, problem.nu)), p)
+        if safe:
+            g[lo:lo + m] = np.asarray(ev['nn_val'])[:, nodes].reshape(-1)[:m]
+        else:
+            ee[lo:lo + m] = np.asarray(ev['ee']).reshape(-1, 3)[:m]
+            rows[lo:lo + m] = np.asarray(ev['row_val']).reshape(-1, np.asarray(ev['row_val']).shape[-1])[:m, :nr]
+    return ee, rows, g
+
+
+def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, last_u=None, ee_ref=None, traj=None, want_safe=False,
+                            chunk=4096, **bounds):
+    """The readable numpy statement of ``BatchedOcpSolver.score_rollout`` (smpc_score_rollout, include/smpc.h), and the host path of
+    ``run_mpc(score=True)``.  STEP-major logs ``x_log [T+1, B, nx]``, ``u_log [T, B, nu]``; ``last_x`` / ``last_u`` [B]: last valid
+    row of each, None = complete; rows past them affect nothing.  Returns ``(out [B, 7], outi [B, 4] int32)`` with the columns
+    ``solver.SCORE_SLOTS`` / ``SCORE_INDEX_SLOTS``:
+
+    * cost = Q ee_err2 + R u2 (metrics_count_fails.py:19-28 for a complete log), ee_err2 = sum_{j <= last_x} |ee(x_j) - ref_j|^2,
+      u2 = sum_{j <= last_u} |u_j|^2, ee_dist = |ee(x_last_x) - ref_last_x| (what mpc.py:273 compares with tol_conv);
+      ref_j = ``ee_ref`` (default: the problem's) or column min(j, L - 1) of ``traj [3, L]``
+    * coll_margin = max over j <= last_x and rows of max(row_lb - v, v - row_ub) (env_model.py:236-243), -inf without rows;
+      box_margin = max over j <= last_x and components of max(x_min - x, x - x_max) (env_model.py:170-172);
+      safe_min = min over j <= last_x of g(x_j, alpha) (safe_set.py:61-68), +inf unless ``want_safe``
+    * coll_step, coll_row, box_step, safe_step: where they were taken, earliest step then lowest row among equals; -1 where there is
+      nothing.  A NaN in a valid row makes the values it enters NaN (placed at the first one).
+
+    Uses only ``solver.eval_nodes`` (``ee``, ``row_val``; ``nn_val`` for g), ``chunk`` states per call."""
+    x = np.transpose(np.asarray(x_log, float), (1, 0, 2))          # [B, T+1, nx]
+    u = np.transpose(np.asarray(u_log, float), (1, 0, 2))          # [B, T, nu]
+    B, T = u.shape[0], u.shape[1]
+    unknown = set(bounds) - {'x_min', 'x_max', 'row_lb', 'row_ub', 'alpha', 'tol_safe'}
+    if unknown:
+        raise TypeError(f'score_rollout_statement: unknown argument(s) {sorted(unknown)}')
+    if T < 1:
+        raise ValueError('a log has at least one step')
+    nr = int(problem.desc.n_rows)
+    x_min, x_max = np.asarray(bounds.get('x_min', problem.x_min), float), np.asarray(bounds.get('x_max', problem.x_max), float)
+    row_lb = np.asarray(bounds.get('row_lb', problem.row_check[:, 0]), float)
+    row_ub = np.asarray(bounds.get('row_ub', problem.row_check[:, 1]), float)
+    alpha = float(bounds.get('alpha', params.alpha))
+    lx = np.full(B, T, np.int64) if last_x is None else np.clip(np.asarray(last_x, np.int64), 0, T)
+    lu = np.full(B, T - 1, np.int64) if last_u is None else np.clip(np.asarray(last_u, np.int64), -1, T - 1)
+    steps = np.arange(T + 1)
+    vx, vu = steps[None, :] <= lx[:, None], steps[None, :T] <= lu[:, None]           # valid rows
+    if traj is not None:
+        traj = np.asarray(traj, float)
+        ref = traj[:, np.minimum(steps, traj.shape[1] - 1)].T[None, :, :]             # [1, T+1, 3]
+    else:
+        ref = np.asarray(problem.ee_ref if ee_ref is None else ee_ref, float)[None, None, :]
+    flat = np.where(vx[:, :, None], x, 0.0).reshape(-1, x.shape[2])                  # invalid rows: any finite state, masked below
+    ee, rv, _ = _score_eval_chunks(solver, problem, flat, alpha, chunk, False)
+    e2 = np.sum((ee.reshape(B, T + 1, 3) - ref) ** 2, axis=2)
+    out, outi = np.zeros((B, 7)), np.full((B, 4), -1, np.int32)
+    out[:, 1] = np.where(vx, e2, 0.0).sum(1)
+    out[:, 2] = np.sum(np.where(vu[:, :, None], u, 0.0) ** 2, axis=2).sum(1)
+    out[:, 0] = params.Q_weight * out[:, 1] + params.R_weight * out[:, 2]
+    out[:, 3] = np.sqrt(e2[np.arange(B), lx])
+    out[:, 4] = -np.inf
+    if nr:
+        rv = rv.reshape(B, T + 1, nr)
+        m = np.where(vx[:, :, None], np.maximum(row_lb - rv, rv - row_ub), -np.inf).reshape(B, -1)
+        at = np.argmax(m, axis=1)                       # first occurrence in (step, row) order; a NaN counts as the maximum
+        out[:, 4], outi[:, 0], outi[:, 1] = m[np.arange(B), at], at // nr, at % nr
+    mb = np.where(vx, np.max(np.maximum(x_min - x, x - x_max), axis=2), -np.inf)
+    at = np.argmax(mb, axis=1)
+    out[:, 5], outi[:, 2] = mb[np.arange(B), at], at
+    out[:, 6] = np.inf
+    if want_safe:
+        if int(problem.desc.nn_mode) == 0:
+            raise ValueError('want_safe needs a formulation with a safe-set row (eval_nodes reports g on the nodes that carry it)')
+        _, _, g = _score_eval_chunks(solver, problem, flat, alpha, chunk, True)
+        g = np.where(vx, g.reshape(B, T + 1), np.inf)
+        at = np.argmin(g, axis=1)
+        out[:, 6], outi[:, 3] = g[np.arange(B), at], at
+    return out, outi
+
+
+def _score_dict(out, outi):
+    from .solver import SCORE_INDEX_SLOTS, SCORE_SLOTS
+    return {**{k: np.array(out[:, i]) for i, k in enumerate(SCORE_SLOTS)},
+            **{k: np.array(outi[:, i]) for i, k in enumerate(SCORE_INDEX_SLOTS)}}
+
+
 def _masked_step(ctrl, x, active):
     """controller.step on all rows, then roll back the rows that must not have stepped."""
     xp = ctrl.xp
@@ -887,9 +988,20 @@ class _Group(InPlaceState):
         if self._collect_times and xp.on_device:
             self._read_times(self._n_steps - 1, final=True)
 
-    def results(self):
+    def results(self, score=False):
         xp, ctrl, params, B, n_steps = self._xp, self._ctrl, self._params, self._B, self._n_steps
         solver, pr = ctrl.ocp_solver, ctrl.problem
+        scored = None
+        if score:
+            # the run's scores: on the device from the logs where they are (one enqueue on the group's stream, ahead of the wait
+            # below), on the host by the statement; the safe-set score where the formulation has a safe-set row
+            want_safe = int(pr.desc.nn_mode) != 0 and getattr(ctrl, 'net', None) is not None
+            traj = getattr(ctrl, 'traj', None)
+            if xp.on_device:
+                scored = solver.score_rollout(self.x_log, self.u_log, self.last_x, self.last_u, traj=traj, want_safe=want_safe)
+            else:
+                scored = score_rollout_statement(solver, pr, params, self.x_log, self.u_log, self.last_x, self.last_u,
+                                                 traj=traj, want_safe=want_safe)
         if xp.on_device:
             solver.sync()
         # convergence at the last step (mpc.py:273): the reference tests x_sim[-1], NaN for instances that broke
@@ -904,7 +1016,8 @@ class _Group(InPlaceState):
         conv = ~np.isnan(x_sim[:, -1]).any(1) & (np.linalg.norm(ee - pr.ee_ref, axis=1) < params.tol_conv)
         if not self._quirks:
             conv &= xp.host(self.alive)        # (the reference tests x_sim[-1] even of an instance it has just recorded as failed)
-        return dict(x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
+        extra = {'score': _score_dict(xp.host(scored[0]), xp.host(scored[1]))} if score else {}
+        return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
                     time_rows=np.array(self._time_rows, float).reshape(-1, len(TIME_FIELDS)), time_lost=self._time_lost,
                     collided=xp.host(self.collided), viable=xp.host(self.viable).astype(np.int64),
                     abort_events=[(e[0], e[1], e[2] if isinstance(e[2], np.ndarray) else xp.host(e[2])) for e in self._abort_events])
@@ -924,7 +1037,8 @@ def time_row(t):
 
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
-            n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False):
+            n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
+            score=False):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -939,7 +1053,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     ``collect_times``: append the controller's solver times at every step like ``stats.append(controller.getTime())`` of
     scripts/mpc.py:239; the result then carries ``'time_stats'`` (one row of ``TIME_FIELDS`` per step and group, seconds) and
     ``'time_q99'`` (the 99 % quantiles mpc.py:300-303 prints).  A captured graph cannot record into the engine's event ring,
-    so this runs the steps as eager launches."""
+    so this runs the steps as eager launches.
+    ``score``: the result gains ``'score'``, a dict of [B] arrays keyed by ``solver.SCORE_SLOTS`` / ``SCORE_INDEX_SLOTS`` -- closed-loop
+    cost, EE distance of the last state, worst collision / state-box margins, least safe-set value and where each was taken
+    (:func:`score_rollout_statement`).  On the device every group scores its logs where they are (smpc_score_rollout); nothing else
+    in the result changes."""
     import time
     B = x_guess.shape[0]
     n_steps = int(n_steps if n_steps is not None else params.n_steps)
@@ -1013,9 +1131,9 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         if streams[g] is not None:
             import torch
             with torch.cuda.stream(streams[g]):
-                outs.append(grp.results())
+                outs.append(grp.results(score))
         else:
-            outs.append(grp.results())
+            outs.append(grp.results(score))
     x_sim = np.concatenate([o['x'] for o in outs], axis=0)
     conv = np.concatenate([o['conv'] for o in outs])
     collided = np.concatenate([o['collided'] for o in outs])
@@ -1045,6 +1163,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         ts = np.concatenate([o['time_rows'] for o in outs], axis=0)
         extra = {'time_stats': ts, 'time_fields': list(TIME_FIELDS), 'time_lost': int(sum(o['time_lost'] for o in outs)),
                  'time_q99': np.quantile(ts, 0.99, axis=0) if len(ts) else np.zeros(len(TIME_FIELDS))}
+    if score:
+        extra['score'] = {k: np.concatenate([o['score'][k] for o in outs]) for k in outs[0]['score']}
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -19,6 +19,7 @@
 #include "kernels_nodes.hpp"
 #include "kernels_sqp.hpp"
 #include "kernels_guess.hpp"
+#include "kernels_score.hpp"
 
 using namespace smpc;
 
@@ -119,6 +120,9 @@ struct smpc_handle {
     DevBuf<int32_t> d_guess;    // scratch of smpc_check_guess: pos[B], where an instance's safe-set row sits in the network pass's list
     DevBuf<double> d_gchk;      // bounds of smpc_check_guess [x_min | x_max | tau_min | tau_max | row_lb | row_ub], uploaded on change
     std::vector<double> gchk_cache;
+    DevBuf<char> d_score;       // scratch of smpc_score_rollout (ScoreScratch): the segments' partials and the running safe-set minimum
+    DevBuf<double> d_schk;      // bounds of smpc_score_rollout [x_min | x_max | row_lb | row_ub | ee_ref], uploaded on change
+    std::vector<double> schk_cache;
     char err[256] = "";
 };
 
@@ -1074,6 +1078,95 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
     return SMPC_OK;
 }
 
+// The small host arrays of smpc_score_rollout, in a device block of their own like upload_guess_bounds': uploaded only when they
+// change, so an unchanged call does not synchronise.
+int upload_score_bounds(smpc_handle* h, const smpc_score_params* par) {
+    const int nx = 2 * h->desc.nq, nr = h->desc.n_rows;
+    std::vector<double> cur((size_t)2 * nx + 2 * SMPC_MAX_ROWS + 3, 0.0);
+    memcpy(cur.data(), par->x_min, sizeof(double) * nx);
+    memcpy(cur.data() + nx, par->x_max, sizeof(double) * nx);
+    if (nr > 0) {
+        memcpy(cur.data() + 2 * nx, par->row_lb_chk, sizeof(double) * nr);
+        memcpy(cur.data() + 2 * nx + SMPC_MAX_ROWS, par->row_ub_chk, sizeof(double) * nr);
+    }
+    // (a call with traj does not read ee_ref: the block keeps the last one, so that alternating calls do not count as a change)
+    if (!par->traj) memcpy(cur.data() + 2 * nx + 2 * SMPC_MAX_ROWS, par->ee_ref, sizeof(double) * 3);
+    else if (h->schk_cache.size() == cur.size()) memcpy(cur.data() + 2 * nx + 2 * SMPC_MAX_ROWS, h->schk_cache.data() + 2 * nx + 2 * SMPC_MAX_ROWS, sizeof(double) * 3);
+    int rc;
+    if ((rc = h->d_schk.reserve(h, "score bounds", cur.size() * sizeof(double)))) return rc;
+    if (cur != h->schk_cache) {
+        if (capturing(h))
+            return fail(h, SMPC_ESTATE, "the score bounds changed while the stream is being captured: run one eager call with these "
+                        "bounds first");
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(h->d_schk.p, cur.data(), cur.size() * sizeof(double), hipMemcpyHostToDevice));
+        h->schk_cache.swap(cur);
+    }
+    return SMPC_OK;
+}
+
+// scratch of smpc_score_rollout: the partials of every (segment, instance) and the running safe-set minimum of every instance
+struct ScoreScratch {
+    double* pd;         // [n_seg][SCORE_PD][B]
+    int32_t* pi;        // [n_seg][SCORE_PI][B]
+    double* gmin;       // [B]
+    int32_t* gstep;     // [B]
+    size_t bytes;
+};
+ScoreScratch score_layout(char* base, int B, int n_seg) {
+    Carve m{base};
+    ScoreScratch w{};
+    w.pd = m.take<double>((size_t)n_seg * SCORE_PD * B);
+    w.pi = m.take<int32_t>((size_t)n_seg * SCORE_PI * B);
+    w.gmin = m.take<double>(B);
+    w.gstep = m.take<int32_t>(B);
+    w.bytes = m.off;
+    return w;
+}
+
+// The network's forward pass reads the state log as flat rows in passes of at most this many rows, so that its buffers are those of
+// one pass whatever n_steps * B is: 1 MiB of outputs with the one-kernel passes (256 wide, three hidden layers: ensure_mlp level 0),
+// 2.1 GiB with the layer-by-layer chain (any other network: level 2, 2129 floats a row at H = 256)
+constexpr long SCORE_MLP_ROWS = 1L << 18;
+
+// out / outi of the instances whose mask byte is set: k_score_seg over (64 instances) x (segment), the network in bounded passes
+// each followed by k_score_safe when the safe-set score is wanted, then k_score_combine
+template <int NQ>
+int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const double* u_log, const int64_t* last_x,
+                 const int64_t* last_u, const smpc_score_params* par, const double* traj, const uint8_t* mask, double* out,
+                 int32_t* outi) {
+    constexpr int nx = 2 * NQ;
+    hipStream_t s = h->stream;
+    const int n_seg = n_steps / SCORE_SEG + 1;          // segments of the n_steps + 1 states
+    int rc;
+    if ((rc = h->d_score.reserve(h, "score scratch", score_layout(nullptr, B, n_seg).bytes))) return rc;
+    const ScoreScratch w = score_layout(h->d_score.p, B, n_seg);
+    const double* d_min = h->d_schk.p;
+    const double* d_max = d_min + nx;
+    const double* d_rlb = d_max + nx;
+    const double* d_rub = d_rlb + SMPC_MAX_ROWS;
+    const double* d_ref = d_rub + SMPC_MAX_ROWS;
+    const unsigned gb = (unsigned)((B + 63) / 64);
+    hipLaunchKernelGGL((k_score_seg<NQ>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x, last_u,
+                       d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi);
+    HIPCHK(h, hipGetLastError());
+    if (par->want_safe) {
+        const long total = (long)(n_steps + 1) * B;
+        for (long m0 = 0; m0 < total; m0 += SCORE_MLP_ROWS) {
+            const long rows = total - m0 < SCORE_MLP_ROWS ? total - m0 : SCORE_MLP_ROWS;
+            if ((rc = run_mlp<NQ>(h, (int)rows, 0, 0, x_log + m0 * nx, false))) return rc;
+            hipLaunchKernelGGL((k_score_safe<NQ>), dim3(gb), dim3(64), 0, s, h->d_desc, B, n_steps, m0, rows, m0 == 0 ? 1 : 0, x_log, last_x,
+                               last_u, par->alpha, mask, (const float*)h->d_y.p, w.gmin, w.gstep);
+            HIPCHK(h, hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_score_combine, dim3(gb), dim3(64), 0, s, B, n_steps, h->desc.Q, h->desc.R, last_x, last_u, mask,
+                       (const double*)w.pd, (const int32_t*)w.pi, par->want_safe ? (const double*)w.gmin : (const double*)nullptr,
+                       (const int32_t*)w.gstep, out, outi);
+    HIPCHK(h, hipGetLastError());
+    return SMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1829,6 +1922,43 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
          })))
         return rc;
     DISPATCH_NQ(h, (launch_check_guess<NQ_>(h, B, dx, du, par, dmask, dflags, dworst)));
+    if (rc) return rc;
+    return io.finish();
+}
+
+int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, const double* u_log, const int64_t* last_x,
+                       const int64_t* last_u, const smpc_score_params* par, const uint8_t* mask, double* out, int32_t* outi,
+                       int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (n_steps < 1) return fail(h, SMPC_EINVAL, "n_steps=%d: a log has at least one step", n_steps);
+    if (B <= 0 || !x_log || !u_log || !par || !out || !outi) return fail(h, SMPC_EINVAL, "bad argument");
+    if (!par->x_min || !par->x_max) return fail(h, SMPC_EINVAL, "state bounds missing");
+    if (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
+    if (par->traj && par->traj_len < 1) return fail(h, SMPC_EINVAL, "traj given with traj_len=%lld", (long long)par->traj_len);
+    if (!par->traj && !par->ee_ref) return fail(h, SMPC_EINVAL, "neither ee_ref nor traj given");
+    if (par->want_safe && h->nlayers == 0) return fail(h, SMPC_ESTATE, "want_safe given but smpc_set_mlp was not called");
+    (void)hipSetDevice(h->device);
+    const int nq = h->desc.nq;
+    int rc;
+    if ((rc = upload_score_bounds(h, par))) return rc;
+    Stage io{h, on_device != 0};
+    const double *dx, *du, *dtraj;
+    const int64_t *dlx, *dlu;
+    const uint8_t* dmask;
+    double* dout;
+    int32_t* douti;
+    if ((rc = io.place([&](Stage& v) {
+             dx = v.in(x_log, (size_t)(n_steps + 1) * B * 2 * nq);
+             du = v.in(u_log, (size_t)n_steps * B * nq);
+             dlx = v.in(last_x, (size_t)B);
+             dlu = v.in(last_u, (size_t)B);
+             dtraj = v.in(par->traj, (size_t)3 * (par->traj ? par->traj_len : 0));
+             dmask = v.in(mask, (size_t)B);
+             dout = v.inout(out, (size_t)B * SCORE_ND);
+             douti = v.inout(outi, (size_t)B * SCORE_NI);
+         })))
+        return rc;
+    DISPATCH_NQ(h, (launch_score<NQ_>(h, B, n_steps, dx, du, dlx, dlu, par, dtraj, dmask, dout, douti)));
     if (rc) return rc;
     return io.finish();
 }

@@ -16,6 +16,12 @@ from . import _lib
 from .problem import JOINT_DTYPE, NODE_EVAL_DTYPE, OcpProblem
 
 
+# columns of BatchedOcpSolver.score_rollout's two results (SMPC_SCORE_ND doubles, SMPC_SCORE_NI int32 of include/smpc.h)
+SCORE_SLOTS = ('cost', 'ee_err2', 'u2', 'ee_dist', 'coll_margin', 'box_margin', 'safe_min')
+SCORE_INDEX_SLOTS = ('coll_step', 'coll_row', 'box_step', 'safe_step')
+SCORE_ND, SCORE_NI = len(SCORE_SLOTS), len(SCORE_INDEX_SLOTS)
+
+
 def _is_torch(a):
     return type(a).__module__.startswith('torch')
 
@@ -364,6 +370,63 @@ class BatchedOcpSolver:
         with self._ordered(dev):
             self._chk(self.L.smpc_check_guess(self.h, B, ptrs[0], ptrs[1], C.byref(gc), ptrs[2], fp, wp, dev))
         return flags, worst
+
+    # -- scoring a closed-loop run --------------------------------------------------------------------------------------
+    def score_rollout(self, x_log, u_log, last_x=None, last_u=None, ee_ref=None, traj=None, want_safe=False, mask=None, out=None,
+                      outi=None, **bounds):
+        """Scores of a closed-loop run from its STEP-major logs ``x_log [n_steps+1, B, nx]``, ``u_log [n_steps, B, nu]``, forward-only
+        on the device (smpc_score_rollout; the numpy statement is closed_loop.score_rollout_statement).  Returns
+        ``(out [B, 7], outi [B, 4] int32)`` with the columns ``SCORE_SLOTS`` / ``SCORE_INDEX_SLOTS``: closed-loop cost
+        (metrics_count_fails.py:19-28), its two sums, the EE distance of the last state (mpc.py:273), the worst collision and
+        state-box margins and the least safe-set value with the step (and row) each was taken at.  ``last_x`` / ``last_u`` (int64
+        [B]): last valid row of each log, None = complete; rows past them affect nothing.  The reference point is ``traj [3, L]``
+        (column min(j, L - 1) at step j) or the constant ``ee_ref`` (default: the problem's).  ``want_safe`` needs a network.
+        ``mask`` (uint8 [B]): instances with 0 are skipped and keep their rows of ``out`` / ``outi``.  ``bounds`` may override
+        x_min, x_max, row_lb, row_ub, alpha, tol_safe (defaults from the problem and its params, as in :meth:`check_guess`)."""
+        pr, par = self.problem, self.problem.params
+        unknown = set(bounds) - {'x_min', 'x_max', 'row_lb', 'row_ub', 'alpha', 'tol_safe'}
+        if unknown:
+            raise TypeError(f'score_rollout: unknown argument(s) {sorted(unknown)}')
+        small = [np.ascontiguousarray(bounds.get(k, d), np.float64)
+                 for k, d in (('x_min', pr.x_min), ('x_max', pr.x_max), ('row_lb', pr.row_check[:, 0]), ('row_ub', pr.row_check[:, 1]))]
+        small.append(np.ascontiguousarray(pr.ee_ref if ee_ref is None else ee_ref, np.float64))
+        for a, n in zip(small, (self.nx, self.nx, len(pr.row_check), len(pr.row_check), 3)):
+            if a.shape != (n,):
+                raise ValueError(f'score_rollout: a bound has shape {a.shape}, expected ({n},)')
+        if x_log.ndim != 3 or u_log.ndim != 3:
+            raise ValueError('score_rollout: x_log [n_steps+1, B, nx] and u_log [n_steps, B, nu] expected')
+        n_steps, B = int(u_log.shape[0]), int(x_log.shape[1])
+        L = int(traj.shape[1]) if traj is not None else 0
+        ptrs, dev, keep = self._prep([x_log, u_log, last_x, last_u, traj, mask, out, outi],
+                                     [(n_steps + 1, B, self.nx), (n_steps, B, self.nu), (B,), (B,), (3, L), (B,), (B, SCORE_ND), (B, SCORE_NI)],
+                                     [np.float64, np.float64, np.int64, np.int64, np.float64, np.uint8, np.float64, np.int32])
+        if dev:
+            import torch
+            if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError('mask must be uint8 or bool')
+            for a in (last_x, last_u):
+                if a is not None and a.dtype != torch.int64:
+                    raise ValueError('last_x / last_u must be int64')
+            if traj is not None and traj.dtype != torch.float64:
+                raise ValueError('traj must be float64')
+            if out is None:
+                out = torch.zeros((B, SCORE_ND), dtype=torch.float64, device=x_log.device)
+            if outi is None:
+                outi = torch.zeros((B, SCORE_NI), dtype=torch.int32, device=x_log.device)
+            if out.dtype != torch.float64 or outi.dtype != torch.int32:
+                raise ValueError('out must be float64 and outi int32')
+            op, ip = out.data_ptr(), outi.data_ptr()
+        else:
+            out = np.zeros((B, SCORE_ND)) if out is None else out
+            outi = np.zeros((B, SCORE_NI), np.int32) if outi is None else outi
+            assert out.dtype == np.float64 and out.shape == (B, SCORE_ND) and out.flags.c_contiguous
+            assert outi.dtype == np.int32 and outi.shape == (B, SCORE_NI) and outi.flags.c_contiguous
+            op, ip = out.ctypes.data, outi.ctypes.data
+        sp = _lib.ScoreParams(float(bounds.get('alpha', par.alpha)), float(bounds.get('tol_safe', par.tol_safe_set)), int(bool(want_safe)), 0,
+                              *[a.ctypes.data for a in small], ptrs[4], L)
+        with self._ordered(dev):
+            self._chk(self.L.smpc_score_rollout(self.h, B, n_steps, ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(sp), ptrs[5], op, ip, dev))
+        return out, outi
 
     # -- callers around the solve (a13, a15, a16) ------------------------------------------------------------------------
     def guess_correction(self, x_guess, u_guess):

@@ -31,7 +31,27 @@ def closed_loop_costs(params, prob, solver, x, u):
     return params.Q_weight * err.sum(1) + params.R_weight * np.sum(np.nan_to_num(u) ** 2, axis=(1, 2))
 
 
-def score_results(params, prob, solver, res):
+def closed_loop_costs_scored(params, prob, solver, x, u):
+    """The same cost from ``score_rollout`` (smpc_score_rollout: forward kinematics only, no linearisation records; the numpy
+    statement closed_loop.score_rollout_statement for a solver without that entry point).  x [n, T+1, nx], u [n, T, nu] as
+    pickled: step-major logs and the last valid row of each are rebuilt from the NaN padding (mpc.py:114).  One difference: a
+    truncated log is summed over its valid rows only, where closed_loop_costs adds the terms of a zero state for the padded rows;
+    for complete logs the two agree."""
+    n, T = u.shape[0], u.shape[1]
+    bad_x, bad_u = np.isnan(x[:, :T + 1]).any(2), np.isnan(u).any(2)
+    last_x = np.where(bad_x.any(1), np.argmax(bad_x, axis=1) - 1, T).astype(np.int64)
+    last_u = np.where(bad_u.any(1), np.argmax(bad_u, axis=1) - 1, T - 1).astype(np.int64)
+    last_x = np.maximum(last_x, np.maximum(last_u, 0))
+    x_log = np.ascontiguousarray(np.transpose(x[:, :T + 1], (1, 0, 2)))
+    u_log = np.ascontiguousarray(np.transpose(u, (1, 0, 2)))
+    if hasattr(solver, 'score_rollout'):
+        out, _ = solver.score_rollout(x_log, u_log, last_x, last_u)
+    else:
+        out, _ = cl.score_rollout_statement(solver, prob, params, x_log, u_log, last_x, last_u)
+    return out[:, 0]
+
+
+def score_results(params, prob, solver, res, scored=False):
     """One controller's entry of the scores dict (metrics_count_fails.py:63-93): every instance has a cost, -100 marking
     the failed ones (:70-71); 'score' is written as 0 by the reference (:87) -- the mean over completed runs is added as
     'mean_cost'."""
@@ -40,7 +60,7 @@ def score_results(params, prob, solver, res):
     done = sorted(set(range(n)) - set(failed))
     costs = np.full(n, -100.0)
     if done:
-        costs[done] = closed_loop_costs(params, prob, solver, res['x'][done], res['u'][done])
+        costs[done] = (closed_loop_costs_scored if scored else closed_loop_costs)(params, prob, solver, res['x'][done], res['u'][done])
     return {'score': 0, 'fails': len(failed), 'costs': costs.tolist(), 'completed_idx': done,
             'mean_cost': float(np.mean(costs[done])) if done else float('nan')}
 
@@ -61,6 +81,10 @@ def main(argv=None, make_solver=None):
     ap.add_argument('--joint_bounds_margin', type=float, default=0.0)
     ap.add_argument('--collision_margin', type=float, default=0.0)
     ap.add_argument('--data_dir', default=None, help='directory of the *_mpc.pkl files (default: <root>/data_noise/)')
+    ap.add_argument('--scored', action='store_true',
+                    help='take the costs from score_rollout (forward kinematics on the logs, no linearisation records).  One '
+                         'difference from the default: a truncated log (an instance that ended in safe abort) is summed over its valid '
+                         'rows only, where the default adds the terms of a zero state for the padded rows; complete logs agree')
     a = ap.parse_args(argv)
     args = {**default_args(), 'horizon': a.horizon, 'alpha': a.alpha, 'noise': a.noise, 'control_noise': a.control_noise,
             'joint_bounds_margin': a.joint_bounds_margin, 'collision_margin': a.collision_margin}
@@ -81,7 +105,7 @@ def main(argv=None, make_solver=None):
             scores[cont] = {'score': 0, 'fails': 0, 'costs': [float('nan')] * 100, 'completed_idx': list(range(params.test_num))}
             continue
         res = pickle.load(open(f, 'rb'))
-        scores[cont] = score_results(params, prob, solver, res)
+        scores[cont] = score_results(params, prob, solver, res, scored=a.scored)
         print(f"{cont:24s} fails {scores[cont]['fails']:4d}  mean cost {scores[cont]['mean_cost']:.4f}")
     out = scores_file(params, 'z1', params.N, params.alpha, a.noise, a.control_noise, a.joint_bounds_margin, a.collision_margin)
     cl.save_pickle(out, scores)
