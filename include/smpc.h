@@ -221,6 +221,27 @@ int smpc_set_stage_bounds(smpc_handle* h, const double* lo, const double* hi);
  * same B until cleared with lo = hi = NULL.  Pointers follow on_device like smpc_solve_batch; the handle keeps a copy. */
 int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const double* hi, int on_device);
 
+/* A scene of its own for every instance: where each collision row's FIXED obstacle sits in the world, per instance.  Geometry only:
+ * the rows themselves stay shared -- kinds, robot points, len2, bounds lb / ub and every check bound come from the descriptor.
+ * geom is [B][n_rows][SMPC_SCENE_ROW] doubles, one 64-byte record {C[3], D[3], offset, 0} per (instance, row), of which a row
+ * reads by kind
+ *   SMPC_ROW_SEG_FIXEDSEG  C, D (the fixed capsule's end points)      SMPC_ROW_SEG_POINT, _POINT_POINT  C (the fixed point)
+ *   SMPC_ROW_COORD         offset (value = P[axis] - offset)          SMPC_ROW_SEG_SEG                  nothing
+ * and the rest is ignored.  The handle keeps a copy (stream-ordered; with host pointers the call waits for it like
+ * smpc_set_instance_bounds), geom == NULL clears the scene.
+ * While a scene is set, every entry point that evaluates collision rows uses it: smpc_solve_batch, smpc_eval_nodes,
+ * smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_check_trajectory, smpc_score_rollout, smpc_policy_step (kinds 0-4) and
+ * smpc_loop_post.  The scene belongs to ITS batch size: a call of these with another B returns SMPC_EINVAL and names both sizes --
+ * it never falls back to the descriptor's obstacles, which would solve in the wrong world without a word.  Clear the scene (or set
+ * one of the new size) first.  SMPC_POLICY_PARALLEL (its candidate slots are not instances) and smpc_rollout_batch (its worker
+ * handles hold no scene) return SMPC_ESTATE while a scene is set.  Without a scene every entry point launches the kernels it
+ * launched before the scene existed.
+ * SMPC_EINVAL: B <= 0, a descriptor without rows, or (host pointers only) a non-finite value in a field that is read.
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+#define SMPC_SCENE_ROW 8   /* doubles per (instance, row): C[3], D[3], offset, 0 */
+int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device);
+
 /* replaces ocp_solver.cost_set(k,'zl'/'zu',v) (controller.py:455-468, 526-527): L1 penalty of the slack on the safe-set row of
  * node k, for the nodes where the formulation made that row soft (nn_soft_e / nn_soft_run >= 0; a hard row has no slack and
  * acados' arrays for it are empty).  zl is [N+1] host doubles shared by all instances (entry 0 unused); NULL restores the

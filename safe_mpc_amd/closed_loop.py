@@ -261,8 +261,53 @@ def _sqp_on_device(ctrl, x0, max_iter, history, verbose, opts):
     return state['status'].cpu().numpy()
 
 
+def _check_scenes(scenes, B, problem):
+    """``scenes`` as a contiguous float64 [B, n_rows, SCENE_ROW] array (problem.row_geometry's layout); ValueError otherwise"""
+    from .problem import SCENE_ROW
+    g = np.ascontiguousarray(scenes, np.float64)
+    want = (int(B), len(problem.rows), SCENE_ROW)
+    if g.shape != want:
+        raise ValueError(f'scenes: shape {g.shape}, expected {want} (one [n_rows, {SCENE_ROW}] geometry per instance)')
+    if not len(problem.rows):
+        raise ValueError('scenes: the problem has no collision rows')
+    return g
+
+
+def _set_scene(solver, geom):
+    if not hasattr(solver, 'set_instance_scene'):
+        raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene')
+    solver.set_instance_scene(geom)
+
+
+def _clear_scene(solver):
+    """the handle keeps no scene behind a run: ``make_controller`` / ``make_backup`` may hand out a solver that is used again, with
+    another batch size (refused while a scene of the old size is set) or with the same one (which would run in the old scenes)"""
+    if hasattr(solver, 'set_instance_scene'):
+        solver.set_instance_scene(None)
+
+
+def _free_starts_per_scene(solver, scenes, cand):
+    """The start states of :func:`generate_guess` with a scene per instance: the Halton candidates ``cand`` are walked in sampling
+    order, each one tested IN THE SCENE OF THE INSTANCE IT WOULD START (the next unfilled one) and skipped if it collides there --
+    with one scene for everybody, the free candidates in order, as without scenes.  The walk pairs all remaining candidates with
+    the remaining instances at once, keeps the pairs up to the first collision and re-pairs behind it: one engine call per
+    rejected candidate.  Returns (x0 [n, nx], filled [n] bool): filled is False where the candidates ran out."""
+    n = scenes.shape[0]
+    x0, filled = np.zeros((n, cand.shape[1])), np.zeros(n, bool)
+    c = k = 0
+    while k < n and c < len(cand):
+        m = min(n - k, len(cand) - c)
+        _set_scene(solver, scenes[k:k + m])
+        free = np.asarray(solver.check_trajectory(cand[c:c + m, None, :], tol_x=0.0)).astype(bool)      # guess_acados.py:109
+        ok = m if free.all() else int(np.argmin(free))          # pairs before the first collision stand
+        x0[k:k + ok], filled[k:k + ok] = cand[c:c + ok], True
+        c, k = c + ok + (ok < m), k + ok
+    _set_scene(solver, None)
+    return x0, filled
+
+
 def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7,
-                   alpha_min=0.05, history=None, on_device=False):
+                   alpha_min=0.05, history=None, on_device=False, scenes=None):
     """guess_acados.py:98-158: Halton q0 in the joint box, collision filter, constant guess, SQP to convergence, checkGuess.
 
     SQP with merit backtracking (the reference runs acados with nlp_solver_type SQP, globalization MERIT_BACKTRACKING,
@@ -277,7 +322,13 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
 
     ``on_device=True``: the same sampling, filter and checkGuess, with the SQP iterations run by the engine on device-resident
     arrays (``solver.sqp``, smpc_sqp_batch) instead of the numpy loop below, which stays the statement the engine's iteration is
-    tested against.  With ``history`` the engine advances one iteration per call and the same keys are appended."""
+    tested against.  With ``history`` the engine advances one iteration per call and the same keys are appended.
+
+    ``scenes`` ([n, n_rows, 8], ``OcpProblem.scene`` / ``jittered_scenes``): instance i is sampled, solved and tested in ITS scene
+    (solver.set_instance_scene): the Halton candidates are walked in order and each is tested against the scene of the instance it
+    would start, so a candidate that collides there is skipped (:func:`_free_starts_per_scene`).  The result gains ``'scenes'``, the
+    geometry of the accepted instances, and the returned mask has one entry per requested instance (False too where the
+    candidates ran out)."""
     make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
     ctrl = make_controller(cont_name, n)
     if on_device and not hasattr(ctrl.ocp_solver, 'sqp'):
@@ -285,20 +336,39 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
                          f'{type(ctrl.ocp_solver).__name__} has none')
     pr = ctrl.problem
     nq = pr.nq
+
     q = pr.x_min[:nq] + halton(4 * n + 16, nq) * (pr.x_max[:nq] - pr.x_min[:nq])        # guess_acados.py:100
     x_all = np.hstack([q, np.zeros_like(q)])
-    free = np.asarray(ctrl.ocp_solver.check_trajectory(x_all[:, None, :], tol_x=0.0))      # guess_acados.py:109
-    x0 = x_all[free][:n]
+    if scenes is not None:
+        scenes = _check_scenes(scenes, n, pr)
+        x0, filled = _free_starts_per_scene(ctrl.ocp_solver, scenes, x_all)
+        x0, scenes = x0[filled], scenes[filled]
+    else:
+        filled = None
+        free = np.asarray(ctrl.ocp_solver.check_trajectory(x_all[:, None, :], tol_x=0.0))      # guess_acados.py:109
+        x0 = x_all[free][:n]
     if len(x0) < n:
         ctrl = make_controller(cont_name, len(x0))
     B = len(x0)
+    if scenes is not None and B:
+        _set_scene(ctrl.ocp_solver, scenes)
+
+    def result(good):
+        out = {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}
+        if filled is None:
+            return out, good
+        out['scenes'] = scenes[good]
+        mask = np.zeros(n, bool)
+        mask[np.where(filled)[0][good]] = True
+        return out, mask
+
     ctrl.setGuess(np.repeat(x0[:, None, :], ctrl.N + 1, axis=1), np.zeros((B, ctrl.N, ctrl.nu)))
     if on_device:
         status = _sqp_on_device(ctrl, x0, int(params.nlp_max_iter), history, verbose,
                                 dict(tol=sqp_tol, armijo=armijo, alpha_reduction=alpha_reduction, alpha_min=alpha_min))
         ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
         good = ((status == 0) | (status == 2)) & ctrl.checkGuess()
-        return {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}, good
+        return result(good)
     done = np.zeros(B, bool)
     status = np.zeros(B, np.int32)
     mu = np.full(B, 10.0)
@@ -339,7 +409,7 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
             break
     ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
     good = ((status == 0) | (status == 2)) & ctrl.checkGuess()              # guess_acados.py:115 accepts status 0 or 2
-    return {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}, good
+    return result(good)
 
 
 class GuessSlots:
@@ -431,7 +501,7 @@ class _FreeStarts:
 
 
 def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accept='final', max_samples=None, make_controller=None,
-                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05):
+                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, scenes=None):
     """guess_acados.py:98-158 with its ``while succ < num_ics``: sample, solve and test warm starts until ``n`` are ACCEPTED, on
     the device.  Returns ``(guess, info)``: ``guess['xg'] [n, N+1, nx]``, ``guess['ug'] [n, N, nu]`` in sampling order.
 
@@ -457,6 +527,9 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
 
     ``info``: 'accepted' / 'failed' (sample indices, sampling order), 'iters' (SQP iterations of every issued sample),
     'status', 'flags' (at the sample's resolution), 'issued', 'rounds', 'instance_iterations', 'exhausted'."""
+    if scenes is not None:
+        raise ValueError('generate_guess_until: per-instance scenes are not supported (a refilled slot would need the scene of its '
+                         'new sample); use generate_guess(scenes=...)')
     if accept not in ('final', 'first'):
         raise ValueError("accept must be 'final' or 'first'")
     check_every = int(check_every)
@@ -582,8 +655,33 @@ def _score_eval_chunks(solver, problem, states, alpha, chunk, safe):
     return ee, rows, g
 
 
+def _score_eval_instances(solver, problem, x, alpha, safe):
+    """:func:`_score_eval_chunks` for a solver that holds a scene per instance: every call evaluates all B instances, instance b's
+    own states packed into the nodes of ITS trajectory (so its rows are formed in its scene).  x [B, M, nx] -> the same three
+    arrays for the B * M states, instance-major."""
+    N, nx, nr = solver.N, problem.nx, int(problem.desc.n_rows)
+    B, M = x.shape[0], x.shape[1]
+    ee, rows, g = np.zeros((B, M, 3)), np.zeros((B, M, nr)), np.zeros((B, M))
+    nodes = slice(0, N + 1) if not safe else (slice(1, N + 1) if int(problem.desc.nn_mode) == 2 else slice(N, N + 1))
+    per = nodes.stop - nodes.start
+    p = np.zeros((B, N + 1, 5))
+    p[:, :, 3], p[:, :, 4] = alpha, 1.0
+    for lo in range(0, M, per):
+        m = min(per, M - lo)
+        xg = np.zeros((B, N + 1, nx))
+        xg[:, nodes.start:nodes.start + m] = x[:, lo:lo + m]
+        ev = solver.eval_nodes(xg, np.zeros((B, N, problem.nu)), p)
+        sl = slice(nodes.start, nodes.start + m)
+        if safe:
+            g[:, lo:lo + m] = np.asarray(ev['nn_val'])[:, sl]
+        else:
+            ee[:, lo:lo + m] = np.asarray(ev['ee'])[:, sl]
+            rows[:, lo:lo + m] = np.asarray(ev['row_val'])[:, sl, :nr]
+    return ee.reshape(-1, 3), rows.reshape(-1, nr), g.reshape(-1)
+
+
 def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, last_u=None, ee_ref=None, traj=None, want_safe=False,
-                            chunk=4096, **bounds):
+                            chunk=4096, per_instance=False, **bounds):
     """The readable numpy statement of ``BatchedOcpSolver.score_rollout`` (smpc_score_rollout, include/smpc.h), and the host path of
     ``run_mpc(score=True)``.  STEP-major logs ``x_log [T+1, B, nx]``, ``u_log [T, B, nu]``; ``last_x`` / ``last_u`` [B]: last valid
     row of each, None = complete; rows past them affect nothing.  Returns ``(out [B, 7], outi [B, 4] int32)`` with the columns
@@ -598,7 +696,9 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
     * coll_step, coll_row, box_step, safe_step: where they were taken, earliest step then lowest row among equals; -1 where there is
       nothing.  A NaN in a valid row makes the values it enters NaN (placed at the first one).
 
-    Uses only ``solver.eval_nodes`` (``ee``, ``row_val``; ``nn_val`` for g), ``chunk`` states per call."""
+    Uses only ``solver.eval_nodes`` (``ee``, ``row_val``; ``nn_val`` for g), ``chunk`` states per call -- or, with ``per_instance``
+    (the solver holds a scene per instance, set_instance_scene), all B instances per call with every instance's states in its own
+    trajectory."""
     x = np.transpose(np.asarray(x_log, float), (1, 0, 2))          # [B, T+1, nx]
     u = np.transpose(np.asarray(u_log, float), (1, 0, 2))          # [B, T, nu]
     B, T = u.shape[0], u.shape[1]
@@ -622,7 +722,10 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
     else:
         ref = np.asarray(problem.ee_ref if ee_ref is None else ee_ref, float)[None, None, :]
     flat = np.where(vx[:, :, None], x, 0.0).reshape(-1, x.shape[2])                  # invalid rows: any finite state, masked below
-    ee, rv, _ = _score_eval_chunks(solver, problem, flat, alpha, chunk, False)
+    if per_instance:
+        ee, rv, _ = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, False)
+    else:
+        ee, rv, _ = _score_eval_chunks(solver, problem, flat, alpha, chunk, False)
     e2 = np.sum((ee.reshape(B, T + 1, 3) - ref) ** 2, axis=2)
     out, outi = np.zeros((B, 7)), np.full((B, 4), -1, np.int32)
     out[:, 1] = np.where(vx, e2, 0.0).sum(1)
@@ -642,7 +745,10 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
     if want_safe:
         if int(problem.desc.nn_mode) == 0:
             raise ValueError('want_safe needs a formulation with a safe-set row (eval_nodes reports g on the nodes that carry it)')
-        _, _, g = _score_eval_chunks(solver, problem, flat, alpha, chunk, True)
+        if per_instance:
+            _, _, g = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, True)
+        else:
+            _, _, g = _score_eval_chunks(solver, problem, flat, alpha, chunk, True)
         g = np.where(vx, g.reshape(B, T + 1), np.inf)
         at = np.argmin(g, axis=1)
         out[:, 6], outi[:, 3] = g[np.arange(B), at], at
@@ -675,11 +781,17 @@ class _Group(InPlaceState):
     is captured once as a hipGraph and replayed: one graph launch instead of ~50 kernel launches per half."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, use_graphs,
-                 collect_times=False):
+                 collect_times=False, scenes=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
         self._xp, self._B = xp, B
+        # a scene per instance (run_mpc(scenes=...)): the controller's handle holds the group's [B, n_rows, 8]; the backup handle gets
+        # the rows of the aborting instances before each of its compact solves (_backup_scene)
+        self._scenes = None
+        if scenes is not None:
+            self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
+            _set_scene(ctrl.ocp_solver, self._scenes)
         # stats.append(controller.getTime()) of scripts/mpc.py:239: one row of the seven time_fields per step of this group's
         # controller.  Device path: the engine keeps HIP events of its last 64 solves (smpc_get_timing_history); they are read
         # at least 32 solves late -- finished by then, so nothing waits inside the loop.
@@ -819,6 +931,7 @@ class _Group(InPlaceState):
         xv_c = xv[rows_b]
         n_c = len(rows)
         xg_c = xp.repeat_nodes(xv_c, Nb + 1)
+        self._backup_scene(rows_b)
         xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c if xp.on_device else np.ascontiguousarray(xv_c), xg_c,
                                                       xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
         self._abort_events.append((rows + self._first, np.full(n_c, j), xp.host(xv_c)))
@@ -839,6 +952,12 @@ class _Group(InPlaceState):
         self.ja = self.ja * xp.cast(~okb, xp.i64)
         self.sa = self.sa | okb
         self.viable = xp.cast(xp.clip_max(xp.cast(self.viable, xp.i64) + xp.cast(okb, xp.i64), 255), xp.u8)   # saturating, like k_loop_apply_backup
+
+    def _backup_scene(self, rows_b):
+        """the backup OCP of an abort event is solved in the scenes of the aborting instances: their geometry rows, gathered in the
+        order of the compact batch, onto the backup handle"""
+        if self._scenes is not None:
+            _set_scene(self._backup.ocp_solver, self._scenes[rows_b])
 
     def _apply_inflight(self):
         if self._inflight is None:
@@ -872,6 +991,7 @@ class _Group(InPlaceState):
         with torch.cuda.stream(self._side):
             self._side.wait_event(ev0)
             xg_c = xp.repeat_nodes(xv_c, Nb + 1)
+            self._backup_scene(rows_b)
             xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
             ev = torch.cuda.Event()
             ev.record(self._side)
@@ -1001,7 +1121,7 @@ class _Group(InPlaceState):
                 scored = solver.score_rollout(self.x_log, self.u_log, self.last_x, self.last_u, traj=traj, want_safe=want_safe)
             else:
                 scored = score_rollout_statement(solver, pr, params, self.x_log, self.u_log, self.last_x, self.last_u,
-                                                 traj=traj, want_safe=want_safe)
+                                                 traj=traj, want_safe=want_safe, per_instance=self._scenes is not None)
         if xp.on_device:
             solver.sync()
         # convergence at the last step (mpc.py:273): the reference tests x_sim[-1], NaN for instances that broke
@@ -1017,6 +1137,10 @@ class _Group(InPlaceState):
         if not self._quirks:
             conv &= xp.host(self.alive)        # (the reference tests x_sim[-1] even of an instance it has just recorded as failed)
         extra = {'score': _score_dict(xp.host(scored[0]), xp.host(scored[1]))} if score else {}
+        if self._scenes is not None:
+            extra['scenes'] = xp.host(self._scenes)
+            _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
+            _clear_scene(self._backup.ocp_solver)
         return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
                     time_rows=np.array(self._time_rows, float).reshape(-1, len(TIME_FIELDS)), time_lost=self._time_lost,
                     collided=xp.host(self.collided), viable=xp.host(self.viable).astype(np.int64),
@@ -1038,7 +1162,7 @@ def time_row(t):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False):
+            score=False, scenes=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1057,9 +1181,21 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     ``score``: the result gains ``'score'``, a dict of [B] arrays keyed by ``solver.SCORE_SLOTS`` / ``SCORE_INDEX_SLOTS`` -- closed-loop
     cost, EE distance of the last state, worst collision / state-box margins, least safe-set value and where each was taken
     (:func:`score_rollout_statement`).  On the device every group scores its logs where they are (smpc_score_rollout); nothing else
-    in the result changes."""
+    in the result changes.
+    ``scenes`` ([B, n_rows, 8], ``OcpProblem.scene`` / ``jittered_scenes``): a scene of its own for every instance -- where the fixed
+    obstacles of its collision rows sit (solver.set_instance_scene; bounds, radii and kinds stay the problem's).  The controller's
+    solves and tests, the plant's outcome test, the scores and the backup OCP of an abort event all run in the instance's scene;
+    the result gains ``'scenes'``, and the controller's and the backup solver's handles are left without a scene when the run ends.
+    Not with the parallel policy (ValueError): its solver works on B x N candidate slots, which are not instances."""
     import time
     B = x_guess.shape[0]
+    if scenes is not None:
+        if cont_name == 'parallel':
+            raise ValueError("scenes: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
+                             "the engine refuses a scene there)")
+        scenes = np.ascontiguousarray(scenes, np.float64)
+        if scenes.ndim != 3 or scenes.shape[0] != B:
+            raise ValueError(f'scenes: expected [{B}, n_rows, 8], got {scenes.shape}')
     n_steps = int(n_steps if n_steps is not None else params.n_steps)
     if on_device:
         make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch, device=device, device_state=True))
@@ -1083,11 +1219,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
                 grp = _Group(params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, graphs,
-                             collect_times)
+                             collect_times, scenes=None if scenes is None else scenes[lo:hi])
         else:
             streams.append(None)
             grp = _Group(params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, False,
-                         collect_times)
+                         collect_times, scenes=None if scenes is None else scenes[lo:hi])
         grps.append(grp)
         gens.append(grp.run())
 
@@ -1165,6 +1301,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
                  'time_q99': np.quantile(ts, 0.99, axis=0) if len(ts) else np.zeros(len(TIME_FIELDS))}
     if score:
         extra['score'] = {k: np.concatenate([o['score'][k] for o in outs]) for k in outs[0]['score']}
+    if scenes is not None:
+        extra['scenes'] = np.concatenate([o['scenes'] for o in outs], axis=0)
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -282,4 +282,21 @@ __device__ __forceinline__ DQ<NQ> ball_segment_dist2(const DV3<NQ>& A, const DV3
     return dot(w, w);
 }
 
+// Where a row's fixed obstacle sits in the world: the descriptor's (SCENE = false: the same loads as before the scene existed)
+// or the instance's own record of smpc_set_instance_scene (SCENE = true), geom_b = the instance's [n_rows][SMPC_SCENE_ROW]
+// block -- 64-byte records {C[3], D[3], offset, 0} in a hipMalloc'ed buffer of the handle, so every record is 16-byte aligned.
+// Everything else of the row (kind, robot points, len2, bounds) comes from the descriptor either way.
+template <bool SCENE> struct RowGeom {
+    const double *C, *D, *offset;
+};
+template <bool SCENE>
+__device__ __forceinline__ RowGeom<SCENE> row_geom(const smpc_row& row, const double* __restrict__ geom_b, int r) {
+    if constexpr (SCENE) {
+        const double* g = static_cast<const double*>(__builtin_assume_aligned(geom_b + (size_t)r * SMPC_SCENE_ROW, 16));
+        return {g, g + 3, g + 6};
+    } else {
+        return {row.C, row.D, &row.offset};
+    }
+}
+
 }  // namespace smpc

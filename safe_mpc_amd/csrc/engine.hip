@@ -54,6 +54,8 @@ struct smpc_handle {
     DevBuf<double> d_zl;            // [N+1] run-time slack weights of the soft safe-set rows (cost_set); empty: the formulation's
     DevBuf<double> d_lo_b, d_hi_b;  // [B][N+1][nx] per-instance bounds (RealReceding), valid for inst_B
     int inst_B = 0;
+    DevBuf<double> d_scene;         // [B][n_rows][SMPC_SCENE_ROW] per-instance obstacle geometry (smpc_set_instance_scene), valid for scene_B
+    int scene_B = 0;                // 0: no scene, every launcher takes the shared-scene kernels
     // network
     int nlayers = 0;
     int act = SMPC_ACT_GELU_TANH;
@@ -396,6 +398,17 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
     return SMPC_OK;
 }
 
+// A scene belongs to its batch size: an entry point that evaluates collision rows refuses any other B while one is set (it would
+// otherwise solve in the descriptor's world without a word).  The launchers below then pick the SCENE instantiation by
+// h->scene_B == B.
+int scene_guard(smpc_handle* h, int B, const char* who) {
+    if (h->scene_B && h->scene_B != B)
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance scene was set for %d instances (smpc_set_instance_scene: clear "
+                    "it or set one of this size)", who, B, h->scene_B);
+    return SMPC_OK;
+}
+const double* scene_of(const smpc_handle* h, int B) { return h->scene_B == B ? h->d_scene.p : nullptr; }
+
 // the nodes' linearisation records by the thread-per-node kernel, the network's row included (smpc_eval_nodes, and the reference
 // set-up of smpc_debug_stage_records; not on the solve path)
 template <int NQ>
@@ -403,8 +416,12 @@ int launch_eval(smpc_handle* h, int B, const double* d_xg, const double* d_ug, c
     const int N = h->N;
     hipStream_t s = h->stream;
     const long n1 = (long)B * (N + 1);
-    hipLaunchKernelGGL((k_node_linearise<NQ>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
-                       d_p, d_ev);
+    if (const double* geom = scene_of(h, B))
+        hipLaunchKernelGGL((k_node_linearise<NQ, true>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
+                           d_p, d_ev, geom);
+    else
+        hipLaunchKernelGGL((k_node_linearise<NQ>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
+                           d_p, d_ev, (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
     int rc;
     if ((rc = launch_nn<NQ>(h, B, d_xg, d_p, d_ev, 0))) return rc;
@@ -465,9 +482,14 @@ int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* 
     const dim3 grd((unsigned)((nodes + 64 / SB_G - 1) / (64 / SB_G))), blk(64);
     const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn.p : nullptr;
     int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
+    const double* const geom = scene_of(h, B);
     with_rows(h, [&](auto MR) {
-        hipLaunchKernelGGL((k_stage_build<NQ, MR>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi, h->d_zl.p, nn,
-                           h->d_ws.p, bd.stride, h->d_active, zero_cnt);
+        if (geom)
+            hipLaunchKernelGGL((k_stage_build<NQ, MR, true>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi,
+                               h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, geom);
+        else
+            hipLaunchKernelGGL((k_stage_build<NQ, MR>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi, h->d_zl.p, nn,
+                               h->d_ws.p, bd.stride, h->d_active, zero_cnt, (const double*)nullptr);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -677,10 +699,19 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
     //  same moment, and next to resident QP wavefronts -- 256 registers each, two fill a SIMD -- it waited for that up to a
     //  millisecond: k_policy_post, six blocks of four waves, averaged 131 us in the three-stream loop; rocprofv3, round 3)
     const dim3 grd((unsigned)((M + 63) / 64)), blk(64);
-    switch (nq) {
-    case 5: hipLaunchKernelGGL((k_check_nodes<5>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes); break;
-    case 6: hipLaunchKernelGGL((k_check_nodes<6>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes); break;
-    default: hipLaunchKernelGGL((k_check_nodes<7>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes); break;
+    if (const double* geom = scene_of(h, B)) {
+        switch (nq) {
+        case 5: hipLaunchKernelGGL((k_check_nodes<5, true>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, geom); break;
+        case 6: hipLaunchKernelGGL((k_check_nodes<6, true>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, geom); break;
+        default: hipLaunchKernelGGL((k_check_nodes<7, true>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, geom); break;
+        }
+    } else {
+        const double* const none = nullptr;
+        switch (nq) {
+        case 5: hipLaunchKernelGGL((k_check_nodes<5>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, none); break;
+        case 6: hipLaunchKernelGGL((k_check_nodes<6>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, none); break;
+        default: hipLaunchKernelGGL((k_check_nodes<7>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, d_min, d_max, tol_x, d_rlb, d_rub, d_ok, coll_nodes, none); break;
+        }
     }
     HIPCHK(h, hipGetLastError());
     if (d_nn) {
@@ -1014,7 +1045,11 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
         if ((rc = run_mlp<NQ>(h, M, 3, N, xn, false))) return rc;
         y = h->d_y.p;
     }
-    hipLaunchKernelGGL((k_merit<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out);
+    if (const double* geom = scene_of(h, B))
+        hipLaunchKernelGGL((k_merit<NQ, true>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out, geom);
+    else
+        hipLaunchKernelGGL((k_merit<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out,
+                           (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
     if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
     return SMPC_OK;
@@ -1070,9 +1105,14 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
     const double* d_thi = d_tlo + NQ;
     const double* d_rlb = d_thi + NQ;
     const double* d_rub = d_rlb + SMPC_MAX_ROWS;
-    hipLaunchKernelGGL((k_check_guess<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
-                       par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, d_min, d_max, d_tlo, d_thi, d_rlb,
-                       d_rub, mask, y, (const int32_t*)h->d_guess.p, flags, worst);
+    if (const double* geom = scene_of(h, B))
+        hipLaunchKernelGGL((k_check_guess<NQ, true>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
+                           par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, d_min, d_max, d_tlo, d_thi, d_rlb,
+                           d_rub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, geom);
+    else
+        hipLaunchKernelGGL((k_check_guess<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
+                           par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, d_min, d_max, d_tlo, d_thi, d_rlb,
+                           d_rub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
     if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
     return SMPC_OK;
@@ -1147,8 +1187,12 @@ int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const 
     const double* d_rub = d_rlb + SMPC_MAX_ROWS;
     const double* d_ref = d_rub + SMPC_MAX_ROWS;
     const unsigned gb = (unsigned)((B + 63) / 64);
-    hipLaunchKernelGGL((k_score_seg<NQ>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x, last_u,
-                       d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi);
+    if (const double* geom = scene_of(h, B))
+        hipLaunchKernelGGL((k_score_seg<NQ, true>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x,
+                           last_u, d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi, geom);
+    else
+        hipLaunchKernelGGL((k_score_seg<NQ>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x, last_u,
+                           d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi, (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
     if (par->want_safe) {
         const long total = (long)(n_steps + 1) * B;
@@ -1360,12 +1404,46 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
     return SMPC_OK;
 }
 
+int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!geom) { h->scene_B = 0; return SMPC_OK; }
+    if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    const int nr = h->desc.n_rows;
+    if (nr == 0) return fail(h, SMPC_EINVAL, "the problem has no collision rows: there is no scene to set");
+    const size_t n = (size_t)B * nr * SMPC_SCENE_ROW;
+    if (!on_device) {
+        // the fields a row's kind reads must be finite (device pointers are taken as they are: reading them back would synchronise)
+        for (int b = 0; b < B; b++)
+            for (int r = 0; r < nr; r++) {
+                const double* g = geom + ((size_t)b * nr + r) * SMPC_SCENE_ROW;
+                const int kind = h->desc.rows[r].kind;
+                const int lo = kind == SMPC_ROW_COORD ? 6 : 0;
+                const int hi = kind == SMPC_ROW_SEG_FIXEDSEG ? 6 : (kind == SMPC_ROW_SEG_POINT || kind == SMPC_ROW_POINT_POINT ? 3 : (kind == SMPC_ROW_COORD ? 7 : 0));
+                for (int i = lo; i < hi; i++)
+                    if (!(g[i] - g[i] == 0.0))
+                        return fail(h, SMPC_EINVAL, "scene of instance %d, row %d (kind %d): entry %d is not finite", b, r, kind, i);
+            }
+    }
+    int rc;
+    // (grown only when the scene grows: a caller that moves its obstacles every step pays one stream-ordered copy)
+    if ((rc = h->d_scene.reserve(h, "instance scene", n * sizeof(double)))) {
+        if (!h->d_scene.p) h->scene_B = 0;      // (a failed growth left no buffer; a refused one keeps the old scene)
+        return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_scene.p, geom, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
+    h->scene_B = B;
+    return SMPC_OK;
+}
+
 int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p,
                      double* x_out, double* u_out, int32_t* status, int32_t* qp_iter, int on_device) {
     if (!h) return SMPC_EINVAL;
     if (B <= 0 || !x0 || !xg || !ug || !p || !x_out || !u_out || !status) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_solve_batch"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
     Stage io{h, on_device != 0};
@@ -1394,6 +1472,7 @@ int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, c
     if (B <= 0 || !xg || !ug || !p || !out) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_eval_nodes"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     hipStream_t s = h->stream;
@@ -1476,6 +1555,7 @@ int smpc_check_trajectory(smpc_handle* h, int B, int n_nodes, const double* x, c
     const size_t M = (size_t)B * n_nodes;
     // (x_min / x_max / row bounds are host pointers on both paths: small, constant per caller)
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_check_trajectory"))) return rc;
     if ((rc = upload_check_bounds(h, x_min, x_max, row_lb_chk, row_ub_chk))) return rc;
     Stage io{h, on_device != 0};
     const double* dx;
@@ -1526,6 +1606,10 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     if (!h) return SMPC_EINVAL;
     if (B <= 0 || n_steps <= 0 || !x0 || !x_guess || !u_guess || !p || !x_traj || !u_traj || !status_traj)
         return fail(h, SMPC_EINVAL, "bad argument");
+    if (h->scene_B)
+        return fail(h, SMPC_ESTATE, "smpc_rollout_batch: an instance scene is set (for %d instances) and the worker handles of the "
+                    "rollout hold none: clear it with smpc_set_instance_scene(h, 0, NULL, 0), or step the loop through "
+                    "smpc_policy_step / smpc_loop_post", h->scene_B);
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
@@ -1641,10 +1725,14 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     if (kind != SMPC_POLICY_NAIVE && (!par->x_min || !par->x_max || (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk))))
         return fail(h, SMPC_EINVAL, "check bounds missing");
     if ((receding || parallel) && h->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
+    if (parallel && h->scene_B)
+        return fail(h, SMPC_ESTATE, "smpc_policy_step: an instance scene is set (for %d instances) and the parallel policy's candidate "
+                    "slots are not instances: clear it with smpc_set_instance_scene(h, 0, NULL, 0)", h->scene_B);
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_policy_step"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     PolScratch w;
     if ((rc = policy_scratch(h, B, &w))) return rc;
@@ -1765,6 +1853,7 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     const int nq = h->desc.nq;
     hipStream_t s = h->stream;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_loop_post"))) return rc;
     PolScratch w;       // (its x_next [B][nx] and ok [B] lie behind smpc_policy_step's part)
     if ((rc = policy_scratch(h, B, &w))) return rc;
     if ((rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
@@ -1789,6 +1878,7 @@ int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, c
     const int N = h->N, nq = h->desc.nq;
     const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_merit_terms"))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, false, &w))) return rc;
     Stage io{h, on_device != 0};
@@ -1827,6 +1917,7 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
     const size_t nX = (size_t)B * nX1, nU = (size_t)B * nU1;
     hipStream_t s = h->stream;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_sqp_batch"))) return rc;
     if ((rc = ensure_batch(h, B, false))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, true, &w))) return rc;
@@ -1907,6 +1998,7 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_check_guess"))) return rc;
     if ((rc = upload_guess_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du;
@@ -1940,6 +2032,7 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
     (void)hipSetDevice(h->device);
     const int nq = h->desc.nq;
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_score_rollout"))) return rc;
     if ((rc = upload_score_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du, *dtraj;
@@ -2062,6 +2155,7 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     int rc;
+    if ((rc = scene_guard(h, B, "smpc_debug_stage_records"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     Stage io{h, false};

@@ -88,13 +88,16 @@ __device__ __forceinline__ double grp_max(double v) {
 }
 
 // One node.  Every lane of the wavefront calls this (cross-lane steps inside); `valid` = this group has a node.  L = the group's
-// LDS block.  ws = the stage's record.  g = lane within the group.
-template <int NQ, int MRT>
+// LDS block.  ws = the stage's record.  g = lane within the group.  SCENE: the fixed obstacles of the collision rows come from
+// geom_b, the instance's [n_rows][SMPC_SCENE_ROW] block of smpc_set_instance_scene, instead of the descriptor (the record of the
+// lane's row, eight doubles, then sits in the lane's registers where the shared scene has scalar loads).
+template <int NQ, int MRT, bool SCENE = false>
 __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict__ D, const QpLayout<NQ>& Ly, const int N, const int k,
                                             const bool valid, const int g, double* __restrict__ L, const double* __restrict__ x0b,
                                             const double* __restrict__ xk, const double* __restrict__ uk, const double* __restrict__ pk,
                                             const double* __restrict__ lo_k, const double* __restrict__ hi_k,
-                                            const double* __restrict__ zl_st, const double* __restrict__ nnk, double* __restrict__ w) {
+                                            const double* __restrict__ zl_st, const double* __restrict__ nnk, double* __restrict__ w,
+                                            const double* __restrict__ geom_b = nullptr) {
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NQP = QpLayout<NQ>::NQP, NZP = QpLayout<NQ>::NZP;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     constexpr int NSLOT = (MR_MAX + SB_G - 1) / SB_G;      // collision rows per lane (row g + 8 s on lane g)
@@ -362,6 +365,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
         const int r = g + SB_G * sl;
         const bool have = r < MR;
         const smpc_row& row = D->rows[have ? r : 0];
+        const RowGeom<SCENE> G = row_geom<SCENE>(row, geom_b, have ? r : 0);
         const rd::V3 Z0v = rd::v3(0, 0, 0);
         rd::V3 PA = Z0v, PB = Z0v, PC = Z0v, PD = Z0v, gA = Z0v, gB = Z0v, gC = Z0v, gD = Z0v;
         int lA = -1, lB = -1, lC = -1, lD = -1;      // links of the moving points (-1: fixed / unused)
@@ -374,7 +378,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
                     PC = ld_pt(row.pc); PD = ld_pt(row.pd);
                     lC = D->points[row.pc].link; lD = D->points[row.pd].link;
                 } else {
-                    PC = rd::v3(row.C[0], row.C[1], row.C[2]); PD = rd::v3(row.D[0], row.D[1], row.D[2]);
+                    PC = rd::v3(G.C[0], G.C[1], G.C[2]); PD = rd::v3(G.D[0], G.D[1], G.D[2]);
                 }
                 // utils.py:94-113
                 const rd::V3 ab = PB - PA, cd = PD - PC, ac = PC - PA;
@@ -413,7 +417,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
             } else if (row.kind == SMPC_ROW_SEG_POINT) {
                 PA = ld_pt(row.pa); PB = ld_pt(row.pb);
                 lA = D->points[row.pa].link; lB = D->points[row.pb].link;
-                const rd::V3 Pp = rd::v3(row.C[0], row.C[1], row.C[2]);
+                const rd::V3 Pp = rd::v3(G.C[0], G.C[1], G.C[2]);
                 // utils.py:115-118 (fmin(fmax(., 0), 1))
                 const rd::V3 pa_ = Pp - PA, ba = PB - PA;
                 const double t0 = rd::dot(pa_, ba) / row.len2;
@@ -429,13 +433,13 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
             } else if (row.kind == SMPC_ROW_POINT_POINT) {
                 PA = ld_pt(row.pa);
                 lA = D->points[row.pa].link;
-                const rd::V3 wv = PA - rd::v3(row.C[0], row.C[1], row.C[2]);
+                const rd::V3 wv = PA - rd::v3(G.C[0], G.C[1], G.C[2]);
                 val = rd::dot(wv, wv);
                 gA = wv * 2.0;
             } else {
                 PA = ld_pt(row.pa);
                 lA = D->points[row.pa].link;
-                val = (row.axis == 0 ? PA.x : (row.axis == 1 ? PA.y : PA.z)) - row.offset;
+                val = (row.axis == 0 ? PA.x : (row.axis == 1 ? PA.y : PA.z)) - *G.offset;
                 gA = rd::v3(row.axis == 0, row.axis == 1, row.axis == 2);
             }
         }
@@ -655,12 +659,14 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
 }
 
 // Standalone launch: one wavefront = 8 nodes.  Node index t over (instance, stage); instances the policy layer masks out are skipped.
-template <int NQ, int MRT>
+// SCENE: geom = [B][n_rows][SMPC_SCENE_ROW], the handle's copy of the per-instance scene (unused and null otherwise).
+template <int NQ, int MRT, bool SCENE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB_WAVES))) void k_stage_build(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                                     const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ pp,
                                                     const double* __restrict__ lo_st, const double* __restrict__ hi_st,
                                                     const double* __restrict__ zl_st, const double* __restrict__ nn, double* __restrict__ ws_all,
-                                                    long bnd_stride, const uint8_t* __restrict__ active, int32_t* __restrict__ zero_cnt) {
+                                                    long bnd_stride, const uint8_t* __restrict__ active, int32_t* __restrict__ zero_cnt,
+                                                    const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ, NU = NQ;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     using LD = SbLds<NQ, MR_MAX>;
@@ -683,8 +689,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB
     const double* uk = ug + ((size_t)b * N + (k < N ? k : N - 1)) * NU;
     const double* pk = pp + ((size_t)b * (N + 1) + k) * SMPC_NP;
     const size_t bo = (size_t)b * bnd_stride + (size_t)k * NX;
-    stage_build<NQ, MRT>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
-                         nn ? nn + (D->nn_mode == SMPC_NN_TERMINAL ? (size_t)b : (size_t)b * (N + 1) + k) * (1 + NX) : nullptr, w);
+    stage_build<NQ, MRT, SCENE>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
+                                nn ? nn + (D->nn_mode == SMPC_NN_TERMINAL ? (size_t)b : (size_t)b * (N + 1) + k) * (1 + NX) : nullptr, w,
+                                SCENE ? geom + (size_t)b * Ly.MR * SMPC_SCENE_ROW : nullptr);
 }
 
 }  // namespace smpc

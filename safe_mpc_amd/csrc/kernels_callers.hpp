@@ -130,11 +130,12 @@ __device__ __forceinline__ bool node_rows_ok(const smpc_problem_desc* __restrict
 
 // checkStateConstraints over trajectories (env_model.py:170-173, 236-243): bounds with tolerance + collision rows within
 // the check bounds.  One thread per (instance, node); instance verdicts are AND-ed with an atomic.
-template <int NQ>
+// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+template <int NQ, bool SCENE = false>
 __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, int n_nodes, const double* __restrict__ x,
                               const double* __restrict__ x_min, const double* __restrict__ x_max, double tol_x,
                               const double* __restrict__ row_lb, const double* __restrict__ row_ub,
-                              int32_t* __restrict__ state_ok, int coll_nodes) {
+                              int32_t* __restrict__ state_ok, int coll_nodes, const double* __restrict__ geom = nullptr) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)B * n_nodes) return;
     constexpr int NX = 2 * NQ;
@@ -154,14 +155,16 @@ __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, in
     Mat3<double> Rw[NQ];
     Vec3<double> pw[NQ], zw[NQ];
     fk_world<NQ>(D->joints, q, Rw, pw, zw);
+    const double* const geom_b = SCENE ? geom + (size_t)(t / n_nodes) * D->n_rows * SMPC_SCENE_ROW : nullptr;
     for (int r = 0; r < D->n_rows; r++) {
         const smpc_row& row = D->rows[r];
+        const RowGeom<SCENE> G = row_geom<SCENE>(row, geom_b, r);
         double v;
         switch (row.kind) {
         case SMPC_ROW_SEG_FIXEDSEG:
             v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(row.C),
-                                  dv_const<NQ>(row.D)).v;
+                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(G.C),
+                                  dv_const<NQ>(G.D)).v;
             break;
         case SMPC_ROW_SEG_SEG:
             v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
@@ -172,16 +175,16 @@ __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, in
         case SMPC_ROW_SEG_POINT:
             v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
                                        point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
-                                       dv_const<NQ>(row.C)).v;
+                                       dv_const<NQ>(G.C)).v;
             break;
         case SMPC_ROW_POINT_POINT: {
-            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(row.C);
+            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(G.C);
             v = dot(w, w).v;
             break;
         }
         default: {
             DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
-            v = (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - row.offset;
+            v = (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - *G.offset;
             break;
         }
         }

@@ -48,7 +48,8 @@ __global__ void k_guess_nn_list(int B, int N, int safe_node, const uint8_t* __re
 //   worst[4]  -g at node safe_node, g as k_check_nn forms it; -inf and bit clear if safe_node < 0
 //                                                                        passes when g >= -tol_safe && g <= 1e6 + tol_safe
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
-template <int NQ>
+// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
                                                     const double* __restrict__ ug, double tol_x, double tol_tau, double tol_dyn,
                                                     double tol_safe, double alpha, int coll_first, int safe_node,
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
                                                     const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                     const uint8_t* __restrict__ mask, const float* __restrict__ y,
                                                     const int32_t* __restrict__ pos, int32_t* __restrict__ flags,
-                                                    double* __restrict__ worst) {
+                                                    double* __restrict__ worst, const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[SQP_PT_DOUBLES];
     __shared__ double s_sim[(SMPC_MAX_N + 1) * NX];
@@ -119,8 +120,9 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
                         spt[(3 * pt + 2) * 64] = w.z;
                     }
             }
+            const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
             for (int r = 0; r < nrows; r++) {
-                const double rv = sqp_row_value(D->rows[r], spt);
+                const double rv = sqp_row_value<SCENE>(D->rows[r], spt, row_geom<SCENE>(D->rows[r], geom_b, r));
                 w_row = guess_nanmax(w_row, guess_nanmax(row_lb[r] - rv, rv - row_ub[r]));
             }
         }

@@ -9,9 +9,11 @@
 namespace smpc {
 
 // ---- K1: geometry + cost, one thread per (b, k), k = 0..N ---------------------------------------------------------------
-template <int NQ>
+// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor
+template <int NQ, bool SCENE = false>
 __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
-                                              const double* __restrict__ p, double* __restrict__ out, const long t) {
+                                              const double* __restrict__ p, double* __restrict__ out, const long t,
+                                              const double* __restrict__ geom = nullptr) {
     if (t >= (long)B * (N + 1)) return;
     constexpr int NX = 2 * NQ;
     const double* x = xg + t * NX;
@@ -66,14 +68,16 @@ __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restric
     }
     // collision rows (env_model.py:263-316)
     const int nrows = D->n_rows;
+    const double* const geom_b = SCENE ? geom + (size_t)(t / (N + 1)) * nrows * SMPC_SCENE_ROW : nullptr;
     for (int r = 0; r < nrows; r++) {
         const smpc_row& row = D->rows[r];
+        const RowGeom<SCENE> G = row_geom<SCENE>(row, geom_b, r);
         DQ<NQ> v;
         switch (row.kind) {
         case SMPC_ROW_SEG_FIXEDSEG:
             v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(row.C),
-                                  dv_const<NQ>(row.D));
+                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(G.C),
+                                  dv_const<NQ>(G.D));
             break;
         case SMPC_ROW_SEG_SEG:
             v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
@@ -84,17 +88,17 @@ __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restric
         case SMPC_ROW_SEG_POINT:
             v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
                                        point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
-                                       dv_const<NQ>(row.C));
+                                       dv_const<NQ>(G.C));
             break;
         case SMPC_ROW_POINT_POINT: {
-            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(row.C);
+            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(G.C);
             v = dot(w, w);
             break;
         }
         default: {
             DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
             v = row.axis == 0 ? P.x : (row.axis == 1 ? P.y : P.z);
-            v.v -= row.offset;
+            v.v -= *G.offset;
             break;
         }
         }
@@ -151,12 +155,13 @@ __device__ __forceinline__ void node_torque(const smpc_problem_desc* __restrict_
 // The linearisation kernel: geometry + cost, then torque row and Jacobians, one thread per node, ONE launch.  As two kernels
 // (rounds 1-2) each of them waited for SIMD room of its own in the three-stream closed loop -- a wavefront of either needs a
 // SIMD that holds no QP wavefront (310 / 512 registers per lane) -- about 0.13 ms per wait against 0.04 / 0.05 ms of work.
-template <int NQ>
+template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_node_linearise(const smpc_problem_desc* __restrict__ D, int B, int N,
                                                        const double* __restrict__ xg, const double* __restrict__ ug,
-                                                       const double* __restrict__ p, double* __restrict__ out) {
+                                                       const double* __restrict__ p, double* __restrict__ out,
+                                                       const double* __restrict__ geom = nullptr) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    node_geometry<NQ>(D, B, N, xg, p, out, t);
+    node_geometry<NQ, SCENE>(D, B, N, xg, p, out, t, geom);
     node_torque<NQ>(D, B, N, xg, ug, out, t);
 }
 

@@ -39,14 +39,16 @@ __device__ __forceinline__ void score_last_rows(int b, int n_steps, const int64_
 // rows name their points by run-time index), adds |ee - ref|^2 and |u|^2 to its two sums and updates the two running maxima with
 // their places.  Rows past last_x / last_u are never loaded.  A lane whose log ends before the segment writes nothing
 // (k_score_combine does not read that segment's partial).  Partials are stored [segment][slot][B], so the stores coalesce too.
-template <int NQ>
+// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __restrict__ D, int B, int n_steps,
                                                   const double* __restrict__ x_log, const double* __restrict__ u_log,
                                                   const int64_t* __restrict__ last_x, const int64_t* __restrict__ last_u,
                                                   const double* __restrict__ x_min, const double* __restrict__ x_max,
                                                   const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                   const double* __restrict__ ee_ref, const double* __restrict__ traj, long traj_len,
-                                                  const uint8_t* __restrict__ mask, double* __restrict__ pd, int32_t* __restrict__ pi) {
+                                                  const uint8_t* __restrict__ mask, double* __restrict__ pd, int32_t* __restrict__ pi,
+                                                  const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[SQP_PT_DOUBLES];
     const int b = blockIdx.x * 64 + threadIdx.x, seg = blockIdx.y;
@@ -59,6 +61,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
     const int j1 = lx < j0 + SCORE_SEG - 1 ? lx : j0 + SCORE_SEG - 1;      // last step of this lane in the segment
     double* const spt = s_pts + threadIdx.x;
     const int np = D->n_points, nrows = D->n_rows, eep = D->ee_point;
+    const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
     for (int pt = 0; pt < np; pt++)
         if (D->points[pt].link < 0) {
 #pragma unroll
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
         if (j == lx) e_last = e2;
         // collision rows: max over the rows of max(lb - v, v - ub), rows ascending
         for (int r = 0; r < nrows; r++) {
-            const double rv = sqp_row_value(D->rows[r], spt);
+            const double rv = sqp_row_value<SCENE>(D->rows[r], spt, row_geom<SCENE>(D->rows[r], geom_b, r));
             const double m = guess_nanmax(row_lb[r] - rv, rv - row_ub[r]);
             if (score_takes_max(m_row, m)) {
                 m_row = m;

@@ -44,22 +44,24 @@ __device__ __forceinline__ DV3<0> sqp_point(const double* __restrict__ spt, int 
     return P;
 }
 
-// value of one collision row from the points' world positions (env_model.py:263-316; the values k_check_nodes tests)
-__device__ __forceinline__ double sqp_row_value(const smpc_row& row, const double* __restrict__ spt) {
+// value of one collision row from the points' world positions (env_model.py:263-316; the values k_check_nodes tests); the
+// fixed obstacle from the descriptor (G = row_geom<false>) or from the instance's scene (row_geom<true>)
+template <bool SCENE>
+__device__ __forceinline__ double sqp_row_value(const smpc_row& row, const double* __restrict__ spt, const RowGeom<SCENE>& G) {
     switch (row.kind) {
     case SMPC_ROW_SEG_FIXEDSEG:
-        return segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), dv_const<0>(row.C), dv_const<0>(row.D)).v;
+        return segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), dv_const<0>(G.C), dv_const<0>(G.D)).v;
     case SMPC_ROW_SEG_SEG:
         return segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), sqp_point(spt, row.pc), sqp_point(spt, row.pd)).v;
     case SMPC_ROW_SEG_POINT:
-        return ball_segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), row.len2, dv_const<0>(row.C)).v;
+        return ball_segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), row.len2, dv_const<0>(G.C)).v;
     case SMPC_ROW_POINT_POINT: {
-        DV3<0> w = sqp_point(spt, row.pa) - dv_const<0>(row.C);
+        DV3<0> w = sqp_point(spt, row.pa) - dv_const<0>(G.C);
         return dot(w, w).v;
     }
     default: {
         DV3<0> P = sqp_point(spt, row.pa);
-        return (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - row.offset;
+        return (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - *G.offset;
     }
     }
 }
@@ -100,12 +102,14 @@ __global__ void k_sqp_trial_states(int B, int per, const double* __restrict__ x,
 // out[b] = {f, viol, gd}.  Nothing per node is written.  gd = grad f . (dx, du) is formed at a_b = 0 only, from the EE point's
 // geometric Jacobian columns (which the forward kinematics has already paid for) against the lane's dq.
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
-template <int NQ>
+// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                               const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ p,
                                               const double* __restrict__ dxg, const double* __restrict__ dug,
                                               const double* __restrict__ alpha, const uint8_t* __restrict__ mask,
-                                              const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out) {
+                                              const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out,
+                                              const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[SQP_PT_DOUBLES];
     const int b = blockIdx.x, k = threadIdx.x;
@@ -186,9 +190,10 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
             }
             // collision rows of nodes 1..N
             const int nrows = D->n_rows;
+            const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
             for (int r = 0; r < nrows; r++) {
                 const smpc_row& row = D->rows[r];
-                const double rv = sqp_row_value(row, spt);
+                const double rv = sqp_row_value<SCENE>(row, spt, row_geom<SCENE>(row, geom_b, r));
                 if (fabs(row.lb) < SMPC_INF) viol += fmax(row.lb - rv, 0.0);
                 if (fabs(row.ub) < SMPC_INF) viol += fmax(rv - row.ub, 0.0);
             }

@@ -16,6 +16,7 @@ from .urdf import SerialChain
 
 ABI_VERSION = 5
 MAX_NQ, MAX_NX, MAX_POINTS, MAX_ROWS, MAX_LAYERS, MAX_N, NP = 7, 14, 12, 12, 6, 63, 5
+SCENE_ROW = 8         # SMPC_SCENE_ROW: doubles per (instance, row) of a scene -- C[3], D[3], offset, 0
 INF = 1.0e5
 
 ROW_SEG_FIXEDSEG, ROW_SEG_SEG, ROW_SEG_POINT, ROW_POINT_POINT, ROW_COORD = 0, 1, 2, 3, 4
@@ -168,6 +169,7 @@ class OcpProblem:
         # collision rows (env_model.py:263-316)
         self.rows = []
         self.row_names = []
+        self.row_obstacle = []         # name of the row's world-fixed element (what a scene moves); None for robot-robot rows
         self.row_check = []            # (lo, hi) used by checkCollision (env_model.py:236-243)
         m2 = 2.0 * params.collision_margin
         tol = params.tol_obs
@@ -184,14 +186,15 @@ class OcpProblem:
                     r.kind = ROW_SEG_SEG
                     r.pc, r.pd = self._capsule_points(e1)
                 r.lb, r.ub = (e0['radius'] + e1['radius'] + m2) ** 2, 1e6
-                self._push_row(r, f"{e0['name']}-{e1['name']}", (e0['radius'] + e1['radius']) ** 2 - tol, 1e6 + tol)
+                self._push_row(r, f"{e0['name']}-{e1['name']}", (e0['radius'] + e1['radius']) ** 2 - tol, 1e6 + tol,
+                               e1['name'] if r.kind == ROW_SEG_FIXEDSEG else None)
             elif pair['type'] == 'capsule-sphere':
                 r.kind = ROW_SEG_POINT
                 r.pa, r.pb = self._capsule_points(e0)
                 r.C[:] = e1['position']
                 r.len2 = e0['length'] ** 2
                 r.lb, r.ub = (e1['radius'] + e0['radius'] + m2) ** 2, 1e6
-                self._push_row(r, f"{e0['name']}-{e1['name']}", (e1['radius'] + e0['radius']) ** 2 - tol, 1e6 + tol)
+                self._push_row(r, f"{e0['name']}-{e1['name']}", (e1['radius'] + e0['radius']) ** 2 - tol, 1e6 + tol, e1['name'])
             elif pair['type'] == 'capsule-plane':
                 for pt in self._capsule_points(e0):
                     r = Row()
@@ -199,12 +202,12 @@ class OcpProblem:
                     r.lb = e1['bounds'][0] + e0['radius'] + m2
                     r.ub = e1['bounds'][1] - e0['radius'] - m2
                     self._push_row(r, f"{e0['name']}-{e1['name']}", e1['bounds'][0] + e0['radius'] - tol,
-                                   e1['bounds'][1] - e0['radius'] + tol)
+                                   e1['bounds'][1] - e0['radius'] + tol, e1['name'])
             elif pair['type'] == 'sphere-sphere':
                 r.kind, r.pa = ROW_POINT_POINT, d.ee_point      # the reference uses t_glob here (env_model.py:300)
                 r.C[:] = e1['position']
                 r.lb, r.ub = (e0['radius'] + e1['radius'] + m2) ** 2, 1e6
-                self._push_row(r, f"{e0['name']}-{e1['name']}", (e0['radius'] + e1['radius']) ** 2 - tol, 1e6 + tol)
+                self._push_row(r, f"{e0['name']}-{e1['name']}", (e0['radius'] + e1['radius']) ** 2 - tol, 1e6 + tol, e1['name'])
             elif pair['type'] == 'sphere-plane':
                 li, lR, lp = self.chain.frame(e0['link_name'])
                 r.kind = ROW_COORD
@@ -214,7 +217,7 @@ class OcpProblem:
                 r.lb = e1['bounds'][0] + e0['radius'] + m2
                 r.ub = e1['bounds'][1] - e0['radius'] - m2
                 self._push_row(r, f"{e0['name']}-{e1['name']}", e1['bounds'][0] + e0['radius'] - tol,
-                               e1['bounds'][1] - e0['radius'] + tol)
+                               e1['bounds'][1] - e0['radius'] + tol, e1['name'])
             else:
                 raise ValueError(f"unsupported collision pair type {pair['type']}")
         if len(self.rows) > MAX_ROWS:
@@ -303,10 +306,42 @@ class OcpProblem:
             cache[cap['name']] = tuple(pts)
         return cache[cap['name']]
 
-    def _push_row(self, r, name, chk_lo, chk_hi):
+    def _push_row(self, r, name, chk_lo, chk_hi, obstacle=None):
         self.rows.append(r)
         self.row_names.append(name)
+        self.row_obstacle.append(obstacle)
         self.row_check.append((chk_lo, chk_hi))
+
+    # -- per-instance scenes (smpc_set_instance_scene) ---------------------------------------------------------------------------
+    def row_geometry(self):
+        """[n_rows, SCENE_ROW]: where every row's world-fixed element sits -- C[3], D[3], offset, 0 -- as the descriptor has it.
+        The record of one (instance, row) of a scene; a row reads C and D (fixed capsule), C (sphere centre, fixed point) or
+        offset (plane) by its kind and nothing of a robot-robot row."""
+        g = np.zeros((len(self.rows), SCENE_ROW))
+        for i, r in enumerate(self.rows):
+            g[i, 0:3], g[i, 3:6], g[i, 6] = r.C[:], r.D[:], r.offset
+        return g
+
+    def scene(self, moves):
+        """The geometry [n_rows, SCENE_ROW] of this problem with some obstacles translated: ``moves = {obstacle name: (dx, dy, dz)}``,
+        names as in ``row_obstacle``.  Capsules and spheres translate; a plane's ``offset`` takes the component of the move along
+        its perpendicular axis.  Bounds, radii and kinds are not part of a scene: they stay the descriptor's."""
+        known = {n for n in self.row_obstacle if n is not None}
+        unknown = sorted(set(moves) - known)
+        if unknown:
+            raise ValueError(f'scene: unknown obstacle name(s) {unknown}; this problem has {sorted(known)}')
+        g = self.row_geometry()
+        for i, (r, name) in enumerate(zip(self.rows, self.row_obstacle)):
+            if name not in moves:
+                continue
+            d = np.asarray(moves[name], float).reshape(3)
+            if r.kind == ROW_COORD:
+                g[i, 6] = g[i, 6] + d[r.axis]
+            else:
+                g[i, 0:3] = g[i, 0:3] + d
+                if r.kind == ROW_SEG_FIXEDSEG:
+                    g[i, 3:6] = g[i, 3:6] + d
+        return g
 
     # per-instance perturbed joint tables for the plant (utils.py:126-171 semantics on the lumped inertias is NOT what
     # the reference does -- it perturbs each URDF link before lumping; see noise.py)
@@ -319,3 +354,37 @@ class OcpProblem:
             for f in ('mass', 'q_min', 'q_max', 'v_max', 'tau_max'):
                 out[i][f] = getattr(J, f)
         return out
+
+
+def _row_signature(prob):
+    """everything of the collision rows that a scene does NOT carry: what two problems must share to be scenes of one descriptor"""
+    return ([(r.kind, r.pa, r.pb, r.pc, r.pd, r.axis, r.len2, r.lb, r.ub) for r in prob.rows],
+            [(int(li), tuple(np.asarray(loc, float))) for li, loc in prob._points], np.asarray(prob.row_check, float).tolist())
+
+
+def scenes_from_problems(base, problems):
+    """[len(problems), n_rows, SCENE_ROW]: the geometry of problems built from moved parameters, as scenes of ``base``.  Every
+    problem must agree with ``base`` in what a scene does not carry -- row kinds, robot points, len2, lb / ub and the check bounds
+    -- so that each scene is a descriptor the oracle understands (``problems[i]`` itself); ValueError otherwise."""
+    ref = _row_signature(base)
+    out = []
+    for i, pr in enumerate(problems):
+        sig = _row_signature(pr)
+        for what, a, b in zip(('rows (kind, points, len2, lb, ub)', 'robot points', 'check bounds'), ref, sig):
+            if a != b:
+                raise ValueError(f'scenes_from_problems: problem {i} differs from the base in its {what}: only the obstacles\' '
+                                 f'positions may differ between scenes')
+        out.append(pr.row_geometry())
+    return np.array(out).reshape(len(out), len(base.rows), SCENE_ROW)
+
+
+def jittered_scenes(prob, B, sigma, seed=0):
+    """[B, n_rows, SCENE_ROW]: B random scenes of ``prob`` -- every obstacle translated by its own N(0, sigma^2) draw per axis,
+    one draw per (scene, obstacle) shared by all the rows that obstacle appears in."""
+    rng = np.random.default_rng(seed)
+    names = sorted({n for n in prob.row_obstacle if n is not None})
+    out = np.empty((B, len(prob.rows), SCENE_ROW))
+    for b in range(B):
+        d = rng.normal(0.0, float(sigma), (len(names), 3))
+        out[b] = prob.scene({n: d[i] for i, n in enumerate(names)})
+    return out

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .problem import JOINT_DTYPE, NODE_EVAL_DTYPE, OcpProblem
+from .problem import JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem
 
 
 # columns of BatchedOcpSolver.score_rollout's two results (SMPC_SCORE_ND doubles, SMPC_SCORE_NI int32 of include/smpc.h)
@@ -134,6 +134,23 @@ class BatchedOcpSolver:
         ptrs, dev, keep = self._prep([lo, hi], [(B, self.N + 1, self.nx)] * 2)
         with self._ordered(dev):
             self._chk(self.L.smpc_set_instance_bounds(self.h, B, ptrs[0], ptrs[1], dev))
+
+    def set_instance_scene(self, geom=None):
+        """A scene of its own for every instance (smpc_set_instance_scene): ``geom [B, n_rows, 8]`` -- per (instance, row) the
+        world-fixed element's C[3], D[3], offset, 0, as ``OcpProblem.row_geometry`` / ``scene`` / ``jittered_scenes`` lay it out --
+        as a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy.  None clears it.  While set, every call that
+        evaluates collision rows uses it and must come with the same B; the parallel policy and :meth:`rollout` refuse it."""
+        if geom is None:
+            self._chk(self.L.smpc_set_instance_scene(self.h, 0, None, 0))
+            return
+        if _is_torch(geom):
+            import torch
+            if geom.dtype != torch.float64:
+                raise ValueError('set_instance_scene: the scene must be float64')
+        B = int(geom.shape[0])
+        ptrs, dev, keep = self._prep([geom], [(B, len(self.problem.rows), SCENE_ROW)])
+        with self._ordered(dev):
+            self._chk(self.L.smpc_set_instance_scene(self.h, B, ptrs[0], dev))
 
     def sync(self):
         self._chk(self.L.smpc_sync(self.h))

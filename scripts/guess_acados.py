@@ -7,6 +7,9 @@
 --on-device: the SQP iterations run inside the engine on device-resident arrays (smpc_sqp_batch) instead of the host loop.
 --until-accepted [--accept first|final] [--batch B] [--check-every K]: the reference's `while succ < num_ics` -- samples are drawn,
 solved and tested on the device until exactly test_num guesses are accepted (closed_loop.generate_guess_until); implies --on-device.
+--scene-jitter SIGMA [--scene-seed S]: every guess is generated in a scene of its own, every obstacle moved by its own N(0, SIGMA^2)
+draw per axis (problem.jittered_scenes); the scenes of the accepted guesses are stored in the pickle as 'scenes', where scripts/mpc.py
+--scene-jitter finds them.  Not with --until-accepted.
 """
 import os
 import sys
@@ -31,16 +34,20 @@ def main(argv=None):
     cont_name = args['controller']
     # every safe-set controller name is generated with the hard-terminal OCP (utils.py:46-58)
     gen_name = cont_name if cont_name in ('naive', 'zerovel') else 'htwa'
+    scenes = None
+    if '--scene-jitter' in raw:
+        from safe_mpc_amd.problem import OcpProblem, jittered_scenes
+        scenes = jittered_scenes(OcpProblem(params, 'naive'), params.test_num, opt('--scene-jitter', 0.0, float), opt('--scene-seed', 0, int))
     t0 = time.time()
     if until:
         guess, info = cl.generate_guess_until(params, gen_name, params.test_num, batch=opt('--batch', None, int),
                                               check_every=opt('--check-every', 50, int), accept=opt('--accept', 'final', str),
-                                              verbose=True)
+                                              verbose=True, scenes=scenes)
         print(f'{len(info["accepted"])}/{params.test_num} guesses accepted from {info["issued"]} samples in {info["rounds"]} rounds, '
               f'{info["instance_iterations"]} instance-iterations, {time.time() - t0:.1f} s'
               + (' (sample stream exhausted)' if info['exhausted'] else ''))
     else:
-        guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device)
+        guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device, scenes=scenes)
         print(f'{good.sum()}/{len(good)} guesses accepted in {time.time() - t0:.1f} s')
     use_net = None if cont_name in ('naive', 'zerovel') else True
     out = cl.guess_file(params, model_name, cont_name, params.N, use_net)

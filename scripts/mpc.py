@@ -2,7 +2,10 @@
 """Closed-loop MPC run -- drop-in for the reference's scripts/mpc.py (same flags, config.yaml, guess / result pickles),
 with every instance of its outer loop (mpc.py:102) solved at once on the MI355X engine.
 
-    python scripts/mpc.py -c st --horizon 30 --alpha 10 [--noise 5 --control_noise 1]
+    python scripts/mpc.py -c st --horizon 30 --alpha 10 [--noise 5 --control_noise 1] [--scene-jitter SIGMA --scene-seed S]
+--scene-jitter SIGMA: every instance runs in a scene of its own -- the scenes stored with the guesses (guess_acados.py
+--scene-jitter) if there are any, else every obstacle moved by its own N(0, SIGMA^2) draw per axis (problem.jittered_scenes,
+seed --scene-seed, default 0).
 Exit code = number of failed instances, as in the reference (mpc.py:317).
 """
 import os
@@ -26,11 +29,20 @@ def main(argv=None):
     print(gfile)
     data = pickle.load(open(gfile, 'rb'))
     x_guess, u_guess = data['xg'][:params.test_num], data['ug'][:params.test_num]
+    raw = list(sys.argv[1:] if argv is None else argv)
+    scenes = None
+    if '--scene-jitter' in raw:
+        if 'scenes' in data:          # the warm starts were generated in these scenes
+            scenes = data['scenes'][:params.test_num]
+        else:
+            from safe_mpc_amd.problem import OcpProblem, jittered_scenes
+            seed = int(raw[raw.index('--scene-seed') + 1]) if '--scene-seed' in raw else 0
+            scenes = jittered_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], float(raw[raw.index('--scene-jitter') + 1]), seed)
     tm = {}
     # all loop state in HBM (policy automaton, abort handling, logs); SMPC_HOST_STATE=1 keeps it in numpy arrays instead
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],
                      callback=True, on_device=os.environ.get('SMPC_HOST_STATE', '0') != '1', timing=tm,
-                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1')
+                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes)
     with_stats = os.environ.get('SMPC_NO_TIME_STATS', '0') != '1'
     print(f"{tm['ms_per_step']:.3f} ms per closed-loop step of {x_guess.shape[0]} instances"
           + (' (eager launches with per-solve HIP events for the time statistics below; SMPC_NO_TIME_STATS=1 replays the step halves as '

@@ -11,7 +11,9 @@ SMPC_WARM_DEVICE=1: generate them with the engine's device-resident SQP (generat
 the host loop; SMPC_WARM_UNTIL=1: generate them until SMPC_B are accepted (generate_guess_until; SMPC_WARM_ACCEPT = final | first,
 SMPC_WARM_EVERY = iterations per round, SMPC_WARM_BATCH = device slots), so the loop runs on as many instances as were asked for;
 SMPC_WARM_STATS=1 runs the generation a second time with a history, to report SQP iterations and trial passes (with SMPC_WARM_UNTIL=1
-it prints the loop's own iteration counts instead)."""
+it prints the loop's own iteration counts instead).
+SMPC_SCENE_JITTER=SIGMA: every instance runs in a scene of its own (run_mpc(scenes=problem.jittered_scenes(prob, B, SIGMA)); 0 = the
+base geometry for every instance, i.e. the same world through the scene-aware kernels: the cost of a scene, profiles/instance_scenes.txt)."""
 import os
 import sys
 import time
@@ -72,6 +74,10 @@ def main():
             print(f'  with a history: {len(hist)} SQP iterations in {dt:.2f} s = {1e3 * dt / len(hist):.2f} ms per iteration, '
                   f'mean trial passes per iteration {np.mean(np.minimum(passes, 10)):.2f}, '
                   f'instances updated per iteration {np.mean([h["updated"].sum() for h in hist]):.0f}', flush=True)
+    scenes = None
+    if 'SMPC_SCENE_JITTER' in os.environ:
+        from safe_mpc_amd.problem import jittered_scenes
+        scenes = jittered_scenes(prob, B, float(os.environ['SMPC_SCENE_JITTER']), int(os.environ.get('SMPC_SCENE_SEED', '0')))
     for name in names:
         for dev in (True, False):
             if not dev and os.environ.get('SMPC_HOST', '0') != '1':
@@ -80,8 +86,8 @@ def main():
             t0 = time.perf_counter()
             res = cl.run_mpc(par, name, xg, ug, n_steps=steps, on_device=dev, timing=tm,
                              groups=int(os.environ['SMPC_GROUPS']) if 'SMPC_GROUPS' in os.environ else None,
-                             graphs=os.environ.get('SMPC_GRAPHS', '1') != '0')
-            print(f"{name:12s} {'device' if dev else 'host  '} state{' (warm starts)' if warm else ''}: {tm['ms_per_step']:.3f} ms/step over {tm['steps']} steps "
+                             graphs=os.environ.get('SMPC_GRAPHS', '1') != '0', scenes=scenes)
+            print(f"{name:12s} {'device' if dev else 'host  '} state{' (warm starts)' if warm else ''}{' (a scene per instance)' if scenes is not None else ''}: {tm['ms_per_step']:.3f} ms/step over {tm['steps']} steps "
                   f"(B={B}, N={N}, groups {tm.get('groups')}; total {time.perf_counter() - t0:.1f} s incl. set-up) | collisions {len(res['collisions_idx'])} "
                   f"viable {len(res['viable_idx'])} converged {len(res['conv_idx'])} unconverged {len(res['unconv_idx'])} abort events {len(res['x_viable'])}", flush=True)
 
