@@ -230,8 +230,8 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
  * and the rest is ignored.  The handle keeps a copy (stream-ordered; with host pointers the call waits for it like
  * smpc_set_instance_bounds), geom == NULL clears the scene.
  * While a scene is set, every entry point that evaluates collision rows uses it: smpc_solve_batch, smpc_eval_nodes,
- * smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_check_trajectory, smpc_score_rollout, smpc_policy_step (kinds 0-4) and
- * smpc_loop_post.  The scene belongs to ITS batch size: a call of these with another B returns SMPC_EINVAL and names both sizes --
+ * smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_ik_batch, smpc_check_trajectory, smpc_score_rollout, smpc_policy_step
+ * (kinds 0-4) and smpc_loop_post.  The scene belongs to ITS batch size: a call of these with another B returns SMPC_EINVAL and names both sizes --
  * it never falls back to the descriptor's obstacles, which would solve in the wrong world without a word.  Clear the scene (or set
  * one of the new size) first.  SMPC_POLICY_PARALLEL (its candidate slots are not instances) and smpc_rollout_batch (its worker
  * handles hold no scene) return SMPC_ESTATE while a scene is set.  Without a scene every entry point launches the kernels it
@@ -343,6 +343,48 @@ typedef struct {
  * captured.  SMPC_EINVAL: safe_node > N.  (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, const smpc_guess_check* par,
                      const uint8_t* mask, int32_t* flags, double* worst, int on_device);
+
+/* ---- start states at a chosen end-effector position: batched multi-start inverse kinematics ------------------------- */
+/* Per instance b: a joint configuration q in [q_lo, q_hi] whose end-effector point (the descriptor's ee_point) sits at target[b]
+ * and whose collision rows meet row_lb <= v_r(q) <= row_ub (a bound with |value| >= SMPC_INF is absent) -- the problem of the
+ * reference's InverseKinematicsOCP (ocp.py:321-326, solved there by IPOPT per instance; guess_acados.py:179-183 takes the start
+ * state of a tracking run from it).  The caller appends the zero velocity.
+ * S starts per instance (q_start[b][s], supplied by the caller: no sampler runs on the device) each run max_iter iterations of a
+ * projected Levenberg-Marquardt method on the stacked residual r(q) = {ee(q) - target; w (lb' - v_r) for the rows below their
+ * pushed bound lb' = lb + push |lb|; w (v_r - ub') for those above ub' = ub - push |ub|}, w = 1 / max(sqrt|bound|, 1e-3):
+ *   dq = -(J^T J + lam I)^-1 J^T r,  q' = clip(q + dq, q_lo, q_hi),  accepted when |r(q')|^2 < |r(q)|^2;
+ *   lam *= damping_accept (floor damping_min) on accept, *= damping_reject (cap damping_max) on reject, lam = damping at the start.
+ * A start succeeds when at its final point |ee - target|_inf <= tol_ee and every row is within its UNPUSHED bounds.  The winner
+ * is the successful start with the lowest index; if none succeeds, the start with the least final |r|^2 (ties: lowest index).
+ * The statement is safe_mpc_amd/ik.py::ik_batch_host. */
+typedef struct {
+    int32_t max_iter;               /* iterations of every start, exactly (40) */
+    int32_t reserved0;
+    double tol_ee;                  /* success: |ee - target|_inf <= tol_ee (1e-6, constr_viol_tol of ocp.py:338) */
+    double push;                    /* relative distance the rows are pushed inside their bounds (1e-2) */
+    double damping;                 /* lam at the start (1e-2) */
+    double damping_accept, damping_reject;  /* factors on lam after an accepted / rejected step (0.3, 4) */
+    double damping_min, damping_max;        /* floor and cap of lam (1e-9, 1e6) */
+    const double *q_lo, *q_hi;      /* HOST [nq] */
+    const double *row_lb, *row_ub;  /* HOST [n_rows] */
+} smpc_ik_params;
+
+/* target [B][3], q_start [B][S][nq] with 1 <= S <= 64; mask[B] (bytes, may be NULL): instances with mask[b] == 0 are skipped and
+ * their outputs left as they are (so the outputs are read as well as written on the host path).
+ *   q_out [B][nq]   the winner's final point: always finite and inside the box (a non-finite start component starts from the
+ *                   middle of its interval)
+ *   info  [B][2]    {index of the winning start, number of starts that succeeded (0 = no solution)}
+ *   resid [B][2]    {|ee - target|_inf, worst row margin max(lb - v, v - ub) over the present bounds; -inf without one}, both at
+ *                   q_out from a final forward-only evaluation
+ * Nothing is summed across starts or instances and no atomics are used: two calls give the same bits, and an instance's result
+ * does not depend on B or on the rest of the batch.  While a scene is set (smpc_set_instance_scene) the rows are formed in the
+ * instance's scene, and a call with another B returns SMPC_EINVAL.  target, q_start, mask, q_out, info, resid follow on_device
+ * like smpc_check_guess; with device pointers the call only enqueues.  The small host arrays of `par` are kept in a device block
+ * of the handle and uploaded only when they change.  SMPC_EINVAL: S outside 1..64, max_iter < 1, missing bounds.  SMPC_ESTATE: the
+ * bounds block would have to change while the stream is being captured.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_ik_batch(smpc_handle* h, int B, int S, const double* target, const double* q_start, const smpc_ik_params* par,
+                  const uint8_t* mask, double* q_out, int32_t* info, double* resid, int on_device);
 
 /* ---- scoring a closed-loop run where its logs are ------------------------------------------------------------------ */
 /* The last step of the experiment: the closed-loop cost of every instance (metrics_count_fails.py:19-28), the distance the

@@ -20,7 +20,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
            'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
-           'smpc_score_rollout', 'smpc_set_instance_scene']
+           'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch']
 
 
 class EngineError(RuntimeError):
@@ -77,6 +77,13 @@ class ScoreParams(C.Structure):
     _fields_ = [('alpha', C.c_double), ('tol_safe', C.c_double), ('want_safe', C.c_int32), ('reserved0', C.c_int32),
                 ('x_min', _vp), ('x_max', _vp), ('row_lb_chk', _vp), ('row_ub_chk', _vp), ('ee_ref', _vp), ('traj', _vp),
                 ('traj_len', C.c_int64)]
+
+
+class IkParams(C.Structure):
+    """smpc_ik_params: iteration settings and HOST pointers to the bounds of smpc_ik_batch"""
+    _fields_ = [('max_iter', C.c_int32), ('reserved0', C.c_int32), ('tol_ee', C.c_double), ('push', C.c_double), ('damping', C.c_double),
+                ('damping_accept', C.c_double), ('damping_reject', C.c_double), ('damping_min', C.c_double), ('damping_max', C.c_double),
+                ('q_lo', _vp), ('q_hi', _vp), ('row_lb', _vp), ('row_ub', _vp)]
 
 
 def build(force=False):
@@ -140,5 +147,6 @@ def lib():
     L.smpc_sqp_batch.argtypes = [vp, C.c_int, C.POINTER(SqpOpts), dp, dp, dp, dp, C.POINTER(SqpState), C.c_int]
     L.smpc_check_guess.argtypes = [vp, C.c_int, dp, dp, C.POINTER(GuessCheck), dp, dp, dp, C.c_int]
     L.smpc_score_rollout.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(ScoreParams), dp, dp, dp, C.c_int]
+    L.smpc_ik_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(IkParams), dp, dp, dp, dp, C.c_int]
     _lib = L
     return L

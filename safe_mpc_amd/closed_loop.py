@@ -36,6 +36,22 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}_mpc.pkl')
 
 
+def tracking_from_cli(params, argv):
+    """The curve of a tracking run as the entry scripts select it: ``--track 8|circle`` on the command line, or ``track_traj: true``
+    in config.yaml (the "8").  Returns ``tracking.tracking_trajectory(params, curve)`` -- which also makes the run
+    n_steps_tracking long and sets ``params.track_traj`` -- or None for the reach task."""
+    from .tracking import tracking_trajectory
+    argv = list(argv)
+    curve = None
+    if '--track' in argv:
+        if argv.index('--track') + 1 >= len(argv):
+            raise ValueError('--track needs a curve: 8 or circle')
+        curve = argv[argv.index('--track') + 1]
+    elif getattr(params, 'track_traj', False):
+        curve = '8'
+    return None if curve is None else tracking_trajectory(params, curve)
+
+
 def halton(n, dim, skip=1):
     """Unscrambled Halton points (guess_acados.py:79 uses scipy's qmc.Halton(d, scramble=False))."""
     primes = [2, 3, 5, 7, 11, 13, 17, 19, 23, 29]
@@ -306,8 +322,54 @@ def _free_starts_per_scene(solver, scenes, cand):
     return x0, filled
 
 
+def ik_starts(solver, problem, target, n, starts_per=16, seed=0, scenes=None, first=0, **over):
+    """n start states at rest whose end effector sits at ``target`` ([3], or [n, 3]) -- the x0 of a tracking run, which the
+    reference takes from InverseKinematicsOCP (guess_acados.py:179-183) -- by the batched multi-start IK (``solver.ik``,
+    smpc_ik_batch; ik.ik_batch_host for a solver without one).  Instance i draws its OWN block of ``starts_per`` Halton points in the
+    joint box (points ``seed + (first + i) * starts_per`` onwards of :func:`halton`), so n instances get n different arm
+    configurations at the same end-effector point.  ``scenes`` [n, n_rows, 8]: instance i is solved in its scene.
+    Returns ``(x0 [n, nx], info [n, 2])``: info[i] = (winning start, number of successful starts); ``info[i, 1] == 0`` means NO
+    solution was found for instance i, and x0[i] is then only the closest point reached."""
+    from .ik import ik, ik_params
+    n, starts_per, nq = int(n), int(starts_per), problem.nq
+    par = ik_params(problem, **over)
+    lo, hi = par['q_lo'], par['q_hi']
+    if n <= 0:
+        return np.zeros((0, problem.nx)), np.zeros((0, 2), np.int32)
+    tg = np.ascontiguousarray(np.broadcast_to(np.asarray(target, float).reshape(-1, 3), (n, 3)))
+    q_start = lo + halton(n * starts_per, nq, skip=1 + int(seed) + int(first) * starts_per).reshape(n, starts_per, nq) * (hi - lo)
+    if scenes is not None:
+        scenes = _check_scenes(scenes, n, problem)
+    q, info, _ = ik(solver, problem, tg, q_start, scenes=scenes, **over)
+    return np.hstack([np.asarray(q, float), np.zeros((n, nq))]), np.asarray(info)
+
+
+class _IkStarts:
+    """The sample stream of a tracking run in chunks: sample j = the j-th instance of :func:`ik_starts` at ``target`` whose IK
+    succeeded (``failed`` lists the instance numbers that did not).  ``take(j)`` as _FreeStarts'."""
+
+    def __init__(self, solver, problem, target, chunk=64, max_barren=16):
+        self.sv, self.pr, self.target, self.chunk, self.max_barren = solver, problem, target, int(chunk), int(max_barren)
+        self.drawn, self.failed = 0, []
+        self.x = np.zeros((0, problem.nx))
+
+    def take(self, j):
+        barren = 0
+        while j >= len(self.x):
+            x0, info = ik_starts(self.sv, self.pr, self.target, self.chunk, first=self.drawn)
+            ok = info[:, 1] > 0
+            self.failed += [int(self.drawn + i) for i in np.where(~ok)[0]]
+            self.drawn += self.chunk
+            barren = 0 if ok.any() else barren + 1
+            if barren >= self.max_barren:
+                raise RuntimeError(f'the inverse kinematics found no start state at {np.asarray(self.target).tolist()} in '
+                                   f'{barren * self.chunk} instances in a row')
+            self.x = np.vstack([self.x, x0[ok]])
+        return self.x[j]
+
+
 def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7,
-                   alpha_min=0.05, history=None, on_device=False, scenes=None):
+                   alpha_min=0.05, history=None, on_device=False, scenes=None, traj=None):
     """guess_acados.py:98-158: Halton q0 in the joint box, collision filter, constant guess, SQP to convergence, checkGuess.
 
     SQP with merit backtracking (the reference runs acados with nlp_solver_type SQP, globalization MERIT_BACKTRACKING,
@@ -328,9 +390,18 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     (solver.set_instance_scene): the Halton candidates are walked in order and each is tested against the scene of the instance it
     would start, so a candidate that collides there is skipped (:func:`_free_starts_per_scene`).  The result gains ``'scenes'``, the
     geometry of the accepted instances, and the returned mask has one entry per requested instance (False too where the
-    candidates ran out)."""
+    candidates ran out).
+
+    ``traj`` ([3, L], tracking.tracking_trajectory): the tracking branch, guess_acados.py:167-226.  The controller follows the curve
+    (setTrajectory: p[:, i, :3] = traj[:, i]) and every start state comes from :func:`ik_starts` at ``traj[:, 0]`` -- instance i in
+    its scene where ``scenes`` is given -- instead of the Halton filter; the guess is constant at it, as the reference builds it,
+    and the SQP and checkGuess are the same.  An instance whose IK found no solution is dropped, never replaced: its entry of the
+    returned mask (one per requested instance) is False and the result's ``'ik_failed'`` lists it."""
     make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
     ctrl = make_controller(cont_name, n)
+    if traj is not None:
+        traj = np.ascontiguousarray(traj, np.float64)
+        ctrl.setTrajectory(traj)
     if on_device and not hasattr(ctrl.ocp_solver, 'sqp'):
         raise ValueError(f'generate_guess(on_device=True) needs a solver with a device SQP (BatchedOcpSolver.sqp); '
                          f'{type(ctrl.ocp_solver).__name__} has none')
@@ -339,7 +410,18 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
 
     q = pr.x_min[:nq] + halton(4 * n + 16, nq) * (pr.x_max[:nq] - pr.x_min[:nq])        # guess_acados.py:100
     x_all = np.hstack([q, np.zeros_like(q)])
-    if scenes is not None:
+    ik_failed = None
+    if traj is not None:
+        if scenes is not None:
+            scenes = _check_scenes(scenes, n, pr)
+        x0, ik_info = ik_starts(ctrl.ocp_solver, pr, traj[:, 0], n, scenes=scenes)      # guess_acados.py:179-183
+        filled = ik_info[:, 1] > 0
+        ik_failed = np.where(~filled)[0]
+        if verbose and len(ik_failed):
+            print(f'inverse kinematics: no start state for {len(ik_failed)} of {n} instances: {ik_failed.tolist()}')
+        x0 = x0[filled]
+        scenes = scenes[filled] if scenes is not None else None
+    elif scenes is not None:
         scenes = _check_scenes(scenes, n, pr)
         x0, filled = _free_starts_per_scene(ctrl.ocp_solver, scenes, x_all)
         x0, scenes = x0[filled], scenes[filled]
@@ -349,15 +431,20 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
         x0 = x_all[free][:n]
     if len(x0) < n:
         ctrl = make_controller(cont_name, len(x0))
+        if traj is not None:
+            ctrl.setTrajectory(traj)
     B = len(x0)
     if scenes is not None and B:
         _set_scene(ctrl.ocp_solver, scenes)
 
     def result(good):
         out = {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}
+        if ik_failed is not None:
+            out['ik_failed'] = ik_failed
         if filled is None:
             return out, good
-        out['scenes'] = scenes[good]
+        if scenes is not None:
+            out['scenes'] = scenes[good]
         mask = np.zeros(n, bool)
         mask[np.where(filled)[0][good]] = True
         return out, mask
@@ -501,7 +588,7 @@ class _FreeStarts:
 
 
 def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accept='final', max_samples=None, make_controller=None,
-                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, scenes=None):
+                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, scenes=None, traj=None):
     """guess_acados.py:98-158 with its ``while succ < num_ics``: sample, solve and test warm starts until ``n`` are ACCEPTED, on
     the device.  Returns ``(guess, info)``: ``guess['xg'] [n, N+1, nx]``, ``guess['ug'] [n, N, nu]`` in sampling order.
 
@@ -524,6 +611,10 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
     count.  Pin the form through ``make_controller`` (``ctrl.ocp_solver.set_qp_mode('throughput')``) where bit-identical results
     across batch sizes are wanted; the tests do.  With ``max_samples`` the stream stops after that many
     samples and ``info['exhausted']`` says whether that cut the result short.
+
+    ``traj`` ([3, L]): the tracking branch (guess_acados.py:167-226, see :func:`generate_guess`): the controller follows the curve
+    and sample j is the j-th instance of :func:`ik_starts` at ``traj[:, 0]`` whose IK succeeded; the instances without a solution are
+    listed in ``info['ik_failed']`` and are not part of the stream.
 
     ``info``: 'accepted' / 'failed' (sample indices, sampling order), 'iters' (SQP iterations of every issued sample),
     'status', 'flags' (at the sample's resolution), 'issued', 'rounds', 'instance_iterations', 'exhausted'."""
@@ -550,6 +641,9 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
         return {'xg': np.zeros((0, N + 1, nx)), 'ug': np.zeros((0, N, nu))}, info
     import torch
     dev = torch.device('cuda', sv.device)
+    if traj is not None:
+        traj = np.ascontiguousarray(traj, np.float64)
+        ctrl.setTrajectory(traj)
     ctrl.p[:, :, 3] = ctrl.params.alpha                     # what ctrl.solve does before every solve
     ctrl._apply_traj()
     to = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), np.float64), device=dev)
@@ -567,7 +661,7 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
     mask_d = torch.zeros((B,), dtype=torch.uint8, device=dev)
     safe_node = N if getattr(ctrl, 'guess_safe_node', False) else None
     budget = -(-int(params.nlp_max_iter) // check_every) * check_every
-    stream = _FreeStarts(sv, ctrl.problem)
+    stream = _FreeStarts(sv, ctrl.problem) if traj is None else _IkStarts(sv, ctrl.problem, traj[:, 0])
     got_x, got_u = {}, {}
     while True:
         new = book.issue()
@@ -618,6 +712,8 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
     order = book.result_order()
     info.update(accepted=order, failed=sorted(book.failed), issued=book.issued, exhausted=book.exhausted,
                 instance_iterations=int(sum(info['iters'].values())))
+    if traj is not None:
+        info['ik_failed'] = list(stream.failed)
     xg_out = np.stack([got_x[j] for j in order]) if order else np.zeros((0, N + 1, nx))
     ug_out = np.stack([got_u[j] for j in order]) if order else np.zeros((0, N, nu))
     return {'xg': xg_out, 'ug': ug_out}, info
@@ -1162,7 +1258,7 @@ def time_row(t):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False, scenes=None):
+            score=False, scenes=None, traj=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1186,7 +1282,9 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     obstacles of its collision rows sit (solver.set_instance_scene; bounds, radii and kinds stay the problem's).  The controller's
     solves and tests, the plant's outcome test, the scores and the backup OCP of an abort event all run in the instance's scene;
     the result gains ``'scenes'``, and the controller's and the backup solver's handles are left without a scene when the run ends.
-    Not with the parallel policy (ValueError): its solver works on B x N candidate slots, which are not instances."""
+    Not with the parallel policy (ValueError): its solver works on B x N candidate slots, which are not instances.
+    ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
+    task of the reference's Tracking8* / TrackingMovingCircle* costs."""
     import time
     B = x_guess.shape[0]
     if scenes is not None:
@@ -1212,6 +1310,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     gens, grps, streams = [], [], []
     for lo, hi in spans:
         ctrl = make_controller(cont_name, hi - lo)
+        if traj is not None:
+            ctrl.setTrajectory(traj)
         backup = make_backup(hi - lo)
         if on_device:
             import torch

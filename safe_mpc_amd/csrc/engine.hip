@@ -20,6 +20,7 @@
 #include "kernels_sqp.hpp"
 #include "kernels_guess.hpp"
 #include "kernels_score.hpp"
+#include "kernels_ik.hpp"
 
 using namespace smpc;
 
@@ -125,6 +126,8 @@ struct smpc_handle {
     DevBuf<char> d_score;       // scratch of smpc_score_rollout (ScoreScratch): the segments' partials and the running safe-set minimum
     DevBuf<double> d_schk;      // bounds of smpc_score_rollout [x_min | x_max | row_lb | row_ub | ee_ref], uploaded on change
     std::vector<double> schk_cache;
+    DevBuf<double> d_ikb;       // bounds of smpc_ik_batch [q_lo | q_hi | row_lb | row_ub], uploaded on change
+    std::vector<double> ikb_cache;
     char err[256] = "";
 };
 
@@ -1118,6 +1121,51 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
     return SMPC_OK;
 }
 
+// The small host arrays of smpc_ik_batch, in a device block of their own like upload_guess_bounds': uploaded only when they
+// change, so an unchanged call does not synchronise.
+int upload_ik_bounds(smpc_handle* h, const smpc_ik_params* par) {
+    const int nq = h->desc.nq, nr = h->desc.n_rows;
+    std::vector<double> cur((size_t)2 * SMPC_MAX_NQ + 2 * SMPC_MAX_ROWS, 0.0);
+    memcpy(cur.data(), par->q_lo, sizeof(double) * nq);
+    memcpy(cur.data() + SMPC_MAX_NQ, par->q_hi, sizeof(double) * nq);
+    if (nr > 0) {
+        memcpy(cur.data() + 2 * SMPC_MAX_NQ, par->row_lb, sizeof(double) * nr);
+        memcpy(cur.data() + 2 * SMPC_MAX_NQ + SMPC_MAX_ROWS, par->row_ub, sizeof(double) * nr);
+    }
+    int rc;
+    if ((rc = h->d_ikb.reserve(h, "inverse kinematics bounds", cur.size() * sizeof(double)))) return rc;
+    if (cur != h->ikb_cache) {
+        if (capturing(h))
+            return fail(h, SMPC_ESTATE, "the inverse kinematics bounds changed while the stream is being captured: run one eager call "
+                        "with these bounds first");
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(h->d_ikb.p, cur.data(), cur.size() * sizeof(double), hipMemcpyHostToDevice));
+        h->ikb_cache.swap(cur);
+    }
+    return SMPC_OK;
+}
+
+// k_ik: one wavefront per instance, lane s = start s
+template <int NQ>
+int launch_ik(smpc_handle* h, int B, int S, const double* target, const double* q_start, const smpc_ik_params* par, const uint8_t* mask,
+              double* q_out, int32_t* info, double* resid) {
+    hipStream_t s = h->stream;
+    const double* d_lo = h->d_ikb.p;
+    const double* d_hi = d_lo + SMPC_MAX_NQ;
+    const double* d_rlb = d_hi + SMPC_MAX_NQ;
+    const double* d_rub = d_rlb + SMPC_MAX_ROWS;
+    if (const double* geom = scene_of(h, B))
+        hipLaunchKernelGGL((k_ik<NQ, true>), dim3(B), dim3(64), 0, s, h->d_desc, B, S, target, q_start, (int)par->max_iter, par->tol_ee,
+                           par->push, par->damping, par->damping_accept, par->damping_reject, par->damping_min, par->damping_max, d_lo,
+                           d_hi, d_rlb, d_rub, mask, q_out, info, resid, geom);
+    else
+        hipLaunchKernelGGL((k_ik<NQ>), dim3(B), dim3(64), 0, s, h->d_desc, B, S, target, q_start, (int)par->max_iter, par->tol_ee,
+                           par->push, par->damping, par->damping_accept, par->damping_reject, par->damping_min, par->damping_max, d_lo,
+                           d_hi, d_rlb, d_rub, mask, q_out, info, resid, (const double*)nullptr);
+    HIPCHK(h, hipGetLastError());
+    return SMPC_OK;
+}
+
 // The small host arrays of smpc_score_rollout, in a device block of their own like upload_guess_bounds': uploaded only when they
 // change, so an unchanged call does not synchronise.
 int upload_score_bounds(smpc_handle* h, const smpc_score_params* par) {
@@ -2014,6 +2062,38 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
          })))
         return rc;
     DISPATCH_NQ(h, (launch_check_guess<NQ_>(h, B, dx, du, par, dmask, dflags, dworst)));
+    if (rc) return rc;
+    return io.finish();
+}
+
+int smpc_ik_batch(smpc_handle* h, int B, int S, const double* target, const double* q_start, const smpc_ik_params* par,
+                  const uint8_t* mask, double* q_out, int32_t* info, double* resid, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (B <= 0 || !target || !q_start || !par || !q_out || !info || !resid) return fail(h, SMPC_EINVAL, "bad argument");
+    if (S < 1 || S > IK_MAX_STARTS) return fail(h, SMPC_EINVAL, "S=%d starts per instance outside 1..%d", S, IK_MAX_STARTS);
+    if (par->max_iter < 1) return fail(h, SMPC_EINVAL, "max_iter=%d: at least one iteration", (int)par->max_iter);
+    if (!par->q_lo || !par->q_hi) return fail(h, SMPC_EINVAL, "joint bounds missing");
+    if (h->desc.n_rows > 0 && (!par->row_lb || !par->row_ub)) return fail(h, SMPC_EINVAL, "row bounds missing");
+    (void)hipSetDevice(h->device);
+    const int nq = h->desc.nq;
+    int rc;
+    if ((rc = scene_guard(h, B, "smpc_ik_batch"))) return rc;
+    if ((rc = upload_ik_bounds(h, par))) return rc;
+    Stage io{h, on_device != 0};
+    const double *dt, *dq;
+    const uint8_t* dmask;
+    double *dqo, *dres;
+    int32_t* dinfo;
+    if ((rc = io.place([&](Stage& v) {
+             dt = v.in(target, (size_t)B * 3);
+             dq = v.in(q_start, (size_t)B * S * nq);
+             dmask = v.in(mask, (size_t)B);
+             dqo = v.inout(q_out, (size_t)B * nq);
+             dinfo = v.inout(info, (size_t)B * 2);
+             dres = v.inout(resid, (size_t)B * 2);
+         })))
+        return rc;
+    DISPATCH_NQ(h, (launch_ik<NQ_>(h, B, S, dt, dq, par, dmask, dqo, dinfo, dres)));
     if (rc) return rc;
     return io.finish();
 }

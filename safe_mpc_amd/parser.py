@@ -204,6 +204,8 @@ class Parameters:
                                                                self.robot_capsules + self.obst_capsules,
                                                                self.spheres_robot))
         self.track_traj = bool(cfg['track_traj'])
+        from .tracking import read_tracking_keys
+        read_tracking_keys(self, cfg)                       # the curves' keys (cost_definition.py:105-114, 205-214)
         self.noise_mass = float(cfg.get('noise_mass', 0.0))
         self.noise_inertia = float(cfg.get('noise_inertia', 0.0))
         self.noise_cm = float(cfg.get('noise_cm', 0.0))

@@ -388,6 +388,52 @@ class BatchedOcpSolver:
             self._chk(self.L.smpc_check_guess(self.h, B, ptrs[0], ptrs[1], C.byref(gc), ptrs[2], fp, wp, dev))
         return flags, worst
 
+    # -- start states at a chosen end-effector position ---------------------------------------------------------------------
+    def ik(self, target, q_start, mask=None, q_out=None, info=None, resid=None, **over):
+        """Batched multi-start inverse kinematics with collision rows on the device (smpc_ik_batch; the numpy statement is
+        ik.ik_batch_host): per instance a q in the joint box with ee(q) = ``target[b]`` and every collision row within its bounds,
+        from the ``S`` starts ``q_start[b]`` (``target [B, 3]``, ``q_start [B, S, nq]``, 1 <= S <= 64).  Returns ``(q_out [B, nq],
+        info [B, 2] int32 = (winning start, number of successful starts; 0 = no solution), resid [B, 2] = (|ee - target|_inf, worst
+        row margin) at q_out)``.  ``mask`` (uint8 [B]): instances with 0 are skipped and keep their rows of the outputs.  While a
+        scene is set (:meth:`set_instance_scene`) the rows are formed in each instance's scene.  ``over`` may override
+        ik.IK_DEFAULTS (max_iter, tol_ee, push, damping, ...) and q_lo, q_hi, row_lb, row_ub (defaults: the model's joint box and
+        the OCP's row bounds)."""
+        from .ik import ik_params
+        par = ik_params(self.problem, **over)
+        if q_start.ndim != 3:
+            raise ValueError('ik: q_start [B, S, nq] expected')
+        B, S = int(q_start.shape[0]), int(q_start.shape[1])
+        ptrs, dev, keep = self._prep([target, q_start, mask, q_out, info, resid], [(B, 3), (B, S, self.nq), (B,), (B, self.nq), (B, 2), (B, 2)],
+                                     [np.float64, np.float64, np.uint8, np.float64, np.int32, np.float64])
+        if dev:
+            import torch
+            if target.dtype != torch.float64 or q_start.dtype != torch.float64:
+                raise ValueError('target and q_start must be float64')
+            if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError('mask must be uint8 or bool')
+            kw = dict(device=target.device)
+            q_out = torch.zeros((B, self.nq), dtype=torch.float64, **kw) if q_out is None else q_out
+            info = torch.zeros((B, 2), dtype=torch.int32, **kw) if info is None else info
+            resid = torch.zeros((B, 2), dtype=torch.float64, **kw) if resid is None else resid
+            if q_out.dtype != torch.float64 or info.dtype != torch.int32 or resid.dtype != torch.float64:
+                raise ValueError('q_out and resid must be float64 and info int32')
+            op = [q_out.data_ptr(), info.data_ptr(), resid.data_ptr()]
+        else:
+            q_out = np.zeros((B, self.nq)) if q_out is None else q_out
+            info = np.zeros((B, 2), np.int32) if info is None else info
+            resid = np.zeros((B, 2)) if resid is None else resid
+            assert q_out.dtype == np.float64 and q_out.shape == (B, self.nq) and q_out.flags.c_contiguous
+            assert info.dtype == np.int32 and info.shape == (B, 2) and info.flags.c_contiguous
+            assert resid.dtype == np.float64 and resid.shape == (B, 2) and resid.flags.c_contiguous
+            op = [q_out.ctypes.data, info.ctypes.data, resid.ctypes.data]
+        small = [par[k] for k in ('q_lo', 'q_hi', 'row_lb', 'row_ub')]
+        ip = _lib.IkParams(par['max_iter'], 0, float(par['tol_ee']), float(par['push']), float(par['damping']),
+                           float(par['damping_accept']), float(par['damping_reject']), float(par['damping_min']),
+                           float(par['damping_max']), *[a.ctypes.data for a in small])
+        with self._ordered(dev):
+            self._chk(self.L.smpc_ik_batch(self.h, B, S, ptrs[0], ptrs[1], C.byref(ip), ptrs[2], *op, dev))
+        return q_out, info, resid
+
     # -- scoring a closed-loop run --------------------------------------------------------------------------------------
     def score_rollout(self, x_log, u_log, last_x=None, last_u=None, ee_ref=None, traj=None, want_safe=False, mask=None, out=None,
                       outi=None, **bounds):

@@ -10,6 +10,9 @@ solved and tested on the device until exactly test_num guesses are accepted (clo
 --scene-jitter SIGMA [--scene-seed S]: every guess is generated in a scene of its own, every obstacle moved by its own N(0, SIGMA^2)
 draw per axis (problem.jittered_scenes); the scenes of the accepted guesses are stored in the pickle as 'scenes', where scripts/mpc.py
 --scene-jitter finds them.  Not with --until-accepted.
+--track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): warm starts of the trajectory-tracking task
+(guess_acados.py:167-226 of the reference) -- every start state is an inverse-kinematics solution at the curve's first point
+(closed_loop.ik_starts, smpc_ik_batch) and the OCP follows the curve.
 """
 import os
 import sys
@@ -34,6 +37,7 @@ def main(argv=None):
     cont_name = args['controller']
     # every safe-set controller name is generated with the hard-terminal OCP (utils.py:46-58)
     gen_name = cont_name if cont_name in ('naive', 'zerovel') else 'htwa'
+    traj = cl.tracking_from_cli(params, raw)
     scenes = None
     if '--scene-jitter' in raw:
         from safe_mpc_amd.problem import OcpProblem, jittered_scenes
@@ -42,12 +46,12 @@ def main(argv=None):
     if until:
         guess, info = cl.generate_guess_until(params, gen_name, params.test_num, batch=opt('--batch', None, int),
                                               check_every=opt('--check-every', 50, int), accept=opt('--accept', 'final', str),
-                                              verbose=True, scenes=scenes)
+                                              verbose=True, scenes=scenes, traj=traj)
         print(f'{len(info["accepted"])}/{params.test_num} guesses accepted from {info["issued"]} samples in {info["rounds"]} rounds, '
               f'{info["instance_iterations"]} instance-iterations, {time.time() - t0:.1f} s'
               + (' (sample stream exhausted)' if info['exhausted'] else ''))
     else:
-        guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device, scenes=scenes)
+        guess, good = cl.generate_guess(params, gen_name, params.test_num, verbose=True, on_device=on_device, scenes=scenes, traj=traj)
         print(f'{good.sum()}/{len(good)} guesses accepted in {time.time() - t0:.1f} s')
     use_net = None if cont_name in ('naive', 'zerovel') else True
     out = cl.guess_file(params, model_name, cont_name, params.N, use_net)

@@ -6,6 +6,8 @@ with every instance of its outer loop (mpc.py:102) solved at once on the MI355X 
 --scene-jitter SIGMA: every instance runs in a scene of its own -- the scenes stored with the guesses (guess_acados.py
 --scene-jitter) if there are any, else every obstacle moved by its own N(0, SIGMA^2) draw per axis (problem.jittered_scenes,
 seed --scene-seed, default 0).
+--track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
+tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 Exit code = number of failed instances, as in the reference (mpc.py:317).
 """
 import os
@@ -25,11 +27,12 @@ def main(argv=None):
     params.back_hor = args['back_hor']
     cont_name = args['controller']
     use_net = None if cont_name in ('naive', 'zerovel') else True          # controller.py:236 / STController
+    raw = list(sys.argv[1:] if argv is None else argv)
+    traj = cl.tracking_from_cli(params, raw)                # (sets params.n_steps / track_traj: the file names carry the token)
     gfile = cl.guess_file(params, model_name, cont_name, params.N, use_net)
     print(gfile)
     data = pickle.load(open(gfile, 'rb'))
     x_guess, u_guess = data['xg'][:params.test_num], data['ug'][:params.test_num]
-    raw = list(sys.argv[1:] if argv is None else argv)
     scenes = None
     if '--scene-jitter' in raw:
         if 'scenes' in data:          # the warm starts were generated in these scenes
@@ -42,7 +45,7 @@ def main(argv=None):
     # all loop state in HBM (policy automaton, abort handling, logs); SMPC_HOST_STATE=1 keeps it in numpy arrays instead
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],
                      callback=True, on_device=os.environ.get('SMPC_HOST_STATE', '0') != '1', timing=tm,
-                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes)
+                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes, traj=traj)
     with_stats = os.environ.get('SMPC_NO_TIME_STATS', '0') != '1'
     print(f"{tm['ms_per_step']:.3f} ms per closed-loop step of {x_guess.shape[0]} instances"
           + (' (eager launches with per-solve HIP events for the time statistics below; SMPC_NO_TIME_STATS=1 replays the step halves as '
