@@ -20,7 +20,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
            'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
-           'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch']
+           'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update']
 
 
 class EngineError(RuntimeError):
@@ -86,6 +86,21 @@ class IkParams(C.Structure):
                 ('q_lo', _vp), ('q_hi', _vp), ('row_lb', _vp), ('row_ub', _vp)]
 
 
+class RayOpts(C.Structure):
+    """smpc_ray_opts"""
+    _fields_ = [('bisect', C.c_int32), ('budget', C.c_int32), ('tol_term', C.c_double), ('mu0', C.c_double)]
+
+
+class RayState(C.Structure):
+    """smpc_ray_state: per-ray arrays [B] (q, d: [B, nq]; x_cert, u_cert: a trajectory per ray)"""
+    FIELDS = (('q', 'f8'), ('d', 'f8'), ('lo', 'f8'), ('hi', 'f8'), ('s', 'f8'), ('trial', 'i4'), ('kind', 'i4'), ('open', 'u1'),
+              ('x_cert', 'f8'), ('u_cert', 'f8'), ('iters_total', 'i4'))
+    _fields_ = [(k, _vp) for k, _ in FIELDS]
+
+
+RAY_OPEN, RAY_DEAD, RAY_SATURATED, RAY_BRACKETED = 0, 1, 2, 3      # SMPC_RAY_* of include/smpc.h
+
+
 def build(force=False):
     """Compile the engine for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(('.hip', '.hpp'))]
@@ -148,5 +163,6 @@ def lib():
     L.smpc_check_guess.argtypes = [vp, C.c_int, dp, dp, C.POINTER(GuessCheck), dp, dp, dp, C.c_int]
     L.smpc_score_rollout.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(ScoreParams), dp, dp, dp, C.c_int]
     L.smpc_ik_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(IkParams), dp, dp, dp, dp, C.c_int]
+    L.smpc_ray_update.argtypes = [vp, C.c_int, C.POINTER(RayOpts), C.POINTER(RayState), C.POINTER(SqpState), dp, dp, dp, dp, dp, C.c_int]
     _lib = L
     return L

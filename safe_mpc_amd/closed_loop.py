@@ -368,6 +368,66 @@ class _IkStarts:
         return self.x[j]
 
 
+def new_host_sqp_state(B, mu0=10.0):
+    """The per-instance state of :func:`sqp_host_advance` at its start values: the fields of ``smpc_sqp_state`` (_lib.SqpState) as
+    numpy arrays, what ``BatchedOcpSolver.new_sqp_state`` returns for the host."""
+    from ._lib import SqpState
+    st = {k: np.zeros(B, dt) for k, dt in SqpState.FIELDS}
+    st['mu'][:] = float(mu0)
+    return st
+
+
+def sqp_host_advance(ctrl, x0, state, max_iter, sqp_tol=1e-6, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, history=None,
+                     verbose=False):
+    """Up to ``max_iter`` iterations of the numpy SQP of :func:`generate_guess` (its docstring states the iteration) on
+    ctrl.x_guess / ctrl.u_guess, resuming from ``state`` (:func:`new_host_sqp_state`, updated in place): the round of an SQP that is
+    looked at between rounds, as ``solver.sqp(max_iter=...)`` is on the device.  k calls of one iteration equal one call of k.  An
+    instance with ``state['done']`` set takes no part; the call returns once every instance is done."""
+    nq = ctrl.problem.nq
+    B = len(x0)
+    done = state['done'].astype(bool)
+    status, mu = state['status'], state['mu']
+    for it in range(int(max_iter)):
+        st = ctrl.solve(x0)
+        dx, du = ctrl.x_temp - ctrl.x_guess, ctrl.u_temp - ctrl.u_guess
+        step = np.maximum(np.abs(dx).reshape(B, -1).max(1), np.abs(du).reshape(B, -1).max(1))
+        f0, gq, gu, c0 = merit_terms(ctrl, x0, ctrl.x_guess, ctrl.u_guess)
+        gd = (gq * dx[:, :, :nq]).sum(axis=(1, 2)) + (gu * du).sum(axis=(1, 2))
+        # penalty large enough for  D = grad f . d - mu |c|_1 < 0  wherever the iterate is infeasible
+        need = np.where(c0 > 1e-12, 2.0 * np.maximum(gd, 0.0) / np.maximum(c0, 1e-12), 0.0)
+        mu[:] = np.minimum(np.maximum(mu, need), 1e8)
+        m0 = f0 + mu * c0
+        D = gd - mu * c0
+        alpha = np.ones(B)
+        settled = done | (st != 0)
+        while True:
+            xt = ctrl.x_guess + alpha[:, None, None] * dx
+            ut = ctrl.u_guess + alpha[:, None, None] * du
+            ft, _, _, ct = merit_terms(ctrl, x0, xt, ut)
+            ok = (ft + mu * ct <= m0 + armijo * alpha * np.minimum(D, 0.0) + 1e-12 * (1.0 + np.abs(m0)))
+            settled = settled | ok | (alpha <= alpha_min)
+            if settled.all():
+                break
+            alpha = np.where(settled, alpha, np.maximum(alpha * alpha_reduction, alpha_min))
+        upd = ~done & (st == 0)
+        ctrl.x_guess = np.where(upd[:, None, None], xt, ctrl.x_guess)
+        ctrl.u_guess = np.where(upd[:, None, None], ut, ctrl.u_guess)
+        status[:] = np.where(~done, st, status)
+        state['iters'] += (~done).astype(np.int32)
+        state['qp_iter_total'] += np.where(~done, np.asarray(ctrl.qp_iter), 0).astype(np.int32)
+        if history is not None:
+            history.append({'merit': np.where(upd, ft + mu * ct, m0), 'merit_before': m0.copy(), 'alpha': np.where(upd, alpha, 0.0),
+                            'mu': mu.copy(), 'violation': np.where(upd, ct, c0), 'updated': upd.copy()})
+        done |= (alpha * step < sqp_tol) | (st != 0)
+        state['done'][:] = done
+        if verbose:
+            print(f'SQP iteration {it}: {done.sum()}/{B} done, max step {step[upd].max() if upd.any() else 0:.2e}, '
+                  f'min alpha {alpha[upd].min() if upd.any() else 1:.2f}')
+        if done.all():
+            break
+    return state
+
+
 def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7,
                    alpha_min=0.05, history=None, on_device=False, scenes=None, traj=None):
     """guess_acados.py:98-158: Halton q0 in the joint box, collision filter, constant guess, SQP to convergence, checkGuess.
@@ -456,44 +516,10 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
         ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
         good = ((status == 0) | (status == 2)) & ctrl.checkGuess()
         return result(good)
-    done = np.zeros(B, bool)
-    status = np.zeros(B, np.int32)
-    mu = np.full(B, 10.0)
-    for it in range(int(params.nlp_max_iter)):
-        st = ctrl.solve(x0)
-        dx, du = ctrl.x_temp - ctrl.x_guess, ctrl.u_temp - ctrl.u_guess
-        step = np.maximum(np.abs(dx).reshape(B, -1).max(1), np.abs(du).reshape(B, -1).max(1))
-        f0, gq, gu, c0 = merit_terms(ctrl, x0, ctrl.x_guess, ctrl.u_guess)
-        gd = (gq * dx[:, :, :nq]).sum(axis=(1, 2)) + (gu * du).sum(axis=(1, 2))
-        # penalty large enough for  D = grad f . d - mu |c|_1 < 0  wherever the iterate is infeasible
-        need = np.where(c0 > 1e-12, 2.0 * np.maximum(gd, 0.0) / np.maximum(c0, 1e-12), 0.0)
-        mu = np.minimum(np.maximum(mu, need), 1e8)
-        m0 = f0 + mu * c0
-        D = gd - mu * c0
-        alpha = np.ones(B)
-        settled = done | (st != 0)
-        while True:
-            xt = ctrl.x_guess + alpha[:, None, None] * dx
-            ut = ctrl.u_guess + alpha[:, None, None] * du
-            ft, _, _, ct = merit_terms(ctrl, x0, xt, ut)
-            ok = (ft + mu * ct <= m0 + armijo * alpha * np.minimum(D, 0.0) + 1e-12 * (1.0 + np.abs(m0)))
-            settled = settled | ok | (alpha <= alpha_min)
-            if settled.all():
-                break
-            alpha = np.where(settled, alpha, np.maximum(alpha * alpha_reduction, alpha_min))
-        upd = ~done & (st == 0)
-        ctrl.x_guess = np.where(upd[:, None, None], xt, ctrl.x_guess)
-        ctrl.u_guess = np.where(upd[:, None, None], ut, ctrl.u_guess)
-        status = np.where(~done, st, status)
-        if history is not None:
-            history.append({'merit': np.where(upd, ft + mu * ct, m0), 'merit_before': m0.copy(), 'alpha': np.where(upd, alpha, 0.0),
-                            'mu': mu.copy(), 'violation': np.where(upd, ct, c0), 'updated': upd.copy()})
-        done |= (alpha * step < sqp_tol) | (st != 0)
-        if verbose:
-            print(f'SQP iteration {it}: {done.sum()}/{B} done, max step {step[upd].max() if upd.any() else 0:.2e}, '
-                  f'min alpha {alpha[upd].min() if upd.any() else 1:.2f}')
-        if done.all():
-            break
+    state = new_host_sqp_state(B)
+    sqp_host_advance(ctrl, x0, state, int(params.nlp_max_iter), sqp_tol=sqp_tol, armijo=armijo, alpha_reduction=alpha_reduction,
+                     alpha_min=alpha_min, history=history, verbose=verbose)
+    status = state['status']
     ctrl.x_temp, ctrl.u_temp = ctrl.x_guess.copy(), ctrl.u_guess.copy()
     good = ((status == 0) | (status == 2)) & ctrl.checkGuess()              # guess_acados.py:115 accepts status 0 or 2
     return result(good)

@@ -21,6 +21,7 @@
 #include "kernels_guess.hpp"
 #include "kernels_score.hpp"
 #include "kernels_ik.hpp"
+#include "kernels_rays.hpp"
 
 using namespace smpc;
 
@@ -2063,6 +2064,63 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
         return rc;
     DISPATCH_NQ(h, (launch_check_guess<NQ_>(h, B, dx, du, par, dmask, dflags, dworst)));
     if (rc) return rc;
+    return io.finish();
+}
+
+int smpc_ray_update(smpc_handle* h, int B, const smpc_ray_opts* opts, const smpc_ray_state* rays, const smpc_sqp_state* sqp,
+                    const int32_t* flags, double* x0, double* x_guess, double* u_guess, int32_t* n_open, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (B <= 0 || !opts || !rays || !sqp || !flags || !x0 || !x_guess || !u_guess || !n_open) return fail(h, SMPC_EINVAL, "bad argument");
+    if (opts->bisect < 0 || opts->budget < 1)
+        return fail(h, SMPC_EINVAL, "ray options: bisect=%d >= 0, budget=%d >= 1", (int)opts->bisect, (int)opts->budget);
+    if (!rays->q || !rays->d || !rays->lo || !rays->hi || !rays->s || !rays->trial || !rays->kind || !rays->open || !rays->x_cert ||
+        !rays->u_cert || !rays->iters_total)
+        return fail(h, SMPC_EINVAL, "ray state incomplete");
+    if (!sqp->mu || !sqp->done || !sqp->status || !sqp->alpha || !sqp->merit_before || !sqp->merit || !sqp->violation || !sqp->updated ||
+        !sqp->iters || !sqp->qp_iter_total)
+        return fail(h, SMPC_EINVAL, "SQP state incomplete");
+    (void)hipSetDevice(h->device);
+    const int N = h->N, nq = h->desc.nq;
+    const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq, nB = (size_t)B;
+    Stage io{h, on_device != 0};
+    smpc_ray_state R;
+    smpc_sqp_state S;
+    const int32_t* dflags;
+    double *dx0, *dxg, *dug;
+    int32_t* dopen;
+    int rc;
+    if ((rc = io.place([&](Stage& v) {
+             R.q = v.in(rays->q, nB * nq);
+             R.d = v.in(rays->d, nB * nq);
+             R.lo = v.inout(rays->lo, nB);
+             R.hi = v.inout(rays->hi, nB);
+             R.s = v.inout(rays->s, nB);
+             R.trial = v.inout(rays->trial, nB);
+             R.kind = v.inout(rays->kind, nB);
+             R.open = v.inout(rays->open, nB);
+             R.x_cert = v.inout(rays->x_cert, nX);
+             R.u_cert = v.inout(rays->u_cert, nU);
+             R.iters_total = v.inout(rays->iters_total, nB);
+             S.mu = v.inout(sqp->mu, nB);
+             S.done = v.inout(sqp->done, nB);
+             S.status = v.inout(sqp->status, nB);
+             S.alpha = v.inout(sqp->alpha, nB);
+             S.merit_before = v.inout(sqp->merit_before, nB);
+             S.merit = v.inout(sqp->merit, nB);
+             S.violation = v.inout(sqp->violation, nB);
+             S.updated = v.inout(sqp->updated, nB);
+             S.iters = v.inout(sqp->iters, nB);
+             S.qp_iter_total = v.inout(sqp->qp_iter_total, nB);
+             dflags = v.in(flags, nB);
+             dx0 = v.inout(x0, nB * 2 * nq);
+             dxg = v.inout(x_guess, nX);
+             dug = v.inout(u_guess, nU);
+             dopen = v.out(n_open, 1);
+         })))
+        return rc;
+    HIPCHK(h, hipMemsetAsync(dopen, 0, sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(k_ray_update, dim3(B), dim3(64), 0, h->stream, B, nq, N, *opts, R, S, dflags, dx0, dxg, dug, dopen);
+    HIPCHK(h, hipGetLastError());
     return io.finish();
 }
 

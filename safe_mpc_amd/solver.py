@@ -26,6 +26,27 @@ def _is_torch(a):
     return type(a).__module__.startswith('torch')
 
 
+def pad_hidden_units(Ws, bs, to=256):
+    """Weights [out, in] and biases of an MLP whose hidden width the engine's network kernels do not take (not a multiple of 64: a
+    small fitted net, safe_set_data.fit_safe_set) with zero units added up to a multiple of ``to``, the width the one-kernel pass is
+    built for; any other net as given.  A unit with zero weights and bias outputs act(0) = 0 for every activation on offer and feeds
+    zero weights, so the value and the input gradient are those of the net as given."""
+    n, H = len(Ws), Ws[0].shape[0]
+    if n < 2 or H % 64 == 0 or any(w.shape[0] != H for w in Ws[:-1]):
+        return Ws, bs
+    Hp = -(-H // to) * to
+    Wo, bo = [], []
+    for l in range(n):
+        rows, cols = (Hp if l < n - 1 else Ws[l].shape[0]), (Hp if l > 0 else Ws[l].shape[1])
+        W = np.zeros((rows, cols), np.float32)
+        W[:Ws[l].shape[0], :Ws[l].shape[1]] = Ws[l]
+        b = np.zeros(rows, np.float32)
+        b[:bs[l].shape[0]] = bs[l]
+        Wo.append(W)
+        bo.append(b)
+    return Wo, bo
+
+
 class BatchedOcpSolver:
     def __init__(self, problem: OcpProblem, net=None, device=0):
         self.problem = problem
@@ -83,10 +104,17 @@ class BatchedOcpSolver:
                 cur.wait_stream(self._ext_stream)
 
     def set_mlp(self, net):
-        """net: SafeSetNet (weights as numpy fp32) -- or anything with .weights/.biases lists of [out, in] / [out]."""
+        """net: SafeSetNet (weights as numpy fp32) -- or anything with .weights/.biases lists of [out, in] / [out].
+
+        The engine's network kernels take hidden widths that are multiples of 64 (smpc_set_mlp refuses any other).  A net of another
+        width -- a small one from safe_set_data.fit_safe_set -- is handed over with ZERO UNITS ADDED up to the next multiple of 256
+        (:func:`pad_hidden_units`): same value and gradient, but the network pass then costs what a 256-wide net costs, up to 64
+        times the arithmetic of a 32-wide one.  ``self.net`` keeps the net as given; fit with a width the engine takes where the
+        pass's cost matters."""
         Ws = [np.ascontiguousarray(w, np.float32) for w in net.weights]
         bs = [np.ascontiguousarray(b, np.float32) for b in net.biases]
         n = len(Ws)
+        Ws, bs = pad_hidden_units(Ws, bs)
         dims = np.array([Ws[0].shape[1]] + [w.shape[0] for w in Ws], np.int32)
         Wp = (C.c_void_p * n)(*[w.ctypes.data for w in Ws])
         bp = (C.c_void_p * n)(*[b.ctypes.data for b in bs])
@@ -215,6 +243,24 @@ class BatchedOcpSolver:
                 keep.append(b)
         return ptrs, int(dev), keep
 
+    def _state_pointers(self, what, d, fields, shapes, B, dev):
+        """pointers of the per-instance arrays ``d[k]`` of a ctypes struct of arrays (``fields``: (name, dtype); ``shapes``: the
+        names that are not [B]), each checked for kind, shape, dtype and contiguity"""
+        out = []
+        for k, dt in fields:
+            a, shp = d[k], tuple(shapes.get(k, (B,)))
+            if _is_torch(a) != bool(dev):
+                raise TypeError('mix of torch and numpy arguments')
+            if dev:
+                if not a.is_cuda or not a.is_contiguous() or tuple(a.shape) != shp or a.element_size() != np.dtype(dt).itemsize:
+                    raise ValueError(f'{what} {k}: expected a contiguous {list(shp)} device tensor of {dt}')
+                out.append(a.data_ptr())
+            else:
+                if a.dtype != np.dtype(dt) or a.shape != shp or not a.flags.c_contiguous:
+                    raise ValueError(f'{what} {k}: expected a contiguous {list(shp)} array of {dt}')
+                out.append(a.ctypes.data)
+        return out
+
     # -- the hot path ------------------------------------------------------------------------------------------------------
     def solve(self, x0, x_guess, u_guess, p, out=None):
         """One SQP-RTI solve per instance (controller.py:136-167).  Returns (x, u, status, qp_iter)."""
@@ -321,20 +367,7 @@ class BatchedOcpSolver:
         ptrs, dev, keep = self._prep([x0, x_guess, u_guess, p], [(B, nx), (B, N + 1, nx), (B, N, nu), (B, N + 1, 5)])
         if not dev:
             ptrs[1], ptrs[2] = x_guess.ctypes.data, u_guess.ctypes.data
-        sp = []
-        for k, dt in _lib.SqpState.FIELDS:
-            a = state[k]
-            if _is_torch(a) != bool(dev):
-                raise TypeError('mix of torch and numpy arguments')
-            if dev:
-                if not a.is_cuda or not a.is_contiguous() or tuple(a.shape) != (B,) or a.element_size() != np.dtype(dt).itemsize:
-                    raise ValueError(f'SQP state {k}: expected a contiguous [{B}] device tensor of {dt}')
-                sp.append(a.data_ptr())
-            else:
-                if a.dtype != np.dtype(dt) or a.shape != (B,) or not a.flags.c_contiguous:
-                    raise ValueError(f'SQP state {k}: expected a contiguous [{B}] array of {dt}')
-                sp.append(a.ctypes.data)
-        cst = _lib.SqpState(*sp)
+        cst = _lib.SqpState(*self._state_pointers('SQP state', state, _lib.SqpState.FIELDS, {}, B, dev))
         with self._ordered(dev):
             self._chk(self.L.smpc_sqp_batch(self.h, B, C.byref(opts), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(cst), dev))
         return x_guess, u_guess, state
@@ -387,6 +420,57 @@ class BatchedOcpSolver:
         with self._ordered(dev):
             self._chk(self.L.smpc_check_guess(self.h, B, ptrs[0], ptrs[1], C.byref(gc), ptrs[2], fp, wp, dev))
         return flags, worst
+
+    # -- safe-set training data: the bookkeeping of ray labelling ---------------------------------------------------------
+    def _ray_shapes(self, B):
+        N, nx, nu, nq = self.N, self.nx, self.nu, self.nq
+        return {'q': (B, nq), 'd': (B, nq), 'x_cert': (B, N + 1, nx), 'u_cert': (B, N, nu)}
+
+    def new_ray_state(self, q, d, s_hi, like=None):
+        """The per-ray in/out arrays of :meth:`ray_update` (smpc_ray_state) for the rays ``(q, d)`` [B, nq] whose velocity box ends
+        at ``s_hi`` [B], before trial 0: bracket [0, s_hi], s = 0, every ray open.  numpy, or tensors on ``like``'s device."""
+        from .safe_set_data import new_ray_state
+        st = new_ray_state(q, d, s_hi, self.N)
+        if like is not None and _is_torch(like):
+            import torch
+            st = {k: torch.as_tensor(v, device=like.device) for k, v in st.items()}
+        return st
+
+    def ray_update(self, rays, state, flags, x0, x_guess, u_guess, n_open=None, bisect=8, budget=30, tol_term=None, mu0=10.0):
+        """One look at every open ray after a round of :meth:`sqp` and :meth:`check_guess` (smpc_ray_update; the numpy statement is
+        safe_set_data.ray_update_statement): resolves the trials that are feasible or have ended, keeps certificates, moves
+        brackets, ends rays or starts their next trial -- all in place on ``rays`` (:meth:`new_ray_state`), ``state``
+        (:meth:`new_sqp_state`), ``x0``, ``x_guess``, ``u_guess``.  Returns ``n_open``: a one-element int32 array / tensor holding
+        the number of rays still open (on the device path nothing is read back: the caller does)."""
+        B = x0.shape[0]
+        N, nx, nu = self.N, self.nx, self.nu
+        ptrs, dev, keep = self._prep([x0, x_guess, u_guess, flags], [(B, nx), (B, N + 1, nx), (B, N, nu), (B,)],
+                                     [np.float64, np.float64, np.float64, np.int32])
+        if dev:
+            import torch
+            if flags.dtype != torch.int32:
+                raise ValueError('flags must be int32')
+            if n_open is None:
+                n_open = torch.zeros((1,), dtype=torch.int32, device=x0.device)
+            if n_open.dtype != torch.int32 or not n_open.is_cuda:
+                raise ValueError('n_open must be an int32 device tensor')
+            open_ptr = n_open.data_ptr()
+        else:
+            for a, dt in ((x0, np.float64), (x_guess, np.float64), (u_guess, np.float64), (flags, np.int32)):
+                if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous:
+                    raise ValueError('ray_update works in place: contiguous float64 x0 / x_guess / u_guess and int32 flags expected')
+            n_open = np.zeros(1, np.int32) if n_open is None else n_open
+            if not isinstance(n_open, np.ndarray) or n_open.dtype != np.int32 or n_open.shape != (1,):
+                raise ValueError('n_open must be a one-element int32 array')
+            open_ptr = n_open.ctypes.data
+
+        rs = _lib.RayState(*self._state_pointers('ray state', rays, _lib.RayState.FIELDS, self._ray_shapes(B), B, dev))
+        cst = _lib.SqpState(*self._state_pointers('SQP state', state, _lib.SqpState.FIELDS, {}, B, dev))
+        ro = _lib.RayOpts(int(bisect), int(budget), float(self.problem.params.tol_x if tol_term is None else tol_term), float(mu0))
+        with self._ordered(dev):
+            self._chk(self.L.smpc_ray_update(self.h, B, C.byref(ro), C.byref(rs), C.byref(cst), ptrs[3], ptrs[0], ptrs[1], ptrs[2],
+                                             open_ptr, dev))
+        return n_open
 
     # -- start states at a chosen end-effector position ---------------------------------------------------------------------
     def ik(self, target, q_start, mask=None, q_out=None, info=None, resid=None, **over):

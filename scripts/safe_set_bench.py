@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""The measurement of profiles/safe_set_data.txt: rays labelled per second at B rays in flight on the backup
+OCP at N = back_hor, bisect = 8, budget 30, a look every 5 iterations -- with the bookkeeping on the device (smpc_ray_update and a
+4-byte read per round) against the statement-driven loop on the same engine (host decisions by ray_update_statement; the engine's
+host-pointer path carries the arrays), alternating the two in one session, wall clock around a synchronise.  Also the time inside
+smpc_ray_update (events on the engine's stream) and inside ray_update_statement (host clock), and the share of rays per kind.
+
+    python scripts/safe_set_bench.py [output file] [--rays 4096] [--reps 2]
+"""
+import os, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from safe_mpc_amd import safe_set_data as sd
+from safe_mpc_amd.controller import SafeBackupController
+from safe_mpc_amd.parser import Parameters
+from safe_mpc_amd.solver import BatchedOcpSolver
+
+args = sys.argv[1:]
+def opt(flag, default):
+    if flag in args:
+        i = args.index(flag)
+        v = int(args[i + 1])
+        del args[i:i + 2]
+        return v
+    return default
+B, REPS = opt('--rays', 4096), opt('--reps', 2)
+OUT = open(args[0], 'w') if args else open(os.devnull, 'w')
+def say(*a):
+    line = ' '.join(str(x) for x in a)
+    print(line, flush=True)
+    OUT.write(line + '\n'); OUT.flush()
+
+par = Parameters({}, 'z1', rti=False)
+par.nq, par.n_dof_safe_set, par.net_size = 6, 6, [12, 256, 1]
+BISECT, BUDGET, EVERY = 8, 30, 5
+ctrl = SafeBackupController(par, B)
+sv = ctrl.ocp_solver
+sv.set_qp_mode('throughput')
+N = ctrl.N
+say(f'# python scripts/safe_set_bench.py -- safe-set ray labelling; Z1-class arm, backup OCP, N = back_hor = {N}, {B} rays in flight, bisect = {BISECT}, '
+    f'budget {BUDGET}, a look every {EVERY} SQP iterations; one MI355X, one session')
+q, d, s_hi = sd.sample_rays(ctrl.problem, B, 0, solver=sv)
+
+_upd, _stmt = BatchedOcpSolver.ray_update, sd.ray_update_statement
+spent = {'events': [], 'host': 0.0}
+def upd_timed(self, *a, **k):
+    # (events on the engine's stream, recorded from outside it: the call keeps ordering its stream against torch's current one.  The
+    #  engine's stream is ordered behind torch's BEFORE the start event, so the interval holds the call's own work only)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    self._ext_stream.wait_stream(torch.cuda.current_stream(self.device))
+    e0.record(self._ext_stream)
+    r = _upd(self, *a, **k)
+    e1.record(self._ext_stream)
+    spent['events'].append((e0, e1))
+    return r
+def stmt_timed(*a, **k):
+    t1 = time.perf_counter()
+    r = _stmt(*a, **k)
+    spent['host'] += time.perf_counter() - t1
+    return r
+BatchedOcpSolver.ray_update, sd.ray_update_statement = upd_timed, stmt_timed
+
+def run(mode):
+    spent['events'], spent['host'] = [], 0.0
+    sv.sync(); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = sd.label_rays(ctrl, q, d, s_hi, bisect=BISECT, budget=BUDGET, check_every=EVERY, bookkeeping=mode)
+    sv.sync(); torch.cuda.synchronize()
+    w = time.perf_counter() - t0
+    book = sum(a.elapsed_time(b) for a, b in spent['events']) * 1e-3 if mode == 'device' else spent['host']
+    return res, w, book
+
+results = {}
+for rep in range(REPS):
+    for mode in ('device', 'statement'):
+        res, w, book = run(mode)
+        results.setdefault(mode, []).append((w, book, res))
+        say(f'run {rep} {mode:9s}: {w:7.2f} s wall, {B / w:8.1f} rays/s, {res["rounds"]} rounds, {int(res["iters"].sum())} instance-iterations, '
+            f'bookkeeping {book * 1e3:9.2f} ms in all ({book * 1e3 / res["rounds"]:.3f} ms per round)')
+a, b = results['device'][-1][2], results['statement'][-1][2]
+same = all(np.array_equal(a[k], b[k], equal_nan=True) for k in ('label', 'kind', 'trials', 'iters', 'x_cert', 'u_cert'))
+say(f'device and statement-driven results identical bit for bit: {same}')
+for mode in ('device', 'statement'):
+    ws = [w for w, _, _ in results[mode]]
+    say(f'{mode:9s}: best of {REPS}: {B / min(ws):.1f} rays/s; all runs {[round(B / w, 1) for w in ws]}')
+kind = a['kind']
+say('share of rays per kind: ' + ', '.join(f'{sd.KIND_NAMES[k]} {100.0 * (kind == k).mean():.1f} %' for k in (sd.DEAD, sd.BRACKETED, sd.SATURATED)))
+lab = a['label'][kind != sd.DEAD]
+say(f'labels of the rays that are not dead: min {lab.min():.3f}, median {np.median(lab):.3f}, max {lab.max():.3f} rad/s; trials per ray mean {a["trials"].mean():.2f}')
+OUT.close()
