@@ -642,7 +642,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                   O_PVA = O_PEND > O_STG ? O_PEND : O_STG, O_PVB = O_PVA + NX, O_PB = O_PVB + NX,
                   O_ZU = O_PB + NX, O_XB = O_ZU + NQP, O_RHO = O_XB + 2 * NX, O_WV = O_RHO + NQP, HALF_D = O_WV + NQP;
     __shared__ __attribute__((aligned(16))) double smem[2 * HALF_D];
-    __shared__ unsigned char triUi[NTRI_U], triUj[NTRI_U], triXi[NTRI_X], triXj[NTRI_X];
+    // Index tables of the factorisation sweep's triangle passes: the same for every stage and iteration of a launch, and shared by
+    // the two halves (lane roles are the same in both).
+    // PASS_TAB: one 32-byte descriptor per (x-x pass, lane) with the BYTE OFFSETS every operand of the lane's element is read at --
+    // relative to the array's start in the half's region; to P_{k+1} for its four entries and to P_k for the two stores, since P
+    // ping-pongs -- packed to 16 bits.  A pass of the P update gets them with two LDS reads and one add per address (the packed
+    // halves are picked by the add itself), where the byte tables of (i, j) take 26 integer instructions between the look-up and
+    // the first operand read; the block an element belongs to is read off the offsets (below).  Lanes past the end of a triangle
+    // hold its last element, as the clamped index did.  With e = lane + 32 pass, (i, j) = element e of the x-x triangle:
+    //   desc[2 e]     .x = i NQP 8 | j NQP 8 << 16   .y = i 8 | j 8 << 16   .z = P(i, j) | P(i, jj) << 16   .w = P(ii, j) | P(ii, jj) << 16
+    //   desc[2 e + 1] .x = P(j, i) | Hqq(iq, jq) << 16   .y = iq MRP 8 | jq MRP 8 << 16      (ii = i mod NQ, iq = min(i, NQ - 1))
+    //                 .z, .w = what .x, .y of desc[2 e] are for element e of the u-u triangle (first pass only: the u-u pass)
+    // (one array, one stride: a second lane address held across the kernel is a register the forward sweeps spill.)
+    // Built where it costs neither a wavefront per CU nor a register: 6-DoF (19.1 KB per block with six rows; eight blocks of 20 KB
+    // fit a CU, which 256 registers cap at eight).  7-DoF has no room (21.6 of 22.8 KB for its seven), and at 5-DoF the same code
+    // spills 20 bytes more: both keep the byte tables, their code unchanged to the instruction.
+    constexpr int XP = (NTRI_X + 31) / 32;
+    constexpr int LDS_CAP = (160 * 1024) / 8;
+    constexpr bool PASS_TAB = NQ == 6 && 2 * HALF_D * 8 + 16 + XP * 32 * 32 <= LDS_CAP;
+    __shared__ uint4 desc[PASS_TAB ? 2 * XP * 32 : 1];
+    __shared__ unsigned char triUi[PASS_TAB ? 1 : NTRI_U], triUj[PASS_TAB ? 1 : NTRI_U], triXi[PASS_TAB ? 1 : NTRI_X],
+        triXj[PASS_TAB ? 1 : NTRI_X];
     double* const sIMG = smem + half * HALF_D;
     double* const sTT = sIMG + Ly.iTT;
     double* const sGT = sIMG + Ly.iGT;
@@ -672,15 +692,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     double* const sWv = sIMG + O_WV;
 
     // (both halves write the same table values: a lone half must not depend on its twin)
-    for (int e = hl; e < NTRI_U; e += 32) {
-        int i = 0, rem = e;
-        while (rem >= NQ - i) { rem -= NQ - i; i++; }
-        triUi[e] = (unsigned char)i;
-        triUj[e] = (unsigned char)(i + rem);
-    }
     // Upper triangle of the x-x block, the q-q corner first; P ping-pongs between two buffers (in place was slower: DESIGN.md section 8)
-    for (int e = hl; e < NTRI_X; e += 32) {
-        int i = 0, j;
+    auto tri_x = [](int e, int& i, int& j) {
+        i = 0;
         if (e < NTRI_U) {
             int rem = e;
             while (rem >= NQ - i) { rem -= NQ - i; i++; }
@@ -690,9 +704,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
             while (rem >= (i < NQ ? NQ : NX - i)) { rem -= (i < NQ ? NQ : NX - i); i++; }
             j = (i < NQ ? NQ : i) + rem;
         }
-        triXi[e] = (unsigned char)i;
-        triXj[e] = (unsigned char)j;
+    };
+    if constexpr (PASS_TAB) {
+        static_assert(8 * HALF_D < 65536 && 8 * NX * NX < 65536, "byte offsets of a descriptor fit 16 bits");
+        for (int e = hl; e < XP * 32; e += 32) {
+            int i, j;
+            tri_x(min(e, NTRI_X - 1), i, j);
+            const int ii = i >= NQ ? i - NQ : i, jj = j >= NQ ? j - NQ : j, iq = min(i, NQ - 1), jq = min(j, NQ - 1);
+            auto pk = [](int lo, int hi) { return (unsigned)(8 * lo) | ((unsigned)(8 * hi) << 16); };
+            desc[2 * e] = uint4{pk(i * NQP, j * NQP), pk(i, j), pk(i * NX + j, i * NX + jj), pk(ii * NX + j, ii * NX + jj)};
+            // (.z, .w: the u-u pass's element of lane e -- the head of the same triangle, clamped to ITS last element)
+            int iu, ju;
+            tri_x(min(e, NTRI_U - 1), iu, ju);
+            desc[2 * e + 1] = uint4{pk(j * NX + i, iq * NQ + jq), pk(iq * MRP, jq * MRP), pk(iu * NQP, ju * NQP), pk(iu, ju)};
+        }
+    } else {
+        for (int e = hl; e < NTRI_U; e += 32) {
+            int i = 0, rem = e;
+            while (rem >= NQ - i) { rem -= NQ - i; i++; }
+            triUi[e] = (unsigned char)i;
+            triUj[e] = (unsigned char)(i + rem);
+        }
+        // Upper triangle of the x-x block, the q-q corner first; P ping-pongs between two buffers (in place was slower: DESIGN.md section 8)
+        for (int e = hl; e < NTRI_X; e += 32) {
+            int i = 0, j;
+            if (e < NTRI_U) {
+                int rem = e;
+                while (rem >= NQ - i) { rem -= NQ - i; i++; }
+                j = i + rem;
+            } else {
+                int rem = e - NTRI_U;
+                while (rem >= (i < NQ ? NQ : NX - i)) { rem -= (i < NQ ? NQ : NX - i); i++; }
+                j = (i < NQ ? NQ : i) + rem;
+            }
+            triXi[e] = (unsigned char)i;
+            triXj[e] = (unsigned char)j;
+        }
     }
+    // an operand at a descriptor's byte offset from the start of its array
+    auto at = [](auto* base, unsigned off) {
+        using T = std::remove_pointer_t<decltype(base)>;
+        if constexpr (std::is_const_v<T>) return reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + off);
+        else return reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off);
+    };
 
     const double* xb0 = xg + (size_t)b * (N + 1) * NX;
     const double* ub0 = ug + (size_t)b * N * NU;
@@ -856,7 +910,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 // -- P b, and the rows scaled by their barrier weights
                 {
                     // (whole 16-byte reads: as twelve scalar ones the compiler, short of registers, waits for each in turn)
-                    const double a = bflag ? pdot(Pc + hl_x * NX, sB, NX / 2) : 0.0;
+                    double a = bflag ? pdot(Pc + hl_x * NX, sB, NX / 2) : 0.0;
+                    // (the end stage's constant zero is formed here: hoisted out of the iteration loop it holds a register pair across
+                    //  the kernel, or a scratch slot whose reload drains the loads just issued for stage N - 1)
+                    if constexpr (last && PASS_TAB) asm volatile("" : "+v"(a));
                     sPB[hl_x] = a;   // (reaches the corrector's backward sweep folded into the stored gradient, below)
                 }
                 // (fixed trip counts with clamped indices instead of data-dependent loop bounds: the passes of one loop are
@@ -910,29 +967,61 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 if (!last) {
 #pragma unroll
                     for (int t = 0; t < (NTRI_U + 31) / 32; t++) {
-                        const int el = min(hl + 32 * t, NTRI_U - 1);   // (lanes past the end repeat the last element)
-                        const int i = triUi[el], j = triUj[el];
-                        // (operands loaded, then held: one batch of reads and one wait per pass, here and in the next loop)
-                        constexpr int H = NQP / 2;
-                        dbl2 ti[H], tj[H];
-                        double sc[5];
+                        if constexpr (PASS_TAB) {
+                            // (operands loaded, then held: one batch of reads and one wait per pass, here and in the next loop)
+                            constexpr int H = NQP / 2;
+                            static_assert(NTRI_U <= 32, "one u-u pass");
+                            const uint4 du = desc[2 * hl + 1];
+                            const unsigned gi = du.w & 0xffffu, gj = du.w >> 16;     // (8 i, 8 j)
+                            const dbl2 *pti = reinterpret_cast<const dbl2*>(at(sTT, du.z & 0xffffu)),
+                                       *ptj = reinterpret_cast<const dbl2*>(at(sTD, du.z >> 16));
+                            const double* p11 = at(Pc, gi * NX + gj);
+                            double *l_ij = at(sLam, gi * NQ + gj), *l_ji = at(sLam, gj * NQ + gi);
+                            const bool diag = gi == gj;
+                            dbl2 ti[H], tj[H];
+                            double sc[5];
 #pragma unroll
-                        for (int h = 0; h < H; h++) {
-                            ti[h] = reinterpret_cast<const dbl2*>(sTT + i * NQP)[h];
-                            tj[h] = reinterpret_cast<const dbl2*>(sTD + j * NQP)[h];
+                            for (int h = 0; h < H; h++) {
+                                ti[h] = pti[h];
+                                tj[h] = ptj[h];
+                            }
+                            sc[0] = sSC[0]; sc[1] = p11[0]; sc[2] = p11[NQ]; sc[3] = p11[NQ * NX];
+                            sc[4] = p11[NQ * NX + NQ];
+                            hold_rows2<H>(ti, tj, sc);
+                            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                            for (int h = 0; h < H; h++) { s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1); }
+                            double a = s0 + s1;
+                            a += diag ? sc[0] : 0.0;
+                            // B^T P B = c^2 P11 + c dt (P12 + P21) + dt^2 P22
+                            a += cB * cB * sc[1] + cB * dt * (sc[2] + sc[3]) + dt * dt * sc[4];
+                            *l_ij = a;
+                            *l_ji = a;
+                        } else {
+                            const int el = min(hl + 32 * t, NTRI_U - 1);   // (lanes past the end repeat the last element)
+                            const int i = triUi[el], j = triUj[el];
+                            // (operands loaded, then held: one batch of reads and one wait per pass, here and in the next loop)
+                            constexpr int H = NQP / 2;
+                            dbl2 ti[H], tj[H];
+                            double sc[5];
+#pragma unroll
+                            for (int h = 0; h < H; h++) {
+                                ti[h] = reinterpret_cast<const dbl2*>(sTT + i * NQP)[h];
+                                tj[h] = reinterpret_cast<const dbl2*>(sTD + j * NQP)[h];
+                            }
+                            sc[0] = sSC[0]; sc[1] = Pc[i * NX + j]; sc[2] = Pc[i * NX + NQ + j]; sc[3] = Pc[(NQ + i) * NX + j];
+                            sc[4] = Pc[(NQ + i) * NX + NQ + j];
+                            hold_rows2<H>(ti, tj, sc);
+                            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                            for (int h = 0; h < H; h++) { s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1); }
+                            double a = s0 + s1;
+                            a += i == j ? sc[0] : 0.0;
+                            // B^T P B = c^2 P11 + c dt (P12 + P21) + dt^2 P22
+                            a += cB * cB * sc[1] + cB * dt * (sc[2] + sc[3]) + dt * dt * sc[4];
+                            sLam[i * NQ + j] = a;
+                            sLam[j * NQ + i] = a;
                         }
-                        sc[0] = sSC[0]; sc[1] = Pc[i * NX + j]; sc[2] = Pc[i * NX + NQ + j]; sc[3] = Pc[(NQ + i) * NX + j];
-                        sc[4] = Pc[(NQ + i) * NX + NQ + j];
-                        hold_rows2<H>(ti, tj, sc);
-                        double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                        for (int h = 0; h < H; h++) { s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1); }
-                        double a = s0 + s1;
-                        a += i == j ? sc[0] : 0.0;
-                        // B^T P B = c^2 P11 + c dt (P12 + P21) + dt^2 P22
-                        a += cB * cB * sc[1] + cB * dt * (sc[2] + sc[3]) + dt * dt * sc[4];
-                        sLam[i * NQ + j] = a;
-                        sLam[j * NQ + i] = a;
                     }
 #pragma unroll
                     for (int t = 0; t < (NQ * NX + 31) / 32; t++) {
@@ -981,11 +1070,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                 if (last) {   // P_N = the x-x block itself; at the other stages it is assembled inside the P update below
 #pragma unroll
                     for (int t = 0; t < (NTRI_X + 31) / 32; t++) {
-                        const int el = min(hl + 32 * t, NTRI_X - 1);
-                        const int ix = triXi[el], jx = triXj[el];
-                        const double a = hxx_elem(ix, jx, 32 * t < NTRI_U);
-                        Pn[ix * NX + jx] = a;
-                        Pn[jx * NX + ix] = a;
+                        if constexpr (PASS_TAB) {
+                            const unsigned gij = desc[2 * (hl + 32 * t)].y, pij = desc[2 * (hl + 32 * t)].z & 0xffffu, pji = desc[2 * (hl + 32 * t) + 1].x & 0xffffu;
+                            const double a = hxx_elem((int)(gij & 0xffffu) >> 3, (int)(gij >> 19), 32 * t < NTRI_U);
+                            *at(Pn, pij) = a;
+                            *at(Pn, pji) = a;
+                        } else {
+                            const int el = min(hl + 32 * t, NTRI_X - 1);
+                            const int ix = triXi[el], jx = triXj[el];
+                            const double a = hxx_elem(ix, jx, 32 * t < NTRI_U);
+                            Pn[ix * NX + jx] = a;
+                            Pn[jx * NX + ix] = a;
+                        }
                     }
                 }
                 // -- gradient: g + C^T e; lanes NU.. keep the x part in a register for the costate update
@@ -1068,49 +1164,103 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
                         // (which needs only the u-u and u-x blocks): three passes, their index look-ups and a buffer fewer
 #pragma unroll
                         for (int t = 0; t < (NTRI_X + 31) / 32; t++) {
-                            const int el = min(hl + 32 * t, NTRI_X - 1);
-                            const int i = triXi[el], j = triXj[el];
-                            // every operand of the element -- rows i, j of the scaled Jacobian and of W, the safe-set row's entries,
-                            // the diagonal extras, the four entries of P_{k+1} (A^T P A by blocks: [P11, dt P11 + P12; dt P11 + P21,
-                            // dt^2 P11 + dt (P12 + P21) + P22], i <= j, clamped indices and zero weights outside a block) -- is
-                            // loaded, then held: one batch of reads, one wait
-                            constexpr int H = NQP / 2;
-                            dbl2 ti[H], tj[H], wi[H], wj[H];
-                            double sc[9];
-                            {
-                                const dbl2 *pti = reinterpret_cast<const dbl2*>(sTT + (NU + i) * NQP),
-                                           *ptj = reinterpret_cast<const dbl2*>(sTD + (NU + j) * NQP),
-                                           *pwi = reinterpret_cast<const dbl2*>(sWT + i * NQP), *pwj = reinterpret_cast<const dbl2*>(sWT + j * NQP);
+                            if constexpr (PASS_TAB) {
+                                // where the element's operands sit: the lane's descriptor (same operands, same arithmetic as below)
+                                const uint4 da = desc[2 * (hl + 32 * t)];
+                                const uint2 db = *reinterpret_cast<const uint2*>(&desc[2 * (hl + 32 * t) + 1]);
+                                const unsigned ri = da.x & 0xffffu, rj = da.x >> 16, gi = da.y & 0xffffu, gj = da.y >> 16;
+                                const dbl2 *pti = reinterpret_cast<const dbl2*>(at(sTT + NU * NQP, ri)),
+                                           *ptj = reinterpret_cast<const dbl2*>(at(sTD + NU * NQP, rj)),
+                                           *pwi = reinterpret_cast<const dbl2*>(at(sWT, ri)), *pwj = reinterpret_cast<const dbl2*>(at(sWT, rj));
+                                const double *gn_i = at(sGN, gi), *gn_j = at(sGN, gj), *d_i = at(sD, gi);
+                                const double *p_ij = at(Pc, da.z & 0xffffu), *p_ijj = at(Pc, da.z >> 16), *p_iij = at(Pc, da.w & 0xffffu),
+                                             *p_iijj = at(Pc, da.w >> 16);
+                                double *pn_ij = at(Pn, da.z & 0xffffu), *pn_ji = at(Pn, db.x & 0xffffu);
+                                const double *hqq = at(sHQQ, db.x >> 16), *gt_i = at(sGT, db.y & 0xffffu), *gd_j = at(sGD, db.y >> 16);
+                                // (which block: i = j where the two offsets agree; a velocity index is one whose entry of the folded block
+                                //  of P lies elsewhere, ii != i -- compares of halves the lane holds anyway, no constant kept in a register)
+                                const bool diag = gi == gj, i_vel = (da.w & 0xffffu) != (da.z & 0xffffu), j_vel = (da.z >> 16) != (da.z & 0xffffu);
+                                // every operand of the element -- rows i, j of the scaled Jacobian and of W, the safe-set row's entries,
+                                // the diagonal extras, the four entries of P_{k+1} (A^T P A by blocks: [P11, dt P11 + P12; dt P11 + P21,
+                                // dt^2 P11 + dt (P12 + P21) + P22], i <= j, clamped indices and zero weights outside a block) -- is
+                                // loaded, then held: one batch of reads, one wait
+                                constexpr int H = NQP / 2;
+                                dbl2 ti[H], tj[H], wi[H], wj[H];
+                                double sc[9];
+                                {
 #pragma unroll
-                                for (int h = 0; h < H; h++) { ti[h] = pti[h]; tj[h] = ptj[h]; wi[h] = pwi[h]; wj[h] = pwj[h]; }
-                                const int ii = i >= NQ ? i - NQ : i, jj = j >= NQ ? j - NQ : j;
-                                sc[0] = sGN[i]; sc[1] = sGN[j]; sc[2] = sD[rNN]; sc[3] = sD[i]; sc[4] = sSC[1];
-                                sc[5] = Pc[i * NX + j]; sc[6] = Pc[i * NX + jj]; sc[7] = Pc[ii * NX + j]; sc[8] = Pc[ii * NX + jj];
-                            }
-                            hold_rows4<H>(ti, tj, wi, wj, sc);
-                            double a;
-                            {
-                                double s0 = 0.0, s1 = 0.0, w0 = 0.0, w1 = 0.0;
-#pragma unroll
-                                for (int h = 0; h < H; h++) {
-                                    s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1);
-                                    w0 = fma(wi[h].x, wj[h].x, w0); w1 = fma(wi[h].y, wj[h].y, w1);
+                                    for (int h = 0; h < H; h++) { ti[h] = pti[h]; tj[h] = ptj[h]; wi[h] = pwi[h]; wj[h] = pwj[h]; }
+                                    sc[0] = *gn_i; sc[1] = *gn_j; sc[2] = sD[rNN]; sc[3] = *d_i; sc[4] = sSC[1];
+                                    sc[5] = *p_ij; sc[6] = *p_ijj; sc[7] = *p_iij; sc[8] = *p_iijj;
                                 }
-                                a = (s0 + s1) - (w0 + w1);
+                                hold_rows4<H>(ti, tj, wi, wj, sc);
+                                double a;
+                                {
+                                    double s0 = 0.0, s1 = 0.0, w0 = 0.0, w1 = 0.0;
+#pragma unroll
+                                    for (int h = 0; h < H; h++) {
+                                        s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1);
+                                        w0 = fma(wi[h].x, wj[h].x, w0); w1 = fma(wi[h].y, wj[h].y, w1);
+                                    }
+                                    a = (s0 + s1) - (w0 + w1);
+                                }
+                                a = fma(sc[0] * sc[2], sc[1], a);
+                                if (32 * t < NTRI_U) {   // (the passes that hold elements of the q-q corner, see the index table)
+                                    const double qq = *hqq + pdot(gt_i, gd_j, MRP >> 1);
+                                    a += !j_vel ? qq : 0.0;
+                                }
+                                a += diag ? sc[3] + (i_vel ? sc[4] : 0.0) : 0.0;
+                                {
+                                    const double cj = j_vel ? dt : 0.0, ci = i_vel ? dt : 0.0;
+                                    a += sc[5] + cj * sc[6] + ci * (sc[7] + dt * sc[8]);
+                                }
+                                *pn_ij = a;
+                                *pn_ji = a;
+                            } else {
+                                const int el = min(hl + 32 * t, NTRI_X - 1);
+                                const int i = triXi[el], j = triXj[el];
+                                // every operand of the element -- rows i, j of the scaled Jacobian and of W, the safe-set row's entries,
+                                // the diagonal extras, the four entries of P_{k+1} (A^T P A by blocks: [P11, dt P11 + P12; dt P11 + P21,
+                                // dt^2 P11 + dt (P12 + P21) + P22], i <= j, clamped indices and zero weights outside a block) -- is
+                                // loaded, then held: one batch of reads, one wait
+                                constexpr int H = NQP / 2;
+                                dbl2 ti[H], tj[H], wi[H], wj[H];
+                                double sc[9];
+                                {
+                                    const dbl2 *pti = reinterpret_cast<const dbl2*>(sTT + (NU + i) * NQP),
+                                               *ptj = reinterpret_cast<const dbl2*>(sTD + (NU + j) * NQP),
+                                               *pwi = reinterpret_cast<const dbl2*>(sWT + i * NQP), *pwj = reinterpret_cast<const dbl2*>(sWT + j * NQP);
+#pragma unroll
+                                    for (int h = 0; h < H; h++) { ti[h] = pti[h]; tj[h] = ptj[h]; wi[h] = pwi[h]; wj[h] = pwj[h]; }
+                                    const int ii = i >= NQ ? i - NQ : i, jj = j >= NQ ? j - NQ : j;
+                                    sc[0] = sGN[i]; sc[1] = sGN[j]; sc[2] = sD[rNN]; sc[3] = sD[i]; sc[4] = sSC[1];
+                                    sc[5] = Pc[i * NX + j]; sc[6] = Pc[i * NX + jj]; sc[7] = Pc[ii * NX + j]; sc[8] = Pc[ii * NX + jj];
+                                }
+                                hold_rows4<H>(ti, tj, wi, wj, sc);
+                                double a;
+                                {
+                                    double s0 = 0.0, s1 = 0.0, w0 = 0.0, w1 = 0.0;
+#pragma unroll
+                                    for (int h = 0; h < H; h++) {
+                                        s0 = fma(ti[h].x, tj[h].x, s0); s1 = fma(ti[h].y, tj[h].y, s1);
+                                        w0 = fma(wi[h].x, wj[h].x, w0); w1 = fma(wi[h].y, wj[h].y, w1);
+                                    }
+                                    a = (s0 + s1) - (w0 + w1);
+                                }
+                                a = fma(sc[0] * sc[2], sc[1], a);
+                                if (32 * t < NTRI_U) {   // (the passes that hold elements of the q-q corner, see the index table)
+                                    const int iq = min(i, NQ - 1), jq = min(j, NQ - 1);
+                                    const double qq = sHQQ[iq * NQ + jq] + pdot(sGT + iq * MRP, sGD + jq * MRP, MRP >> 1);
+                                    a += j < NQ ? qq : 0.0;
+                                }
+                                a += i == j ? sc[3] + (i >= NQ ? sc[4] : 0.0) : 0.0;
+                                {
+                                    const double cj = j >= NQ ? dt : 0.0, ci = i >= NQ ? dt : 0.0;
+                                    a += sc[5] + cj * sc[6] + ci * (sc[7] + dt * sc[8]);
+                                }
+                                Pn[i * NX + j] = a;
+                                Pn[j * NX + i] = a;
                             }
-                            a = fma(sc[0] * sc[2], sc[1], a);
-                            if (32 * t < NTRI_U) {   // (the passes that hold elements of the q-q corner, see the index table)
-                                const int iq = min(i, NQ - 1), jq = min(j, NQ - 1);
-                                const double qq = sHQQ[iq * NQ + jq] + pdot(sGT + iq * MRP, sGD + jq * MRP, MRP >> 1);
-                                a += j < NQ ? qq : 0.0;
-                            }
-                            a += i == j ? sc[3] + (i >= NQ ? sc[4] : 0.0) : 0.0;
-                            {
-                                const double cj = j >= NQ ? dt : 0.0, ci = i >= NQ ? dt : 0.0;
-                                a += sc[5] + cj * sc[6] + ci * (sc[7] + dt * sc[8]);
-                            }
-                            Pn[i * NX + j] = a;
-                            Pn[j * NX + i] = a;
                         }
                         {
                             // p_k = gh_x + A^T (p_{k+1} + P b) - W^T w  (every lane reads, the state lanes write)
