@@ -242,6 +242,27 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
 #define SMPC_SCENE_ROW 8   /* doubles per (instance, row): C[3], D[3], offset, 0 */
 int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device);
 
+/* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
+ * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle
+ * keeps a copy like a scene (stream-ordered; with host pointers the call checks every entry for finiteness and waits for the
+ * copy; device pointers are taken as they are), curves == NULL clears them.  A call with the same (B, L) overwrites the handle's
+ * buffer in place, so a step captured in a hipGraph keeps seeing it.
+ * While curves are set
+ *   smpc_policy_step (all six kinds, SMPC_POLICY_PARALLEL included): before the solve, for the stepping instances,
+ *       p[b][i][0:3] = curves[b][:, clamp(current_step[b] + i, 0, L - 1)]
+ *     -- what a non-NULL st->traj does from the shared table; instances that do not step keep their p.  A non-NULL st->traj is
+ *     SMPC_EINVAL (two sources for one input).
+ *   smpc_score_rollout with par->traj == NULL and par->ee_ref == NULL: ref_j of instance b is column min(j, L - 1) of curves[b].
+ *     With either pointer given the call does not read the curves.
+ * The curves belong to THEIR batch size: these two calls with another B return SMPC_EINVAL and name both sizes; the engine never
+ * falls back to the shared reference.  Nothing else reads them: smpc_solve_batch, smpc_sqp_batch, smpc_merit_terms and
+ * smpc_check_guess take p from the caller, smpc_rollout_batch has no reference trajectory.
+ * Memory: 24 bytes x L x B.  The shipped n_steps_tracking = 5000 with N = 30 gives L = 5031: 121 KB per instance, 495 MB at 4096.
+ * SMPC_EINVAL: B <= 0, L < 1, or (host pointers only) a non-finite entry.
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* curves, int on_device);
+
 /* replaces ocp_solver.cost_set(k,'zl'/'zu',v) (controller.py:455-468, 526-527): L1 penalty of the slack on the safe-set row of
  * node k, for the nodes where the formulation made that row soft (nn_soft_e / nn_soft_run >= 0; a hard row has no slack and
  * acados' arrays for it are empty).  zl is [N+1] host doubles shared by all instances (entry 0 unused); NULL restores the
@@ -456,7 +477,7 @@ typedef struct {
     int32_t reserved0;
     const double *x_min, *x_max;            /* HOST [nx] */
     const double *row_lb_chk, *row_ub_chk;  /* HOST [n_rows] */
-    const double *ee_ref;                   /* HOST [3], used when traj == NULL */
+    const double *ee_ref;                   /* HOST [3], used when traj == NULL; both NULL: the handle's curves (smpc_set_instance_curves) */
     const double *traj; int64_t traj_len;   /* [3][traj_len], follows on_device; or NULL */
 } smpc_score_params;
 
@@ -551,7 +572,8 @@ typedef struct {                    /* what a controller object holds per instan
                                        Not NULL: before the solve, p[b][i][0:3] = traj[:, current_step[b] + i] for every node i of the
                                        stepping instances -- what solve() does through ocp_solver.set(i, 'p', .) at
                                        controller.py:153-156 (column index clamped to traj_len - 1).  NULL: p[:, :, 0:3] is left as the
-                                       caller set it (the constant ee_ref of the ReachTarget costs). */
+                                       caller set it (the constant ee_ref of the ReachTarget costs) -- unless the handle holds curves
+                                       (smpc_set_instance_curves), which then feed p the same way and with which traj must be NULL. */
     int64_t traj_len;
 } smpc_policy_state;
 

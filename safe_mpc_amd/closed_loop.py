@@ -36,12 +36,23 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}_mpc.pkl')
 
 
-def tracking_from_cli(params, argv):
+def tracking_from_cli(params, argv, n=None):
     """The curve of a tracking run as the entry scripts select it: ``--track 8|circle`` on the command line, or ``track_traj: true``
     in config.yaml (the "8").  Returns ``tracking.tracking_trajectory(params, curve)`` -- which also makes the run
-    n_steps_tracking long and sets ``params.track_traj`` -- or None for the reach task."""
-    from .tracking import tracking_trajectory
+    n_steps_tracking long and sets ``params.track_traj`` -- or None for the reach task.
+
+    ``--track-jitter SIGMA [--track-scale-jitter S] [--track-seed S]``: a curve of its own for each of the ``n`` instances,
+    ``tracking.jittered_curves(params, curve, n, SIGMA, seed, S)`` ``[n, 3, L]``.  Only with a tracking run (ValueError
+    otherwise); without ``n`` the options are checked and the plain curve is returned."""
+    from .tracking import jittered_curves, tracking_trajectory
     argv = list(argv)
+
+    def opt(flag, default, cast):
+        if flag not in argv:
+            return default
+        if argv.index(flag) + 1 >= len(argv):
+            raise ValueError(f'{flag} needs a value')
+        return cast(argv[argv.index(flag) + 1])
     curve = None
     if '--track' in argv:
         if argv.index('--track') + 1 >= len(argv):
@@ -49,6 +60,14 @@ def tracking_from_cli(params, argv):
         curve = argv[argv.index('--track') + 1]
     elif getattr(params, 'track_traj', False):
         curve = '8'
+    jitter = [f for f in ('--track-jitter', '--track-scale-jitter', '--track-seed') if f in argv]
+    if jitter and curve is None:
+        raise ValueError(f"{jitter[0]} is valid only for a tracking run: give --track 8|circle (or track_traj: true in config.yaml)")
+    if jitter and '--track-jitter' not in argv:
+        raise ValueError(f'{jitter[0]} needs --track-jitter SIGMA')
+    if jitter and n is not None:
+        return jittered_curves(params, curve, int(n), opt('--track-jitter', 0.0, float), opt('--track-seed', 0, int),
+                               opt('--track-scale-jitter', 0.0, float))
     return None if curve is None else tracking_trajectory(params, curve)
 
 
@@ -456,11 +475,17 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     (setTrajectory: p[:, i, :3] = traj[:, i]) and every start state comes from :func:`ik_starts` at ``traj[:, 0]`` -- instance i in
     its scene where ``scenes`` is given -- instead of the Halton filter; the guess is constant at it, as the reference builds it,
     and the SQP and checkGuess are the same.  An instance whose IK found no solution is dropped, never replaced: its entry of the
-    returned mask (one per requested instance) is False and the result's ``'ik_failed'`` lists it."""
+    returned mask (one per requested instance) is False and the result's ``'ik_failed'`` lists it.
+    ``traj`` [n, 3, L] (tracking.tracking_curves / jittered_curves): a curve of its own for every instance -- instance i starts from
+    an IK solution at ``traj[i, :, 0]`` and follows ``traj[i]`` (p[i, k, :3] = traj[i, :, k]); the result gains ``'curves'``, the
+    curves of the accepted instances."""
     make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
     ctrl = make_controller(cont_name, n)
+    curves = traj is not None and np.ndim(traj) == 3
     if traj is not None:
         traj = np.ascontiguousarray(traj, np.float64)
+        if curves and (traj.shape[0] != n or traj.shape[1] != 3):
+            raise ValueError(f'traj: expected [3, L] or [{n}, 3, L], got {traj.shape}')
         ctrl.setTrajectory(traj)
     if on_device and not hasattr(ctrl.ocp_solver, 'sqp'):
         raise ValueError(f'generate_guess(on_device=True) needs a solver with a device SQP (BatchedOcpSolver.sqp); '
@@ -474,13 +499,14 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     if traj is not None:
         if scenes is not None:
             scenes = _check_scenes(scenes, n, pr)
-        x0, ik_info = ik_starts(ctrl.ocp_solver, pr, traj[:, 0], n, scenes=scenes)      # guess_acados.py:179-183
+        x0, ik_info = ik_starts(ctrl.ocp_solver, pr, traj[:, :, 0] if curves else traj[:, 0], n, scenes=scenes)   # guess_acados.py:179-183
         filled = ik_info[:, 1] > 0
         ik_failed = np.where(~filled)[0]
         if verbose and len(ik_failed):
             print(f'inverse kinematics: no start state for {len(ik_failed)} of {n} instances: {ik_failed.tolist()}')
         x0 = x0[filled]
         scenes = scenes[filled] if scenes is not None else None
+        traj = traj[filled] if curves else traj
     elif scenes is not None:
         scenes = _check_scenes(scenes, n, pr)
         x0, filled = _free_starts_per_scene(ctrl.ocp_solver, scenes, x_all)
@@ -505,6 +531,8 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
             return out, good
         if scenes is not None:
             out['scenes'] = scenes[good]
+        if curves:
+            out['curves'] = traj[good]
         mask = np.zeros(n, bool)
         mask[np.where(filled)[0][good]] = True
         return out, mask
@@ -647,6 +675,9 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
     if scenes is not None:
         raise ValueError('generate_guess_until: per-instance scenes are not supported (a refilled slot would need the scene of its '
                          'new sample); use generate_guess(scenes=...)')
+    if traj is not None and np.ndim(traj) == 3:
+        raise ValueError('generate_guess_until: per-instance curves are not supported (a refilled slot would need a curve for its '
+                         'new sample); use generate_guess(traj=[n, 3, L])')
     if accept not in ('final', 'first'):
         raise ValueError("accept must be 'final' or 'first'")
     check_every = int(check_every)
@@ -811,7 +842,8 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
 
     * cost = Q ee_err2 + R u2 (metrics_count_fails.py:19-28 for a complete log), ee_err2 = sum_{j <= last_x} |ee(x_j) - ref_j|^2,
       u2 = sum_{j <= last_u} |u_j|^2, ee_dist = |ee(x_last_x) - ref_last_x| (what mpc.py:273 compares with tol_conv);
-      ref_j = ``ee_ref`` (default: the problem's) or column min(j, L - 1) of ``traj [3, L]``
+      ref_j = ``ee_ref`` (default: the problem's) or column min(j, L - 1) of ``traj [3, L]`` -- of ``traj[b]`` for instance b
+      with ``traj [B, 3, L]``
     * coll_margin = max over j <= last_x and rows of max(row_lb - v, v - row_ub) (env_model.py:236-243), -inf without rows;
       box_margin = max over j <= last_x and components of max(x_min - x, x - x_max) (env_model.py:170-172);
       safe_min = min over j <= last_x of g(x_j, alpha) (safe_set.py:61-68), +inf unless ``want_safe``
@@ -840,7 +872,12 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
     vx, vu = steps[None, :] <= lx[:, None], steps[None, :T] <= lu[:, None]           # valid rows
     if traj is not None:
         traj = np.asarray(traj, float)
-        ref = traj[:, np.minimum(steps, traj.shape[1] - 1)].T[None, :, :]             # [1, T+1, 3]
+        if traj.ndim == 3:
+            if traj.shape[0] != B or traj.shape[1] != 3:
+                raise ValueError(f'traj: expected [3, L] or [{B}, 3, L], got {traj.shape}')
+            ref = np.transpose(traj[:, :, np.minimum(steps, traj.shape[2] - 1)], (0, 2, 1))      # [B, T+1, 3]
+        else:
+            ref = traj[:, np.minimum(steps, traj.shape[1] - 1)].T[None, :, :]         # [1, T+1, 3]
     else:
         ref = np.asarray(problem.ee_ref if ee_ref is None else ee_ref, float)[None, None, :]
     flat = np.where(vx[:, :, None], x, 0.0).reshape(-1, x.shape[2])                  # invalid rows: any finite state, masked below
@@ -1243,7 +1280,8 @@ class _Group(InPlaceState):
                 scored = solver.score_rollout(self.x_log, self.u_log, self.last_x, self.last_u, traj=traj, want_safe=want_safe)
             else:
                 scored = score_rollout_statement(solver, pr, params, self.x_log, self.u_log, self.last_x, self.last_u,
-                                                 traj=traj, want_safe=want_safe, per_instance=self._scenes is not None)
+                                                 traj=None if traj is None else xp.host(traj), want_safe=want_safe,
+                                                 per_instance=self._scenes is not None)
         if xp.on_device:
             solver.sync()
         # convergence at the last step (mpc.py:273): the reference tests x_sim[-1], NaN for instances that broke
@@ -1263,6 +1301,8 @@ class _Group(InPlaceState):
             extra['scenes'] = xp.host(self._scenes)
             _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
             _clear_scene(self._backup.ocp_solver)
+        if getattr(ctrl, 'traj', None) is not None and ctrl.traj.ndim == 3 and hasattr(solver, 'set_instance_curves'):
+            solver.set_instance_curves(None)       # (nor curves: the controller hands them over again should it step once more)
         return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
                     time_rows=np.array(self._time_rows, float).reshape(-1, len(TIME_FIELDS)), time_lost=self._time_lost,
                     collided=xp.host(self.collided), viable=xp.host(self.viable).astype(np.int64),
@@ -1310,7 +1350,10 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     the result gains ``'scenes'``, and the controller's and the backup solver's handles are left without a scene when the run ends.
     Not with the parallel policy (ValueError): its solver works on B x N candidate slots, which are not instances.
     ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
-    task of the reference's Tracking8* / TrackingMovingCircle* costs."""
+    task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
+    jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle
+    holds the curves, solver.set_instance_curves), the score uses each instance's own curve, the backup OCP has zero cost and needs
+    none, and the handles are left without curves when the run ends."""
     import time
     B = x_guess.shape[0]
     if scenes is not None:
@@ -1320,6 +1363,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         scenes = np.ascontiguousarray(scenes, np.float64)
         if scenes.ndim != 3 or scenes.shape[0] != B:
             raise ValueError(f'scenes: expected [{B}, n_rows, 8], got {scenes.shape}')
+    curves = traj is not None and np.ndim(traj) == 3
+    if curves:
+        traj = np.ascontiguousarray(traj, np.float64)
+        if traj.shape[0] != B or traj.shape[1] != 3:
+            raise ValueError(f'traj: expected [3, L] or [{B}, 3, L], got {traj.shape}')
     n_steps = int(n_steps if n_steps is not None else params.n_steps)
     if on_device:
         make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch, device=device, device_state=True))
@@ -1337,7 +1385,7 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     for lo, hi in spans:
         ctrl = make_controller(cont_name, hi - lo)
         if traj is not None:
-            ctrl.setTrajectory(traj)
+            ctrl.setTrajectory(traj[lo:hi] if curves else traj)
         backup = make_backup(hi - lo)
         if on_device:
             import torch

@@ -85,21 +85,34 @@ class AbstractController(InPlaceState):
     def setTrajectory(self, traj):
         """``cost.traj`` of the reference (cost_definition.py:30-31, 89): ``[3, n_steps + 1 + N]`` reference points, of which
         ``solve`` hands node i the column ``current_step + i`` (controller.py:153-156).  ``None`` (the default) = the constant
-        ``ee_ref`` of the ReachTarget / Zero costs, for which the indexing changes nothing."""
+        ``ee_ref`` of the ReachTarget / Zero costs, for which the indexing changes nothing.
+
+        ``[B, 3, n_columns]`` (tracking.tracking_curves / jittered_curves): a curve of its own for every instance, instance b
+        reading ``traj[b]`` the same way.  On a device-backed controller the engine's handle then holds the curves
+        (``solver.set_instance_curves``) and the policy step is called without a shared table; going back to ``[3, n_columns]``
+        or ``None`` clears them."""
+        had_curves = self.traj is not None and self.traj.ndim == 3
+        to_engine = self.xp.on_device and hasattr(self.ocp_solver, 'set_instance_curves')
         if traj is None:
             self.traj = None
             self.p[:, :, :3] = self.xp.asarray(self.problem.ee_ref, self.xp.f64)
+            if had_curves and to_engine:
+                self.ocp_solver.set_instance_curves(None)
             return
         traj = np.ascontiguousarray(traj, float)
-        if traj.ndim != 2 or traj.shape[0] != 3 or traj.shape[1] < 1:
+        if traj.ndim == 3:
+            if traj.shape[0] != self.B or traj.shape[1] != 3 or traj.shape[2] < 1:
+                raise ValueError(f'traj must be [3, n_columns] or [{self.B}, 3, n_columns] (one curve per instance of the batch), '
+                                 f'got {traj.shape}')
+        elif traj.ndim != 2 or traj.shape[0] != 3 or traj.shape[1] < 1:
             raise ValueError('traj must be [3, n_columns]')
         # the reference indexes cost.traj[:, current_step + i] for i <= N over a run of n_steps steps and would raise on a shorter
         # array; here the column index is clamped (the device kernel must not read past the end), so say so instead of silently
         # holding the last point
         need = int(getattr(self.params, 'n_steps', 0)) + 1 + self.N
-        if traj.shape[1] < need:
+        if traj.shape[-1] < need:
             import warnings
-            warnings.warn(f'setTrajectory: {traj.shape[1]} columns < n_steps + 1 + N = {need}: the reference would fail with an '
+            warnings.warn(f'setTrajectory: {traj.shape[-1]} columns < n_steps + 1 + N = {need}: the reference would fail with an '
                           'IndexError past the end; this engine holds the last column', RuntimeWarning, stacklevel=2)
         new = self.xp.asarray(traj, self.xp.f64)
         if self.traj is not None and tuple(self.traj.shape) == tuple(new.shape):
@@ -107,14 +120,20 @@ class AbstractController(InPlaceState):
         else:
             self.traj = new
             self._traj_rebound = True  # (closed_loop._Group drops its captured graphs when it sees this)
+        if to_engine and (new.ndim == 3 or had_curves):
+            # the handle's copy follows: same (B, L) overwrites the handle's buffer in place, which a captured step keeps reading
+            self.ocp_solver.set_instance_curves(self.traj if new.ndim == 3 else None)
 
     def _apply_traj(self, rows=None):
         """p[b, i, 0:3] = traj[:, current_step[b] + i] (controller.py:153-156)"""
         if self.traj is None:
             return
         xp = self.xp
-        col = xp.clip_max(self.current_step[:, None] + xp.arange(self.N + 1)[None, :], self.traj.shape[1] - 1)     # [B, N+1]
-        ref = xp.swap_last(self.traj[:, col])                  # [3, B, N+1] -> [B, N+1, 3]
+        col = xp.clip_max(self.current_step[:, None] + xp.arange(self.N + 1)[None, :], self.traj.shape[-1] - 1)    # [B, N+1]
+        if self.traj.ndim == 3:                                    # a curve per instance: traj[b, :, col[b, i]]
+            ref = xp.swap_last(self.traj[xp.arange(self.B)[None, :, None], xp.arange(3)[:, None, None], col[None]])
+        else:
+            ref = xp.swap_last(self.traj[:, col])                  # [3, B, N+1] -> [B, N+1, 3]
         if rows is None:
             self.p[:, :, :3] = ref
         else:

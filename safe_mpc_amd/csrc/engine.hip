@@ -58,6 +58,9 @@ struct smpc_handle {
     int inst_B = 0;
     DevBuf<double> d_scene;         // [B][n_rows][SMPC_SCENE_ROW] per-instance obstacle geometry (smpc_set_instance_scene), valid for scene_B
     int scene_B = 0;                // 0: no scene, every launcher takes the shared-scene kernels
+    DevBuf<double> d_curves;        // [B][3][L] per-instance reference curves (smpc_set_instance_curves), valid for curves_B / curves_L
+    int curves_B = 0;               // 0: no curves, the policy step and the score take the caller's shared table (or none)
+    int64_t curves_L = 0;
     // network
     int nlayers = 0;
     int act = SMPC_ACT_GELU_TANH;
@@ -412,6 +415,37 @@ int scene_guard(smpc_handle* h, int B, const char* who) {
     return SMPC_OK;
 }
 const double* scene_of(const smpc_handle* h, int B) { return h->scene_B == B ? h->d_scene.p : nullptr; }
+
+// The curves belong to their batch size in the same way: the two entry points that read them refuse another B while they are set,
+// never the shared reference instead.
+int curves_guard(smpc_handle* h, int B, const char* who) {
+    if (h->curves_B && h->curves_B != B)
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance curves were set for %d instances (smpc_set_instance_curves: "
+                    "clear them or set curves of this size)", who, B, h->curves_B);
+    return SMPC_OK;
+}
+
+// The reference table of a policy step: the handle's curves (a table per instance) or the caller's shared one (stride 0), or none.
+struct TrajSrc {
+    const double* p = nullptr;
+    long len = 0, stride = 0;
+};
+int policy_traj_src(smpc_handle* h, int B, const smpc_policy_state* st, TrajSrc* out) {
+    int rc;
+    if ((rc = curves_guard(h, B, "smpc_policy_step"))) return rc;
+    if (h->curves_B) {
+        if (st->traj)
+            return fail(h, SMPC_EINVAL, "smpc_policy_step: st->traj given (traj_len %lld) while instance curves are set (%d instances, "
+                        "%lld columns): two sources for one input, clear one", (long long)st->traj_len, h->curves_B, (long long)h->curves_L);
+        *out = TrajSrc{h->d_curves.p, (long)h->curves_L, 3 * (long)h->curves_L};
+        return SMPC_OK;
+    }
+    if (st->traj) {
+        if (st->traj_len < 1) return fail(h, SMPC_EINVAL, "traj_len must be >= 1");
+        *out = TrajSrc{st->traj, (long)st->traj_len, 0};
+    }
+    return SMPC_OK;
+}
 
 // the nodes' linearisation records by the thread-per-node kernel, the network's row included (smpc_eval_nodes, and the reference
 // set-up of smpc_debug_stage_records; not on the solve path)
@@ -881,17 +915,17 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
     int rc;
     if ((rc = ensure_parallel(h, B))) return rc;
     if ((rc = ensure_nn_idx(h, (size_t)B * (N + 1)))) return rc;
+    TrajSrc tr;
+    if ((rc = policy_traj_src(h, B, st, &tr))) return rc;
     const ParScratch c = par_layout(h->d_par.p, B, N, nq);
     const dim3 blk(64);
     const auto grid = [](long n) { return dim3((unsigned)((n + 63) / 64)); };
     // guessCorrection; also resets *any_abort and presets the state-test verdicts of phase 1
     hipLaunchKernelGGL(k_guess_correction, grid((long)B * nq), blk, 0, s, B, N, nq, h->desc.dt, st->x_guess, st->u_guess, stepping,
                        any_abort, d_ok);
-    if (st->traj) {      // controller.py:153-156, into the instance's own p (what solve() writes there)
-        if (st->traj_len < 1) return fail(h, SMPC_EINVAL, "traj_len must be >= 1");
-        hipLaunchKernelGGL(k_policy_traj, grid((long)B * (N + 1)), blk, 0, s, B, N, stepping, st->current_step, st->traj,
-                           (long)st->traj_len, st->p);
-    }
+    if (tr.p)            // controller.py:153-156, into the instance's own p (what solve() writes there)
+        hipLaunchKernelGGL(k_policy_traj, grid((long)B * (N + 1)), blk, 0, s, B, N, stepping, st->current_step, tr.p, tr.len, tr.stride,
+                           st->p);
     hipLaunchKernelGGL(k_par_fanout1, grid((long)B * (N + 1)), blk, 0, s, B, N, stepping, st->p, c.p1, c.n_open);
     HIPCHK(h, hipGetLastError());
     const int coll = par->collision_first_node ? 1 : N + 1;
@@ -1179,7 +1213,8 @@ int upload_score_bounds(smpc_handle* h, const smpc_score_params* par) {
         memcpy(cur.data() + 2 * nx + SMPC_MAX_ROWS, par->row_ub_chk, sizeof(double) * nr);
     }
     // (a call with traj does not read ee_ref: the block keeps the last one, so that alternating calls do not count as a change)
-    if (!par->traj) memcpy(cur.data() + 2 * nx + 2 * SMPC_MAX_ROWS, par->ee_ref, sizeof(double) * 3);
+    // (nor does a call against the handle's curves, which gives neither)
+    if (!par->traj && par->ee_ref) memcpy(cur.data() + 2 * nx + 2 * SMPC_MAX_ROWS, par->ee_ref, sizeof(double) * 3);
     else if (h->schk_cache.size() == cur.size()) memcpy(cur.data() + 2 * nx + 2 * SMPC_MAX_ROWS, h->schk_cache.data() + 2 * nx + 2 * SMPC_MAX_ROWS, sizeof(double) * 3);
     int rc;
     if ((rc = h->d_schk.reserve(h, "score bounds", cur.size() * sizeof(double)))) return rc;
@@ -1222,8 +1257,8 @@ constexpr long SCORE_MLP_ROWS = 1L << 18;
 // each followed by k_score_safe when the safe-set score is wanted, then k_score_combine
 template <int NQ>
 int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const double* u_log, const int64_t* last_x,
-                 const int64_t* last_u, const smpc_score_params* par, const double* traj, const uint8_t* mask, double* out,
-                 int32_t* outi) {
+                 const int64_t* last_u, const smpc_score_params* par, const double* traj, long traj_len, long traj_stride,
+                 const uint8_t* mask, double* out, int32_t* outi) {
     constexpr int nx = 2 * NQ;
     hipStream_t s = h->stream;
     const int n_seg = n_steps / SCORE_SEG + 1;          // segments of the n_steps + 1 states
@@ -1238,10 +1273,10 @@ int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const 
     const unsigned gb = (unsigned)((B + 63) / 64);
     if (const double* geom = scene_of(h, B))
         hipLaunchKernelGGL((k_score_seg<NQ, true>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x,
-                           last_u, d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi, geom);
+                           last_u, d_min, d_max, d_rlb, d_rub, d_ref, traj, traj_len, traj_stride, mask, w.pd, w.pi, geom);
     else
         hipLaunchKernelGGL((k_score_seg<NQ>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x, last_u,
-                           d_min, d_max, d_rlb, d_rub, d_ref, traj, (long)par->traj_len, mask, w.pd, w.pi, (const double*)nullptr);
+                           d_min, d_max, d_rlb, d_rub, d_ref, traj, traj_len, traj_stride, mask, w.pd, w.pi, (const double*)nullptr);
     HIPCHK(h, hipGetLastError());
     if (par->want_safe) {
         const long total = (long)(n_steps + 1) * B;
@@ -1483,6 +1518,32 @@ int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_de
     HIPCHK(h, hipMemcpyAsync(h->d_scene.p, geom, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
     h->scene_B = B;
+    return SMPC_OK;
+}
+
+int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* curves, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!curves) { h->curves_B = 0; h->curves_L = 0; return SMPC_OK; }
+    if (B <= 0 || L < 1) return fail(h, SMPC_EINVAL, "smpc_set_instance_curves: B=%d, L=%lld: need B > 0 and L >= 1", B, (long long)L);
+    const size_t n = (size_t)B * 3 * (size_t)L;
+    if (!on_device) {
+        // (device pointers are taken as they are: reading them back would synchronise)
+        for (size_t i = 0; i < n; i++)
+            if (!(curves[i] - curves[i] == 0.0))
+                return fail(h, SMPC_EINVAL, "curve of instance %lld (of B=%d), axis %d, column %lld (of L=%lld) is not finite",
+                            (long long)(i / (3 * (size_t)L)), B, (int)(i / (size_t)L % 3), (long long)(i % (size_t)L), (long long)L);
+    }
+    int rc;
+    // (grown only when the curves grow: the same (B, L) is overwritten in place, and a captured step keeps seeing this buffer)
+    if ((rc = h->d_curves.reserve(h, "instance curves", n * sizeof(double)))) {
+        if (!h->d_curves.p) { h->curves_B = 0; h->curves_L = 0; }      // (a failed growth left no buffer; a refused one keeps the old curves)
+        return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_curves.p, curves, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
+    h->curves_B = B;
+    h->curves_L = L;
     return SMPC_OK;
 }
 
@@ -1782,6 +1843,8 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     hipStream_t s = h->stream;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_policy_step"))) return rc;
+    TrajSrc tr;
+    if (!parallel && (rc = policy_traj_src(h, B, st, &tr))) return rc;     // (before anything is enqueued; the parallel step asks itself)
     if ((rc = ensure_batch(h, B))) return rc;
     PolScratch w;
     if ((rc = policy_scratch(h, B, &w))) return rc;
@@ -1806,11 +1869,9 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
                            kind == SMPC_POLICY_REAL_RECEDING ? any_abort : (int32_t*)nullptr,
                            kind == SMPC_POLICY_REAL_RECEDING ? d_ok : (int32_t*)nullptr);
     }
-    if (st->traj) {      // controller.py:153-156: the nodes' reference points follow the step counter
-        if (st->traj_len < 1) return fail(h, SMPC_EINVAL, "traj_len must be >= 1");
+    if (tr.p)            // controller.py:153-156: the nodes' reference points follow the step counter
         hipLaunchKernelGGL(k_policy_traj, dim3((unsigned)(((size_t)B * (N + 1) + 63) / 64)), dim3(64), 0, s, B, N, stepping,
-                           st->current_step, st->traj, (long)st->traj_len, st->p);
-    }
+                           st->current_step, tr.p, tr.len, tr.stride, st->p);
     HIPCHK(h, hipGetLastError());
     h->d_active = stepping;
     // (the receding policies carry the row at node r and at the end node, and test nodes r + 2 .. N afterwards -- in steady state one or
@@ -2165,12 +2226,15 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
     if (!par->x_min || !par->x_max) return fail(h, SMPC_EINVAL, "state bounds missing");
     if (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
     if (par->traj && par->traj_len < 1) return fail(h, SMPC_EINVAL, "traj given with traj_len=%lld", (long long)par->traj_len);
-    if (!par->traj && !par->ee_ref) return fail(h, SMPC_EINVAL, "neither ee_ref nor traj given");
+    // neither pointer: the reference of instance b is its own curve (smpc_set_instance_curves), if the handle holds curves
+    const bool own = !par->traj && !par->ee_ref && h->curves_B;
+    if (!par->traj && !par->ee_ref && !own) return fail(h, SMPC_EINVAL, "neither ee_ref nor traj given");
     if (par->want_safe && h->nlayers == 0) return fail(h, SMPC_ESTATE, "want_safe given but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
     const int nq = h->desc.nq;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_score_rollout"))) return rc;
+    if (own && (rc = curves_guard(h, B, "smpc_score_rollout"))) return rc;
     if ((rc = upload_score_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du, *dtraj;
@@ -2189,7 +2253,9 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
              douti = v.inout(outi, (size_t)B * SCORE_NI);
          })))
         return rc;
-    DISPATCH_NQ(h, (launch_score<NQ_>(h, B, n_steps, dx, du, dlx, dlu, par, dtraj, dmask, dout, douti)));
+    const double* ref = own ? h->d_curves.p : dtraj;
+    const long ref_len = own ? (long)h->curves_L : (long)par->traj_len, ref_stride = own ? 3 * (long)h->curves_L : 0L;
+    DISPATCH_NQ(h, (launch_score<NQ_>(h, B, n_steps, dx, du, dlx, dlu, par, ref, ref_len, ref_stride, dmask, dout, douti)));
     if (rc) return rc;
     return io.finish();
 }

@@ -41,9 +41,11 @@ __global__ void k_policy_pre(int B, int N, int nx, int kind, const uint8_t* __re
 
 // solve() feeds every node its column of the reference trajectory, p[i][0:3] = cost.traj[:, current_step + i]
 // (controller.py:153-156; cost_definition.py:30-31, 89: traj has n_steps + 1 + N columns).  One thread per (instance, node);
-// launched only when the caller gave a trajectory.
+// launched only when the caller gave a trajectory or the handle holds curves.  Instance b's table starts at traj + b * stride:
+// stride = 0 is the shared [3][traj_len] table, stride = 3 * traj_len the per-instance curves of smpc_set_instance_curves (the
+// lanes of one wavefront then read from up to 64 / (N + 1) + 1 tables).
 __global__ void k_policy_traj(int B, int N, const uint8_t* __restrict__ stepping, const int64_t* __restrict__ current_step,
-                              const double* __restrict__ traj, long traj_len, double* __restrict__ p) {
+                              const double* __restrict__ traj, long traj_len, long stride, double* __restrict__ p) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)B * (N + 1)) return;
     const long b = t / (N + 1);
@@ -51,7 +53,8 @@ __global__ void k_policy_traj(int B, int N, const uint8_t* __restrict__ stepping
     if (stepping && !stepping[b]) return;
     long c = (long)current_step[b] + k;
     c = c < 0 ? 0 : (c < traj_len ? c : traj_len - 1);
-    for (int i = 0; i < 3; i++) p[t * SMPC_NP + i] = traj[(size_t)i * traj_len + c];
+    const double* tb = traj + (size_t)b * stride;
+    for (int i = 0; i < 3; i++) p[t * SMPC_NP + i] = tb[(size_t)i * traj_len + c];
 }
 
 // The receding policies move r to the last safe node of the NEW trajectory, looking at nodes r + 2 .. N only

@@ -40,6 +40,8 @@ __device__ __forceinline__ void score_last_rows(int b, int n_steps, const int64_
 // their places.  Rows past last_x / last_u are never loaded.  A lane whose log ends before the segment writes nothing
 // (k_score_combine does not read that segment's partial).  Partials are stored [segment][slot][B], so the stores coalesce too.
 // SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// traj_stride: instance b's reference table starts at traj + b * traj_stride -- 0 for the shared table, 3 * traj_len for the
+// handle's per-instance curves (smpc_set_instance_curves); a run-time argument, so the curves add no instantiation.
 template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __restrict__ D, int B, int n_steps,
                                                   const double* __restrict__ x_log, const double* __restrict__ u_log,
@@ -47,8 +49,8 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
                                                   const double* __restrict__ x_min, const double* __restrict__ x_max,
                                                   const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                   const double* __restrict__ ee_ref, const double* __restrict__ traj, long traj_len,
-                                                  const uint8_t* __restrict__ mask, double* __restrict__ pd, int32_t* __restrict__ pi,
-                                                  const double* __restrict__ geom = nullptr) {
+                                                  long traj_stride, const uint8_t* __restrict__ mask, double* __restrict__ pd,
+                                                  int32_t* __restrict__ pi, const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[SQP_PT_DOUBLES];
     const int b = blockIdx.x * 64 + threadIdx.x, seg = blockIdx.y;
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
     double* const spt = s_pts + threadIdx.x;
     const int np = D->n_points, nrows = D->n_rows, eep = D->ee_point;
     const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
+    const double* const traj_b = traj ? traj + (size_t)b * traj_stride : nullptr;
     for (int pt = 0; pt < np; pt++)
         if (D->points[pt].link < 0) {
 #pragma unroll
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
         if (traj) {
             const long c = j < traj_len - 1 ? (long)j : traj_len - 1;
 #pragma unroll
-            for (int a = 0; a < 3; a++) ref[a] = traj[a * traj_len + c];
+            for (int a = 0; a < 3; a++) ref[a] = traj_b[a * traj_len + c];
         } else {
 #pragma unroll
             for (int a = 0; a < 3; a++) ref[a] = ee_ref[a];

@@ -180,6 +180,35 @@ class BatchedOcpSolver:
         with self._ordered(dev):
             self._chk(self.L.smpc_set_instance_scene(self.h, B, ptrs[0], dev))
 
+    def set_instance_curves(self, curves=None):
+        """A reference curve of its own for every instance of the tracking task (smpc_set_instance_curves): ``curves [B, 3, L]``
+        (tracking.tracking_curves / jittered_curves), a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy
+        (24 B x L x B).  None clears them.  While set, :meth:`policy_step` feeds instance b the columns of ``curves[b]`` (and
+        refuses a shared table), ``score_rollout(traj='instance')`` scores against them, and both must come with the same B."""
+        if curves is None:
+            self._chk(self.L.smpc_set_instance_curves(self.h, 0, 0, None, 0))
+            self._curves_src = self._curves_host = None
+            return
+        if _is_torch(curves):
+            import torch
+            if curves.dtype != torch.float64:
+                raise ValueError('set_instance_curves: the curves must be float64')
+        if curves.ndim != 3 or curves.shape[1] != 3:
+            raise ValueError(f'set_instance_curves: expected [B, 3, L], got {tuple(curves.shape)}')
+        B, L = int(curves.shape[0]), int(curves.shape[2])
+        ptrs, dev, keep = self._prep([curves], [(B, 3, L)])
+        with self._ordered(dev):
+            self._chk(self.L.smpc_set_instance_curves(self.h, B, L, ptrs[0], dev))
+        # what the handle holds: the tensor it was copied from (its owner says when it changes), or a copy of the host array
+        self._curves_src = curves if dev else None
+        self._curves_host = None if dev else np.array(curves, np.float64)
+
+    def _holds_curves(self, curves):
+        if _is_torch(curves):
+            return getattr(self, '_curves_src', None) is curves
+        held = getattr(self, '_curves_host', None)
+        return held is not None and held.shape == tuple(curves.shape) and np.array_equal(held, curves)
+
     def sync(self):
         self._chk(self.L.smpc_sync(self.h))
 
@@ -527,7 +556,9 @@ class BatchedOcpSolver:
         (metrics_count_fails.py:19-28), its two sums, the EE distance of the last state (mpc.py:273), the worst collision and
         state-box margins and the least safe-set value with the step (and row) each was taken at.  ``last_x`` / ``last_u`` (int64
         [B]): last valid row of each log, None = complete; rows past them affect nothing.  The reference point is ``traj [3, L]``
-        (column min(j, L - 1) at step j) or the constant ``ee_ref`` (default: the problem's).  ``want_safe`` needs a network.
+        (column min(j, L - 1) at step j) or the constant ``ee_ref`` (default: the problem's).  ``traj [B, 3, L]``: instance b is
+        scored against ``traj[b]`` -- the curves are handed to the handle first unless they are the ones it holds
+        (:meth:`set_instance_curves`) -- and ``traj='instance'`` scores against the curves already held.  ``want_safe`` needs a network.
         ``mask`` (uint8 [B]): instances with 0 are skipped and keep their rows of ``out`` / ``outi``.  ``bounds`` may override
         x_min, x_max, row_lb, row_ub, alpha, tol_safe (defaults from the problem and its params, as in :meth:`check_guess`)."""
         pr, par = self.problem, self.problem.params
@@ -543,6 +574,17 @@ class BatchedOcpSolver:
         if x_log.ndim != 3 or u_log.ndim != 3:
             raise ValueError('score_rollout: x_log [n_steps+1, B, nx] and u_log [n_steps, B, nu] expected')
         n_steps, B = int(u_log.shape[0]), int(x_log.shape[1])
+        own = isinstance(traj, str) or (traj is not None and traj.ndim == 3)       # against the handle's curves: neither pointer is passed
+        if isinstance(traj, str):
+            if traj != 'instance':
+                raise ValueError(f"score_rollout: traj must be an array or 'instance', got {traj!r}")
+        elif own:
+            if traj.shape[0] != B:
+                raise ValueError(f'score_rollout: {traj.shape[0]} curves for logs of {B} instances')
+            if not self._holds_curves(traj):
+                self.set_instance_curves(traj)
+        if own:
+            traj = None
         L = int(traj.shape[1]) if traj is not None else 0
         ptrs, dev, keep = self._prep([x_log, u_log, last_x, last_u, traj, mask, out, outi],
                                      [(n_steps + 1, B, self.nx), (n_steps, B, self.nu), (B,), (B,), (3, L), (B,), (B, SCORE_ND), (B, SCORE_NI)],
@@ -571,6 +613,8 @@ class BatchedOcpSolver:
             op, ip = out.ctypes.data, outi.ctypes.data
         sp = _lib.ScoreParams(float(bounds.get('alpha', par.alpha)), float(bounds.get('tol_safe', par.tol_safe_set)), int(bool(want_safe)), 0,
                               *[a.ctypes.data for a in small], ptrs[4], L)
+        if own:
+            sp.ee_ref = None
         with self._ordered(dev):
             self._chk(self.L.smpc_score_rollout(self.h, B, n_steps, ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(sp), ptrs[5], op, ip, dev))
         return out, outi
@@ -699,10 +743,14 @@ class BatchedOcpSolver:
         ptr = lambda t: t.data_ptr() if t is not None else None
         pp = self._policy_params(ctrl.policy_kind, getattr(ctrl, 'abort_flag', False), getattr(ctrl, 'TUBE', 0.0),
                                  getattr(ctrl, '_stage_lo', None), getattr(ctrl, '_stage_hi', None))
+        traj = getattr(ctrl, 'traj', None)
+        if traj is not None and traj.ndim == 3:     # a curve per instance: the handle holds them and the step passes no shared table
+            if not self._holds_curves(traj):        # (cleared, or another controller's, since setTrajectory handed them over)
+                self.set_instance_curves(traj)
+            traj = None
         st = _lib.PolicyState(ptr(ctrl.x_guess), ptr(ctrl.u_guess), ptr(ctrl.x_temp), ptr(ctrl.u_temp), ptr(ctrl.p), ptr(ctrl.x_viable),
                               ptr(ctrl.fails), ptr(ctrl.current_step), ptr(getattr(ctrl, 'r', None)), ptr(ctrl.last_status),
-                              ptr(ctrl.qp_iter), ptr(getattr(ctrl, 'traj', None)),
-                              int(ctrl.traj.shape[1]) if getattr(ctrl, 'traj', None) is not None else 0)
+                              ptr(ctrl.qp_iter), ptr(traj), int(traj.shape[1]) if traj is not None else 0)
         u_out = ctrl._u_out if u_out is None else u_out
         with self._ordered(1):
             self._chk(self.L.smpc_policy_step(self.h, ctrl.B, C.byref(pp), C.byref(st), x.data_ptr(), ptr(stepping), ptr(u_other),

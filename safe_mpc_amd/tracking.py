@@ -5,6 +5,8 @@ takes -- column ``current_step + i`` is the reference of node i (controller.py:1
 * :func:`lemniscate_trajectory`    -- generate_8shape_trajectory (cost_definition.py:170-199)
 * :func:`moving_circle_trajectory` -- generate_moving_circle_trajectory (cost_definition.py:264-288)
 * :func:`tracking_trajectory`      -- the entry: picks the curve and sets ``params.n_steps`` like the reference's cost classes
+* :func:`tracking_curves`          -- the batched form: ``[B, 3, L]``, a displaced / resized / re-timed curve per instance
+* :func:`jittered_curves`          -- ``tracking_curves`` with seeded normal draws on the offset and log-normal ones on the size
 
 Both curves advance their parameter theta by ``velocity * dt`` divided by the curve's speed per unit theta, one column at a time;
 with ``vel_const: false`` the velocity ramps from 0 by ``v_max / (n_steps_tracking * acc_time)`` per column while it is <= v_max.
@@ -105,3 +107,94 @@ def tracking_trajectory(params, curve='8'):
     params.n_steps = int(params.n_steps_tracking)
     params.track_traj = True
     return lemniscate_trajectory(params) if curve == '8' else moving_circle_trajectory(params)
+
+
+def _per_instance(name, value, default, B, tail):
+    """``value`` ([B, *tail], or None = the key's value for everybody) as a float array [B, *tail]"""
+    if value is None:
+        return np.broadcast_to(np.asarray(default, float), (B,) + tail).copy()
+    a = np.asarray(value, float)
+    if a.shape != (B,) + tail:
+        raise ValueError(f'{name}: shape {a.shape}, expected {(B,) + tail}')
+    return a
+
+
+def tracking_curves(params, curve='8', offsets=None, sizes=None, v_max=None, rotations=None, B=None):
+    """The batched form of :func:`tracking_trajectory`: ``[B, 3, n_steps_tracking + 1 + N]``, instance b's curve being what
+    ``tracking_trajectory`` gives on a copy of ``params`` with b's entries for the keys
+
+    * ``offsets [B, 3]``   -> offset_traj / circle_offset_traj          * ``sizes [B]`` -> dim_shape_8 / circle_rad
+    * ``v_max [B]``        -> vel_max_traj / circle_traj_vel            * ``rotations [B, 3]`` -> theta_rot_traj (the "8" only)
+
+    An argument left None keeps the key's value for every instance; B is the arrays' first dimension (``B=`` where none is given,
+    default 1).  Same arithmetic as the two generators above -- the ramp ``while vel <= v_max``, the circle's turn once y has passed
+    -0.5 / +0.5 -- as array operations over the instances inside the column loop (L iterations).  Sets ``params.n_steps`` and
+    ``params.track_traj`` like :func:`tracking_trajectory`."""
+    curve = str(curve)
+    if curve not in CURVES:
+        raise ValueError(f"curve must be one of {CURVES}, got {curve!r}")
+    given = [np.asarray(a).shape[0] for a in (offsets, sizes, v_max, rotations) if a is not None]
+    if B is None:
+        B = given[0] if given else 1
+    B = int(B)
+    if B < 1 or any(g != B for g in given):
+        raise ValueError(f'tracking_curves: the per-instance arrays have {given} entries for B = {B}')
+    if curve != '8' and rotations is not None:
+        raise ValueError("rotations apply to the '8' only")
+    eight = curve == '8'
+    off = _per_instance('offsets', offsets, params.offset_traj if eight else params.circle_offset_traj, B, (3,))
+    size = _per_instance('sizes', sizes, params.dim_shape_8 if eight else params.circle_rad, B, ())
+    vmax = _per_instance('v_max', v_max, params.vel_max_traj if eight else params.circle_traj_vel, B, ())
+    params.n_steps = int(params.n_steps_tracking)
+    params.track_traj = True
+    dt, n = float(params.dt), _columns(params)
+    ramp = not params.vel_const
+    vel = np.zeros(B) if ramp else vmax.copy()
+    acc = vmax / (int(params.n_steps_tracking) * float(params.acc_time)) if ramp else np.zeros(B)
+    theta = np.zeros(B)
+    out = np.zeros((B, 3, n))
+    if eight:
+        a = size
+        for i in range(n):
+            s, c = np.sin(theta), np.cos(theta)
+            den = 1.0 + s * s
+            out[:, 0, i] = a * c / den
+            out[:, 1, i] = a * c * s / den
+            dx = -a * s * (3.0 - s * s) / (den * den)
+            dy = a * (1.0 - 3.0 * s * s) / (den * den)
+            theta = theta + vel / np.sqrt(dx * dx + dy * dy) * dt
+            if ramp:
+                vel = np.where(vel <= vmax, vel + acc, vel)
+        rot = _per_instance('rotations', rotations, params.theta_rot_traj, B, (3,))
+        R = np.stack([_rot_xyz(th) for th in rot])
+        return np.matmul(R, out) + off[:, :, None]
+    cvel = float(params.circle_center_vel)
+    slide, sign = np.zeros(B), np.ones(B)
+    for i in range(n):
+        slide = slide - sign * cvel * dt
+        out[:, 0, i] = -size * np.cos(theta) + off[:, 0]
+        out[:, 1, i] = size * np.sin(theta) + slide + off[:, 1]
+        out[:, 2, i] = 0.0 + off[:, 2]
+        theta = theta + vel / np.sqrt(size * (np.sin(theta) ** 2 + np.cos(theta) ** 2)) * dt
+        y = out[:, 1, i]
+        sign = np.where((sign > 0) & (y < -0.5), -1.0, sign)
+        sign = np.where((sign < 0) & (y > 0.5), 1.0, sign)
+        if ramp:
+            vel = np.where(vel <= vmax, vel + acc, vel)
+    return out
+
+
+def jittered_curves(params, curve, B, sigma, seed=0, scale_sigma=0.0):
+    """B curves for a Monte-Carlo study of the tracking task: instance b's offset is the key's plus three N(0, sigma^2) draws and its
+    size the key's times exp of one N(0, scale_sigma^2) draw, from ``np.random.default_rng(seed)`` taken instance by instance in that
+    order.  The fourth draw is always taken, so the offsets do not depend on whether the size is jittered.  ``[B, 3, L]``
+    (:func:`tracking_curves`)."""
+    eight = str(curve) == '8'
+    rng = np.random.default_rng(seed)
+    base = np.asarray(params.offset_traj if eight else params.circle_offset_traj, float)
+    size = float(params.dim_shape_8 if eight else params.circle_rad)
+    offsets, sizes = np.zeros((int(B), 3)), np.zeros(int(B))
+    for b in range(int(B)):
+        offsets[b] = base + rng.normal(0.0, 1.0, 3) * float(sigma)
+        sizes[b] = size * np.exp(rng.normal(0.0, 1.0) * float(scale_sigma))
+    return tracking_curves(params, curve, offsets=offsets, sizes=sizes)

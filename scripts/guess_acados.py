@@ -13,6 +13,9 @@ draw per axis (problem.jittered_scenes); the scenes of the accepted guesses are 
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): warm starts of the trajectory-tracking task
 (guess_acados.py:167-226 of the reference) -- every start state is an inverse-kinematics solution at the curve's first point
 (closed_loop.ik_starts, smpc_ik_batch) and the OCP follows the curve.
+--track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every guess follows a curve of its own, the
+offset moved by N(0, SIGMA^2) per axis and the size scaled by exp N(0, S^2) (tracking.jittered_curves); the curves of the accepted
+guesses are stored in the pickle as 'curves', where scripts/mpc.py --track-jitter finds them.  Not with --until-accepted.
 """
 import os
 import sys
@@ -37,7 +40,7 @@ def main(argv=None):
     cont_name = args['controller']
     # every safe-set controller name is generated with the hard-terminal OCP (utils.py:46-58)
     gen_name = cont_name if cont_name in ('naive', 'zerovel') else 'htwa'
-    traj = cl.tracking_from_cli(params, raw)
+    traj = cl.tracking_from_cli(params, raw, n=params.test_num)
     scenes = None
     if '--scene-jitter' in raw:
         from safe_mpc_amd.problem import OcpProblem, jittered_scenes

@@ -8,6 +8,8 @@ with every instance of its outer loop (mpc.py:102) solved at once on the MI355X 
 seed --scene-seed, default 0).
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
+--track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
+the curves stored with the guesses (guess_acados.py --track-jitter) if there are any, else tracking.jittered_curves.
 Exit code = number of failed instances, as in the reference (mpc.py:317).
 """
 import os
@@ -33,6 +35,9 @@ def main(argv=None):
     print(gfile)
     data = pickle.load(open(gfile, 'rb'))
     x_guess, u_guess = data['xg'][:params.test_num], data['ug'][:params.test_num]
+    if '--track-jitter' in raw:
+        # the warm starts were generated along their own curves; without stored ones, a curve per loaded guess
+        traj = data['curves'][:params.test_num] if 'curves' in data else cl.tracking_from_cli(params, raw, n=x_guess.shape[0])
     scenes = None
     if '--scene-jitter' in raw:
         if 'scenes' in data:          # the warm starts were generated in these scenes
