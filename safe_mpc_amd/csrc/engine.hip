@@ -1292,6 +1292,43 @@ int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const 
     return SMPC_OK;
 }
 
+// ---- the streams of handles and rollout workers ----------------------------------------------------------------------------------
+// SMPC_STREAM_PRIORITY (read once per process): 0 `default` = hipStreamCreateWithFlags as before this function existed, 1 `high` (what
+// an unset variable means), 2 `low`; -1 = anything else, which smpc_create refuses.
+int stream_route() {
+    static const int v = [] {
+        const char* e = getenv("SMPC_STREAM_PRIORITY");
+        if (!e || !strcmp(e, "high")) return 1;
+        return !strcmp(e, "default") ? 0 : (!strcmp(e, "low") ? 2 : -1);
+    }();
+    return v;
+}
+
+// The one place that makes an engine stream (smpc_create; the rollout workers are handles).  The runtime keeps a pool of hardware
+// queues PER PRIORITY LEVEL, at most GPU_MAX_HW_QUEUES each (4 unless the process sets it), and gives a new stream the queue of its
+// level's pool with the fewest users once the pool is full; two streams on one queue run in order.  At the default level the engine
+// shares that pool with the null stream, torch's stream pool, RCCL and the runtime's own queues, and the third sub-batch of a bench
+// process landed on a queue that already carried another (point 4b).  So every engine stream of the process is
+// made at ONE level that nothing else in the process uses (the highest unless SMPC_STREAM_PRIORITY says otherwise; the handles stay
+// equals, only the pool changes).  Where it stops helping: handles beyond the pool's size share queues as before -- the fifth live
+// handle of a process with four queues per level (C3's five horizon groups beside the probe handle) takes turns with another.
+// A device with one level, or a runtime that refuses the call as invalid / unsupported, gets the plain call; any other error is the
+// caller's to report.
+hipError_t create_handle_stream(int device, hipStream_t* s) {
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return e;
+    const int route = stream_route();
+    if (route > 0) {
+        int least = 0, greatest = 0;     // (numerically: greatest priority <= least priority)
+        e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e == hipSuccess && least != greatest) e = hipStreamCreateWithPriority(s, hipStreamNonBlocking, route == 1 ? greatest : least);
+        else if (e == hipSuccess) e = hipErrorNotSupported;
+        if (e != hipErrorInvalidValue && e != hipErrorNotSupported) return e;
+        (void)hipGetLastError();
+    }
+    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1303,6 +1340,8 @@ const char* smpc_last_error(const smpc_handle* h) { return h ? h->err : g_create
 int smpc_create(const smpc_problem_desc* desc, int device, smpc_handle** out) {
     if (!desc || !out) return fail(nullptr, SMPC_EINVAL, "null argument");
     *out = nullptr;
+    if (stream_route() < 0)
+        return fail(nullptr, SMPC_EINVAL, "SMPC_STREAM_PRIORITY=%s: expected default, high or low", getenv("SMPC_STREAM_PRIORITY"));
     if (desc->abi_version != SMPC_ABI_VERSION)
         return fail(nullptr, SMPC_EINVAL, "descriptor ABI %d, library ABI %d", desc->abi_version, SMPC_ABI_VERSION);
     if (desc->nq < 5 || desc->nq > SMPC_MAX_NQ) return fail(nullptr, SMPC_EINVAL, "nq=%d unsupported", desc->nq);
@@ -1329,8 +1368,7 @@ int smpc_create(const smpc_problem_desc* desc, int device, smpc_handle** out) {
     h->desc = *desc;
     h->device = device;
     h->N = desc->N;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = create_handle_stream(device, &h->stream);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_desc, sizeof(smpc_problem_desc));
     if (e == hipSuccess) e = hipMemcpy(h->d_desc, desc, sizeof(smpc_problem_desc), hipMemcpyHostToDevice);
     for (int i = 0; i < 5 * smpc_handle::EV_RING && e == hipSuccess; i++) e = hipEventCreate(&h->ev_sets[i / 5][i % 5]);
