@@ -257,6 +257,14 @@ __device__ __forceinline__ DV3<NQ> point_with_jacobian(const smpc_point& P, cons
     }
     return out;
 }
+// the same point without its Jacobian, for the forward-only evaluations
+__device__ __forceinline__ DV3<0> point_world(const smpc_point& P, const Mat3<double>* Rw, const Vec3<double>* pw) {
+    DV3<0> out = dv_const<0>(P.local);
+    if (P.link < 0) return out;
+    const Vec3<double> w = pw[P.link] + mulc(Rw[P.link], P.local);
+    out.x.v = w.x; out.y.v = w.y; out.z.v = w.z;
+    return out;
+}
 
 // squared segment-segment distance exactly as the reference writes it (utils.py:94-113)
 template <int NQ>
@@ -297,6 +305,126 @@ __device__ __forceinline__ RowGeom<SCENE> row_geom(const smpc_row& row, const do
     } else {
         return {row.C, row.D, &row.offset};
     }
+}
+
+// Value (and, ND = NQ, gradient) of one collision row (env_model.py:263-316), as row_value<T> is the oracle's.  pt(i) yields robot
+// point i as a DV3<ND>: point_with_jacobian (the linearisation), point_world (the node tests) or column_point below (k_check_guess,
+// which keeps the points in LDS).  The fixed obstacle comes from G = row_geom<SCENE>.  Three kernels do NOT go through it and keep
+// the copies they had, because through it they did not keep their time (profiles/device_model_refactor.txt): k_merit and
+// k_score_seg (sqp_row_value, kernels_sqp.hpp) and k_ik (ik_row, kernels_ik.hpp).  (k_stage_build forms its rows
+// lane-cooperatively, a different formulation: kernel_build.hpp.)
+template <int ND, bool SCENE, class PT>
+__device__ __forceinline__ DQ<ND> row_value(const smpc_row& row, const RowGeom<SCENE>& G, PT&& pt) {
+    switch (row.kind) {
+    case SMPC_ROW_SEG_FIXEDSEG: return segment_dist2<ND>(pt(row.pa), pt(row.pb), dv_const<ND>(G.C), dv_const<ND>(G.D));
+    case SMPC_ROW_SEG_SEG: return segment_dist2<ND>(pt(row.pa), pt(row.pb), pt(row.pc), pt(row.pd));
+    case SMPC_ROW_SEG_POINT: return ball_segment_dist2<ND>(pt(row.pa), pt(row.pb), row.len2, dv_const<ND>(G.C));
+    case SMPC_ROW_POINT_POINT: {
+        DV3<ND> w = pt(row.pa) - dv_const<ND>(G.C);
+        return dot(w, w);
+    }
+    default: {
+        DV3<ND> P = pt(row.pa);
+        DQ<ND> v = row.axis == 0 ? P.x : (row.axis == 1 ? P.y : P.z);
+        v.v -= *G.offset;
+        return v;
+    }
+    }
+}
+
+// ---- the robot points' world positions, one column per lane in LDS -------------------------------------------------------------
+// The rows name their points by index, and a lane's registers cannot be indexed by a run-time value without spilling to scratch.
+// Element c of point pt of lane l sits at [(3 pt + c) * 64 + l]: a wavefront's accesses fall in 64 consecutive doubles.  spt is
+// the lane's own column (base + l) of a __shared__ double[PT_COL_DOUBLES].
+constexpr int PT_COL_DOUBLES = SMPC_MAX_POINTS * 3 * 64;
+__device__ __forceinline__ DV3<0> column_point(const double* __restrict__ spt, int pt) {
+    DV3<0> P;
+    P.x.v = spt[(3 * pt) * 64];
+    P.y.v = spt[(3 * pt + 1) * 64];
+    P.z.v = spt[(3 * pt + 2) * 64];
+    return P;
+}
+// the world-fixed points (link < 0): they do not move with q, so a kernel that walks many states fills them once
+__device__ __forceinline__ void point_column_fixed(const smpc_problem_desc* __restrict__ D, double* spt) {
+    const int np = D->n_points;
+    for (int pt = 0; pt < np; pt++)
+        if (D->points[pt].link < 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) spt[(3 * pt + c) * 64] = D->points[pt].local[c];
+        }
+}
+// the joint walk at q: every point that rides on a link  (k_merit and k_score_seg keep walks of their own, see row_value)
+template <int NQ> __device__ __forceinline__ void point_column_fk(const smpc_problem_desc* __restrict__ D, const double* q, double* spt) {
+    const int np = D->n_points;
+    Mat3<double> R;
+#pragma unroll
+    for (int i = 0; i < 9; i++) R.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    Vec3<double> pc;
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        pc = pc + mulc(R, D->joints[i].p0);
+        advance_rotation(R, D->joints[i], q[i]);
+        for (int pt = 0; pt < np; pt++)
+            if (D->points[pt].link == i) {
+                const Vec3<double> w = pc + mulc(R, D->points[pt].local);
+                spt[(3 * pt) * 64] = w.x;
+                spt[(3 * pt + 1) * 64] = w.y;
+                spt[(3 * pt + 2) * 64] = w.z;
+            }
+    }
+}
+
+// ---- NaN-keeping maximum and the wavefront reductions ----------------------------------------------------------------------------
+constexpr double NEG_INF = -__builtin_huge_val();
+constexpr double POS_INF = __builtin_huge_val();
+// max that keeps a NaN once it has seen one (fmax drops it, and a NaN has to fail its predicate)
+__device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ double wave_nanmax(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_xor(v, o));
+    return v;
+}
+// sum / max over the wavefront in a fixed order (xor butterfly: every lane ends with the same bits, run after run)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// ---- the learned safe set's value and the state-box margin ------------------------------------------------------------------------
+// |v + eps e_0|^2 over the first nn_dof joints (safe_set.py:61-68, 94); v[NQ] = the node's joint velocities.  Used by k_check_nn and
+// k_check_guess.  (k_score_safe, which walks a log, reads nn_dof and nn_eps once before its step loop and keeps its own copy of this
+// loop, kernels_score.hpp; k_merit keeps the code it had, see row_value.)
+template <int NQ> __device__ __forceinline__ double safe_speed2(const smpc_problem_desc* __restrict__ D, const double* v) {
+    const int nd = D->nn_dof;
+    double vn2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        const double w = i < nd ? v[i] + (i == 0 ? D->nn_eps : 0.0) : 0.0;
+        vn2 += w * w;
+    }
+    return vn2;
+}
+// g = y (100 - alpha) / 100 - |v + eps e_0|, in this order of operations.  (k_merit scales by the quotient (100 - alpha) / 100
+// formed first, which rounds differently: that is another expression, not a copy of this one.)
+__device__ __forceinline__ double safe_value(double y, double alpha, double vn2) { return y * (100.0 - alpha) / 100.0 - sqrt(vn2); }
+
+// max over the components of max(x_min - x, x - x_max), x = (q, v); joint i's position before its velocity, a NaN is kept
+template <int NQ>
+__device__ __forceinline__ double box_margin(const double* q, const double* v, const double* __restrict__ x_min,
+                                             const double* __restrict__ x_max) {
+    double w = NEG_INF;
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        w = nanmax(w, nanmax(x_min[i] - q[i], q[i] - x_max[i]));
+        w = nanmax(w, nanmax(x_min[NQ + i] - v[i], v[i] - x_max[NQ + i]));
+    }
+    return w;
 }
 
 }  // namespace smpc

@@ -71,9 +71,8 @@ __global__ void k_provide_control(int B, int N, int nq, const int32_t* __restric
 }
 
 // checkStateConstraints of one node (env_model.py:170-173, 236-243), in two parts: the state within the model bounds widened by
-// tol_x, and (node_rows_ok, starting from that verdict) the collision rows within their check bounds.  The same test as
-// k_check_nodes below, for kernels that test a device-counted subset of nodes (k_par_check_state).  (k_check_nodes keeps its own
-// copy: written through these two functions its gfx950 code changed, and the existing kernels' code is kept as it is.)
+// tol_x, and (node_rows_ok, starting from that verdict) the collision rows within their check bounds.  k_check_nodes below tests
+// every node of a trajectory with them, k_par_check_state a device-counted subset of nodes.
 template <int NQ>
 __device__ __forceinline__ bool node_box_ok(const double* __restrict__ xk, const double* __restrict__ x_min, const double* __restrict__ x_max,
                                             double tol_x) {
@@ -83,9 +82,11 @@ __device__ __forceinline__ bool node_box_ok(const double* __restrict__ xk, const
     for (int i = 0; i < NX; i++) ok = ok && (xk[i] >= x_min[i] - tol_x) && (xk[i] <= x_max[i] + tol_x);
     return ok;
 }
-template <int NQ>
+// geom_b: the instance's [n_rows][SMPC_SCENE_ROW] block of a scene (SCENE = true), not read otherwise
+template <int NQ, bool SCENE>
 __device__ __forceinline__ bool node_rows_ok(const smpc_problem_desc* __restrict__ D, const double* __restrict__ xk, bool ok,
-                                             const double* __restrict__ row_lb, const double* __restrict__ row_ub) {
+                                             const double* __restrict__ row_lb, const double* __restrict__ row_ub,
+                                             const double* __restrict__ geom_b) {
     double q[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; i++) q[i] = xk[i];
@@ -94,35 +95,7 @@ __device__ __forceinline__ bool node_rows_ok(const smpc_problem_desc* __restrict
     fk_world<NQ>(D->joints, q, Rw, pw, zw);
     for (int r = 0; r < D->n_rows; r++) {
         const smpc_row& row = D->rows[r];
-        double v;
-        switch (row.kind) {
-        case SMPC_ROW_SEG_FIXEDSEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(row.C),
-                                  dv_const<NQ>(row.D)).v;
-            break;
-        case SMPC_ROW_SEG_SEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pc], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pd], Rw, pw, zw)).v;
-            break;
-        case SMPC_ROW_SEG_POINT:
-            v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                       point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
-                                       dv_const<NQ>(row.C)).v;
-            break;
-        case SMPC_ROW_POINT_POINT: {
-            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(row.C);
-            v = dot(w, w).v;
-            break;
-        }
-        default: {
-            DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
-            v = (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - row.offset;
-            break;
-        }
-        }
+        const double v = row_value<0, SCENE>(row, row_geom<SCENE>(row, geom_b, r), [&](int i) { return point_world(D->points[i], Rw, pw); }).v;
         ok = ok && (row_lb[r] <= v) && (v <= row_ub[r]);
     }
     return ok;
@@ -138,58 +111,16 @@ __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, in
                               int32_t* __restrict__ state_ok, int coll_nodes, const double* __restrict__ geom = nullptr) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)B * n_nodes) return;
-    constexpr int NX = 2 * NQ;
-    const double* xk = x + t * NX;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NX; i++) ok = ok && (xk[i] >= x_min[i] - tol_x) && (xk[i] <= x_max[i] + tol_x);
+    const double* xk = x + t * 2 * NQ;
+    bool ok = node_box_ok<NQ>(xk, x_min, x_max, tol_x);
     // (the reference's checkCollision returns after the first row of a trajectory, env_model.py:238-243: callers that keep
     //  that quirk collision-test the leading coll_nodes nodes only)
     if ((int)(t % n_nodes) >= coll_nodes) {
         if (!ok) atomicAnd(&state_ok[t / n_nodes], 0);
         return;
     }
-    double q[NQ];
-#pragma unroll
-    for (int i = 0; i < NQ; i++) q[i] = xk[i];
-    Mat3<double> Rw[NQ];
-    Vec3<double> pw[NQ], zw[NQ];
-    fk_world<NQ>(D->joints, q, Rw, pw, zw);
     const double* const geom_b = SCENE ? geom + (size_t)(t / n_nodes) * D->n_rows * SMPC_SCENE_ROW : nullptr;
-    for (int r = 0; r < D->n_rows; r++) {
-        const smpc_row& row = D->rows[r];
-        const RowGeom<SCENE> G = row_geom<SCENE>(row, geom_b, r);
-        double v;
-        switch (row.kind) {
-        case SMPC_ROW_SEG_FIXEDSEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(G.C),
-                                  dv_const<NQ>(G.D)).v;
-            break;
-        case SMPC_ROW_SEG_SEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pc], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pd], Rw, pw, zw)).v;
-            break;
-        case SMPC_ROW_SEG_POINT:
-            v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                       point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
-                                       dv_const<NQ>(G.C)).v;
-            break;
-        case SMPC_ROW_POINT_POINT: {
-            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(G.C);
-            v = dot(w, w).v;
-            break;
-        }
-        default: {
-            DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
-            v = (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - *G.offset;
-            break;
-        }
-        }
-        ok = ok && (row_lb[r] <= v) && (v <= row_ub[r]);
-    }
+    ok = node_rows_ok<NQ, SCENE>(D, xk, ok, row_lb, row_ub, geom_b);
     if (!ok) atomicAnd(&state_ok[t / n_nodes], 0);
 }
 
@@ -203,14 +134,8 @@ __global__ void k_check_nn(const smpc_problem_desc* __restrict__ D, int M, const
     if (m_live && m >= *m_live) return;
     const long node = idx ? idx[m] : m;        // (compacted list of nodes, kernels_mlp.hpp mode 3; verdicts land at the nodes)
     const double* xk = x + (size_t)node * 2 * NQ;
-    const int nd = D->nn_dof;
-    double vn2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NQ; i++) {
-        const double v = i < nd ? xk[NQ + i] + (i == 0 ? D->nn_eps : 0.0) : 0.0;
-        vn2 += v * v;
-    }
-    const double g = (double)y[m] * (100.0 - alpha) / 100.0 - sqrt(vn2);
+    const double vn2 = safe_speed2<NQ>(D, xk + NQ);
+    const double g = safe_value((double)y[m], alpha, vn2);
     nn_ok[node] = (g >= -tol_safe) && (g <= 1e6 + tol_safe);
 }
 

@@ -4,20 +4,10 @@
 // safe_set.py:61-68 of the reference).
 #pragma once
 #include "device_model.hpp"
-#include "kernels_sqp.hpp"      // sqp_point / sqp_row_value / sqp_wave_sum: helpers only, k_merit's code is not touched
 
 namespace smpc {
 
 constexpr int GUESS_N_WORST = 5;
-constexpr double GUESS_NEG_INF = -__builtin_huge_val();
-
-// max that keeps a NaN once it has seen one (fmax drops it, and a NaN has to fail its predicate)
-__device__ __forceinline__ double guess_nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ double guess_wave_nanmax(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = guess_nanmax(v, __shfl_xor(v, o));
-    return v;
-}
 
 // The safe-set node of the instances whose mask byte is set: idx[m] = node (what the network pass reads, mode 3 of run_mlp),
 // pos[b] = m (where k_check_guess finds the instance's output).  The order of the list is whatever the atomics give; a row's
@@ -60,7 +50,7 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
                                                     const int32_t* __restrict__ pos, int32_t* __restrict__ flags,
                                                     double* __restrict__ worst, const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
-    __shared__ double s_pts[SQP_PT_DOUBLES];
+    __shared__ double s_pts[PT_COL_DOUBLES];
     __shared__ double s_sim[(SMPC_MAX_N + 1) * NX];
     const int b = blockIdx.x, k = threadIdx.x;
     if (b >= B) return;
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
         }
     }
     __syncthreads();
-    double w_box = GUESS_NEG_INF, w_row = GUESS_NEG_INF, w_tau = GUESS_NEG_INF, d2 = 0.0;
+    double w_box = NEG_INF, w_row = NEG_INF, w_tau = NEG_INF, d2 = 0.0;
     if (k <= N) {
         const double* xk = xb + k * NX;
         double q[NQ], v[NQ];
@@ -89,41 +79,20 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
         for (int i = 0; i < NQ; i++) {
             q[i] = xk[i];
             v[i] = xk[NQ + i];
-            w_box = guess_nanmax(w_box, guess_nanmax(x_min[i] - q[i], q[i] - x_max[i]));
-            w_box = guess_nanmax(w_box, guess_nanmax(x_min[NQ + i] - v[i], v[i] - x_max[NQ + i]));
             const double eq = q[i] - s_sim[k * NX + i], ev = v[i] - s_sim[k * NX + NQ + i];
             d2 += eq * eq + ev * ev;
         }
+        w_box = box_margin<NQ>(q, v, x_min, x_max);
         const int nrows = D->n_rows;
         if (nrows > 0 && (k == 0 || !coll_first)) {
             // forward kinematics: the points' world positions into this lane's LDS column
             double* const spt = s_pts + k;
-            const int np = D->n_points;
-            for (int pt = 0; pt < np; pt++)
-                if (D->points[pt].link < 0) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) spt[(3 * pt + c) * 64] = D->points[pt].local[c];
-                }
-            Mat3<double> R;
-#pragma unroll
-            for (int i = 0; i < 9; i++) R.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
-            Vec3<double> pc;
-#pragma unroll
-            for (int i = 0; i < NQ; i++) {
-                pc = pc + mulc(R, D->joints[i].p0);
-                advance_rotation(R, D->joints[i], q[i]);
-                for (int pt = 0; pt < np; pt++)
-                    if (D->points[pt].link == i) {
-                        const Vec3<double> w = pc + mulc(R, D->points[pt].local);
-                        spt[(3 * pt) * 64] = w.x;
-                        spt[(3 * pt + 1) * 64] = w.y;
-                        spt[(3 * pt + 2) * 64] = w.z;
-                    }
-            }
+            point_column_fixed(D, spt);
+            point_column_fk<NQ>(D, q, spt);
             const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
             for (int r = 0; r < nrows; r++) {
-                const double rv = sqp_row_value<SCENE>(D->rows[r], spt, row_geom<SCENE>(D->rows[r], geom_b, r));
-                w_row = guess_nanmax(w_row, guess_nanmax(row_lb[r] - rv, rv - row_ub[r]));
+                const double rv = row_value<0, SCENE>(D->rows[r], row_geom<SCENE>(D->rows[r], geom_b, r), [&](int i) { return column_point(spt, i); }).v;
+                w_row = nanmax(w_row, nanmax(row_lb[r] - rv, rv - row_ub[r]));
             }
         }
         if (k < N) {
@@ -133,16 +102,16 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
             for (int i = 0; i < NQ; i++) u[i] = uk[i];
             rnea_world<NQ, double>(D->joints, D->gravity, q, v, u, tau);
 #pragma unroll
-            for (int i = 0; i < NQ; i++) w_tau = guess_nanmax(w_tau, guess_nanmax(tau_min[i] - tau[i], tau[i] - tau_max[i]));
+            for (int i = 0; i < NQ; i++) w_tau = nanmax(w_tau, nanmax(tau_min[i] - tau[i], tau[i] - tau_max[i]));
         }
     }
-    w_box = guess_wave_nanmax(w_box);
-    w_row = guess_wave_nanmax(w_row);
-    w_tau = guess_wave_nanmax(w_tau);
-    d2 = sqp_wave_sum(d2);
+    w_box = wave_nanmax(w_box);
+    w_row = wave_nanmax(w_row);
+    w_tau = wave_nanmax(w_tau);
+    d2 = wave_sum(d2);
     if (k != 0) return;
     const double w_dyn = sqrt(d2);
-    double w_safe = GUESS_NEG_INF;
+    double w_safe = NEG_INF;
     int32_t f = 0;
     if (!(w_box <= tol_x)) f |= 1;
     if (!(w_row <= 0.0)) f |= 2;
@@ -151,14 +120,8 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
     if (safe_node >= 0) {
         // safe_set.py:61-68, the expression of k_check_nn
         const double* xs = xb + safe_node * NX;
-        const int nd = D->nn_dof;
-        double vn2 = 0.0;
-#pragma unroll
-        for (int i = 0; i < NQ; i++) {
-            const double vv = i < nd ? xs[NQ + i] + (i == 0 ? D->nn_eps : 0.0) : 0.0;
-            vn2 += vv * vv;
-        }
-        const double g = (double)y[pos[b]] * (100.0 - alpha) / 100.0 - sqrt(vn2);
+        const double vn2 = safe_speed2<NQ>(D, xs + NQ);
+        const double g = safe_value((double)y[pos[b]], alpha, vn2);
         w_safe = -g;
         if (!((g >= -tol_safe) && (g <= 1e6 + tol_safe))) f |= 16;
     }

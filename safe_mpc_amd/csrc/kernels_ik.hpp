@@ -4,16 +4,18 @@
 // for step, is safe_mpc_amd/ik.py::ik_batch_host.
 #pragma once
 #include "device_model.hpp"
-#include "kernels_guess.hpp"    // guess_nanmax / GUESS_NEG_INF: helpers only
 
 namespace smpc {
 
 constexpr int IK_MAX_STARTS = 64;
-constexpr double IK_POS_INF = __builtin_huge_val();
 
 // index of (i, j), i >= j, in a packed lower triangle
 __host__ __device__ constexpr int ik_tri(int i, int j) { return i * (i + 1) / 2 + j; }
 
+// k_ik keeps the code it had before row_value and point_world existed -- ik_point and ik_row below, a copy of the row switch: through
+// the shared statements the 7-DoF instantiation came out measurably slower (profiles/device_model_refactor.txt, section 4), and a
+// kernel that does not keep its time keeps its code.  A sixth row kind, or a change to a row's expression, has to be made here as
+// well as in row_value.
 // world position of a robot point, with its Jacobian columns when ND = NQ (point_with_jacobian) and without when ND = 0
 template <int NQ, int ND>
 __device__ __forceinline__ DV3<ND> ik_point(const smpc_point& P, const Mat3<double>* Rw, const Vec3<double>* pw, const Vec3<double>* zw) {
@@ -66,7 +68,7 @@ __device__ __forceinline__ void ik_eval(const smpc_problem_desc* __restrict__ D,
         const DV3<ND> ee = ik_point<NQ, ND>(D->points[D->ee_point], Rw, pw, zw);
         const double ex = ee.x.v - tgt[0], ey = ee.y.v - tgt[1], ez = ee.z.v - tgt[2];
         F = ex * ex + ey * ey + ez * ez;
-        ee_inf = guess_nanmax(guess_nanmax(fabs(ex), fabs(ey)), fabs(ez));
+        ee_inf = nanmax(nanmax(fabs(ex), fabs(ey)), fabs(ez));
         if constexpr (ND > 0) {
 #pragma unroll
             for (int i = 0; i < NQ; i++) {
@@ -76,7 +78,7 @@ __device__ __forceinline__ void ik_eval(const smpc_problem_desc* __restrict__ D,
             }
         }
     }
-    margin = GUESS_NEG_INF;
+    margin = NEG_INF;
     const int nrows = D->n_rows;
     for (int r = 0; r < nrows; r++) {
         const smpc_row& row = D->rows[r];
@@ -86,7 +88,7 @@ __device__ __forceinline__ void ik_eval(const smpc_problem_desc* __restrict__ D,
             const double bound = side == 0 ? row_lb[r] : row_ub[r];
             if (!(fabs(bound) < SMPC_INF)) continue;
             const double sign = side == 0 ? -1.0 : 1.0;     // lower bound: violated below it
-            margin = guess_nanmax(margin, sign * (v.v - bound));
+            margin = nanmax(margin, sign * (v.v - bound));
             const double bp = bound - sign * push * fabs(bound);
             const double w = 1.0 / fmax(sqrt(fabs(bound)), 1e-3);
             const double res = w * sign * (v.v - bp);
@@ -169,13 +171,13 @@ __global__ __launch_bounds__(64) void k_ik(const smpc_problem_desc* __restrict__
     const double* const tgt = target + (size_t)b * 3;
     const double* const geom_b = SCENE ? geom + (size_t)b * D->n_rows * SMPC_SCENE_ROW : nullptr;
     double q[NQ];
-    double F = IK_POS_INF, ee_inf = IK_POS_INF, margin = IK_POS_INF;
+    double F = POS_INF, ee_inf = POS_INF, margin = POS_INF;
     if (live) {
         const double* qs = q_start + ((size_t)b * S + s) * NQ;
 #pragma unroll
         for (int i = 0; i < NQ; i++) {
             const double v = qs[i];
-            q[i] = (fabs(v) < IK_POS_INF) ? fmin(fmax(v, q_lo[i]), q_hi[i]) : 0.5 * (q_lo[i] + q_hi[i]);   // (a NaN fails the test)
+            q[i] = (fabs(v) < POS_INF) ? fmin(fmax(v, q_lo[i]), q_hi[i]) : 0.5 * (q_lo[i] + q_hi[i]);   // (a NaN fails the test)
         }
         double g[NQ], A[NT];
         double lam = lam0;
@@ -188,10 +190,10 @@ __global__ __launch_bounds__(64) void k_ik(const smpc_problem_desc* __restrict__
 #pragma unroll
             for (int i = 0; i < NQ; i++) {
                 const double v = q[i] + dq[i];
-                finite = finite && (fabs(v) < IK_POS_INF);
+                finite = finite && (fabs(v) < POS_INF);
                 qn[i] = fmin(fmax(v, q_lo[i]), q_hi[i]);
             }
-            double Fn = IK_POS_INF, en, mn;
+            double Fn = POS_INF, en, mn;
             if (finite) ik_eval<NQ, 0, SCENE>(D, qn, tgt, push, row_lb, row_ub, geom_b, Fn, en, mn, nullptr, nullptr);
             const bool acc = finite && (Fn < F);
             if (acc) {
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(64) void k_ik(const smpc_problem_desc* __restrict__
     if (okm) {
         win = __ffsll((long long)okm) - 1;
     } else {
-        double bf = (live && F == F) ? F : IK_POS_INF;
+        double bf = (live && F == F) ? F : POS_INF;
         int bi = s;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {

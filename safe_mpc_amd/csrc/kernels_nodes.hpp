@@ -71,37 +71,8 @@ __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restric
     const double* const geom_b = SCENE ? geom + (size_t)(t / (N + 1)) * nrows * SMPC_SCENE_ROW : nullptr;
     for (int r = 0; r < nrows; r++) {
         const smpc_row& row = D->rows[r];
-        const RowGeom<SCENE> G = row_geom<SCENE>(row, geom_b, r);
-        DQ<NQ> v;
-        switch (row.kind) {
-        case SMPC_ROW_SEG_FIXEDSEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), dv_const<NQ>(G.C),
-                                  dv_const<NQ>(G.D));
-            break;
-        case SMPC_ROW_SEG_SEG:
-            v = segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pc], Rw, pw, zw),
-                                  point_with_jacobian<NQ>(D->points[row.pd], Rw, pw, zw));
-            break;
-        case SMPC_ROW_SEG_POINT:
-            v = ball_segment_dist2<NQ>(point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw),
-                                       point_with_jacobian<NQ>(D->points[row.pb], Rw, pw, zw), row.len2,
-                                       dv_const<NQ>(G.C));
-            break;
-        case SMPC_ROW_POINT_POINT: {
-            DV3<NQ> w = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw) - dv_const<NQ>(G.C);
-            v = dot(w, w);
-            break;
-        }
-        default: {
-            DV3<NQ> P = point_with_jacobian<NQ>(D->points[row.pa], Rw, pw, zw);
-            v = row.axis == 0 ? P.x : (row.axis == 1 ? P.y : P.z);
-            v.v -= *G.offset;
-            break;
-        }
-        }
+        const DQ<NQ> v = row_value<NQ, SCENE>(row, row_geom<SCENE>(row, geom_b, r),
+                                              [&](int i) { return point_with_jacobian<NQ>(D->points[i], Rw, pw, zw); });
         put(F_RV + r, v.v);
 #pragma unroll
         for (int i = 0; i < NQ; i++) put(F_RG + r * NQ + i, v.d[i]);

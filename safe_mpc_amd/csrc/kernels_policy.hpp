@@ -265,7 +265,7 @@ __global__ void k_par_check_state(const smpc_problem_desc* __restrict__ D, int S
     const int k = (int)(t - s * (N + 1));
     const double* xk = x + t * 2 * NQ;
     bool ok = node_box_ok<NQ>(xk, x_min, x_max, tol_x);
-    if (ok && k < coll_nodes) ok = node_rows_ok<NQ>(D, xk, ok, row_lb, row_ub);
+    if (ok && k < coll_nodes) ok = node_rows_ok<NQ, false>(D, xk, ok, row_lb, row_ub, nullptr);
     if (!ok) atomicAnd(&state_ok[s], 0);
 }
 

@@ -4,8 +4,7 @@
 // forward-only.  The statement they follow is closed_loop.py::score_rollout_statement.
 #pragma once
 #include "device_model.hpp"
-#include "kernels_sqp.hpp"      // sqp_point / sqp_row_value: helpers only
-#include "kernels_guess.hpp"    // guess_nanmax
+#include "kernels_sqp.hpp"      // sqp_row_value: k_score_seg keeps the code it had (see there)
 
 namespace smpc {
 
@@ -17,8 +16,6 @@ constexpr int SCORE_NI = 4;         // int32 per instance: where the margins wer
 constexpr int SCORE_SEG = 32;
 constexpr int SCORE_PD = 5;         // partial doubles per (segment, instance): s1, s2, |ee - ref|^2 at step last_x, coll margin, box margin
 constexpr int SCORE_PI = 3;         // partial int32: step and row of the coll margin, step of the box margin
-constexpr double SCORE_NEG_INF = -__builtin_huge_val();
-constexpr double SCORE_POS_INF = __builtin_huge_val();
 
 // "b replaces a" of a running maximum / minimum that keeps the FIRST NaN it sees and, among equal values, the first one
 __device__ __forceinline__ bool score_takes_max(double a, double b) { return b > a || (b != b && a == a); }
@@ -52,7 +49,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
                                                   long traj_stride, const uint8_t* __restrict__ mask, double* __restrict__ pd,
                                                   int32_t* __restrict__ pi, const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
-    __shared__ double s_pts[SQP_PT_DOUBLES];
+    __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x * 64 + threadIdx.x, seg = blockIdx.y;
     if (b >= B) return;
     if (mask && !mask[b]) return;
@@ -70,7 +67,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
 #pragma unroll
             for (int c = 0; c < 3; c++) spt[(3 * pt + c) * 64] = D->points[pt].local[c];
         }
-    double s1 = 0.0, s2 = 0.0, e_last = 0.0, m_row = SCORE_NEG_INF, m_box = SCORE_NEG_INF;
+    double s1 = 0.0, s2 = 0.0, e_last = 0.0, m_row = NEG_INF, m_box = NEG_INF;
     int st_row = -1, r_row = -1, st_box = -1;
     for (int j = j0; j <= j1; j++) {
         const double* xj = x_log + ((long)j * B + b) * NX;
@@ -81,11 +78,11 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
             v[i] = xj[NQ + i];
         }
         // state box: max over the components of max(x_min - x, x - x_max)
-        double w = SCORE_NEG_INF;
+        double w = NEG_INF;
 #pragma unroll
         for (int i = 0; i < NQ; i++) {
-            w = guess_nanmax(w, guess_nanmax(x_min[i] - q[i], q[i] - x_max[i]));
-            w = guess_nanmax(w, guess_nanmax(x_min[NQ + i] - v[i], v[i] - x_max[NQ + i]));
+            w = nanmax(w, nanmax(x_min[i] - q[i], q[i] - x_max[i]));
+            w = nanmax(w, nanmax(x_min[NQ + i] - v[i], v[i] - x_max[NQ + i]));
         }
         if (score_takes_max(m_box, w)) {
             m_box = w;
@@ -125,7 +122,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
         // collision rows: max over the rows of max(lb - v, v - ub), rows ascending
         for (int r = 0; r < nrows; r++) {
             const double rv = sqp_row_value<SCENE>(D->rows[r], spt, row_geom<SCENE>(D->rows[r], geom_b, r));
-            const double m = guess_nanmax(row_lb[r] - rv, rv - row_ub[r]);
+            const double m = nanmax(row_lb[r] - rv, rv - row_ub[r]);
             if (score_takes_max(m_row, m)) {
                 m_row = m;
                 st_row = j;
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(64) void k_score_safe(const smpc_problem_desc* __re
     if (mask && !mask[b]) return;
     int lx, lu;
     score_last_rows(b, n_steps, last_x, last_u, lx, lu);
-    double best = first ? SCORE_POS_INF : gmin[b];
+    double best = first ? POS_INF : gmin[b];
     int at = first ? -1 : gstep[b];
     const int nd = D->nn_dof;
     const double eps = D->nn_eps;
@@ -176,6 +173,8 @@ __global__ __launch_bounds__(64) void k_score_safe(const smpc_problem_desc* __re
     for (; j <= lx && j * B + b < m0 + rows; j++) {
         const long m = j * B + b;
         const double* xj = x_log + m * NX;
+        // (safe_speed2 / safe_value of device_model.hpp written out, with nd and eps read before the loop: called from inside
+        //  this loop they changed the kernel's gfx950 code, and the kernel is kept as it was)
         double vn2 = 0.0;
 #pragma unroll
         for (int i = 0; i < NQ; i++) {
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(64) void k_score_combine(int B, int n_steps, double
     int lx, lu;
     score_last_rows(b, n_steps, last_x, last_u, lx, lu);
     const int s_last = lx / SCORE_SEG;
-    double s1 = 0.0, s2 = 0.0, e_last = 0.0, m_row = SCORE_NEG_INF, m_box = SCORE_NEG_INF;
+    double s1 = 0.0, s2 = 0.0, e_last = 0.0, m_row = NEG_INF, m_box = NEG_INF;
     int st_row = -1, r_row = -1, st_box = -1;
     for (int s = 0; s <= s_last; s++) {
         const long at = (long)s * SCORE_PD * B + b, ai = (long)s * SCORE_PI * B + b;
@@ -230,7 +229,7 @@ __global__ __launch_bounds__(64) void k_score_combine(int B, int n_steps, double
     o[3] = sqrt(e_last);
     o[4] = m_row;
     o[5] = m_box;
-    o[6] = gmin ? gmin[b] : SCORE_POS_INF;
+    o[6] = gmin ? gmin[b] : POS_INF;
     int32_t* oi = outi + (long)b * SCORE_NI;
     oi[0] = st_row;
     oi[1] = r_row;

@@ -20,47 +20,31 @@ __device__ __forceinline__ bool sqp_armijo_ok(double merit, double m0, double D,
     return merit <= m0 + armijo * a * fmin(D, 0.0) + 1e-12 * (1.0 + fabs(m0));
 }
 
-// sum over the wavefront in a fixed order (xor butterfly: every lane ends with the same bits, run after run)
-__device__ __forceinline__ double sqp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double sqp_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
+// (kernels_rays.hpp reduces with this name; the reduction itself is device_model.hpp's.  An alias to retire when that header is
+//  next edited.)
+__device__ __forceinline__ double sqp_wave_max(double v) { return wave_max(v); }
 
-// World positions of the robot's points, one column per lane in LDS: the rows name their points by index, and a lane's registers
-// cannot be indexed by a run-time value without spilling to scratch.  Element c of point pt of lane l sits at
-// [(3 pt + c) * 64 + l]: a wavefront's accesses fall in 64 consecutive doubles.
-constexpr int SQP_PT_DOUBLES = SMPC_MAX_POINTS * 3 * 64;
-__device__ __forceinline__ DV3<0> sqp_point(const double* __restrict__ spt, int pt) {
-    DV3<0> P;
-    P.x.v = spt[(3 * pt) * 64];
-    P.y.v = spt[(3 * pt + 1) * 64];
-    P.z.v = spt[(3 * pt + 2) * 64];
-    return P;
-}
-
+// k_merit and k_score_seg (kernels_score.hpp) keep the code they had before row_value and point_column_fk existed -- this copy of the
+// row switch over the LDS column, and their own joint walks: through the shared statements both came out measurably slower
+// (profiles/device_model_refactor.txt, section 4), and a kernel that does not keep its time keeps its code.  A sixth row kind, or a
+// change to a row's expression, has to be made here as well as in row_value.
 // value of one collision row from the points' world positions (env_model.py:263-316; the values k_check_nodes tests); the
 // fixed obstacle from the descriptor (G = row_geom<false>) or from the instance's scene (row_geom<true>)
 template <bool SCENE>
 __device__ __forceinline__ double sqp_row_value(const smpc_row& row, const double* __restrict__ spt, const RowGeom<SCENE>& G) {
     switch (row.kind) {
     case SMPC_ROW_SEG_FIXEDSEG:
-        return segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), dv_const<0>(G.C), dv_const<0>(G.D)).v;
+        return segment_dist2<0>(column_point(spt, row.pa), column_point(spt, row.pb), dv_const<0>(G.C), dv_const<0>(G.D)).v;
     case SMPC_ROW_SEG_SEG:
-        return segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), sqp_point(spt, row.pc), sqp_point(spt, row.pd)).v;
+        return segment_dist2<0>(column_point(spt, row.pa), column_point(spt, row.pb), column_point(spt, row.pc), column_point(spt, row.pd)).v;
     case SMPC_ROW_SEG_POINT:
-        return ball_segment_dist2<0>(sqp_point(spt, row.pa), sqp_point(spt, row.pb), row.len2, dv_const<0>(G.C)).v;
+        return ball_segment_dist2<0>(column_point(spt, row.pa), column_point(spt, row.pb), row.len2, dv_const<0>(G.C)).v;
     case SMPC_ROW_POINT_POINT: {
-        DV3<0> w = sqp_point(spt, row.pa) - dv_const<0>(G.C);
+        DV3<0> w = column_point(spt, row.pa) - dv_const<0>(G.C);
         return dot(w, w).v;
     }
     default: {
-        DV3<0> P = sqp_point(spt, row.pa);
+        DV3<0> P = column_point(spt, row.pa);
         return (row.axis == 0 ? P.x.v : (row.axis == 1 ? P.y.v : P.z.v)) - *G.offset;
     }
     }
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
                                               const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out,
                                               const double* __restrict__ geom = nullptr) {
     constexpr int NX = 2 * NQ;
-    __shared__ double s_pts[SQP_PT_DOUBLES];
+    __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x, k = threadIdx.x;
     if (b >= B) return;
     if (mask && !mask[b]) return;
@@ -238,9 +222,9 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
             for (int i = 0; i < NQ; i++) viol += fmax(fabs(tau[i]) - D->joints[i].tau_max, 0.0);
         }
     }
-    f = sqp_wave_sum(f);
-    viol = sqp_wave_sum(viol);
-    gd = sqp_wave_sum(gd);
+    f = wave_sum(f);
+    viol = wave_sum(viol);
+    gd = wave_sum(gd);
     if (k == 0) {
         out[(long)b * 3] = f;
         out[(long)b * 3 + 1] = viol;
@@ -278,7 +262,7 @@ __global__ __launch_bounds__(64) void k_sqp_direction(int B, int nX, int nU, con
         bad = bad || d != d;
         m = fmax(m, fabs(d));
     }
-    m = sqp_wave_max(m);
+    m = wave_max(m);
     // (numpy's max propagates a NaN, fmax drops it: a step with a NaN in it has no length)
     if (__any(bad)) m = __builtin_nan("");
     if (lane == 0) step[b] = m;
