@@ -1,10 +1,11 @@
-"""Array backend of the policy layer: the same controller / closed-loop code runs on numpy arrays (host path of the engine,
-CPU tests with the oracle double) or on ROCm torch tensors (device path: every per-instance state array of the policy
-automata lives in HBM and no step of the loop copies it to the host).  Only the handful of operations the policies use.
+"""Array backend of what the policy layer does AROUND its steps: allocation and set-up of a controller's or a loop's state
+(initialize, setGuess, setTrajectory), the feasibility predicates (checkGuess and its parts), the abort-event bookkeeping and
+the result assembly.  That code is written once and runs on numpy arrays (host state: host path of the engine, CPU tests with
+the oracle double) or on ROCm torch tensors (``device_state=True``: every per-instance state array lives in HBM).
 
-On the device the per-step automata themselves run as engine kernels (smpc_policy_step / smpc_loop_*, kernels_policy.hpp);
-what goes through TorchOps there is the set-up (initialize, setGuess, checkGuess), the abort-event bookkeeping and the
-result assembly -- and any step() of a controller driven by a solver object that does not offer those kernels.
+The steps themselves do not go through it.  On host state they are plain numpy (controller.py ``_step_host``,
+closed_loop._HostGroup); on device state they are engine kernels (smpc_policy_step / smpc_loop_*, kernels_policy.hpp), and a
+solver without those kernels is refused for device state.  Only the handful of operations that code uses.
 """
 from __future__ import annotations
 
@@ -64,18 +65,6 @@ class NumpyOps:
         """all() over every axis but the first"""
         return np.all(m.reshape(m.shape[0], -1), axis=1)
 
-    def any(self, m):
-        return bool(np.any(m))
-
-    def last_true(self, m):
-        """index of the last True along axis 1, -1 if none"""
-        n = m.shape[1]
-        return np.where(m.any(1), n - 1 - np.argmax(m[:, ::-1], axis=1), -1)
-
-    def take_rows(self, a, idx):
-        """a[b, idx[b]] for every b"""
-        return a[np.arange(a.shape[0]), idx]
-
     def norm_tail(self, a):
         return np.linalg.norm(a.reshape(a.shape[0], -1), axis=1)
 
@@ -88,19 +77,6 @@ class NumpyOps:
 
     def host(self, a):
         return np.asarray(a)
-
-    # step-indexed logs: `j` is a python int here, a one-element device tensor on the torch backend
-    def step_index(self, j0=0):
-        return [j0]
-
-    def put_row(self, log, j, value, offset=0):
-        log[j[0] + offset] = value
-
-    def step_vec(self, j, n, offset=0):
-        return np.full(n, j[0] + offset, np.int64)
-
-    def step_advance(self, j):
-        j[0] += 1
 
 
 class TorchOps:
@@ -143,17 +119,6 @@ class TorchOps:
     def all_tail(self, m):
         return m.reshape(m.shape[0], -1).all(dim=1)
 
-    def any(self, m):
-        return bool(m.any().item())          # the ONE host synchronisation a caller may ask for
-
-    def last_true(self, m):
-        n = m.shape[1]
-        idx = self.t.arange(n, device=m.device)[None, :]
-        return self.t.where(m, idx, self.t.full_like(idx, -1)).max(dim=1).values
-
-    def take_rows(self, a, idx):
-        return a[self.t.arange(a.shape[0], device=a.device), idx]
-
     def norm_tail(self, a):
         return self.t.linalg.vector_norm(a.reshape(a.shape[0], -1), dim=1)
 
@@ -167,13 +132,5 @@ class TorchOps:
         return a.detach().cpu().numpy()
 
     def step_index(self, j0=0):
+        """the step counter of the device loop: one int64 in HBM, read and advanced by smpc_loop_* (a captured step replays it)"""
         return self.t.full((1,), j0, dtype=self.i64, device=self.device)
-
-    def put_row(self, log, j, value, offset=0):
-        log.index_copy_(0, j + offset if offset else j, value[None])
-
-    def step_vec(self, j, n, offset=0):
-        return (j + offset).expand(n)
-
-    def step_advance(self, j):
-        j.add_(1)

@@ -17,7 +17,6 @@ import pickle
 
 import numpy as np
 
-from ._xp import InPlaceState
 from .controller import SafeBackupController, get_controller
 from .problem import JOINT_DTYPE
 from .urdf import Inertial, Origin, RobotDescription, SerialChain
@@ -921,26 +920,26 @@ def _score_dict(out, outi):
 
 
 def _masked_step(ctrl, x, active):
-    """controller.step on all rows, then roll back the rows that must not have stepped."""
-    xp = ctrl.xp
-    snap = {k: xp.copy(getattr(ctrl, k)) for k in _STATE if hasattr(ctrl, k)}
+    """controller.step on all rows, then roll back the rows that must not have stepped (host state: numpy)."""
+    snap = {k: np.copy(getattr(ctrl, k)) for k in _STATE if hasattr(ctrl, k)}
     u, abort = ctrl.step(x)
     for k, v in snap.items():
         cur = getattr(ctrl, k)
         m = active.reshape((-1,) + (1,) * (cur.ndim - 1))
-        setattr(ctrl, k, xp.where(m, cur, v))
+        setattr(ctrl, k, np.where(m, cur, v))
     return u, abort & active
 
 
-class _Group(InPlaceState):
+class _Group:
     """The closed loop of ONE group of instances (global indices first .. first + B): the driver's safe-abort automaton around
-    the controller's ``step``.  A step has two enqueue-only halves, :meth:`part_a` (PD abort tracking, controller step) and
-    :meth:`part_b` (plant, outcome tests, logs), with the step's single host decision between them (``did any instance
-    raise abort?``).  On the device every state array keeps its address (InPlaceState), so after a few eager steps each half
-    is captured once as a hipGraph and replayed: one graph launch instead of ~50 kernel launches per half."""
+    the controller's ``step``.  A step has two halves, ``part_a`` (PD abort tracking, controller step) and ``part_b`` (plant,
+    outcome tests, logs), with the step's single host decision between them (``did any instance raise abort?``,
+    ``handle_aborts``).  This base holds what the two loops share -- arguments, noise tables, logs and flags (numpy arrays or
+    device tensors, by the controller's backend), the generator around the loop and the results; :class:`_HostGroup` is the
+    numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
-    def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, use_graphs,
-                 collect_times=False, scenes=None):
+    def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
+                 scenes=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -952,27 +951,20 @@ class _Group(InPlaceState):
             self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
             _set_scene(ctrl.ocp_solver, self._scenes)
         # stats.append(controller.getTime()) of scripts/mpc.py:239: one row of the seven time_fields per step of this group's
-        # controller.  Device path: the engine keeps HIP events of its last 64 solves (smpc_get_timing_history); they are read
-        # at least 32 solves late -- finished by then, so nothing waits inside the loop.
+        # controller (host: read when step() returns; device: _DeviceGroup._read_times)
         self._collect_times = bool(collect_times) and hasattr(ctrl.ocp_solver, 'timing_history')
-        self._time_rows, self._time_next, self._time_lost = [], 0, 0
+        self._time_rows, self._time_lost = [], 0
         if self._collect_times:
             ctrl.ocp_solver.enable_timing(2)
         pr, nq, nx, nu = ctrl.problem, ctrl.nq, ctrl.nx, ctrl.nu
         self._Nb = backup.N
         seeds = np.arange(first, first + B)
-        joints_noisy = perturbed_joint_tables(params, nq, noise, seeds) if noise > 0 else None          # mpc.py:106-107
+        self._joints_noisy = perturbed_joint_tables(params, nq, noise, seeds) if noise > 0 else None          # mpc.py:106-107
         # model.reset_seed(i) is called at EVERY step (mpc.py:126): each instance sees the same torque-noise draw each step
-        tau_noise = None
+        self._tau_noise = None
         if control_noise > 0:
-            tau_noise = np.stack([np.random.default_rng(int(i)).normal(np.zeros(nu), pr.tau_max * control_noise / 100, nu)
-                                  for i in seeds])
-        if xp.on_device:
-            if joints_noisy is not None:          # [B, nq] smpc_joint records as a float64 tensor (33 doubles each)
-                joints_noisy = xp.asarray(np.ascontiguousarray(joints_noisy).view(np.float64).reshape(B, nq, -1), xp.f64)
-            if tau_noise is not None:
-                tau_noise = xp.asarray(tau_noise, xp.f64)
-        self._joints_noisy, self._tau_noise = joints_noisy, tau_noise
+            self._tau_noise = np.stack([np.random.default_rng(int(i)).normal(np.zeros(nu), pr.tau_max * control_noise / 100, nu)
+                                        for i in seeds])
         # step-major logs (one contiguous [B, .] slab per step); transposed to the reference's [B, step, .] at the end
         nan = float('nan')
         self.x_log = xp.full((n_steps + 1, B, nx), nan)
@@ -989,250 +981,26 @@ class _Group(InPlaceState):
         self.u_abort = xp.zeros((B, self._Nb, nu))
         self.collided = xp.full((B,), False, xp.bool_)
         self.viable = xp.zeros((B,), xp.u8)            # successful abort events so far (mpc.py:189 appends once per event)
-        self.resumed = xp.full((B,), False, xp.bool_)   # left the backup trajectory at this step (mpc.py:137-141)
         self._quirks = bool(getattr(params, 'reference_quirks', True))
         self.u = xp.zeros((B, nu))
-        self.new_abort = xp.full((B,), False, xp.bool_)
         # last valid row of the state / input logs of every instance (mpc.py:114 pre-fills with NaN, :240-264 and :186-190 break)
         self.last_x, self.last_u = xp.full((B,), n_steps, xp.i64), xp.full((B,), n_steps - 1, xp.i64)
-        self._jt = xp.step_index(0)           # the step counter (a device tensor on the torch backend: graphs replay it)
-        self._zeros_u = xp.zeros((B, nu))
         self._abort_events = []
-        self._ever_aborted = False
-        self._use_graphs = bool(use_graphs and xp.on_device)
-        self._graphs = {}                     # (half, ever_aborted) -> captured graph
-        # device path: both halves of a step are engine kernels (smpc_loop_pre / smpc_policy_step / smpc_loop_post); the numpy
-        # code below is the readable statement of the same automaton and what the host path runs
-        self._fused = bool(xp.on_device and hasattr(ctrl.ocp_solver, 'loop_pre'))
-        if self._fused:
-            self._u_other = xp.zeros((B, nu))
-            self._stepping = xp.full((B,), True, xp.bool_)
-            self.new_abort = ctrl._abort_out          # (the controller's own output buffer: no copy per step)
-            # abort events: the backup OCPs of a step's events are solved on the backup solver's own stream WHILE the next
-            # step's solve runs; until their outcome is applied (smpc_loop_apply_backup) the instances are only kept from stepping
-            self._pending = xp.full((B,), False, xp.bool_)
-            self._resumed = xp.full((B,), False, xp.bool_)      # written by smpc_loop_pre
-            self._any_event = xp.zeros((1,), xp.i32)            # written by smpc_loop_classify_aborts
-            self._inflight = None
-            import torch
-            bs = backup.ocp_solver
-            self._side = torch.cuda.ExternalStream(bs.L.smpc_stream(bs.h), device=torch.device('cuda', bs.device))
-        self._inplace = xp.on_device
 
-    # ---- first half: everything up to the controller's verdict ---------------------------------------------------------------
-    def part_a(self):
-        xp, ctrl, B, Nb = self._xp, self._ctrl, self._B, self._Nb
-        nq = ctrl.nq
-        if self._fused:
-            sv = ctrl.ocp_solver
-            sv.loop_pre(self, getattr(ctrl, 'r', None), self._pending, self._u_other, self._stepping)
-            ctrl.step_on_device(self.x_cur, self._stepping, self._u_other, u_out=self.u)
-            if ctrl.can_abort:
-                sv.loop_classify_aborts(self, self.new_abort, self._any_event)
-            return
-        kp, kd = 1.0, 1e2                                                               # mpc.py:97
-        x_cur = self.x_cur
-        if self._ever_aborted:
-            # --- instances following their safe-abort trajectory (mpc.py:130-146)
-            in_abort = self.sa & self.alive
-            follow = in_abort & (self.ja < Nb)
-            idx = xp.clip_max(self.ja, Nb - 1)
-            xa = xp.take_rows(self.x_abort, idx)
-            ua = xp.take_rows(self.u_abort, idx)
-            u_f = ua - (kp * (x_cur[:, :nq] - xa[:, :nq]) + kd * (x_cur[:, nq:] - xa[:, nq:]))
-            u = xp.where(follow[:, None], u_f, self._zeros_u)
-            hold = in_abort & (self.ja >= Nb)
-            resume = hold & xp.all_tail(x_cur[:, nq:] < 5e-3)                         # mpc.py:138
-            still = hold & ~resume
-            xe = self.x_abort[:, -1]
-            u_h = -(kp * (x_cur[:, :nq] - xe[:, :nq]) + 3e2 * (x_cur[:, nq:] - xe[:, nq:]))
-            u = xp.where(still[:, None], u_h, u)
-            self.sa = self.sa & ~resume
-            self.ja = self.ja + xp.cast(in_abort, xp.i64)
-            self.resumed = resume
-        else:
-            u = self._zeros_u
-        # --- instances under MPC (mpc.py:151)
-        stepping = self.alive & ~self.sa
-        if hasattr(ctrl, 'r'):
-            xp.put_row(self.r_log, self._jt, xp.where(stepping, ctrl.r, xp.full((B,), -1, xp.i64)))
-        # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
-        #  read again, so they may step along)
-        if self._ever_aborted:
-            u_m, ab = _masked_step(ctrl, x_cur, stepping)
-        else:
-            u_m, ab = ctrl.step(x_cur)
-        self.u = xp.where(stepping[:, None], u_m, u)
-        self.new_abort = ab & stepping
-        if self._ever_aborted and self._quirks:
-            # An abort raised on the very step an instance resumed MPC sits inside the reference's `if sa_flag:` branch
-            # (mpc.py:137-141): no viable state is recorded and no backup OCP solved -- the instance is in safe abort again
-            # with its OLD backup trajectory, its abort clock keeps running, and it re-tests its velocity at the next step.
-            again = self.new_abort & self.resumed
-            self.sa = self.sa | again
-            self.new_abort = self.new_abort & ~again
-
-    # ---- the step's host decision: abort events (mpc.py:161-190) -----------------------------------------------------------------
-    def handle_aborts(self, j=None):
-        xp, ctrl, backup, B, Nb = self._xp, self._ctrl, self._backup, self._B, self._Nb
-        if not ctrl.can_abort:
-            return
-        if self._fused:
-            return self._handle_aborts_fused(j)
-        if not xp.any(self.new_abort):                                               # (the step's one host synchronisation)
-            return
-        self._ever_aborted = True
-        # the backup OCP is solved for the aborting instances only (a compact batch), from their viable states
-        rows = np.where(xp.host(self.new_abort))[0]
-        j = int(xp.host(self._jt)[0]) if xp.on_device else self._jt[0]
-        xv = ctrl.getLastViableState()
-        rows_b = xp.asarray(rows, xp.i64)
-        xv_c = xv[rows_b]
-        n_c = len(rows)
-        xg_c = xp.repeat_nodes(xv_c, Nb + 1)
-        self._backup_scene(rows_b)
-        xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c if xp.on_device else np.ascontiguousarray(xv_c), xg_c,
-                                                      xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
-        self._abort_events.append((rows + self._first, np.full(n_c, j), xp.host(xv_c)))
-        ok_c = st_c == 0 if xp.on_device else np.asarray(st_c) == 0
-        failed = xp.full((B,), False, xp.bool_)
-        okb = xp.full((B,), False, xp.bool_)
-        failed[rows_b] = ~ok_c
-        okb[rows_b] = ok_c
-        xa_new, ua_new = xp.copy(self.x_abort), xp.copy(self.u_abort)
-        xa_new[rows_b] = xo_c if xp.on_device else np.asarray(xo_c)
-        ua_new[rows_b] = uo_c if xp.on_device else np.asarray(uo_c)
-        self.collided = self.collided | failed
-        self.alive = self.alive & ~failed
-        jj = xp.step_vec(self._jt, B)
-        self.last_x, self.last_u = xp.where(failed, jj, self.last_x), xp.where(failed, jj, self.last_u)   # mpc.py:186-190
-        self.x_abort = xp.where(okb[:, None, None], xa_new, self.x_abort)
-        self.u_abort = xp.where(okb[:, None, None], ua_new, self.u_abort)
-        self.ja = self.ja * xp.cast(~okb, xp.i64)
-        self.sa = self.sa | okb
-        self.viable = xp.cast(xp.clip_max(xp.cast(self.viable, xp.i64) + xp.cast(okb, xp.i64), 255), xp.u8)   # saturating, like k_loop_apply_backup
-
-    def _backup_scene(self, rows_b):
+    def _backup_scene(self, rows):
         """the backup OCP of an abort event is solved in the scenes of the aborting instances: their geometry rows, gathered in the
         order of the compact batch, onto the backup handle"""
         if self._scenes is not None:
-            _set_scene(self._backup.ocp_solver, self._scenes[rows_b])
+            _set_scene(self._backup.ocp_solver, self._scenes[rows])
 
-    def _apply_inflight(self):
-        if self._inflight is None:
-            return
-        import torch
-        rows_b, xv_c, xo_c, uo_c, st_c, ev = self._inflight
-        torch.cuda.current_stream().wait_event(ev)
-        self._ctrl.ocp_solver.loop_apply_backup(self, rows_b, st_c, xo_c, uo_c, self.viable, self.u, self._pending)
-        self._inflight = None
-
-    def _handle_aborts_fused(self, j):
-        """Device path of :meth:`handle_aborts`.  Same events, same outcomes; what differs is WHEN the backup OCP's result is
-        consumed: the solve is enqueued on the backup solver's stream and its outcome applied one step later, after the next
-        controller step has been enqueued -- in between the instance only must not step (``_pending``), which is all the
-        reference's loop needs of it (it either follows the backup trajectory from the next step on or is lost at this one)."""
-        import torch
-        xp, ctrl, backup, Nb = self._xp, self._ctrl, self._backup, self._Nb
-        self._apply_inflight()                               # the previous step's events (their first tracking control goes into u)
-        if not bool(self._any_event.item()):                 # (the step's one host synchronisation)
-            return
-        self._ever_aborted = True
-        rows = np.where(xp.host(self.new_abort))[0]
-        rows_b = xp.asarray(rows, xp.i64)
-        xv_c = ctrl.x_viable[rows_b]
-        n_c = len(rows)
-        self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))      # (xv_c goes to the host in results())
-        self._pending.copy_(self.new_abort)
-        main = torch.cuda.current_stream()
-        ev0 = torch.cuda.Event()
-        ev0.record(main)
-        with torch.cuda.stream(self._side):
-            self._side.wait_event(ev0)
-            xg_c = xp.repeat_nodes(xv_c, Nb + 1)
-            self._backup_scene(rows_b)
-            xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
-            ev = torch.cuda.Event()
-            ev.record(self._side)
-        # (These tensors cross streams.  Their lifetimes are ordered by the events, not by the caching allocator: they are released
-        #  in _apply_inflight, after the main stream has been told to wait for `ev`, and the side stream's next work waits for an
-        #  event recorded on the main stream after that.  torch's record_stream is not usable here -- on this ROCm build it
-        #  faults on an ExternalStream.)
-        self._inflight = (rows_b, xv_c, xo_c, uo_c, st_c, ev)
-
-    # ---- second half: plant, outcome tests, logs ----------------------------------------------------------------------------------
-    def part_b(self):
-        xp, ctrl, B = self._xp, self._ctrl, self._B
-        solver = ctrl.ocp_solver
-        if self._fused:
-            solver.loop_post(self, self.u, self._joints_noisy, self._tau_noise)
-            return
-        # plant (mpc.py:240, env_model.py:192-206).  Logs are written unmasked; rows of an instance after its failure are
-        # blanked at the end from the step it died at (mpc.py:114 pre-fills them with NaN)
-        xp.put_row(self.u_log, self._jt, self.u)
-        x_next, _ = solver.plant_step(self.x_cur, self.u, self._joints_noisy, self._tau_noise)
-        # outcome tests on the new state (mpc.py:246-264): one node per instance, so the engine's box + collision test
-        # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints
-        okn = solver.check_trajectory(x_next[:, None, :] if not xp.on_device else x_next[:, None, :].contiguous())
-        okn = (okn != 0) if xp.on_device else np.asarray(okn)
-        xp.put_row(self.x_log, self._jt, x_next, offset=1)
-        bad = self.alive & ~okn
-        jj = xp.step_vec(self._jt, B)
-        self.last_x, self.last_u = xp.where(bad, jj + 1, self.last_x), xp.where(bad, jj, self.last_u)   # the failing state stays logged
-        self.collided = self.collided | bad
-        self.alive = self.alive & ~bad
-        self.x_cur = xp.where(self.alive[:, None], x_next, self.x_cur)
-        xp.step_advance(self._jt)
-
-    def _run_half(self, half, fn, j):
-        """eager for the first steps (workspaces get allocated), then captured once per code path and replayed"""
-        if getattr(self._ctrl, '_traj_rebound', False):      # setTrajectory bound a new device tensor: captured steps hold the old one
-            self._graphs.clear()
-            self._ctrl._traj_rebound = False
-        key = (half, self._ever_aborted)
-        g = self._graphs.get(key)
-        if g is None and self._use_graphs and j >= 3 and key not in self._graphs:
-            import torch
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=torch.cuda.current_stream(), capture_error_mode='relaxed'):
-                    fn()                  # (capturing records the launches without executing them)
-                self._graphs[key] = g
-            except Exception as e:        # report once, stay eager
-                print(f'[run_mpc] hipGraph capture of step half {half} failed ({type(e).__name__}: {e}); eager launches')
-                self._graphs[key], self._use_graphs, g = None, False, None
-        if g is not None:
-            g.replay()
-        else:
-            fn()
-
-    def _read_times(self, j, final=False):
-        """rows of the solves up to step j whose events have finished (device path: never the 32 most recent unless ``final``)"""
-        sv = self._ctrl.ocp_solver
-        if final:
-            sv.sync()                              # end of the run: everything has finished, drain the ring
-        while self._time_next <= j:
-            back = j - self._time_next
-            if back >= 64:                         # the ring has lapped it (the host ran more than 64 solves ahead of this read)
-                self._time_lost += 1
-                self._time_next += 1
-                continue
-            if not final and back < 32:
-                break
-            if not final and back >= 56:
-                sv.sync()                          # about to be lapped: wait rather than lose the row
-            tm = sv.timing_history(back)
-            if tm is None:
-                if final:
-                    self._time_lost += 1
-                    self._time_next += 1
-                    continue
-                break
-            self._time_rows.append(time_row(tm))
-            self._time_next += 1
+    def _progress(self, j):
+        xp = self._xp
+        if self._callback and j % 50 == 0:
+            print(f'step {j} (instances {self._first}..{self._first + self._B - 1}): alive {int(xp.host(self.alive).sum())}/{self._B}, '
+                  f'in abort {int(xp.host(self.sa & self.alive).sum())}, failures {int(xp.host(self.collided).sum())}')
 
     def run(self):
-        """generator: yields once per step, after the first half is enqueued (run_mpc serves the other groups meanwhile)"""
+        """generator: yields once per step, after the first half has run / is enqueued (run_mpc serves the other groups meanwhile)"""
         try:
             yield from self._run()
         finally:
@@ -1244,28 +1012,6 @@ class _Group(InPlaceState):
                     sv.enable_timing(0)
                 except Exception:
                     pass
-
-    def _run(self):
-        xp = self._xp
-        for j in range(self._n_steps):
-            self._run_half('a', self.part_a, j)
-            if self._collect_times:
-                if xp.on_device:
-                    self._read_times(j)
-                else:                              # host path: the solve has finished when step() returns
-                    self._time_rows.append(self._ctrl.getTime())
-            yield j
-            self.handle_aborts(j)
-            self._run_half('b', self.part_b, j)
-            if self._callback and j % 50 == 0:
-                print(f'step {j} (instances {self._first}..{self._first + self._B - 1}): alive {int(xp.host(self.alive).sum())}/{self._B}, '
-                      f'in abort {int(xp.host(self.sa & self.alive).sum())}, failures {int(xp.host(self.collided).sum())}')
-            if not xp.on_device and not self.alive.any():
-                break
-        if self._fused:
-            self._apply_inflight()            # (events of the last step)
-        if self._collect_times and xp.on_device:
-            self._read_times(self._n_steps - 1, final=True)
 
     def results(self, score=False):
         xp, ctrl, params, B, n_steps = self._xp, self._ctrl, self._params, self._B, self._n_steps
@@ -1306,7 +1052,273 @@ class _Group(InPlaceState):
         return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
                     time_rows=np.array(self._time_rows, float).reshape(-1, len(TIME_FIELDS)), time_lost=self._time_lost,
                     collided=xp.host(self.collided), viable=xp.host(self.viable).astype(np.int64),
-                    abort_events=[(e[0], e[1], e[2] if isinstance(e[2], np.ndarray) else xp.host(e[2])) for e in self._abort_events])
+                    abort_events=[(e[0], e[1], xp.host(e[2])) for e in self._abort_events])
+
+
+class _HostGroup(_Group):
+    """The loop on host state, in numpy: the readable statement of scripts/mpc.py:118-287 for B instances at once, what
+    ``run_mpc(on_device=False)`` runs (CPU double, or the engine's host path) and what the GPU tests hold :class:`_DeviceGroup`
+    against."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        B = self._B
+        self.resumed = np.zeros(B, bool)          # left the backup trajectory at this step (mpc.py:137-141)
+        self.new_abort = np.zeros(B, bool)
+        self._zeros_u = np.zeros((B, self._ctrl.nu))
+        self._jt = 0                              # the step counter
+        self._ever_aborted = False
+
+    # ---- first half: everything up to the controller's verdict ---------------------------------------------------------------
+    def part_a(self):
+        ctrl, B, Nb = self._ctrl, self._B, self._Nb
+        nq = ctrl.nq
+        kp, kd = 1.0, 1e2                                                               # mpc.py:97
+        x_cur = self.x_cur
+        if self._ever_aborted:
+            # --- instances following their safe-abort trajectory (mpc.py:130-146)
+            in_abort = self.sa & self.alive
+            follow = in_abort & (self.ja < Nb)
+            idx = np.minimum(self.ja, Nb - 1)
+            xa = self.x_abort[np.arange(B), idx]
+            ua = self.u_abort[np.arange(B), idx]
+            u_f = ua - (kp * (x_cur[:, :nq] - xa[:, :nq]) + kd * (x_cur[:, nq:] - xa[:, nq:]))
+            u = np.where(follow[:, None], u_f, self._zeros_u)
+            hold = in_abort & (self.ja >= Nb)
+            resume = hold & np.all(x_cur[:, nq:] < 5e-3, axis=1)                      # mpc.py:138
+            still = hold & ~resume
+            xe = self.x_abort[:, -1]
+            u_h = -(kp * (x_cur[:, :nq] - xe[:, :nq]) + 3e2 * (x_cur[:, nq:] - xe[:, nq:]))
+            u = np.where(still[:, None], u_h, u)
+            self.sa = self.sa & ~resume
+            self.ja = self.ja + in_abort.astype(np.int64)
+            self.resumed = resume
+        else:
+            u = self._zeros_u
+        # --- instances under MPC (mpc.py:151)
+        stepping = self.alive & ~self.sa
+        if hasattr(ctrl, 'r'):
+            self.r_log[self._jt] = np.where(stepping, ctrl.r, -1)
+        # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
+        #  read again, so they may step along)
+        if self._ever_aborted:
+            u_m, ab = _masked_step(ctrl, x_cur, stepping)
+        else:
+            u_m, ab = ctrl.step(x_cur)
+        self.u = np.where(stepping[:, None], u_m, u)
+        self.new_abort = ab & stepping
+        if self._ever_aborted and self._quirks:
+            # An abort raised on the very step an instance resumed MPC sits inside the reference's `if sa_flag:` branch
+            # (mpc.py:137-141): no viable state is recorded and no backup OCP solved -- the instance is in safe abort again
+            # with its OLD backup trajectory, its abort clock keeps running, and it re-tests its velocity at the next step.
+            again = self.new_abort & self.resumed
+            self.sa = self.sa | again
+            self.new_abort = self.new_abort & ~again
+
+    # ---- the step's decision: abort events (mpc.py:161-190) ----------------------------------------------------------------------
+    def handle_aborts(self):
+        ctrl, backup, B, Nb = self._ctrl, self._backup, self._B, self._Nb
+        if not ctrl.can_abort or not self.new_abort.any():
+            return
+        self._ever_aborted = True
+        # the backup OCP is solved for the aborting instances only (a compact batch), from their viable states
+        rows = np.where(self.new_abort)[0]
+        j, n_c = self._jt, len(rows)
+        xv_c = ctrl.getLastViableState()[rows]
+        xg_c = np.repeat(xv_c[:, None, :], Nb + 1, axis=1)
+        self._backup_scene(rows)
+        xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(np.ascontiguousarray(xv_c), xg_c, np.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
+        self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))
+        ok_c = np.asarray(st_c) == 0
+        failed, okb = np.zeros(B, bool), np.zeros(B, bool)
+        failed[rows] = ~ok_c
+        okb[rows] = ok_c
+        xa_new, ua_new = np.copy(self.x_abort), np.copy(self.u_abort)
+        xa_new[rows] = np.asarray(xo_c)
+        ua_new[rows] = np.asarray(uo_c)
+        self.collided = self.collided | failed
+        self.alive = self.alive & ~failed
+        self.last_x, self.last_u = np.where(failed, j, self.last_x), np.where(failed, j, self.last_u)   # mpc.py:186-190
+        self.x_abort = np.where(okb[:, None, None], xa_new, self.x_abort)
+        self.u_abort = np.where(okb[:, None, None], ua_new, self.u_abort)
+        self.ja = self.ja * (~okb).astype(np.int64)
+        self.sa = self.sa | okb
+        self.viable = np.minimum(self.viable.astype(np.int64) + okb.astype(np.int64), 255).astype(np.uint8)   # saturating, like k_loop_apply_backup
+
+    # ---- second half: plant, outcome tests, logs ----------------------------------------------------------------------------------
+    def part_b(self):
+        solver, j = self._ctrl.ocp_solver, self._jt
+        # plant (mpc.py:240, env_model.py:192-206).  Logs are written unmasked; rows of an instance after its failure are
+        # blanked at the end from the step it died at (mpc.py:114 pre-fills them with NaN)
+        self.u_log[j] = self.u
+        x_next, _ = solver.plant_step(self.x_cur, self.u, self._joints_noisy, self._tau_noise)
+        # outcome tests on the new state (mpc.py:246-264): one node per instance, so the engine's box + collision test
+        # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints
+        okn = np.asarray(solver.check_trajectory(x_next[:, None, :]))
+        self.x_log[j + 1] = x_next
+        bad = self.alive & ~okn
+        self.last_x, self.last_u = np.where(bad, j + 1, self.last_x), np.where(bad, j, self.last_u)   # the failing state stays logged
+        self.collided = self.collided | bad
+        self.alive = self.alive & ~bad
+        self.x_cur = np.where(self.alive[:, None], x_next, self.x_cur)
+        self._jt += 1
+
+    def _run(self):
+        for j in range(self._n_steps):
+            self.part_a()
+            if self._collect_times:
+                self._time_rows.append(self._ctrl.getTime())       # the solve has finished when step() returns
+            yield j
+            self.handle_aborts()
+            self.part_b()
+            self._progress(j)
+            if not self.alive.any():
+                break
+
+
+class _DeviceGroup(_Group):
+    """The loop with all state in HBM: both halves of a step are engine kernels (smpc_loop_pre / smpc_policy_step /
+    smpc_loop_classify_aborts, then smpc_loop_post) on state tensors that keep their addresses for the whole run -- nothing here
+    rebinds one -- so after a few eager steps each half is captured once as a hipGraph and replayed: one graph launch instead of
+    ~50 kernel launches per half.  :class:`_HostGroup` is the readable statement of the same automaton."""
+
+    def __init__(self, *args, use_graphs=True, **kw):
+        super().__init__(*args, **kw)
+        import torch
+        xp, ctrl, B, nu = self._xp, self._ctrl, self._B, self._ctrl.nu
+        if self._joints_noisy is not None:            # [B, nq] smpc_joint records as a float64 tensor (33 doubles each)
+            self._joints_noisy = xp.asarray(np.ascontiguousarray(self._joints_noisy).view(np.float64).reshape(B, ctrl.nq, -1), xp.f64)
+        if self._tau_noise is not None:
+            self._tau_noise = xp.asarray(self._tau_noise, xp.f64)
+        self._jt = xp.step_index(0)               # the step counter, a device tensor: smpc_loop_post advances it, graphs replay it
+        self._use_graphs = bool(use_graphs)
+        self._graphs = {}                         # half -> captured graph
+        self._u_other = xp.zeros((B, nu))
+        self._stepping = xp.full((B,), True, xp.bool_)
+        self.new_abort = ctrl._abort_out          # (the controller's own output buffer: no copy per step)
+        # abort events: the backup OCPs of a step's events are solved on the backup solver's own stream WHILE the next
+        # step's solve runs; until their outcome is applied (smpc_loop_apply_backup) the instances are only kept from stepping
+        self._pending = xp.full((B,), False, xp.bool_)
+        self._resumed = xp.full((B,), False, xp.bool_)      # written by smpc_loop_pre
+        self._any_event = xp.zeros((1,), xp.i32)            # written by smpc_loop_classify_aborts
+        self._inflight = None
+        bs = self._backup.ocp_solver
+        self._side = torch.cuda.ExternalStream(bs.L.smpc_stream(bs.h), device=torch.device('cuda', bs.device))
+        # the engine keeps HIP events of its last 64 solves (smpc_get_timing_history); they are read at least 32 solves late --
+        # finished by then, so nothing waits inside the loop
+        self._time_next = 0
+
+    def part_a(self):
+        ctrl, sv = self._ctrl, self._ctrl.ocp_solver
+        sv.loop_pre(self, getattr(ctrl, 'r', None), self._pending, self._u_other, self._stepping)
+        ctrl.step_on_device(self.x_cur, self._stepping, self._u_other, u_out=self.u)
+        if ctrl.can_abort:
+            sv.loop_classify_aborts(self, self.new_abort, self._any_event)
+
+    def _apply_inflight(self):
+        if self._inflight is None:
+            return
+        import torch
+        rows_b, xv_c, xo_c, uo_c, st_c, ev = self._inflight
+        torch.cuda.current_stream().wait_event(ev)
+        self._ctrl.ocp_solver.loop_apply_backup(self, rows_b, st_c, xo_c, uo_c, self.viable, self.u, self._pending)
+        self._inflight = None
+
+    def handle_aborts(self, j):
+        """Same events and outcomes as :meth:`_HostGroup.handle_aborts`; what differs is WHEN the backup OCP's result is
+        consumed: the solve is enqueued on the backup solver's stream and its outcome applied one step later, after the next
+        controller step has been enqueued -- in between the instance only must not step (``_pending``), which is all the
+        reference's loop needs of it (it either follows the backup trajectory from the next step on or is lost at this one)."""
+        import torch
+        xp, ctrl, backup, Nb = self._xp, self._ctrl, self._backup, self._Nb
+        if not ctrl.can_abort:
+            return
+        self._apply_inflight()                               # the previous step's events (their first tracking control goes into u)
+        if not bool(self._any_event.item()):                 # (the step's one host synchronisation)
+            return
+        rows = np.where(xp.host(self.new_abort))[0]
+        rows_b = xp.asarray(rows, xp.i64)
+        xv_c = ctrl.x_viable[rows_b]
+        n_c = len(rows)
+        self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))      # (xv_c goes to the host in results())
+        self._pending.copy_(self.new_abort)
+        main = torch.cuda.current_stream()
+        ev0 = torch.cuda.Event()
+        ev0.record(main)
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(ev0)
+            xg_c = xp.repeat_nodes(xv_c, Nb + 1)
+            self._backup_scene(rows_b)
+            xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        # (These tensors cross streams.  Their lifetimes are ordered by the events, not by the caching allocator: they are released
+        #  in _apply_inflight, after the main stream has been told to wait for `ev`, and the side stream's next work waits for an
+        #  event recorded on the main stream after that.  torch's record_stream is not usable here -- on this ROCm build it
+        #  faults on an ExternalStream.)
+        self._inflight = (rows_b, xv_c, xo_c, uo_c, st_c, ev)
+
+    def part_b(self):
+        self._ctrl.ocp_solver.loop_post(self, self.u, self._joints_noisy, self._tau_noise)
+
+    def _run_half(self, half, fn, j):
+        """eager for the first steps (workspaces get allocated), then captured once and replayed"""
+        if getattr(self._ctrl, '_traj_rebound', False):      # setTrajectory bound a new device tensor: captured steps hold the old one
+            self._graphs.clear()
+            self._ctrl._traj_rebound = False
+        g = self._graphs.get(half)
+        if g is None and self._use_graphs and j >= 3:
+            import torch
+            try:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=torch.cuda.current_stream(), capture_error_mode='relaxed'):
+                    fn()                  # (capturing records the launches without executing them)
+                self._graphs[half] = g
+            except Exception as e:        # report once, stay eager
+                print(f'[run_mpc] hipGraph capture of step half {half} failed ({type(e).__name__}: {e}); eager launches')
+                self._use_graphs, g = False, None
+        if g is not None:
+            g.replay()
+        else:
+            fn()
+
+    def _read_times(self, j, final=False):
+        """rows of the solves up to step j whose events have finished (never the 32 most recent unless ``final``)"""
+        sv = self._ctrl.ocp_solver
+        if final:
+            sv.sync()                              # end of the run: everything has finished, drain the ring
+        while self._time_next <= j:
+            back = j - self._time_next
+            if back >= 64:                         # the ring has lapped it (the host ran more than 64 solves ahead of this read)
+                self._time_lost += 1
+                self._time_next += 1
+                continue
+            if not final and back < 32:
+                break
+            if not final and back >= 56:
+                sv.sync()                          # about to be lapped: wait rather than lose the row
+            tm = sv.timing_history(back)
+            if tm is None:
+                if final:
+                    self._time_lost += 1
+                    self._time_next += 1
+                    continue
+                break
+            self._time_rows.append(time_row(tm))
+            self._time_next += 1
+
+    def _run(self):
+        for j in range(self._n_steps):
+            self._run_half('a', self.part_a, j)
+            if self._collect_times:
+                self._read_times(j)
+            yield j
+            self.handle_aborts(j)
+            self._run_half('b', self.part_b, j)
+            self._progress(j)
+        self._apply_inflight()                # (events of the last step)
+        if self._collect_times:
+            self._read_times(self._n_steps - 1, final=True)
 
 
 TIME_FIELDS = ('time_lin', 'time_sim', 'time_qp', 'time_qp_solver_call', 'time_glob', 'time_reg', 'time_tot')   # controller.py:123-124
@@ -1320,6 +1332,17 @@ def time_row(t):
     qp_setup, qp_ipm = t.get('time_qp_setup', 0.0), t.get('time_qp_ipm', 0.0)
     qp = t['time_qp'] if 'time_qp' in t else qp_setup + qp_ipm
     return [t.get('time_lin', 0.0) + t.get('time_nn', 0.0), 0.0, qp, qp_ipm, 0.0, 0.0, t.get('time_tot', 0.0)]
+
+
+def _check_state_kind(ctrl, backup, on_device):
+    """run_mpc's two loops take the state where they expect it: ValueError, before anything is enqueued, otherwise"""
+    for c in (ctrl, backup):
+        if bool(c.xp.on_device) != bool(on_device):
+            raise ValueError(f'run_mpc(on_device={bool(on_device)}): {type(c).__name__} was built with device_state={bool(c.xp.on_device)}; '
+                             'make_controller / make_backup must hand back controllers with device_state=on_device')
+    if on_device and not hasattr(ctrl.ocp_solver, 'loop_pre'):
+        raise ValueError(f'run_mpc(on_device=True) needs a solver with the engine\'s loop kernels (BatchedOcpSolver.loop_pre); '
+                         f'{type(ctrl.ocp_solver).__name__} has none')
 
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
@@ -1384,20 +1407,20 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     gens, grps, streams = [], [], []
     for lo, hi in spans:
         ctrl = make_controller(cont_name, hi - lo)
+        backup = make_backup(hi - lo)
+        _check_state_kind(ctrl, backup, on_device)
         if traj is not None:
             ctrl.setTrajectory(traj[lo:hi] if curves else traj)
-        backup = make_backup(hi - lo)
+        args = (params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, collect_times)
         if on_device:
             import torch
             sv = ctrl.ocp_solver
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
-                grp = _Group(params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, graphs,
-                             collect_times, scenes=None if scenes is None else scenes[lo:hi])
+                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs)
         else:
             streams.append(None)
-            grp = _Group(params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, False,
-                         collect_times, scenes=None if scenes is None else scenes[lo:hi])
+            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi])
         grps.append(grp)
         gens.append(grp.run())
 

@@ -7,6 +7,11 @@ the B instances that the reference walks one at a time (scripts/mpc.py:102).  ``
 ``(u[B, nu], abort[B])``.  The numerics all go through ``self.ocp_solver`` (a :class:`BatchedOcpSolver`, i.e. the HIP
 engine); this file is pure bookkeeping, so it can be unit-tested with a scripted fake solver.
 
+Two paths, each stated once.  The host path is the numpy statement of each class (``_step_host``, ``provideControl``,
+``_set_flags`` / ``_post_solve``), written to be read next to the reference.  A ``device_state=True`` controller never runs it:
+its ``step`` is ``step_on_device``, the same automaton as engine kernels (smpc_policy_step), which the GPU tests hold against the
+statement.  There is no third path: ``device_state=True`` with a solver that lacks those kernels is refused in the constructor.
+
 Instances whose ``step`` returns ``abort=True`` keep their guess unshifted and their step counter unchanged, exactly
 like the early ``return self.u_guess[0], True`` of the reference (controller.py:384-385, 483-487).
 """
@@ -31,7 +36,6 @@ class AbstractController(InPlaceState):
     def __init__(self, params, batch, cost='ext', N=None, solver=None, net=None, device=0, device_state=False):
         self.params = params
         self.B = int(batch)
-        self.xp = TorchOps(device) if device_state else NumpyOps()
         self.problem = OcpProblem(params, self.cont_name, cost, N=N)
         self.model = self.problem                      # x_min/x_max/tau_max/ee_ref live here (AdamModel's role)
         self.N = self.problem.N
@@ -44,7 +48,11 @@ class AbstractController(InPlaceState):
         if solver is None:
             from .solver import BatchedOcpSolver
             solver = BatchedOcpSolver(self.problem, net, device=device)
+        if device_state and not hasattr(solver, 'policy_step'):
+            raise ValueError(f'device_state=True needs a solver with the engine\'s policy kernels (BatchedOcpSolver.policy_step): '
+                             f'{type(solver).__name__} has none; the numpy statement runs on host state only')
         self.ocp_solver = solver
+        self.xp = TorchOps(device) if device_state else NumpyOps()     # set-up, predicates and results; never a step (_xp.py)
         self.time_fields = ['time_lin', 'time_sim', 'time_qp', 'time_qp_solver_call', 'time_glob', 'time_reg', 'time_tot']
         xp = self.xp
         self._x_min, self._x_max = xp.asarray(self.problem.x_min, xp.f64), xp.asarray(self.problem.x_max, xp.f64)
@@ -119,7 +127,7 @@ class AbstractController(InPlaceState):
             self.traj[...] = new       # in place: a captured step (hipGraph) keeps the device pointer and length it was captured with
         else:
             self.traj = new
-            self._traj_rebound = True  # (closed_loop._Group drops its captured graphs when it sees this)
+            self._traj_rebound = True  # (closed_loop._DeviceGroup drops its captured graphs when it sees this)
         if to_engine and (new.ndim == 3 or had_curves):
             # the handle's copy follows: same (B, L) overwrites the handle's buffer in place, which a captured step keeps reading
             self.ocp_solver.set_instance_curves(self.traj if new.ndim == 3 else None)
@@ -187,20 +195,15 @@ class AbstractController(InPlaceState):
 
     def provideControl(self, active=None):
         """controller.py:169-184.  ``active`` masks out instances that returned early (abort)."""
-        xp = self.xp
-        accept = xp.cast(self.fails == 0, xp.i32)
-        keep = active is not None
-        # the engine's device path shifts the guess in place: keep the old one for the instances that must not shift
-        old_xg = xp.copy(self.x_guess) if keep and xp.on_device else self.x_guess
-        old_ug = xp.copy(self.u_guess) if keep and xp.on_device else self.u_guess
+        accept = (self.fails == 0).astype(np.int32)
         xg, ug, u = self.ocp_solver.provide_control(accept, self.x_temp, self.u_temp, self.x_guess, self.u_guess)
-        if not keep:
+        if active is None:
             self.x_guess, self.u_guess = xg, ug
         else:
-            u = xp.where(active[:, None], u, old_ug[:, 0])
-            self.x_guess = xp.where(active[:, None, None], xg, old_xg)
-            self.u_guess = xp.where(active[:, None, None], ug, old_ug)
-        return u, xp.zeros((self.B,), xp.bool_)
+            u = np.where(active[:, None], u, self.u_guess[:, 0])
+            self.x_guess = np.where(active[:, None, None], xg, self.x_guess)
+            self.u_guess = np.where(active[:, None, None], ug, self.u_guess)
+        return u, np.zeros((self.B,), np.bool_)
 
     # -- feasibility predicates (env_model.py:170-243, safe_set.py:61-68) ------------------------------------------------
     def _as_state(self, x):
@@ -271,11 +274,17 @@ class AbstractController(InPlaceState):
         return xp.cast(good, xp.i64)
 
     def step(self, x):
+        """x[B, nx] -> (u[B, nu], abort[B]): the engine kernels for a device-state controller, the class's numpy statement otherwise"""
+        if self.xp.on_device:
+            return self.step_on_device(x)
+        return self._step_host(x)
+
+    def _step_host(self, x):
         raise NotImplementedError
 
     def step_on_device(self, x, stepping=None, u_other=None, u_out=None):
         """``step`` with the state in HBM: the class's automaton as engine kernels (smpc_policy_step, kernels_policy.hpp) -- the
-        numpy ``step`` of each class is the readable statement of the same thing, and the GPU tests run the two side by side.
+        numpy ``_step_host`` of each class is the readable statement of the same thing, and the GPU tests run the two side by side.
         ``stepping`` masks out instances that must not step (they are left untouched and get ``u_other``)."""
         return self.ocp_solver.policy_step(self, x, stepping, u_other, u_out)
 
@@ -283,13 +292,11 @@ class AbstractController(InPlaceState):
 class NaiveController(AbstractController):
     cont_name = 'naive'
 
-    def step(self, x):
+    def _step_host(self, x):
         """controller.py:274-284"""
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
         self.guessCorrection()
         status = self.solve(x)
-        self.fails = (self.fails + 1) * self.xp.cast(status != 0, self.xp.i64)      # 0 on success, fails + 1 otherwise
+        self.fails = (self.fails + 1) * (status != 0).astype(np.int64)      # 0 on success, fails + 1 otherwise
         self.current_step = self.current_step + 1
         return self.provideControl()
 
@@ -315,24 +322,21 @@ class STWAController(STController):
     def checkGuess(self):
         return super().checkGuess() & self.checkSafeConstraints(self.x_temp[:, -1])
 
-    def step(self, x):
+    def _step_host(self, x):
         """controller.py:375-388"""
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
-        xp = self.xp
         self.guessCorrection()
         status = self.solve(x)
         ok = (status == 0) & self.checkStateConstraints(self.x_temp)
         first_fail = ~ok & (self.fails == 0)
-        self.x_viable = xp.where(first_fail[:, None], self.x_guess[:, -2], self.x_viable)
+        self.x_viable = np.where(first_fail[:, None], self.x_guess[:, -2], self.x_viable)
         abort = ~ok & (self.fails == self.N - 1)
-        u_abort = xp.copy(self.u_guess[:, 0])
+        u_abort = np.copy(self.u_guess[:, 0])
         # ok: 0 ; abort: unchanged ; otherwise fails + 1
-        self.fails = xp.where(abort, self.fails, self.fails + 1) * xp.cast(~ok, xp.i64)
+        self.fails = np.where(abort, self.fails, self.fails + 1) * (~ok).astype(np.int64)
         active = ~abort
-        self.current_step = self.current_step + xp.cast(active, xp.i64)
+        self.current_step = self.current_step + active.astype(np.int64)
         u, _ = self.provideControl(active)
-        return xp.where(abort[:, None], u_abort, u), abort
+        return np.where(abort[:, None], u_abort, u), abort
 
 
 class HTWAController(STWAController):
@@ -354,42 +358,39 @@ class RecedingController(STWAController):
 
     def _set_flags(self):
         """controller.py:452-469: running nodes off except node r; terminal node always on."""
-        xp = self.xp
-        k = xp.arange(self.N + 1)[None, :]
+        k = np.arange(self.N + 1)[None, :]
         r = self.r[:, None]
         on = (k == self.N) | ((k == r) & (r < self.N)) | (k == 0)   # node 0 keeps the default flag (never carries the row anyway)
-        self.p[:, :, 4] = xp.cast(on, xp.f64) * 2.0 - 1.0
+        self.p[:, :, 4] = on.astype(np.float64) * 2.0 - 1.0
 
     def _post_solve(self, x, status, u_abort):
-        xp = self.xp
         if self.abort_flag:
             self.r = self.r - 1
             abort = self.r == 0
         else:
-            self.r = self.r - xp.cast(self.r > 0, xp.i64)
-            abort = xp.zeros((self.B,), xp.bool_)
-        self.x_viable = xp.where(abort[:, None], self.x_guess[:, 1], self.x_viable)
-        self.r = self.r + xp.cast(abort, xp.i64) * self.N            # r = 0 -> N for the aborting instances
+            self.r = self.r - (self.r > 0).astype(np.int64)
+            abort = np.zeros((self.B,), np.bool_)
+        self.x_viable = np.where(abort[:, None], self.x_guess[:, 1], self.x_viable)
+        self.r = self.r + abort.astype(np.int64) * self.N            # r = 0 -> N for the aborting instances
         ok = (status == 0) & self.checkStateConstraints(self.x_temp) & ~abort
         # r <- largest i-1, i in r+2..N, whose node passes the safe-set test (controller.py:491-494)
         safe = self.checkSafeConstraints(self.x_temp)                      # [B, N+1]
-        i = xp.arange(self.N + 1)[None, :]
-        best = xp.last_true(safe & (i >= (self.r[:, None] + 2)))           # largest such i, -1 if none
-        self.r = xp.where(ok & (best >= 0), best - 1, self.r)
+        i = np.arange(self.N + 1)[None, :]
+        cand = safe & (i >= (self.r[:, None] + 2))
+        best = np.where(cand.any(1), self.N - np.argmax(cand[:, ::-1], axis=1), -1)      # largest such i, -1 if none
+        self.r = np.where(ok & (best >= 0), best - 1, self.r)
         # abort: unchanged ; ok: 0 ; otherwise fails + 1
-        self.fails = xp.where(abort, self.fails, (self.fails + 1) * xp.cast(~ok, xp.i64))
+        self.fails = np.where(abort, self.fails, (self.fails + 1) * (~ok).astype(np.int64))
         active = ~abort
-        self.current_step = self.current_step + xp.cast(active, xp.i64)
+        self.current_step = self.current_step + active.astype(np.int64)
         u, _ = self.provideControl(active)
-        return xp.where(abort[:, None], u_abort, u), abort
+        return np.where(abort[:, None], u_abort, u), abort
 
-    def step(self, x):
+    def _step_host(self, x):
         """controller.py:448-498"""
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
         self.guessCorrection()
         self._set_flags()
-        u_abort = self.xp.copy(self.u_guess[:, 0])
+        u_abort = np.copy(self.u_guess[:, 0])
         status = self.solve(x)
         return self._post_solve(x, status, u_abort)
 
@@ -408,24 +409,21 @@ class RealReceding(RecedingController):
             self._stage_lo = xp.asarray(np.vstack([np.tile(self.problem.x_min, (self.N, 1)), self.problem.lbx_e[None, :]]), xp.f64)
             self._stage_hi = xp.asarray(np.vstack([np.tile(self.problem.x_max, (self.N, 1)), self.problem.ubx_e[None, :]]), xp.f64)
 
-    def step(self, x):
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
-        xp, pr, N = self.xp, self.problem, self.N
+    def _step_host(self, x):
+        """controller.py:524-565"""
+        N = self.N
         # other nodes: the model bounds (:534-536); the terminal node keeps lbx_e / ubx_e
-        k = xp.arange(N + 1)[None, :, None]
+        k = np.arange(N + 1)[None, :, None]
         last = k == N
-        lo = xp.where(last, self._lbx_e[None, None, :], self._x_min[None, None, :])
-        hi = xp.where(last, self._ubx_e[None, None, :], self._x_max[None, None, :])
+        lo = np.where(last, self._lbx_e[None, None, :], self._x_min[None, None, :])
+        hi = np.where(last, self._ubx_e[None, None, :], self._x_max[None, None, :])
         sel = self.r < N
-        centre = xp.take_rows(self.x_guess, xp.clip_max(self.r, N - 1) + 1)[:, None, :]     # x_guess[b, r_b + 1]
+        centre = self.x_guess[np.arange(self.B), np.minimum(self.r, N - 1) + 1][:, None, :]     # x_guess[b, r_b + 1]
         at_r = (k == self.r[:, None, None]) & sel[:, None, None]
-        lo = xp.where(at_r, centre - self.TUBE, lo + 0.0 * centre)      # (+ 0 * centre: broadcast to [B, N+1, nx])
-        hi = xp.where(at_r, centre + self.TUBE, hi + 0.0 * centre)
-        if xp.on_device:
-            lo, hi = lo.contiguous(), hi.contiguous()
+        lo = np.where(at_r, centre - self.TUBE, lo + 0.0 * centre)      # (+ 0 * centre: broadcast to [B, N+1, nx])
+        hi = np.where(at_r, centre + self.TUBE, hi + 0.0 * centre)
         self.ocp_solver.set_instance_bounds(lo, hi)
-        u_abort = xp.copy(self.u_guess[:, 0])
+        u_abort = np.copy(self.u_guess[:, 0])
         status = self.solve(x)
         return self._post_solve(x, status, u_abort)
 
@@ -449,11 +447,9 @@ class ParallelController(RecedingController):
         k, n = np.arange(N + 1)[None, :], np.arange(N, 0, -1)[:, None]
         return np.where(k == n, 1.0, -1.0)
 
-    def step(self, x):
+    def _step_host(self, x):
         """controller.py:614-640 with every candidate evaluated: the choice is the one the reference's loop (order N .. 1, break at
         the first result N) makes; status / qp_iter (and x_temp / u_temp on failure) are those of the last candidate it solves"""
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
         B, N, nx, nu = self.B, self.N, self.nx, self.nu
         self.guessCorrection()
         xg, ug = np.asarray(self.x_guess), np.asarray(self.u_guess)
@@ -505,15 +501,12 @@ class ControllerSafeSetEverywhere(STController):
     cont_name = 'constraint_everywhere'
     policy_kind = 1
 
-    def step(self, x):
+    def _step_host(self, x):
         """controller.py:651-661"""
-        if self.xp.on_device and hasattr(self.ocp_solver, 'policy_step'):
-            return self.step_on_device(x)
-        xp = self.xp
         self.guessCorrection()
         status = self.solve(x)
         ok = (status == 0) & self.checkStateConstraints(self.x_temp)
-        self.fails = (self.fails + 1) * xp.cast(~ok, xp.i64)
+        self.fails = (self.fails + 1) * (~ok).astype(np.int64)
         self.current_step = self.current_step + 1
         return self.provideControl()
 

@@ -764,7 +764,7 @@ class BatchedOcpSolver:
                               ptr(getattr(g, '_resumed', None)))
 
     def loop_pre(self, g, r, pending, u_other, stepping):
-        """scripts/mpc.py:130-151 for the group ``g`` (closed_loop._Group, device state)"""
+        """scripts/mpc.py:130-151 for the group ``g`` (closed_loop._DeviceGroup)"""
         ls = self._loop_state(g)
         with self._ordered(1):
             self._chk(self.L.smpc_loop_pre(self.h, g._B, g._Nb, C.byref(ls), r.data_ptr() if r is not None else None,

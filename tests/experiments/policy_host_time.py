@@ -23,9 +23,9 @@ def timed(cls, name, label=None):
     setattr(cls, name, w)
 
 
-timed(cl._Group, '_run_half')
-timed(cl._Group, '_apply_inflight')
-timed(cl._Group, 'handle_aborts')
+timed(cl._DeviceGroup, '_run_half')
+timed(cl._DeviceGroup, '_apply_inflight')
+timed(cl._DeviceGroup, 'handle_aborts')
 _item = torch.Tensor.item
 def item(self):
     t = time.perf_counter()

@@ -193,7 +193,7 @@ def test_run_mpc_collects_solver_times_like_the_reference():
 
 
 def test_event_ring_reader_never_loses_or_duplicates_a_solve():
-    """closed_loop._Group._read_times against a simulated 64-deep event ring (smpc_get_timing_history): solves finish a varying
+    """closed_loop._DeviceGroup._read_times against a simulated 64-deep event ring (smpc_get_timing_history): solves finish a varying
     number of steps after they were enqueued; the reader takes entries at least 32 solves old, waits (sync) rather than letting the
     ring lap an unread entry, and drains the rest at the end -- every solve's row exactly once, in order."""
     class Ring:
@@ -213,7 +213,7 @@ def test_event_ring_reader_never_loses_or_duplicates_a_solve():
 
     for lag in (0, 5, 40, 100):                      # how far the GPU trails the host's enqueueing
         ring = Ring()
-        g = cl._Group.__new__(cl._Group)
+        g = cl._DeviceGroup.__new__(cl._DeviceGroup)
         g._ctrl = type('C', (), {'ocp_solver': ring})()
         g._time_rows, g._time_next, g._time_lost = [], 0, 0
         n = 150

@@ -200,7 +200,7 @@ def test_device_pointer_path_matches_host_path():
 
 def test_buffer_growth_inside_a_graph_capture_is_a_state_error():
     """A handle's buffers grow in eager calls only.  The engine's stream joins a capture through BatchedOcpSolver._ordered, as in
-    closed_loop._Group._run_half: a captured solve of a warmed-up batch size replays what the eager solve computed, and a captured
+    closed_loop._DeviceGroup._run_half: a captured solve of a warmed-up batch size replays what the eager solve computed, and a captured
     solve that would have to grow a buffer fails with SMPC_ESTATE instead of synchronising the capturing stream -- the capture still
     ends cleanly, and the next eager call grows the buffers."""
     import warnings
