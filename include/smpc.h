@@ -242,6 +242,32 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
 #define SMPC_SCENE_ROW 8   /* doubles per (instance, row): C[3], D[3], offset, 0 */
 int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device);
 
+/* Obstacles that move along the horizon: a TRACK of scenes per instance.  geom is [B][T][n_rows][SMPC_SCENE_ROW] doubles, one scene
+ * record (as above) per (instance, time column, row); memory 64 * n_rows * T * B bytes.  What a scene does not carry, a track does
+ * not carry either.  THE column rule: the scene at time c is column
+ *     col(c) = clamp(c, 0, T - 1)
+ * -- before the track's first column the world stands as in column 0, behind its last as in column T - 1.  With t = the value of
+ * the scene clock when a kernel runs (smpc_set_scene_clock; 0 without one):
+ *   smpc_solve_batch, smpc_eval_nodes, smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_check_trajectory,
+ *   smpc_debug_stage_records, and the solve and the x_temp test of smpc_policy_step (kinds 0-4):   node k in column col(t + k)
+ *   smpc_loop_post (its one node is the plant's NEXT state):                                       column col(t + 1)
+ *   smpc_ik_batch:                                                                                 column col(t)
+ *   smpc_score_rollout (the log starts at time 0, the clock is not read):                          state j of the log in col(j)
+ * A track and a scene are ONE slot of the handle: setting one replaces the other, smpc_set_instance_scene(h, B, geom, ..) is exactly
+ * a track with T = 1, and smpc_set_instance_scene(h, 0, NULL, 0) clears a track too (as geom == NULL does here).  Everything said
+ * of a scene holds: the copy is stream-ordered and a call with host pointers checks the fields that the row kinds read for
+ * non-finite values and waits; the track belongs to its batch size (another B: SMPC_EINVAL naming both); SMPC_POLICY_PARALLEL and
+ * smpc_rollout_batch return SMPC_ESTATE.  SMPC_EINVAL also for T < 1.  SMPC_ESTATE: the copy would have to grow while the stream is
+ * being captured (the old contents stay).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device);
+
+/* The time of node 0, for a track: d_clock is a DEVICE pointer to ONE int64 that the caller owns and keeps alive; NULL = time 0.
+ * The cell is read on the device when a kernel runs -- no host synchronisation, and a captured graph replays with whatever the cell
+ * holds then; smpc_loop_state.step is the intended cell.  Without a track, or with T = 1, the clock is not read.  The clock stays
+ * set across smpc_set_instance_scene / _track calls until it is replaced or cleared here. */
+int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
+
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle
  * keeps a copy like a scene (stream-ordered; with host pointers the call checks every entry for finiteness and waits for the

@@ -20,7 +20,8 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
            'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
-           'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves']
+           'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves',
+           'smpc_set_instance_scene_track', 'smpc_set_scene_clock']
 
 
 class EngineError(RuntimeError):
@@ -134,6 +135,8 @@ def lib():
     L.smpc_set_slack_weights.argtypes = [vp, dp]
     L.smpc_set_instance_bounds.argtypes = [vp, C.c_int, dp, dp, C.c_int]
     L.smpc_set_instance_scene.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.smpc_set_instance_scene_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
+    L.smpc_set_scene_clock.argtypes = [vp, dp]
     L.smpc_set_instance_curves.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_solve_batch.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_eval_nodes.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int]

@@ -296,28 +296,63 @@ def _sqp_on_device(ctrl, x0, max_iter, history, verbose, opts):
 
 
 def _check_scenes(scenes, B, problem):
-    """``scenes`` as a contiguous float64 [B, n_rows, SCENE_ROW] array (problem.row_geometry's layout); ValueError otherwise"""
+    """``scenes`` as a contiguous float64 array: [B, n_rows, SCENE_ROW] (problem.row_geometry's layout per instance), or a track
+    [B, T, n_rows, SCENE_ROW] with T >= 1 time columns (problem.moving_scenes); ValueError otherwise"""
     from .problem import SCENE_ROW
     g = np.ascontiguousarray(scenes, np.float64)
     want = (int(B), len(problem.rows), SCENE_ROW)
-    if g.shape != want:
-        raise ValueError(f'scenes: shape {g.shape}, expected {want} (one [n_rows, {SCENE_ROW}] geometry per instance)')
+    if g.ndim == 4:
+        if (g.shape[0],) + g.shape[2:] != want or g.shape[1] < 1:
+            raise ValueError(f'scenes: shape {g.shape}, expected {want[:1] + ("T >= 1",) + want[1:]} (a track: one [n_rows, '
+                             f'{SCENE_ROW}] geometry per instance and time column)')
+    elif g.shape != want:
+        raise ValueError(f'scenes: shape {g.shape}, expected {want} (one [n_rows, {SCENE_ROW}] geometry per instance) or '
+                         f'{want[:1] + ("T",) + want[1:]} (a track)')
     if not len(problem.rows):
         raise ValueError('scenes: the problem has no collision rows')
     return g
 
 
 def _set_scene(solver, geom):
+    """the scenes [B, n_rows, 8], or the scene track [B, T, n_rows, 8], of a batch onto the solver (None clears either)"""
     if not hasattr(solver, 'set_instance_scene'):
         raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene')
-    solver.set_instance_scene(geom)
+    if geom is not None and geom.ndim == 4:
+        if not hasattr(solver, 'set_instance_scene_track'):
+            raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene_track')
+        solver.set_instance_scene_track(geom)
+    else:
+        solver.set_instance_scene(geom)
 
 
 def _clear_scene(solver):
-    """the handle keeps no scene behind a run: ``make_controller`` / ``make_backup`` may hand out a solver that is used again, with
-    another batch size (refused while a scene of the old size is set) or with the same one (which would run in the old scenes)"""
+    """the handle keeps no scene (or track, or clock) behind a run: ``make_controller`` / ``make_backup`` may hand out a solver
+    that is used again, with another batch size (refused while a scene of the old size is set) or with the same one (which would
+    run in the old scenes)"""
     if hasattr(solver, 'set_instance_scene'):
         solver.set_instance_scene(None)
+    if hasattr(solver, 'set_scene_clock'):
+        solver.set_scene_clock(None)
+
+
+def _new_scene_clock(solver):
+    """a one-element int64 cell for ``solver.set_scene_clock`` on a host loop: in HBM for an engine handle (the kernels read it
+    there), a numpy array for a CPU double"""
+    if hasattr(solver, 'L'):
+        import torch
+        return torch.zeros((1,), dtype=torch.int64, device=torch.device('cuda', solver.device))
+    return np.zeros(1, np.int64)
+
+
+def _write_scene_clock(cell, t):
+    """cell <- t, finished before the next engine call is enqueued (the engine runs on a stream of its own; a host loop waits
+    for every call anyway)"""
+    if cell is None:
+        return
+    cell[0] = int(t)
+    if not isinstance(cell, np.ndarray):
+        import torch
+        torch.cuda.current_stream(cell.device).synchronize()
 
 
 def _free_starts_per_scene(solver, scenes, cand):
@@ -329,6 +364,8 @@ def _free_starts_per_scene(solver, scenes, cand):
     n = scenes.shape[0]
     x0, filled = np.zeros((n, cand.shape[1])), np.zeros(n, bool)
     c = k = 0
+    if hasattr(solver, 'set_scene_clock'):
+        solver.set_scene_clock(None)                # (a track: its column 0, where the instance starts)
     while k < n and c < len(cand):
         m = min(n - k, len(cand) - c)
         _set_scene(solver, scenes[k:k + m])
@@ -345,7 +382,8 @@ def ik_starts(solver, problem, target, n, starts_per=16, seed=0, scenes=None, fi
     reference takes from InverseKinematicsOCP (guess_acados.py:179-183) -- by the batched multi-start IK (``solver.ik``,
     smpc_ik_batch; ik.ik_batch_host for a solver without one).  Instance i draws its OWN block of ``starts_per`` Halton points in the
     joint box (points ``seed + (first + i) * starts_per`` onwards of :func:`halton`), so n instances get n different arm
-    configurations at the same end-effector point.  ``scenes`` [n, n_rows, 8]: instance i is solved in its scene.
+    configurations at the same end-effector point.  ``scenes`` [n, n_rows, 8]: instance i is solved in its scene (of a track
+    [n, T, n_rows, 8]: in its column 0, where the run starts).
     Returns ``(x0 [n, nx], info [n, 2])``: info[i] = (winning start, number of successful starts); ``info[i, 1] == 0`` means NO
     solution was found for instance i, and x0[i] is then only the closest point reached."""
     from .ik import ik, ik_params
@@ -358,6 +396,8 @@ def ik_starts(solver, problem, target, n, starts_per=16, seed=0, scenes=None, fi
     q_start = lo + halton(n * starts_per, nq, skip=1 + int(seed) + int(first) * starts_per).reshape(n, starts_per, nq) * (hi - lo)
     if scenes is not None:
         scenes = _check_scenes(scenes, n, problem)
+        if scenes.ndim == 4:
+            scenes = np.ascontiguousarray(scenes[:, 0])
     q, info, _ = ik(solver, problem, tg, q_start, scenes=scenes, **over)
     return np.hstack([np.asarray(q, float), np.zeros((n, nq))]), np.asarray(info)
 
@@ -521,6 +561,8 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     B = len(x0)
     if scenes is not None and B:
         _set_scene(ctrl.ocp_solver, scenes)
+        if hasattr(ctrl.ocp_solver, 'set_scene_clock'):
+            ctrl.ocp_solver.set_scene_clock(None)       # (a track: the guess is made at time 0, node k in column min(k, T - 1))
 
     def result(good):
         out = {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}
@@ -807,10 +849,12 @@ def _score_eval_chunks(solver, problem, states, alpha, chunk, safe):
     return ee, rows, g
 
 
-def _score_eval_instances(solver, problem, x, alpha, safe):
+def _score_eval_instances(solver, problem, x, alpha, safe, scene_clock=None):
     """:func:`_score_eval_chunks` for a solver that holds a scene per instance: every call evaluates all B instances, instance b's
     own states packed into the nodes of ITS trajectory (so its rows are formed in its scene).  x [B, M, nx] -> the same three
-    arrays for the B * M states, instance-major."""
+    arrays for the B * M states, instance-major.  ``scene_clock``: the cell of ``solver.set_scene_clock`` when the solver holds a
+    scene TRACK -- a call that packs the states j0, j0 + 1, .. into the nodes n0, n0 + 1, .. runs at time j0 - n0, so that state
+    j is formed in column clip(j, 0, T - 1): the log starts at time 0."""
     N, nx, nr = solver.N, problem.nx, int(problem.desc.n_rows)
     B, M = x.shape[0], x.shape[1]
     ee, rows, g = np.zeros((B, M, 3)), np.zeros((B, M, nr)), np.zeros((B, M))
@@ -822,6 +866,7 @@ def _score_eval_instances(solver, problem, x, alpha, safe):
         m = min(per, M - lo)
         xg = np.zeros((B, N + 1, nx))
         xg[:, nodes.start:nodes.start + m] = x[:, lo:lo + m]
+        _write_scene_clock(scene_clock, lo - nodes.start)
         ev = solver.eval_nodes(xg, np.zeros((B, N, problem.nu)), p)
         sl = slice(nodes.start, nodes.start + m)
         if safe:
@@ -833,7 +878,7 @@ def _score_eval_instances(solver, problem, x, alpha, safe):
 
 
 def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, last_u=None, ee_ref=None, traj=None, want_safe=False,
-                            chunk=4096, per_instance=False, **bounds):
+                            chunk=4096, per_instance=False, scene_clock=None, **bounds):
     """The readable numpy statement of ``BatchedOcpSolver.score_rollout`` (smpc_score_rollout, include/smpc.h), and the host path of
     ``run_mpc(score=True)``.  STEP-major logs ``x_log [T+1, B, nx]``, ``u_log [T, B, nu]``; ``last_x`` / ``last_u`` [B]: last valid
     row of each, None = complete; rows past them affect nothing.  Returns ``(out [B, 7], outi [B, 4] int32)`` with the columns
@@ -851,7 +896,9 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
 
     Uses only ``solver.eval_nodes`` (``ee``, ``row_val``; ``nn_val`` for g), ``chunk`` states per call -- or, with ``per_instance``
     (the solver holds a scene per instance, set_instance_scene), all B instances per call with every instance's states in its own
-    trajectory."""
+    trajectory.  With a scene TRACK on the solver (set_instance_scene_track) pass ``scene_clock``, the cell handed to
+    ``solver.set_scene_clock``: state j of the log is then evaluated in column clip(j, 0, T - 1) of its instance's track, as
+    smpc_score_rollout does (the statement writes the cell before every call and leaves it at its last value)."""
     x = np.transpose(np.asarray(x_log, float), (1, 0, 2))          # [B, T+1, nx]
     u = np.transpose(np.asarray(u_log, float), (1, 0, 2))          # [B, T, nu]
     B, T = u.shape[0], u.shape[1]
@@ -881,7 +928,7 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
         ref = np.asarray(problem.ee_ref if ee_ref is None else ee_ref, float)[None, None, :]
     flat = np.where(vx[:, :, None], x, 0.0).reshape(-1, x.shape[2])                  # invalid rows: any finite state, masked below
     if per_instance:
-        ee, rv, _ = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, False)
+        ee, rv, _ = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, False, scene_clock)
     else:
         ee, rv, _ = _score_eval_chunks(solver, problem, flat, alpha, chunk, False)
     e2 = np.sum((ee.reshape(B, T + 1, 3) - ref) ** 2, axis=2)
@@ -904,7 +951,7 @@ def score_rollout_statement(solver, problem, params, x_log, u_log, last_x=None, 
         if int(problem.desc.nn_mode) == 0:
             raise ValueError('want_safe needs a formulation with a safe-set row (eval_nodes reports g on the nodes that carry it)')
         if per_instance:
-            _, _, g = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, True)
+            _, _, g = _score_eval_instances(solver, problem, flat.reshape(B, T + 1, -1), alpha, True, scene_clock)
         else:
             _, _, g = _score_eval_chunks(solver, problem, flat, alpha, chunk, True)
         g = np.where(vx, g.reshape(B, T + 1), np.inf)
@@ -945,11 +992,17 @@ class _Group:
         xp = ctrl.xp
         self._xp, self._B = xp, B
         # a scene per instance (run_mpc(scenes=...)): the controller's handle holds the group's [B, n_rows, 8]; the backup handle gets
-        # the rows of the aborting instances before each of its compact solves (_backup_scene)
-        self._scenes = None
+        # the rows of the aborting instances before each of its compact solves (_backup_scene).  A track [B, T, n_rows, 8] goes the
+        # same way; the loop's step counter is then the scene clock of both handles (the subclasses say where the cell lives)
+        self._scenes, self._track = None, False
         if scenes is not None:
             self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
+            self._track = self._scenes.ndim == 4
             _set_scene(ctrl.ocp_solver, self._scenes)
+            if self._track:
+                for sv in (ctrl.ocp_solver, backup.ocp_solver):
+                    if not hasattr(sv, 'set_scene_clock'):
+                        raise ValueError(f'scenes: {type(sv).__name__} has no set_scene_clock')
         # stats.append(controller.getTime()) of scripts/mpc.py:239: one row of the seven time_fields per step of this group's
         # controller (host: read when step() returns; device: _DeviceGroup._read_times)
         self._collect_times = bool(collect_times) and hasattr(ctrl.ocp_solver, 'timing_history')
@@ -1027,7 +1080,8 @@ class _Group:
             else:
                 scored = score_rollout_statement(solver, pr, params, self.x_log, self.u_log, self.last_x, self.last_u,
                                                  traj=None if traj is None else xp.host(traj), want_safe=want_safe,
-                                                 per_instance=self._scenes is not None)
+                                                 per_instance=self._scenes is not None,
+                                                 scene_clock=self._clock if self._track else None)
         if xp.on_device:
             solver.sync()
         # convergence at the last step (mpc.py:273): the reference tests x_sim[-1], NaN for instances that broke
@@ -1068,6 +1122,13 @@ class _HostGroup(_Group):
         self._zeros_u = np.zeros((B, self._ctrl.nu))
         self._jt = 0                              # the step counter
         self._ever_aborted = False
+        # a scene track: the step counter as the scene clock, one cell per handle, written before the calls of a step
+        self._clock = self._backup_clock = None
+        if self._track:
+            self._clock = _new_scene_clock(self._ctrl.ocp_solver)
+            self._backup_clock = _new_scene_clock(self._backup.ocp_solver)
+            self._ctrl.ocp_solver.set_scene_clock(self._clock)
+            self._backup.ocp_solver.set_scene_clock(self._backup_clock)
 
     # ---- first half: everything up to the controller's verdict ---------------------------------------------------------------
     def part_a(self):
@@ -1099,6 +1160,7 @@ class _HostGroup(_Group):
         stepping = self.alive & ~self.sa
         if hasattr(ctrl, 'r'):
             self.r_log[self._jt] = np.where(stepping, ctrl.r, -1)
+        _write_scene_clock(self._clock, self._jt)           # node k of this step's solve and tests: time j + k
         # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
         #  read again, so they may step along)
         if self._ever_aborted:
@@ -1127,6 +1189,7 @@ class _HostGroup(_Group):
         xv_c = ctrl.getLastViableState()[rows]
         xg_c = np.repeat(xv_c[:, None, :], Nb + 1, axis=1)
         self._backup_scene(rows)
+        _write_scene_clock(self._backup_clock, j)
         xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(np.ascontiguousarray(xv_c), xg_c, np.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
         self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))
         ok_c = np.asarray(st_c) == 0
@@ -1153,7 +1216,9 @@ class _HostGroup(_Group):
         self.u_log[j] = self.u
         x_next, _ = solver.plant_step(self.x_cur, self.u, self._joints_noisy, self._tau_noise)
         # outcome tests on the new state (mpc.py:246-264): one node per instance, so the engine's box + collision test
-        # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints
+        # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints; the new state is
+        # the state of time j + 1, which is where a scene track is read
+        _write_scene_clock(self._clock, j + 1)
         okn = np.asarray(solver.check_trajectory(x_next[:, None, :]))
         self.x_log[j + 1] = x_next
         bad = self.alive & ~okn
@@ -1191,6 +1256,14 @@ class _DeviceGroup(_Group):
         if self._tau_noise is not None:
             self._tau_noise = xp.asarray(self._tau_noise, xp.f64)
         self._jt = xp.step_index(0)               # the step counter, a device tensor: smpc_loop_post advances it, graphs replay it
+        # a scene track: the step counter IS the controller handle's scene clock (smpc_loop_post reads column j + 1 and then
+        # advances it).  The backup handle solves on its own stream while the loop goes on, so its clock is a cell of its own
+        # that receives the counter's value at the abort event, on the loop's stream (handle_aborts).
+        self._clock = self._backup_clock = None
+        if self._track:
+            self._clock, self._backup_clock = self._jt, xp.step_index(0)
+            ctrl.ocp_solver.set_scene_clock(self._clock)
+            self._backup.ocp_solver.set_scene_clock(self._backup_clock)
         self._use_graphs = bool(use_graphs)
         self._graphs = {}                         # half -> captured graph
         self._u_other = xp.zeros((B, nu))
@@ -1242,6 +1315,8 @@ class _DeviceGroup(_Group):
         n_c = len(rows)
         self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))      # (xv_c goes to the host in results())
         self._pending.copy_(self.new_abort)
+        if self._backup_clock is not None:
+            self._backup_clock.copy_(self._jt)               # (the previous event's solve has finished: _apply_inflight above)
         main = torch.cuda.current_stream()
         ev0 = torch.cuda.Event()
         ev0.record(main)
@@ -1372,6 +1447,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     solves and tests, the plant's outcome test, the scores and the backup OCP of an abort event all run in the instance's scene;
     the result gains ``'scenes'``, and the controller's and the backup solver's handles are left without a scene when the run ends.
     Not with the parallel policy (ValueError): its solver works on B x N candidate slots, which are not instances.
+    ``scenes`` [B, T, n_rows, 8] (``OcpProblem.scene_track`` / ``moving_scenes``): obstacles that MOVE, a scene per instance and
+    time column (solver.set_instance_scene_track).  The loop's step counter j is the scene clock of both handles: node k of
+    step j's solve and tests is formed in column min(j + k, T - 1), the plant's new state is tested in column min(j + 1, T - 1),
+    state j of the log is scored there, and the backup OCP of an abort event at step j is solved at clock j in the aborting
+    instances' tracks.  Both handles are left without a track and without a clock when the run ends.
     ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
     task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
     jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle
@@ -1384,8 +1464,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
             raise ValueError("scenes: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
                              "the engine refuses a scene there)")
         scenes = np.ascontiguousarray(scenes, np.float64)
-        if scenes.ndim != 3 or scenes.shape[0] != B:
-            raise ValueError(f'scenes: expected [{B}, n_rows, 8], got {scenes.shape}')
+        if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
+            raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)

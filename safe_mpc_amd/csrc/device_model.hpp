@@ -297,6 +297,32 @@ __device__ __forceinline__ DQ<NQ> ball_segment_dist2(const DV3<NQ>& A, const DV3
 template <bool SCENE> struct RowGeom {
     const double *C, *D, *offset;
 };
+// A scene that moves along the horizon (smpc_set_instance_scene_track): geom = [B][T][n_rows][SMPC_SCENE_ROW], one scene per
+// (instance, time column); a scene that stands still is the track with T = 1.  clock: the device cell of smpc_set_scene_clock
+// (null: time 0; the engine passes null for T = 1, so the cell is not read then), off: what the launcher adds to it
+// (smpc_loop_post tests the plant's NEXT state).  The kernels take it by value as their last argument and do not touch it
+// when SCENE is false -- there the argument stays the null pointer it was before tracks existed (SceneArg), so that the
+// shared-scene instantiations keep their signatures, and with them their code.
+struct SceneSrc {
+    const double* geom = nullptr;
+    const int64_t* clock = nullptr;
+    int64_t T = 1;
+    int64_t off = 0;
+};
+template <bool SCENE> using SceneArg = std::conditional_t<SCENE, SceneSrc, const double* __restrict__>;
+// THE column rule (include/smpc.h): the scene at time c is column clamp(c, 0, T - 1)
+__device__ __forceinline__ int64_t scene_col(int64_t c, int64_t T) { return c < 0 ? 0 : (c < T ? c : T - 1); }
+// the time of a kernel's node 0: one uniform load per kernel (held to +-2^62, so that adding a node index cannot wrap)
+__device__ __forceinline__ int64_t scene_time(const SceneSrc& sc) {
+    constexpr int64_t LIM = (int64_t)1 << 62;
+    const int64_t t = sc.clock ? *sc.clock : 0;
+    return (t < -LIM ? -LIM : (t > LIM ? LIM : t)) + sc.off;
+}
+// instance b's [n_rows][SMPC_SCENE_ROW] block at time c: what row_geom takes as geom_b.  (The kernels call the two under
+// `if constexpr (SCENE)`, so that a shared-scene instantiation holds not one expression more than it did.)
+__device__ __forceinline__ const double* scene_block(const SceneSrc& sc, long b, int64_t c, int n_rows) {
+    return sc.geom + ((size_t)b * (size_t)sc.T + (size_t)scene_col(c, sc.T)) * n_rows * SMPC_SCENE_ROW;
+}
 template <bool SCENE>
 __device__ __forceinline__ RowGeom<SCENE> row_geom(const smpc_row& row, const double* __restrict__ geom_b, int r) {
     if constexpr (SCENE) {

@@ -65,8 +65,11 @@ struct smpc_handle {
     DevBuf<double> d_zl;            // [N+1] run-time slack weights of the soft safe-set rows (cost_set); empty: the formulation's
     DevBuf<double> d_lo_b, d_hi_b;  // [B][N+1][nx] per-instance bounds (RealReceding), valid for inst_B
     int inst_B = 0;
-    DevBuf<double> d_scene;         // [B][n_rows][SMPC_SCENE_ROW] per-instance obstacle geometry (smpc_set_instance_scene), valid for scene_B
+    DevBuf<double> d_scene;         // [B][T][n_rows][SMPC_SCENE_ROW] per-instance obstacle geometry along time (smpc_set_instance_scene_track;
+                                    // smpc_set_instance_scene: T = 1), valid for scene_B
     int scene_B = 0;                // 0: no scene, every launcher takes the shared-scene kernels
+    int64_t scene_T = 1;            // time columns of d_scene
+    const int64_t* scene_clock = nullptr;   // the caller's device cell of smpc_set_scene_clock; null: time 0
     DevBuf<double> d_curves;        // [B][3][L] per-instance reference curves (smpc_set_instance_curves), valid for curves_B / curves_L
     int curves_B = 0;               // 0: no curves, the policy step and the score take the caller's shared table (or none)
     int64_t curves_L = 0;
@@ -453,11 +456,13 @@ int scene_guard(smpc_handle* h, int B, const char* who) {
                     "it or set one of this size)", who, B, h->scene_B);
     return SMPC_OK;
 }
-// f(std::true_type{}, geom) with the handle's scene when it was set for B instances, else f(std::false_type{}, nullptr): a launcher
+// f(std::true_type{}, sc) with the handle's scene track when it was set for B instances, else f(std::false_type{}, nullptr): a launcher
 // names its kernel and its arguments once, as with with_rows below.  (The SCENE instantiation first: a kernel's place in the code
-// object follows its first mention, see ensure_batch.)
-template <class F> int with_scene(const smpc_handle* h, int B, F&& f) {
-    if (h->scene_B == B) return f(std::true_type{}, (const double*)h->d_scene.p);
+// object follows its first mention, see ensure_batch.)  off: added to the clock (smpc_loop_post); clocked = false: the kernel
+// counts time from 0 (smpc_score_rollout).  A single column needs no time, so the clock is not handed on with T = 1.
+template <class F> int with_scene(const smpc_handle* h, int B, F&& f, int64_t off = 0, bool clocked = true) {
+    if (h->scene_B == B)
+        return f(std::true_type{}, SceneSrc{h->d_scene.p, clocked && h->scene_T > 1 ? h->scene_clock : nullptr, h->scene_T, off});
     return f(std::false_type{}, (const double*)nullptr);
 }
 
@@ -499,9 +504,9 @@ int launch_eval(smpc_handle* h, int B, const double* d_xg, const double* d_ug, c
     const int N = h->N;
     hipStream_t s = h->stream;
     const long n1 = (long)B * (N + 1);
-    with_scene(h, B, [&](auto SCENE, const double* geom) {
+    with_scene(h, B, [&](auto SCENE, auto sc) {
         hipLaunchKernelGGL((k_node_linearise<NQ, SCENE>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
-                           d_p, d_ev, geom);
+                           d_p, d_ev, sc);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -565,9 +570,9 @@ int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* 
     const double* nn = h->desc.nn_mode != SMPC_NN_NONE ? h->d_nn.p : nullptr;
     int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
     with_rows(h, [&](auto MR) {
-        return with_scene(h, B, [&](auto SCENE, const double* geom) {
+        return with_scene(h, B, [&](auto SCENE, auto sc) {
             hipLaunchKernelGGL((k_stage_build<NQ, MR, SCENE>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi,
-                               h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, geom);
+                               h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, sc);
             return SMPC_OK;
         });
     });
@@ -754,9 +759,11 @@ int upload_check_bounds(smpc_handle* h, const double* x_min, const double* x_max
 }
 
 // state test (+ safe-set test if d_nn) of B trajectories of n_nodes nodes on the device, against the uploaded check bounds;
-// collision rows on the leading coll_nodes nodes only
+// collision rows on the leading coll_nodes nodes only.  scene_off: node k sits at time clock + scene_off + k of a scene track (1 for
+// smpc_loop_post, whose one node is the plant's next state).
 int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, double tol_x, int coll_nodes, double alpha,
-                    double tol_safe, int32_t* d_ok, int32_t* d_nn, bool nn_listed = false, bool ok_prefilled = false) {
+                    double tol_safe, int32_t* d_ok, int32_t* d_nn, bool nn_listed = false, bool ok_prefilled = false,
+                    int64_t scene_off = 0) {
     hipStream_t s = h->stream;
     const size_t M = (size_t)B * n_nodes;
     const ChkBlock c = chk_block(h->chk.d.p, h->desc.nq);
@@ -767,13 +774,13 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
     //  millisecond: k_policy_post, six blocks of four waves, averaged 131 us in the three-stream loop; rocprofv3, round 3)
     const dim3 grd((unsigned)((M + 63) / 64)), blk(64);
     int rc;
-    if ((rc = with_scene(h, B, [&](auto SCENE, const double* geom) {
+    if ((rc = with_scene(h, B, [&](auto SCENE, auto sc) {
              return with_nq(h, [&](auto NQ) {
                  hipLaunchKernelGGL((k_check_nodes<NQ, SCENE>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, c.x_min, c.x_max, tol_x, c.row_lb,
-                                    c.row_ub, d_ok, coll_nodes, geom);
+                                    c.row_ub, d_ok, coll_nodes, sc);
                  return SMPC_OK;
              });
-         })))
+         }, scene_off)))
         return rc;
     HIPCHK(h, hipGetLastError());
     if (d_nn) {
@@ -1097,8 +1104,8 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
         if ((rc = run_mlp<NQ>(h, M, 3, N, xn, false))) return rc;
         y = h->d_y.p;
     }
-    with_scene(h, B, [&](auto SCENE, const double* geom) {
-        hipLaunchKernelGGL((k_merit<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out, geom);
+    with_scene(h, B, [&](auto SCENE, auto sc) {
+        hipLaunchKernelGGL((k_merit<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out, sc);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -1153,10 +1160,10 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
         y = h->d_y.p;
     }
     const GchkBlock c = gchk_block(h->gchk.d.p, NQ);
-    with_scene(h, B, [&](auto SCENE, const double* geom) {
+    with_scene(h, B, [&](auto SCENE, auto sc) {
         hipLaunchKernelGGL((k_check_guess<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
                            par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, c.x_min, c.x_max, c.tau_min, c.tau_max,
-                           c.row_lb, c.row_ub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, geom);
+                           c.row_lb, c.row_ub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, sc);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -1193,10 +1200,10 @@ int launch_ik(smpc_handle* h, int B, int S, const double* target, const double* 
               double* q_out, int32_t* info, double* resid) {
     hipStream_t s = h->stream;
     const IkbBlock c = ikb_block(h->ikb.d.p);
-    with_scene(h, B, [&](auto SCENE, const double* geom) {
+    with_scene(h, B, [&](auto SCENE, auto sc) {
         hipLaunchKernelGGL((k_ik<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, S, target, q_start, (int)par->max_iter, par->tol_ee,
                            par->push, par->damping, par->damping_accept, par->damping_reject, par->damping_min, par->damping_max, c.q_lo,
-                           c.q_hi, c.row_lb, c.row_ub, mask, q_out, info, resid, geom);
+                           c.q_hi, c.row_lb, c.row_ub, mask, q_out, info, resid, sc);
         return SMPC_OK;
     });
     HIPCHK(h, hipGetLastError());
@@ -1269,11 +1276,11 @@ int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const 
     const ScoreScratch w = score_layout(h->d_score.p, B, n_seg);
     const SchkBlock c = schk_block(h->schk.d.p, NQ);
     const unsigned gb = (unsigned)((B + 63) / 64);
-    with_scene(h, B, [&](auto SCENE, const double* geom) {
+    with_scene(h, B, [&](auto SCENE, auto sc) {
         hipLaunchKernelGGL((k_score_seg<NQ, SCENE>), dim3(gb, (unsigned)n_seg), dim3(64), 0, s, h->d_desc, B, n_steps, x_log, u_log, last_x,
-                           last_u, c.x_min, c.x_max, c.row_lb, c.row_ub, c.ee_ref, traj, traj_len, traj_stride, mask, w.pd, w.pi, geom);
+                           last_u, c.x_min, c.x_max, c.row_lb, c.row_ub, c.ee_ref, traj, traj_len, traj_stride, mask, w.pd, w.pi, sc);
         return SMPC_OK;
-    });
+    }, 0, false);      // (a log starts at time 0: state j in column col(j), whatever the clock says)
     HIPCHK(h, hipGetLastError());
     if (par->want_safe) {
         const long total = (long)(n_steps + 1) * B;
@@ -1523,36 +1530,52 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
     return SMPC_OK;
 }
 
-int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device) {
+int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
-    if (!geom) { h->scene_B = 0; return SMPC_OK; }
+    if (!geom) { h->scene_B = 0; h->scene_T = 1; return SMPC_OK; }
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    if (T < 1) return fail(h, SMPC_EINVAL, "smpc_set_instance_scene_track: T=%lld: a track has at least one time column", (long long)T);
     const int nr = h->desc.n_rows;
     if (nr == 0) return fail(h, SMPC_EINVAL, "the problem has no collision rows: there is no scene to set");
-    const size_t n = (size_t)B * nr * SMPC_SCENE_ROW;
+    const size_t n = (size_t)B * (size_t)T * nr * SMPC_SCENE_ROW;
     if (!on_device) {
         // the fields a row's kind reads must be finite (device pointers are taken as they are: reading them back would synchronise)
-        for (int b = 0; b < B; b++)
+        for (size_t bt = 0; bt < (size_t)B * (size_t)T; bt++)
             for (int r = 0; r < nr; r++) {
-                const double* g = geom + ((size_t)b * nr + r) * SMPC_SCENE_ROW;
+                const double* g = geom + (bt * nr + r) * SMPC_SCENE_ROW;
                 const int kind = h->desc.rows[r].kind;
                 const int lo = kind == SMPC_ROW_COORD ? 6 : 0;
                 const int hi = kind == SMPC_ROW_SEG_FIXEDSEG ? 6 : (kind == SMPC_ROW_SEG_POINT || kind == SMPC_ROW_POINT_POINT ? 3 : (kind == SMPC_ROW_COORD ? 7 : 0));
                 for (int i = lo; i < hi; i++)
-                    if (!(g[i] - g[i] == 0.0))
-                        return fail(h, SMPC_EINVAL, "scene of instance %d, row %d (kind %d): entry %d is not finite", b, r, kind, i);
+                    if (!(g[i] - g[i] == 0.0)) {
+                        if (T == 1) return fail(h, SMPC_EINVAL, "scene of instance %d, row %d (kind %d): entry %d is not finite", (int)bt, r, kind, i);
+                        return fail(h, SMPC_EINVAL, "scene track of instance %d, column %lld, row %d (kind %d): entry %d is not finite",
+                                    (int)(bt / (size_t)T), (long long)(bt % (size_t)T), r, kind, i);
+                    }
             }
     }
     int rc;
-    // (grown only when the scene grows: a caller that moves its obstacles every step pays one stream-ordered copy)
+    // (grown only when the track grows: a caller that moves its obstacles every step pays one stream-ordered copy)
     if ((rc = h->d_scene.reserve(h, "instance scene", n * sizeof(double)))) {
-        if (!h->d_scene.p) h->scene_B = 0;      // (a failed growth left no buffer; a refused one keeps the old scene)
+        if (!h->d_scene.p) { h->scene_B = 0; h->scene_T = 1; }      // (a failed growth left no buffer; a refused one keeps the old scene)
         return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_scene.p, geom, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
     h->scene_B = B;
+    h->scene_T = T;
+    return SMPC_OK;
+}
+
+// a scene that stands still: the track of one column
+int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_device) {
+    return smpc_set_instance_scene_track(h, B, 1, geom, on_device);
+}
+
+int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock) {
+    if (!h) return SMPC_EINVAL;
+    h->scene_clock = d_clock;      // (read by the kernels when they run, never here)
     return SMPC_OK;
 }
 
@@ -2003,7 +2026,7 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     if ((rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
     if ((rc = smpc_plant_step(h, B, ls->x_cur, u, joints_noisy, tau_noise, w.xn, nullptr, 1))) return rc;
     // one node per instance: the model bounds widened by tol_x and the rows against their check bounds = checkStateConstraints
-    if ((rc = check_nodes_dev(h, B, 1, w.xn, par->tol_x, 1, 0.0, 0.0, w.okn, nullptr))) return rc;
+    if ((rc = check_nodes_dev(h, B, 1, w.xn, par->tol_x, 1, 0.0, 0.0, w.okn, nullptr, false, false, 1))) return rc;
     hipLaunchKernelGGL(k_loop_post, dim3((B + 63) / 64), dim3(64), 0, s, B, nq, u, w.xn, w.okn, ls->step, ls->x_log, ls->u_log,
                        ls->alive, ls->collided, ls->last_x, ls->last_u, ls->x_cur);
     hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(1), 0, s, ls->step);

@@ -659,14 +659,14 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
 }
 
 // Standalone launch: one wavefront = 8 nodes.  Node index t over (instance, stage); instances the policy layer masks out are skipped.
-// SCENE: geom = [B][n_rows][SMPC_SCENE_ROW], the handle's copy of the per-instance scene (unused and null otherwise).
+// SCENE: sc = the handle's scene track; stage k reads column scene_col(time + k) of its instance (unused otherwise).
 template <int NQ, int MRT, bool SCENE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB_WAVES))) void k_stage_build(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                                     const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ pp,
                                                     const double* __restrict__ lo_st, const double* __restrict__ hi_st,
                                                     const double* __restrict__ zl_st, const double* __restrict__ nn, double* __restrict__ ws_all,
                                                     long bnd_stride, const uint8_t* __restrict__ active, int32_t* __restrict__ zero_cnt,
-                                                    const double* __restrict__ geom = nullptr) {
+                                                    const SceneArg<SCENE> sc = {}) {
     constexpr int NX = 2 * NQ, NU = NQ;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     using LD = SbLds<NQ, MR_MAX>;
@@ -689,9 +689,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB
     const double* uk = ug + ((size_t)b * N + (k < N ? k : N - 1)) * NU;
     const double* pk = pp + ((size_t)b * (N + 1) + k) * SMPC_NP;
     const size_t bo = (size_t)b * bnd_stride + (size_t)k * NX;
+    const double* geom_b = nullptr;
+    if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc) + k, Ly.MR);
     stage_build<NQ, MRT, SCENE>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
                                 nn ? nn + (D->nn_mode == SMPC_NN_TERMINAL ? (size_t)b : (size_t)b * (N + 1) + k) * (1 + NX) : nullptr, w,
-                                SCENE ? geom + (size_t)b * Ly.MR * SMPC_SCENE_ROW : nullptr);
+                                geom_b);
 }
 
 }  // namespace smpc

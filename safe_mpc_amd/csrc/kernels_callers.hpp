@@ -103,12 +103,12 @@ __device__ __forceinline__ bool node_rows_ok(const smpc_problem_desc* __restrict
 
 // checkStateConstraints over trajectories (env_model.py:170-173, 236-243): bounds with tolerance + collision rows within
 // the check bounds.  One thread per (instance, node); instance verdicts are AND-ed with an atomic.
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
 template <int NQ, bool SCENE = false>
 __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, int n_nodes, const double* __restrict__ x,
                               const double* __restrict__ x_min, const double* __restrict__ x_max, double tol_x,
                               const double* __restrict__ row_lb, const double* __restrict__ row_ub,
-                              int32_t* __restrict__ state_ok, int coll_nodes, const double* __restrict__ geom = nullptr) {
+                              int32_t* __restrict__ state_ok, int coll_nodes, const SceneArg<SCENE> sc = {}) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)B * n_nodes) return;
     const double* xk = x + t * 2 * NQ;
@@ -119,7 +119,8 @@ __global__ void k_check_nodes(const smpc_problem_desc* __restrict__ D, int B, in
         if (!ok) atomicAnd(&state_ok[t / n_nodes], 0);
         return;
     }
-    const double* const geom_b = SCENE ? geom + (size_t)(t / n_nodes) * D->n_rows * SMPC_SCENE_ROW : nullptr;
+    const double* geom_b = nullptr;
+    if constexpr (SCENE) geom_b = scene_block(sc, t / n_nodes, scene_time(sc) + t % n_nodes, D->n_rows);
     ok = node_rows_ok<NQ, SCENE>(D, xk, ok, row_lb, row_ub, geom_b);
     if (!ok) atomicAnd(&state_ok[t / n_nodes], 0);
 }

@@ -38,7 +38,7 @@ __global__ void k_guess_nn_list(int B, int N, int safe_node, const uint8_t* __re
 //   worst[4]  -g at node safe_node, g as k_check_nn forms it; -inf and bit clear if safe_node < 0
 //                                                                        passes when g >= -tol_safe && g <= 1e6 + tol_safe
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
 template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
                                                     const double* __restrict__ ug, double tol_x, double tol_tau, double tol_dyn,
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
                                                     const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                     const uint8_t* __restrict__ mask, const float* __restrict__ y,
                                                     const int32_t* __restrict__ pos, int32_t* __restrict__ flags,
-                                                    double* __restrict__ worst, const double* __restrict__ geom = nullptr) {
+                                                    double* __restrict__ worst, const SceneArg<SCENE> sc = {}) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     __shared__ double s_sim[(SMPC_MAX_N + 1) * NX];
@@ -89,7 +89,8 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
             double* const spt = s_pts + k;
             point_column_fixed(D, spt);
             point_column_fk<NQ>(D, q, spt);
-            const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
+            const double* geom_b = nullptr;
+            if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc) + k, nrows);
             for (int r = 0; r < nrows; r++) {
                 const double rv = row_value<0, SCENE>(D->rows[r], row_geom<SCENE>(D->rows[r], geom_b, r), [&](int i) { return column_point(spt, i); }).v;
                 w_row = nanmax(w_row, nanmax(row_lb[r] - rv, rv - row_ub[r]));

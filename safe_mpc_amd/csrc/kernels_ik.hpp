@@ -154,7 +154,7 @@ template <int NQ> __device__ __forceinline__ void ik_solve(const double* A, cons
 // +inf, ties go to the lowest lane).  The winner's lane writes q_out[b], info[b] = {its index, number of successful starts} and
 // resid[b] = {|ee - target|_inf, margin}.  No atomics, no LDS, nothing depends on B or on another instance.
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// SCENE: the rows' fixed obstacles from the scene track sc, column scene_col(time), instead of the descriptor.
 template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_ik(const smpc_problem_desc* __restrict__ D, int B, int S, const double* __restrict__ target,
                                            const double* __restrict__ q_start, int max_iter, double tol_ee, double push, double lam0,
@@ -162,14 +162,15 @@ __global__ __launch_bounds__(64) void k_ik(const smpc_problem_desc* __restrict__
                                            const double* __restrict__ q_lo, const double* __restrict__ q_hi,
                                            const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                            const uint8_t* __restrict__ mask, double* __restrict__ q_out, int32_t* __restrict__ info,
-                                           double* __restrict__ resid, const double* __restrict__ geom = nullptr) {
+                                           double* __restrict__ resid, const SceneArg<SCENE> sc = {}) {
     constexpr int NT = NQ * (NQ + 1) / 2;
     const int b = blockIdx.x, s = threadIdx.x;
     if (b >= B) return;
     if (mask && !mask[b]) return;              // (the same for every lane of the block)
     const bool live = s < S;
     const double* const tgt = target + (size_t)b * 3;
-    const double* const geom_b = SCENE ? geom + (size_t)b * D->n_rows * SMPC_SCENE_ROW : nullptr;
+    const double* geom_b = nullptr;
+    if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc), D->n_rows);
     double q[NQ];
     double F = POS_INF, ee_inf = POS_INF, margin = POS_INF;
     if (live) {

@@ -9,11 +9,11 @@
 namespace smpc {
 
 // ---- K1: geometry + cost, one thread per (b, k), k = 0..N ---------------------------------------------------------------
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor
+// SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor
 template <int NQ, bool SCENE = false>
 __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
                                               const double* __restrict__ p, double* __restrict__ out, const long t,
-                                              const double* __restrict__ geom = nullptr) {
+                                              const SceneArg<SCENE> sc = {}) {
     if (t >= (long)B * (N + 1)) return;
     constexpr int NX = 2 * NQ;
     const double* x = xg + t * NX;
@@ -68,7 +68,8 @@ __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restric
     }
     // collision rows (env_model.py:263-316)
     const int nrows = D->n_rows;
-    const double* const geom_b = SCENE ? geom + (size_t)(t / (N + 1)) * nrows * SMPC_SCENE_ROW : nullptr;
+    const double* geom_b = nullptr;
+    if constexpr (SCENE) geom_b = scene_block(sc, t / (N + 1), scene_time(sc) + t % (N + 1), nrows);
     for (int r = 0; r < nrows; r++) {
         const smpc_row& row = D->rows[r];
         const DQ<NQ> v = row_value<NQ, SCENE>(row, row_geom<SCENE>(row, geom_b, r),
@@ -130,9 +131,9 @@ template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_node_linearise(const smpc_problem_desc* __restrict__ D, int B, int N,
                                                        const double* __restrict__ xg, const double* __restrict__ ug,
                                                        const double* __restrict__ p, double* __restrict__ out,
-                                                       const double* __restrict__ geom = nullptr) {
+                                                       const SceneArg<SCENE> sc = {}) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    node_geometry<NQ, SCENE>(D, B, N, xg, p, out, t, geom);
+    node_geometry<NQ, SCENE>(D, B, N, xg, p, out, t, sc);
     node_torque<NQ>(D, B, N, xg, ug, out, t);
 }
 

@@ -36,7 +36,8 @@ __device__ __forceinline__ void score_last_rows(int b, int n_steps, const int64_
 // rows name their points by run-time index), adds |ee - ref|^2 and |u|^2 to its two sums and updates the two running maxima with
 // their places.  Rows past last_x / last_u are never loaded.  A lane whose log ends before the segment writes nothing
 // (k_score_combine does not read that segment's partial).  Partials are stored [segment][slot][B], so the stores coalesce too.
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// SCENE: the rows' fixed obstacles from the scene track sc instead of the descriptor: state j of the log in column scene_col(j)
+// (the log starts at time 0; the clock is not read).
 // traj_stride: instance b's reference table starts at traj + b * traj_stride -- 0 for the shared table, 3 * traj_len for the
 // handle's per-instance curves (smpc_set_instance_curves); a run-time argument, so the curves add no instantiation.
 template <int NQ, bool SCENE = false>
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
                                                   const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                   const double* __restrict__ ee_ref, const double* __restrict__ traj, long traj_len,
                                                   long traj_stride, const uint8_t* __restrict__ mask, double* __restrict__ pd,
-                                                  int32_t* __restrict__ pi, const double* __restrict__ geom = nullptr) {
+                                                  int32_t* __restrict__ pi, const SceneArg<SCENE> sc = {}) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x * 64 + threadIdx.x, seg = blockIdx.y;
@@ -60,7 +61,6 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
     const int j1 = lx < j0 + SCORE_SEG - 1 ? lx : j0 + SCORE_SEG - 1;      // last step of this lane in the segment
     double* const spt = s_pts + threadIdx.x;
     const int np = D->n_points, nrows = D->n_rows, eep = D->ee_point;
-    const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
     const double* const traj_b = traj ? traj + (size_t)b * traj_stride : nullptr;
     for (int pt = 0; pt < np; pt++)
         if (D->points[pt].link < 0) {
@@ -119,7 +119,9 @@ __global__ __launch_bounds__(64) void k_score_seg(const smpc_problem_desc* __res
         const double e2 = dot(del, del);
         s1 += e2;
         if (j == lx) e_last = e2;
-        // collision rows: max over the rows of max(lb - v, v - ub), rows ascending
+        // collision rows: max over the rows of max(lb - v, v - ub), rows ascending; state j of the log in the scene of time j
+        const double* geom_b = nullptr;
+        if constexpr (SCENE) geom_b = scene_block(sc, b, j, nrows);
         for (int r = 0; r < nrows; r++) {
             const double rv = sqp_row_value<SCENE>(D->rows[r], spt, row_geom<SCENE>(D->rows[r], geom_b, r));
             const double m = nanmax(row_lb[r] - rv, rv - row_ub[r]);

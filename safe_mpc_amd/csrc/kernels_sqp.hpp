@@ -86,14 +86,14 @@ __global__ void k_sqp_trial_states(int B, int per, const double* __restrict__ x,
 // out[b] = {f, viol, gd}.  Nothing per node is written.  gd = grad f . (dx, du) is formed at a_b = 0 only, from the EE point's
 // geometric Jacobian columns (which the forward kinematics has already paid for) against the lane's dq.
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
-// SCENE: the rows' fixed obstacles from geom [B][n_rows][SMPC_SCENE_ROW] (smpc_set_instance_scene) instead of the descriptor.
+// SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
 template <int NQ, bool SCENE = false>
 __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                               const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ p,
                                               const double* __restrict__ dxg, const double* __restrict__ dug,
                                               const double* __restrict__ alpha, const uint8_t* __restrict__ mask,
                                               const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out,
-                                              const double* __restrict__ geom = nullptr) {
+                                              const SceneArg<SCENE> sc = {}) {
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x, k = threadIdx.x;
@@ -174,7 +174,8 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
             }
             // collision rows of nodes 1..N
             const int nrows = D->n_rows;
-            const double* const geom_b = SCENE ? geom + (size_t)b * nrows * SMPC_SCENE_ROW : nullptr;
+            const double* geom_b = nullptr;
+            if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc) + k, nrows);
             for (int r = 0; r < nrows; r++) {
                 const smpc_row& row = D->rows[r];
                 const double rv = sqp_row_value<SCENE>(row, spt, row_geom<SCENE>(row, geom_b, r));

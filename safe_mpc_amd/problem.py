@@ -343,6 +343,14 @@ class OcpProblem:
                     g[i, 3:6] = g[i, 3:6] + d
         return g
 
+    def scene_track(self, moves):
+        """[T, n_rows, SCENE_ROW]: a scene per time column (smpc_set_instance_scene_track) -- ``moves[j]`` is the ``moves`` of
+        :meth:`scene` for column j, so ``scene_track([{}])`` is ``row_geometry()`` with a leading axis."""
+        moves = list(moves)
+        if not moves:
+            raise ValueError('scene_track: a track has at least one time column')
+        return np.stack([self.scene(m) for m in moves])
+
     # per-instance perturbed joint tables for the plant (utils.py:126-171 semantics on the lumped inertias is NOT what
     # the reference does -- it perturbs each URDF link before lumping; see noise.py)
     def joint_table(self):
@@ -388,3 +396,45 @@ def jittered_scenes(prob, B, sigma, seed=0):
         d = rng.normal(0.0, float(sigma), (len(names), 3))
         out[b] = prob.scene({n: d[i] for i, n in enumerate(names)})
     return out
+
+
+def moving_scenes(prob, B, T, sigma_v, seed=0, sigma=0.0):
+    """[B, T, n_rows, SCENE_ROW]: B constant-velocity scene tracks of ``prob`` over T time columns, one column per time step ``prob.desc.dt``.
+    Every world-fixed obstacle of instance b moves by ``v * dt`` per column, ``v ~ N(0, sigma_v^2)`` per axis, one draw per
+    (instance, obstacle) shared by all the rows that obstacle appears in (plane rows take the component along their axis, as
+    :meth:`OcpProblem.scene` does).  Column 0 is ``jittered_scenes(prob, B, sigma, seed)``: the problem's own geometry with the
+    default ``sigma = 0``."""
+    B, T = int(B), int(T)
+    if T < 1:
+        raise ValueError('moving_scenes: a track has at least one time column')
+    names = sorted({n for n in prob.row_obstacle if n is not None})
+    rng0, rngv = np.random.default_rng(seed), np.random.default_rng([int(seed), 1])
+    # the draws in the order of jittered_scenes: instance by instance, one [obstacle, axis] block each
+    d0 = np.stack([rng0.normal(0.0, float(sigma), (len(names), 3)) for _ in range(B)]).reshape(B, len(names), 3)
+    v = np.stack([rngv.normal(0.0, float(sigma_v), (len(names), 3)) for _ in range(B)]).reshape(B, len(names), 3)
+    move = d0[:, None] + v[:, None] * (float(prob.desc.dt) * np.arange(T))[None, :, None, None]      # [B, T, obstacle, axis]
+    out = np.broadcast_to(prob.row_geometry(), (B, T, len(prob.rows), SCENE_ROW)).copy()
+    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):          # OcpProblem.scene, for all (instance, column) at once
+        if name is None:
+            continue
+        d = move[:, :, names.index(name)]
+        if r.kind == ROW_COORD:
+            out[:, :, i, 6] += d[:, :, r.axis]
+        else:
+            out[:, :, i, 0:3] += d
+            if r.kind == ROW_SEG_FIXEDSEG:
+                out[:, :, i, 3:6] += d
+    return out
+
+
+def extend_tracks(tracks, T):
+    """Scene tracks [B, T0, n_rows, SCENE_ROW] continued to T columns at constant velocity -- the step between their last two
+    columns (none for T0 = 1) -- or cut to T columns: what turns the tracks stored with warm starts (one horizon long) into the
+    tracks of a closed-loop run."""
+    tracks = np.asarray(tracks, float)
+    T0, T = tracks.shape[1], int(T)
+    if T <= T0:
+        return np.ascontiguousarray(tracks[:, :max(T, 1)])
+    step = tracks[:, -1] - tracks[:, -2] if T0 > 1 else np.zeros_like(tracks[:, -1])
+    more = tracks[:, -1:, :, :] + step[:, None] * np.arange(1, T - T0 + 1)[None, :, None, None]
+    return np.concatenate([tracks, more], axis=1)

@@ -180,6 +180,45 @@ class BatchedOcpSolver:
         with self._ordered(dev):
             self._chk(self.L.smpc_set_instance_scene(self.h, B, ptrs[0], dev))
 
+    def set_instance_scene_track(self, geom=None):
+        """Obstacles that move along the horizon (smpc_set_instance_scene_track): ``geom [B, T, n_rows, 8]``, one scene of
+        :meth:`set_instance_scene`'s layout per (instance, time column) -- ``OcpProblem.scene_track`` / ``moving_scenes`` -- as a
+        numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy (64 B x n_rows x T x B).  Node k of a call is
+        formed in column ``clip(t + k, 0, T - 1)``, t = the scene clock (:meth:`set_scene_clock`; 0 without one); the table of
+        include/smpc.h says it for every entry point.  A track and a scene are one slot: setting one replaces the other, and None
+        (here or in ``set_instance_scene``) clears both."""
+        if geom is None:
+            self._chk(self.L.smpc_set_instance_scene_track(self.h, 0, 1, None, 0))
+            return
+        if _is_torch(geom):
+            import torch
+            if geom.dtype != torch.float64:
+                raise ValueError('set_instance_scene_track: the track must be float64')
+        if geom.ndim != 4:
+            raise ValueError(f'set_instance_scene_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+        B, T = int(geom.shape[0]), int(geom.shape[1])
+        if T < 1:
+            raise ValueError('set_instance_scene_track: a track has at least one time column')
+        ptrs, dev, keep = self._prep([geom], [(B, T, len(self.problem.rows), SCENE_ROW)])
+        with self._ordered(dev):
+            self._chk(self.L.smpc_set_instance_scene_track(self.h, B, T, ptrs[0], dev))
+
+    def set_scene_clock(self, clock=None):
+        """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on
+        the device whenever a kernel runs -- write to it between calls (stream-ordered, no synchronisation), or hand over the
+        step counter of a device loop.  The solver keeps a reference, so the cell lives as long as it is set.  None: time 0."""
+        if clock is None:
+            self._chk(self.L.smpc_set_scene_clock(self.h, None))
+            self._scene_clock = None
+            return
+        import torch
+        if not _is_torch(clock) or clock.dtype != torch.int64 or clock.numel() != 1 or not clock.is_cuda:
+            raise ValueError('set_scene_clock: expected a one-element int64 tensor on the device')
+        if clock.device.index != self.device:
+            raise ValueError(f'set_scene_clock: the cell is on device {clock.device.index}, the solver on {self.device}')
+        self._chk(self.L.smpc_set_scene_clock(self.h, clock.data_ptr()))
+        self._scene_clock = clock
+
     def set_instance_curves(self, curves=None):
         """A reference curve of its own for every instance of the tracking task (smpc_set_instance_curves): ``curves [B, 3, L]``
         (tracking.tracking_curves / jittered_curves), a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy

@@ -10,6 +10,10 @@ solved and tested on the device until exactly test_num guesses are accepted (clo
 --scene-jitter SIGMA [--scene-seed S]: every guess is generated in a scene of its own, every obstacle moved by its own N(0, SIGMA^2)
 draw per axis (problem.jittered_scenes); the scenes of the accepted guesses are stored in the pickle as 'scenes', where scripts/mpc.py
 --scene-jitter finds them.  Not with --until-accepted.
+--scene-velocity SIGMA: obstacles that move -- every guess is generated in a constant-velocity track of scenes, horizon + 1 time
+columns long, every obstacle with its own N(0, SIGMA^2) velocity draw per axis (problem.moving_scenes; it shares --scene-seed, and
+--scene-jitter moves the start positions); the tracks of the accepted guesses are stored as 'scenes' [n, T, n_rows, 8], which
+scripts/mpc.py --scene-velocity continues.  Not with --until-accepted.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): warm starts of the trajectory-tracking task
 (guess_acados.py:167-226 of the reference) -- every start state is an inverse-kinematics solution at the curve's first point
 (closed_loop.ik_starts, smpc_ik_batch) and the OCP follows the curve.
@@ -45,6 +49,10 @@ def main(argv=None):
     if '--scene-jitter' in raw:
         from safe_mpc_amd.problem import OcpProblem, jittered_scenes
         scenes = jittered_scenes(OcpProblem(params, 'naive'), params.test_num, opt('--scene-jitter', 0.0, float), opt('--scene-seed', 0, int))
+    if '--scene-velocity' in raw:
+        from safe_mpc_amd.problem import OcpProblem, moving_scenes
+        scenes = moving_scenes(OcpProblem(params, 'naive'), params.test_num, int(params.N) + 1, opt('--scene-velocity', 0.0, float),
+                               opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
     t0 = time.time()
     if until:
         guess, info = cl.generate_guess_until(params, gen_name, params.test_num, batch=opt('--batch', None, int),

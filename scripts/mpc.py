@@ -6,6 +6,10 @@ with every instance of its outer loop (mpc.py:102) solved at once on the MI355X 
 --scene-jitter SIGMA: every instance runs in a scene of its own -- the scenes stored with the guesses (guess_acados.py
 --scene-jitter) if there are any, else every obstacle moved by its own N(0, SIGMA^2) draw per axis (problem.jittered_scenes,
 seed --scene-seed, default 0).
+--scene-velocity SIGMA: obstacles that move -- every instance gets a constant-velocity track of scenes, n_steps + 1 + horizon time
+columns long: the tracks stored with the guesses (guess_acados.py --scene-velocity) continued at their velocity if there are any,
+else every obstacle with its own N(0, SIGMA^2) velocity draw per axis (problem.moving_scenes; seed --scene-seed, start positions
+jittered by --scene-jitter if that is given too).
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -46,6 +50,15 @@ def main(argv=None):
             from safe_mpc_amd.problem import OcpProblem, jittered_scenes
             seed = int(raw[raw.index('--scene-seed') + 1]) if '--scene-seed' in raw else 0
             scenes = jittered_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], float(raw[raw.index('--scene-jitter') + 1]), seed)
+    if '--scene-velocity' in raw:
+        from safe_mpc_amd.problem import OcpProblem, extend_tracks, moving_scenes
+        T = int(params.n_steps) + 1 + int(params.N)
+        if 'scenes' in data and data['scenes'].ndim == 4:
+            scenes = extend_tracks(data['scenes'][:params.test_num], T)
+        else:
+            opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
+            scenes = moving_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], T, opt('--scene-velocity', 0.0, float),
+                                   opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
     tm = {}
     # all loop state in HBM (policy automaton, abort handling, logs); SMPC_HOST_STATE=1 keeps it in numpy arrays instead
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],

@@ -13,7 +13,10 @@ SMPC_WARM_EVERY = iterations per round, SMPC_WARM_BATCH = device slots), so the 
 SMPC_WARM_STATS=1 runs the generation a second time with a history, to report SQP iterations and trial passes (with SMPC_WARM_UNTIL=1
 it prints the loop's own iteration counts instead).
 SMPC_SCENE_JITTER=SIGMA: every instance runs in a scene of its own (run_mpc(scenes=problem.jittered_scenes(prob, B, SIGMA)); 0 = the
-base geometry for every instance, i.e. the same world through the scene-aware kernels: the cost of a scene, profiles/instance_scenes.txt)."""
+base geometry for every instance, i.e. the same world through the scene-aware kernels: the cost of a scene, profiles/instance_scenes.txt).
+SMPC_SCENE_VELOCITY=SIGMA: every instance runs in a scene TRACK of its own, steps + 1 + N columns (run_mpc(scenes=problem.moving_scenes(prob,
+B, T, SIGMA, sigma=SMPC_SCENE_JITTER or 0)); 0 = the base geometry in every column, the same world through the track: the cost of a track,
+profiles/scene_tracks.txt)."""
 import os
 import sys
 import time
@@ -78,6 +81,10 @@ def main():
     if 'SMPC_SCENE_JITTER' in os.environ:
         from safe_mpc_amd.problem import jittered_scenes
         scenes = jittered_scenes(prob, B, float(os.environ['SMPC_SCENE_JITTER']), int(os.environ.get('SMPC_SCENE_SEED', '0')))
+    if 'SMPC_SCENE_VELOCITY' in os.environ:
+        from safe_mpc_amd.problem import moving_scenes
+        scenes = moving_scenes(prob, B, steps + 1 + N, float(os.environ['SMPC_SCENE_VELOCITY']), int(os.environ.get('SMPC_SCENE_SEED', '0')),
+                               sigma=float(os.environ.get('SMPC_SCENE_JITTER', '0')))
     for name in names:
         for dev in (True, False):
             if not dev and os.environ.get('SMPC_HOST', '0') != '1':
@@ -87,7 +94,7 @@ def main():
             res = cl.run_mpc(par, name, xg, ug, n_steps=steps, on_device=dev, timing=tm,
                              groups=int(os.environ['SMPC_GROUPS']) if 'SMPC_GROUPS' in os.environ else None,
                              graphs=os.environ.get('SMPC_GRAPHS', '1') != '0', scenes=scenes)
-            print(f"{name:12s} {'device' if dev else 'host  '} state{' (warm starts)' if warm else ''}{' (a scene per instance)' if scenes is not None else ''}: {tm['ms_per_step']:.3f} ms/step over {tm['steps']} steps "
+            print(f"{name:12s} {'device' if dev else 'host  '} state{' (warm starts)' if warm else ''}{'' if scenes is None else (' (a scene per instance)' if scenes.ndim == 3 else f' (a track of {scenes.shape[1]} scenes per instance)')}: {tm['ms_per_step']:.3f} ms/step over {tm['steps']} steps "
                   f"(B={B}, N={N}, groups {tm.get('groups')}; total {time.perf_counter() - t0:.1f} s incl. set-up) | collisions {len(res['collisions_idx'])} "
                   f"viable {len(res['viable_idx'])} converged {len(res['conv_idx'])} unconverged {len(res['unconv_idx'])} abort events {len(res['x_viable'])}", flush=True)
 
