@@ -289,6 +289,34 @@ int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
  * (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* curves, int on_device);
 
+/* A safe-set network that knows its scene: n_ctx extra inputs (a CONTEXT, numbers of the instance's scene) behind the 2 n_dof_safe_set
+ * state features.  The network's first layer is W0 = [Ws | Wc], Ws [H][2 nd] handed over by smpc_set_mlp and Wc [H][n_ctx] (row-major,
+ * H = dims[1]) here; for an instance with context c the row's value and gradient are those of the plain network with first-layer
+ * weights Ws and first-layer bias b0 + Wc ((c - ctx_mean) / ctx_std).  No derivative with respect to the context is formed.
+ * Call it after smpc_set_mlp.  ctx_default[n_ctx] is the context every row gets while no instance context is set (the shared scene's).
+ * n_ctx = 0 or Wc == NULL clears the context columns; smpc_set_mlp drops them too (new weights mean no context).  Setting or clearing
+ * also drops an instance context.  on_device != 0: all four pointers are device memory.  The call synchronises the stream.
+ * The input of layer 0 is padded to 16 columns, so n_ctx <= 16 - 2 n_dof_safe_set (4 for six joints, 2 for seven).
+ * SMPC_EINVAL (the message names the limit): n_ctx outside that range, a non-finite value, a ctx_std <= 0.
+ * SMPC_ESTATE: no network (smpc_set_mlp was not called).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const double* ctx_mean, const double* ctx_std,
+                         const double* ctx_default, int on_device);
+
+/* The context of every instance: ctx is [B][n_ctx] doubles; the handle keeps a normalised fp32 copy.  The copy is stream-ordered;
+ * with host pointers the call checks for non-finite values and waits, with device pointers a small kernel normalises.  NULL clears it
+ * (every row then gets ctx_default again).  The context is a slot of its own: the engine does not derive it from the instance scene.
+ * It belongs to ITS batch size: smpc_solve_batch, smpc_eval_nodes, smpc_merit_terms, smpc_sqp_batch, smpc_check_guess,
+ * smpc_check_trajectory, smpc_score_rollout, smpc_policy_step and smpc_debug_stage_records with another B return SMPC_EINVAL and name
+ * both sizes.  SMPC_POLICY_PARALLEL and smpc_rollout_batch return SMPC_ESTATE while it is set (candidate slots and worker handles are
+ * not instances); both run with the default context.
+ * Which instance a network row belongs to: node / (N + 1) on the [B][N+1] node arrays, node / n_nodes in smpc_check_trajectory,
+ * row % B in the step-major log of smpc_score_rollout.
+ * SMPC_EINVAL: no context columns, B <= 0, or (host pointers only) a non-finite entry.
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured (the old contents stay).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device);
+
 /* replaces ocp_solver.cost_set(k,'zl'/'zu',v) (controller.py:455-468, 526-527): L1 penalty of the slack on the safe-set row of
  * node k, for the nodes where the formulation made that row soft (nn_soft_e / nn_soft_run >= 0; a hard row has no slack and
  * acados' arrays for it are empty).  zl is [N+1] host doubles shared by all instances (entry 0 unused); NULL restores the

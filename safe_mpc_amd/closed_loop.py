@@ -313,10 +313,29 @@ def _check_scenes(scenes, B, problem):
     return g
 
 
+def _context_select(solver):
+    """the ``(row, slot)`` pairs of the solver's safe-set net if that net has a context, else None"""
+    net = getattr(solver, 'net', None)
+    if not getattr(net, 'n_ctx', 0) or not hasattr(solver, 'set_instance_context'):
+        return None
+    if not net.ctx_select:
+        raise ValueError(f'scenes: the safe-set network has {net.n_ctx} context inputs but no ctx_select that says which numbers of '
+                         f'a scene they are')
+    return net.ctx_select
+
+
 def _set_scene(solver, geom):
-    """the scenes [B, n_rows, 8], or the scene track [B, T, n_rows, 8], of a batch onto the solver (None clears either)"""
+    """the scenes [B, n_rows, 8], or the scene track [B, T, n_rows, 8], of a batch onto the solver (None clears either).  Where the
+    solver's safe-set net has a context, the instances' contexts go on and off with the scenes."""
     if not hasattr(solver, 'set_instance_scene'):
         raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene')
+    select = _context_select(solver)
+    if select is not None:
+        if geom is not None and geom.ndim == 4 and geom.shape[1] > 1:
+            raise ValueError(f'scenes: a track of T = {geom.shape[1]} time columns with a safe-set network that has a context: the '
+                             f'context is a constant of the instance, one that moves along a track is not supported')
+        from .problem import scene_context
+        solver.set_instance_context(None if geom is None else scene_context(geom.reshape((geom.shape[0],) + geom.shape[-2:]), select))
     if geom is not None and geom.ndim == 4:
         if not hasattr(solver, 'set_instance_scene_track'):
             raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene_track')
@@ -331,6 +350,8 @@ def _clear_scene(solver):
     run in the old scenes)"""
     if hasattr(solver, 'set_instance_scene'):
         solver.set_instance_scene(None)
+    if hasattr(solver, 'set_instance_context'):
+        solver.set_instance_context(None)
     if hasattr(solver, 'set_scene_clock'):
         solver.set_scene_clock(None)
 

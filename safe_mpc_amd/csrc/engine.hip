@@ -83,6 +83,14 @@ struct smpc_handle {
     float* d_Wfwd[SMPC_MAX_LAYERS] = {nullptr};  // [K][N] = W^T (layer 0 padded to MLP_KPAD rows)
     float* d_Wbwd[SMPC_MAX_LAYERS] = {nullptr};  // [out][in] as given (layer 0 padded to MLP_NPAD columns)
     float* d_bias[SMPC_MAX_LAYERS] = {nullptr};
+    // the network's context (smpc_set_mlp_context): n_ctx numbers of the instance's scene behind the 2 nn_dof
+    // state features of layer 0's input
+    int n_ctx = 0;                  // 0: a network without context columns
+    double ctx_mean[MLP_KPAD] = {0}, ctx_std[MLP_KPAD] = {0};
+    DevBuf<float> d_ctx_def;        // [MLP_KPAD] the normalised default context (empty in a worker: it borrows its parent's)
+    const float* ctx_def = nullptr; // the default row the kernels read: d_ctx_def.p, or the parent's
+    DevBuf<float> d_ctx;            // [B][n_ctx] normalised per-instance context (smpc_set_instance_context), valid for ctx_B
+    int ctx_B = 0;                  // 0: none, every row takes the default
     // per-batch scratch of the solve path (ensure_batch)
     DevBuf<double> d_ev;    // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
     DevBuf<double> d_nn;    // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
@@ -336,14 +344,29 @@ int ensure_nn_idx(smpc_handle* h, size_t M) {
     return SMPC_OK;
 }
 
+// Which instance a network row belongs to (CtxSrc, kernels_mlp.hpp): node / per on instance-major node arrays with `per` nodes per
+// instance; (m0 + m) % B on a step-major log read from flat row m0.
+CtxSrc rows_of_nodes(int per) { CtxSrc c; c.per = per; return c; }
+CtxSrc rows_step_major(int B, long m0) { CtxSrc c; c.mod = B; c.m0 = (int)(m0 % B); return c; }
+
 // forward (and optionally backward) pass of the network over M rows whose states are found through (mode, N) in x.
 // mode 3: the rows are the compacted list h->d_nn_idx of live nodes; their count is only known on the device (h->d_nn_cnt), so
 // the grids cover all M candidate rows and the blocks past the count return at once.
 // d_p / d_ev: when given and the pass ran as the fused kernel, the chain rule to the node records is done as well and *chained
 // is set (the caller then skips k_nn_chain).
-template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const double* d_x, bool backward, const double* d_p = nullptr,
-                              double* d_ev = nullptr, bool* chained = nullptr, int compact = 0) {
+// rows: which instance a row belongs to (rows_of_nodes / rows_step_major), for the context of a network that has one; the table it
+// indexes is the handle's.
+template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const double* d_x, bool backward, CtxSrc rows,
+                              const double* d_p = nullptr, double* d_ev = nullptr, bool* chained = nullptr, int compact = 0) {
     int rc;
+    // the instances' own rows when they are set (every entry point has checked its B against ctx_B: ctx_guard), else the default row
+    // for all; without context columns the kernels' context loop has no iteration
+    CtxSrc cx = rows;
+    if (h->n_ctx > 0) {
+        cx.n = h->n_ctx;
+        cx.p = h->ctx_B ? h->d_ctx.p : h->ctx_def;
+        cx.stride = h->ctx_B ? h->n_ctx : 0;
+    }
     const int Mp = (M + 127) / 128 * 128, H = h->H, L = h->nlayers;
     hipStream_t s = h->stream;
     const int32_t* idx = mode == 3 ? h->d_nn_idx.p : nullptr;
@@ -363,10 +386,10 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(256);
             if (backward)
                 hipLaunchKernelGGL((k_mlp_fused<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
-                                   compact);
+                                   compact, cx);
             else
                 hipLaunchKernelGGL((k_mlp_fused<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
-                                   (double*)nullptr, 0);
+                                   (double*)nullptr, 0, cx);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
             return SMPC_OK;
@@ -382,10 +405,10 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(64);
             if (backward)
                 hipLaunchKernelGGL((k_mlp_wave<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
-                                   compact, h->d_dg[0].p, h->d_dg[1].p, h->d_dg[2].p);
+                                   compact, h->d_dg[0].p, h->d_dg[1].p, h->d_dg[2].p, cx);
             else
                 hipLaunchKernelGGL((k_mlp_wave<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
-                                   (double*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+                                   (double*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, cx);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
             return SMPC_OK;
@@ -393,7 +416,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     }
     if ((rc = ensure_mlp(h, (size_t)M))) return rc;
     hipLaunchKernelGGL((k_nn_features<NQ>), dim3((Mp + 63) / 64), dim3(64), 0, s, h->d_desc, M, Mp, N, mode, d_x,
-                       h->d_S.p, idx, live);
+                       h->d_S.p, idx, live, cx);
     // The layer-by-layer GEMMs (round 4): k_gemm_f32 as ONE-WAVE blocks -- a wavefront of it is self-contained (32 x 64 tile,
     // operands from L2, 90-130 registers, no LDS), so its blocks start on any SIMD with one free slot.  A 128 x 128 LDS-tiled kernel
     // (256-thread blocks: 200 registers per lane on all four SIMDs of one CU at once + 37 KB of LDS), since retired, was 12 % faster
@@ -438,7 +461,7 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
         hipLaunchKernelGGL(k_nn_compact, dim3((M + 63) / 64), dim3(64), 0, s, M, N, d_p, h->d_nn_idx.p, h->d_nn_cnt);
     }
     bool chained = false;
-    if ((rc = run_mlp<NQ>(h, M, mode, N, d_xg, true, d_p, d_out, &chained, compact))) return rc;
+    if ((rc = run_mlp<NQ>(h, M, mode, N, d_xg, true, rows_of_nodes(N + 1), d_p, d_out, &chained, compact))) return rc;
     if (!chained)
         hipLaunchKernelGGL((k_nn_chain<NQ>), dim3((M + 63) / 64), dim3(64), 0, s, h->d_desc, M, N, mode, d_xg, d_p,
                            h->d_y.p, h->d_GS.p, d_out, mode == 3 ? h->d_nn_idx.p : (const int32_t*)nullptr,
@@ -464,6 +487,15 @@ template <class F> int with_scene(const smpc_handle* h, int B, F&& f, int64_t of
     if (h->scene_B == B)
         return f(std::true_type{}, SceneSrc{h->d_scene.p, clocked && h->scene_T > 1 ? h->scene_clock : nullptr, h->scene_T, off});
     return f(std::false_type{}, (const double*)nullptr);
+}
+
+// The instance context belongs to its batch size in the same way: every entry point that runs the network refuses another B while
+// one is set, never the default context instead.
+int ctx_guard(smpc_handle* h, int B, const char* who) {
+    if (h->ctx_B && h->ctx_B != B)
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance context was set for %d instances (smpc_set_instance_context: "
+                    "clear it or set one of this size)", who, B, h->ctx_B);
+    return SMPC_OK;
 }
 
 // The curves belong to their batch size in the same way: the two entry points that read them refuse another B while they are set,
@@ -786,7 +818,7 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
     if (d_nn) {
         // nn_listed: only the nodes in h->d_nn_idx (length on the device, h->d_nn_cnt) are evaluated; their verdicts land at the
         // nodes' own positions of d_nn, the rest of d_nn is left as it is
-        if ((rc = with_nq(h, [&](auto NQ) { return run_mlp<NQ>(h, (int)M, nn_listed ? 3 : 0, 0, d_x, false); }))) return rc;
+        if ((rc = with_nq(h, [&](auto NQ) { return run_mlp<NQ>(h, (int)M, nn_listed ? 3 : 0, 0, d_x, false, rows_of_nodes(n_nodes)); }))) return rc;
         const int32_t* li = nn_listed ? h->d_nn_idx.p : nullptr;
         const int32_t* lc = nn_listed ? h->d_nn_cnt : nullptr;
         if ((rc = with_nq(h, [&](auto NQ) {
@@ -865,6 +897,8 @@ int rollout_workers(smpc_handle* h, int n) {
         k->H = h->H;
         for (int l = 0; l <= SMPC_MAX_LAYERS; l++) k->dims[l] = h->dims[l];
         for (int l = 0; l < SMPC_MAX_LAYERS; l++) { k->d_Wfwd[l] = h->d_Wfwd[l]; k->d_Wbwd[l] = h->d_Wbwd[l]; k->d_bias[l] = h->d_bias[l]; }
+        k->n_ctx = h->n_ctx;            // (with the weights goes the default context; a worker holds no instance context)
+        k->ctx_def = h->ctx_def;
         // stage bounds and slack weights follow the parent (small; stream-ordered on the worker's stream)
         const size_t nb = (size_t)(h->N + 1) * 2 * h->desc.nq;
         HIPCHK(h, hipMemcpyAsync(k->d_lo.p, h->d_lo.p, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
@@ -994,7 +1028,7 @@ int policy_step_parallel(smpc_handle* h, int B, const smpc_policy_params* par, c
             hipLaunchKernelGGL((k_par_check_state<NQ>), grid(M), blk, 0, s, h->d_desc, (int)S, N, c.n_open, c.xo, cb.x_min, cb.x_max, par->tol_x,
                                cb.row_lb, cb.row_ub, c.st, c.ok, coll);
             HIPCHK(h, hipGetLastError());
-            if (const int e = run_mlp<NQ>(h, (int)M, 3, 0, c.xo, false)) return e;
+            if (const int e = run_mlp<NQ>(h, (int)M, 3, 0, c.xo, false, rows_of_nodes(N + 1))) return e;
             hipLaunchKernelGGL((k_check_nn<NQ>), grid(M), blk, 0, s, h->d_desc, (int)M, c.xo, par->alpha, par->tol_safe, h->d_y.p, c.safe,
                                h->d_nn_idx.p, h->d_nn_cnt);
             HIPCHK(h, hipGetLastError());
@@ -1101,7 +1135,7 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
         hipLaunchKernelGGL(k_sqp_nn_list, dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, s, B, N, terminal, p, mask, h->d_nn_idx.p, w.pos,
                            h->d_nn_cnt);
         HIPCHK(h, hipGetLastError());
-        if ((rc = run_mlp<NQ>(h, M, 3, N, xn, false))) return rc;
+        if ((rc = run_mlp<NQ>(h, M, 3, N, xn, false, rows_of_nodes(N + 1)))) return rc;
         y = h->d_y.p;
     }
     with_scene(h, B, [&](auto SCENE, auto sc) {
@@ -1156,7 +1190,7 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
         hipLaunchKernelGGL(k_guess_nn_list, dim3((B + 63) / 64), dim3(64), 0, s, B, N, (int)par->safe_node, mask, h->d_nn_idx.p, h->d_guess.p,
                            h->d_nn_cnt);
         HIPCHK(h, hipGetLastError());
-        if ((rc = run_mlp<NQ>(h, B, 3, N, x, false))) return rc;
+        if ((rc = run_mlp<NQ>(h, B, 3, N, x, false, rows_of_nodes(N + 1)))) return rc;
         y = h->d_y.p;
     }
     const GchkBlock c = gchk_block(h->gchk.d.p, NQ);
@@ -1286,7 +1320,7 @@ int launch_score(smpc_handle* h, int B, int n_steps, const double* x_log, const 
         const long total = (long)(n_steps + 1) * B;
         for (long m0 = 0; m0 < total; m0 += SCORE_MLP_ROWS) {
             const long rows = total - m0 < SCORE_MLP_ROWS ? total - m0 : SCORE_MLP_ROWS;
-            if ((rc = run_mlp<NQ>(h, (int)rows, 0, 0, x_log + m0 * nx, false))) return rc;
+            if ((rc = run_mlp<NQ>(h, (int)rows, 0, 0, x_log + m0 * nx, false, rows_step_major(B, m0)))) return rc;
             hipLaunchKernelGGL((k_score_safe<NQ>), dim3(gb), dim3(64), 0, s, h->d_desc, B, n_steps, m0, rows, m0 == 0 ? 1 : 0, x_log, last_x,
                                last_u, par->alpha, mask, (const float*)h->d_y.p, w.gmin, w.gstep);
             HIPCHK(h, hipGetLastError());
@@ -1421,6 +1455,8 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
     for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers borrow the weight buffers rewritten below)
     h->kids.clear();
     h->nlayers = 0;     // (no network until every layer is in place)
+    h->n_ctx = 0;       // (new weights mean no context: layer 0's context rows are rewritten as zeros below)
+    h->ctx_B = 0;
     // one block for every layer's W^T (layer 0 padded to MLP_KPAD rows), W (layer 0 padded to MLP_NPAD columns) and b
     const auto layout = [&](char* base) {
         Carve m{base};
@@ -1462,6 +1498,101 @@ int smpc_set_mlp_activation(smpc_handle* h, int act) {
     if (act < SMPC_ACT_GELU_TANH || act > SMPC_ACT_SILU) return fail(h, SMPC_EINVAL, "unknown activation %d", act);
     h->act = act;
     for (smpc_handle* k : h->kids) k->act = act;
+    return SMPC_OK;
+}
+
+int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const double* ctx_mean, const double* ctx_std,
+                         const double* ctx_default, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if (h->nlayers == 0) return fail(h, SMPC_ESTATE, "smpc_set_mlp_context: smpc_set_mlp was not called");
+    const int nd2 = 2 * h->desc.nn_dof, room = MLP_KPAD - nd2, H = h->dims[1];
+    if (n_ctx < 0 || n_ctx > room)
+        return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: n_ctx=%d outside 0..%d: layer 0's input is padded to %d columns and the state "
+                    "takes 2*n_dof_safe_set = %d of them", n_ctx, room, MLP_KPAD, nd2);
+    const bool clear = n_ctx == 0 || !Wc;
+    if (!clear && (!ctx_mean || !ctx_std || !ctx_default)) return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: null argument");
+    (void)hipSetDevice(h->device);
+    std::vector<float> wc;
+    double mean[MLP_KPAD] = {0}, std_[MLP_KPAD] = {0}, def[MLP_KPAD] = {0};
+    if (!clear) {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+        wc.resize((size_t)H * n_ctx);
+        HIPCHK(h, hipMemcpy(wc.data(), Wc, wc.size() * sizeof(float), kind));
+        HIPCHK(h, hipMemcpy(mean, ctx_mean, sizeof(double) * n_ctx, kind));
+        HIPCHK(h, hipMemcpy(std_, ctx_std, sizeof(double) * n_ctx, kind));
+        HIPCHK(h, hipMemcpy(def, ctx_default, sizeof(double) * n_ctx, kind));
+        for (size_t i = 0; i < wc.size(); i++)
+            if (!(wc[i] - wc[i] == 0.0f))
+                return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: Wc[%zu][%zu] is not finite", i / n_ctx, i % n_ctx);
+        for (int c = 0; c < n_ctx; c++) {
+            if (!(mean[c] - mean[c] == 0.0) || !(std_[c] - std_[c] == 0.0) || !(def[c] - def[c] == 0.0))
+                return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: ctx_mean / ctx_std / ctx_default of context number %d is not finite", c);
+            if (!(std_[c] > 0.0)) return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: ctx_std[%d] = %g: must be > 0", c, std_[c]);
+        }
+    }
+    // rows 2 nn_dof .. MLP_KPAD - 1 of layer 0's forward operand W^T [MLP_KPAD][H]: the context columns, zero behind them.  The
+    // backward operand keeps its zero columns: no derivative with respect to the context is formed.
+    std::vector<float> rows((size_t)room * H, 0.0f);
+    float defn[MLP_KPAD] = {0};
+    if (!clear) {
+        for (int o = 0; o < H; o++)
+            for (int c = 0; c < n_ctx; c++) rows[(size_t)c * H + o] = wc[(size_t)o * n_ctx + c];
+        for (int c = 0; c < n_ctx; c++) defn[c] = (float)((def[c] - mean[c]) / std_[c]);
+    }
+    int rc;
+    if (!clear && (rc = h->d_ctx_def.reserve(h, "default context", sizeof(defn)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (smpc_handle* k : h->kids) HIPCHK(h, hipStreamSynchronize(k->stream));      // (the workers read these weights too)
+    h->n_ctx = 0;
+    h->ctx_B = 0;       // (an instance context belongs to the context columns it was normalised for)
+    if (room > 0) HIPCHK(h, hipMemcpy(h->d_Wfwd[0] + (size_t)nd2 * H, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (clear) {
+        for (smpc_handle* k : h->kids) k->n_ctx = 0;
+        return SMPC_OK;
+    }
+    HIPCHK(h, hipMemcpy(h->d_ctx_def.p, defn, sizeof(defn), hipMemcpyHostToDevice));
+    h->ctx_def = h->d_ctx_def.p;
+    for (int c = 0; c < MLP_KPAD; c++) { h->ctx_mean[c] = mean[c]; h->ctx_std[c] = c < n_ctx ? std_[c] : 1.0; }
+    h->n_ctx = n_ctx;
+    for (smpc_handle* k : h->kids) { k->n_ctx = n_ctx; k->ctx_def = h->ctx_def; }
+    return SMPC_OK;
+}
+
+int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!ctx) { h->ctx_B = 0; return SMPC_OK; }
+    if (h->n_ctx == 0)
+        return fail(h, SMPC_EINVAL, "smpc_set_instance_context: the network has no context columns (smpc_set_mlp_context was not called)");
+    if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    const int nc = h->n_ctx;
+    const size_t n = (size_t)B * nc;
+    std::vector<float> norm;
+    if (!on_device) {
+        // (device pointers are taken as they are: reading them back would synchronise)
+        norm.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            if (!(ctx[i] - ctx[i] == 0.0))
+                return fail(h, SMPC_EINVAL, "context of instance %zu (of B=%d), number %zu (of %d) is not finite", i / nc, B, i % nc, nc);
+            norm[i] = (float)((ctx[i] - h->ctx_mean[i % nc]) / h->ctx_std[i % nc]);
+        }
+    }
+    int rc;
+    // (grown only when the batch grows: the same B is overwritten in place, stream-ordered, and a captured step keeps seeing this buffer)
+    if ((rc = h->d_ctx.reserve(h, "instance context", n * sizeof(float)))) {
+        if (!h->d_ctx.p) h->ctx_B = 0;      // (a failed growth left no buffer; a refused one keeps the old context)
+        return rc;
+    }
+    if (on_device) {
+        CtxNorm nm;
+        for (int c = 0; c < MLP_KPAD; c++) { nm.mean[c] = h->ctx_mean[c]; nm.std[c] = h->ctx_std[c]; }
+        hipLaunchKernelGGL(k_ctx_normalise, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, (long)n, nc, ctx, nm, h->d_ctx.p);
+        HIPCHK(h, hipGetLastError());
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->d_ctx.p, norm.data(), n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
+    }
+    h->ctx_B = B;
     return SMPC_OK;
 }
 
@@ -1612,6 +1743,7 @@ int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, 
     (void)hipSetDevice(h->device);
     int rc;
     if ((rc = scene_guard(h, B, "smpc_solve_batch"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_solve_batch"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
     Stage io{h, on_device != 0};
@@ -1640,6 +1772,7 @@ int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, c
     (void)hipSetDevice(h->device);
     int rc;
     if ((rc = scene_guard(h, B, "smpc_eval_nodes"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_eval_nodes"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     hipStream_t s = h->stream;
@@ -1722,6 +1855,7 @@ int smpc_check_trajectory(smpc_handle* h, int B, int n_nodes, const double* x, c
     // (x_min / x_max / row bounds are host pointers on both paths: small, constant per caller)
     int rc;
     if ((rc = scene_guard(h, B, "smpc_check_trajectory"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_check_trajectory"))) return rc;
     if ((rc = upload_check_bounds(h, x_min, x_max, row_lb_chk, row_ub_chk))) return rc;
     Stage io{h, on_device != 0};
     const double* dx;
@@ -1777,6 +1911,10 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
         return fail(h, SMPC_ESTATE, "smpc_rollout_batch: an instance scene is set (for %d instances) and the worker handles of the "
                     "rollout hold none: clear it with smpc_set_instance_scene(h, 0, NULL, 0), or step the loop through "
                     "smpc_policy_step / smpc_loop_post", h->scene_B);
+    if (h->ctx_B)
+        return fail(h, SMPC_ESTATE, "smpc_rollout_batch: an instance context is set (for %d instances) and the worker handles of the "
+                    "rollout hold none: clear it with smpc_set_instance_context(h, 0, NULL, 0), or step the loop through "
+                    "smpc_policy_step / smpc_loop_post", h->ctx_B);
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
@@ -1895,11 +2033,15 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     if (parallel && h->scene_B)
         return fail(h, SMPC_ESTATE, "smpc_policy_step: an instance scene is set (for %d instances) and the parallel policy's candidate "
                     "slots are not instances: clear it with smpc_set_instance_scene(h, 0, NULL, 0)", h->scene_B);
+    if (parallel && h->ctx_B)
+        return fail(h, SMPC_ESTATE, "smpc_policy_step: an instance context is set (for %d instances) and the parallel policy's candidate "
+                    "slots are not instances: clear it with smpc_set_instance_context(h, 0, NULL, 0)", h->ctx_B);
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_policy_step"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_policy_step"))) return rc;
     TrajSrc tr;
     if (!parallel && (rc = policy_traj_src(h, B, st, &tr))) return rc;     // (before anything is enqueued; the parallel step asks itself)
     if ((rc = ensure_batch(h, B))) return rc;
@@ -2046,6 +2188,7 @@ int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, c
     const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_merit_terms"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_merit_terms"))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, false, &w))) return rc;
     Stage io{h, on_device != 0};
@@ -2084,6 +2227,7 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
     hipStream_t s = h->stream;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_sqp_batch"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_sqp_batch"))) return rc;
     if ((rc = ensure_batch(h, B, false))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, true, &w))) return rc;
@@ -2163,6 +2307,7 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
     const int N = h->N, nq = h->desc.nq;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_check_guess"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_check_guess"))) return rc;
     if ((rc = upload_guess_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du;
@@ -2286,6 +2431,7 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
     const int nq = h->desc.nq;
     int rc;
     if ((rc = scene_guard(h, B, "smpc_score_rollout"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_score_rollout"))) return rc;
     if (own && (rc = curves_guard(h, B, "smpc_score_rollout"))) return rc;
     if ((rc = upload_score_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
@@ -2412,6 +2558,7 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     (void)hipSetDevice(h->device);
     int rc;
     if ((rc = scene_guard(h, B, "smpc_debug_stage_records"))) return rc;
+    if ((rc = ctx_guard(h, B, "smpc_debug_stage_records"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     Stage io{h, false};

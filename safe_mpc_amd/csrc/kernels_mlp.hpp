@@ -18,7 +18,7 @@ namespace smpc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int MLP_KPAD = 16;   // padded input width (2*nn_dof <= 14)
+constexpr int MLP_KPAD = 16;   // padded input width (2*nn_dof <= 14; the columns behind them take the row's context, CtxSrc)
 constexpr int MLP_NPAD = 64;   // padded width of the last backward GEMM (tile width)
 
 __device__ __forceinline__ float gelu_tanh_f(float a, float* dg) {
@@ -143,19 +143,34 @@ __global__ void k_nn_compact(int M, int N, const double* __restrict__ p, int32_t
     const long node = nn_row_to_node(2, N, m);
     if (p[node * SMPC_NP + 4] > 0.0) idx[atomicAdd(m_live, 1)] = (int32_t)node;
 }
+
+// The context of a network row: the columns 2 nn_dof .. 2 nn_dof + n - 1 of layer 0's padded input, constants
+// of the row's INSTANCE (numbers of its scene), which the engine keeps normalised as floats.  Which instance a row belongs to is the
+// launcher's knowledge, handed over by value (after the model of SceneSrc):
+//   per:  the rows are nodes of instance-major arrays with `per` nodes each: instance = node / per, node = nn_row_to_node(..) -- N + 1
+//         for the [B][N+1] node arrays of modes 1, 2, 3 (mode 3: the list's order is the atomics', so the node is idx[m], never m),
+//         n_nodes for the lists of check_nodes_dev;
+//   mod:  > 0, a step-major log read in chunks that start at flat row m0 (launch_score): instance = (m0 + m) % mod.
+// stride = 0: the one default row serves every instance.  n = 0: a network without context, and nothing below is executed.
+struct CtxSrc {
+    const float* p = nullptr;   // [instances][stride] normalised context (stride = 0: one row)
+    int n = 0;                  // context numbers per row, <= MLP_KPAD - 2 nn_dof
+    int stride = 0;
+    int per = 1;
+    int mod = 0;
+    int m0 = 0;                 // (m0 of the chunk) % mod
+};
+
+// One row of layer 0's input, s[MLP_KPAD] (safe_set.py:82-87): s = [(q - mean)/std ; v/|v| ; context ; 0 ..], v = qd with eps on v_0.
+// A row past the live count is all-zero.  One thread per row.
 template <int NQ>
-__global__ void k_nn_features(const smpc_problem_desc* __restrict__ D, int M, int Mpad, int N, int mode,
-                              const double* __restrict__ xg, float* __restrict__ S, const int32_t* __restrict__ idx,
-                              const int32_t* __restrict__ m_live) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= Mpad) return;
-    const int live = m_live ? *m_live : M;
-    if (m >= ((live + 127) & ~127)) return;      // (only the tiles that will be computed need defined rows)
-    float* s = S + (size_t)m * MLP_KPAD;
+__device__ __forceinline__ void nn_feature_row(const smpc_problem_desc* __restrict__ D, const double* __restrict__ xg, int mode, int N,
+                                               int m, bool is_live, const int32_t* __restrict__ idx, const CtxSrc& cx, float* s) {
 #pragma unroll
     for (int i = 0; i < MLP_KPAD; i++) s[i] = 0.0f;
-    if (m >= live) return;
-    const double* x = xg + nn_row_to_node(mode, N, m, idx) * (2 * NQ);
+    if (!is_live) return;
+    const long node = nn_row_to_node(mode, N, m, idx);
+    const double* x = xg + node * (2 * NQ);
     const int nd = D->nn_dof;
     double v[NQ], vn2 = 0.0;
 #pragma unroll
@@ -171,6 +186,32 @@ __global__ void k_nn_features(const smpc_problem_desc* __restrict__ D, int M, in
             s[nd + i] = (float)(v[i] * inv);
         }
     }
+    if (cx.n > 0) {
+        const unsigned inst = cx.mod > 0 ? (unsigned)(cx.m0 + m) % (unsigned)cx.mod : (unsigned)node / (unsigned)cx.per;
+        const float* c = cx.p + (size_t)inst * cx.stride;
+        for (int i = 0; i < cx.n; i++) s[2 * nd + i] = c[i];
+    }
+}
+
+template <int NQ>
+__global__ void k_nn_features(const smpc_problem_desc* __restrict__ D, int M, int Mpad, int N, int mode,
+                              const double* __restrict__ xg, float* __restrict__ S, const int32_t* __restrict__ idx,
+                              const int32_t* __restrict__ m_live, CtxSrc cx) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= Mpad) return;
+    const int live = m_live ? *m_live : M;
+    if (m >= ((live + 127) & ~127)) return;      // (only the tiles that will be computed need defined rows)
+    nn_feature_row<NQ>(D, xg, mode, N, m, m < live, idx, cx, S + (size_t)m * MLP_KPAD);
+}
+
+// k_ctx_normalise: out[i] = (float)((ctx[i] - mean[c]) / std[c]), c = i % n_ctx -- the device-pointer path of
+// smpc_set_instance_context (the host path does the same arithmetic on the host)
+struct CtxNorm { double mean[MLP_KPAD], std[MLP_KPAD]; };
+__global__ void k_ctx_normalise(long n, int n_ctx, const double* __restrict__ ctx, CtxNorm nm, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % n_ctx);
+    out[i] = (float)((ctx[i] - nm.mean[c]) / nm.std[c]);
 }
 
 // output layer y = a . w + b  and  delta = w (.) gelu'(z) of the last hidden layer; one wave per row
@@ -256,7 +297,7 @@ template <int NQ, bool BWD>
 __global__ __launch_bounds__(256) void k_mlp_fused(const smpc_problem_desc* __restrict__ D, int M, int N, int mode, int act,
                                                    MlpWeights Wt, const double* __restrict__ xg, const double* __restrict__ p,
                                                    const int32_t* __restrict__ idx, const int32_t* __restrict__ m_live,
-                                                   float* __restrict__ y_out, double* __restrict__ ev_out, int compact) {
+                                                   float* __restrict__ y_out, double* __restrict__ ev_out, int compact, CtxSrc cx) {
     constexpr int H = MLPF_H, LD = MLPF_LD, R = MLPF_ROWS;
     __shared__ __attribute__((aligned(16))) float bufA[R * LD];
     __shared__ __attribute__((aligned(16))) float bufB[R * LD];
@@ -268,29 +309,7 @@ __global__ __launch_bounds__(256) void k_mlp_fused(const smpc_problem_desc* __re
     const int live = m_live ? *m_live : M;
     if (m0 >= live) return;                                  // (uniform: before the first barrier)
     // ---- features (safe_set.py:82-87), one thread per row; rows past the live count are zero
-    if (t < R) {
-        const int m = m0 + t;
-        float* sf = sfeat + t * MLP_KPAD;
-#pragma unroll
-        for (int i = 0; i < MLP_KPAD; i++) sf[i] = 0.0f;
-        if (m < live) {
-            const double* x = xg + nn_row_to_node(mode, N, m, idx) * (2 * NQ);
-            const int nd = D->nn_dof;
-            double v[NQ], vn2 = 0.0;
-#pragma unroll
-            for (int i = 0; i < NQ; i++) {
-                v[i] = i < nd ? x[NQ + i] + (i == 0 ? D->nn_eps : 0.0) : 0.0;
-                vn2 += v[i] * v[i];
-            }
-            const double inv = 1.0 / sqrt(vn2);
-#pragma unroll
-            for (int i = 0; i < NQ; i++)
-                if (i < nd) {
-                    sf[i] = (float)((x[i] - D->nn_mean[i]) / D->nn_std[i]);
-                    sf[nd + i] = (float)(v[i] * inv);
-                }
-        }
-    }
+    if (t < R) nn_feature_row<NQ>(D, xg, mode, N, m0 + t, m0 + t < live, idx, cx, sfeat + t * MLP_KPAD);
     __syncthreads();
     const int c0 = 64 * w + 4 * j;                           // this lane's four columns c0 .. c0 + 3 (one per tile)
     f32x4 acc[4];
@@ -490,7 +509,7 @@ __global__ __launch_bounds__(64) void k_mlp_wave(const smpc_problem_desc* __rest
                                                  MlpWeights Wt, const double* __restrict__ xg, const double* __restrict__ p,
                                                  const int32_t* __restrict__ idx, const int32_t* __restrict__ m_live,
                                                  float* __restrict__ y_out, double* __restrict__ ev_out, int compact,
-                                                 float* __restrict__ dg0, float* __restrict__ dg1, float* __restrict__ dg2) {
+                                                 float* __restrict__ dg0, float* __restrict__ dg1, float* __restrict__ dg2, CtxSrc cx) {
     constexpr int H = MLPF_H, LD = MLPF_LD, R = MLPF_ROWS;
     __shared__ __attribute__((aligned(16))) float buf[R * LD];       // the current layer's input (features / activations / deltas)
     __shared__ float sy[R];
@@ -503,29 +522,7 @@ __global__ __launch_bounds__(64) void k_mlp_wave(const smpc_problem_desc* __rest
         __builtin_amdgcn_wave_barrier();
     };
     // ---- features (safe_set.py:82-87), one lane per row, into the head of the buffer with row stride MLP_KPAD
-    if (lane < R) {
-        const int m = m0 + lane;
-        float* sf = buf + lane * MLP_KPAD;
-#pragma unroll
-        for (int i = 0; i < MLP_KPAD; i++) sf[i] = 0.0f;
-        if (m < live) {
-            const double* x = xg + nn_row_to_node(mode, N, m, idx) * (2 * NQ);
-            const int nd = D->nn_dof;
-            double v[NQ], vn2 = 0.0;
-#pragma unroll
-            for (int i = 0; i < NQ; i++) {
-                v[i] = i < nd ? x[NQ + i] + (i == 0 ? D->nn_eps : 0.0) : 0.0;
-                vn2 += v[i] * v[i];
-            }
-            const double inv = 1.0 / sqrt(vn2);
-#pragma unroll
-            for (int i = 0; i < NQ; i++)
-                if (i < nd) {
-                    sf[i] = (float)((x[i] - D->nn_mean[i]) / D->nn_std[i]);
-                    sf[nd + i] = (float)(v[i] * inv);
-                }
-        }
-    }
+    if (lane < R) nn_feature_row<NQ>(D, xg, mode, N, m0 + lane, m0 + lane < live, idx, cx, buf + lane * MLP_KPAD);
     wave_sync();
     f32x4 acc[4];
     float outH[4][4][4];                                     // [column group][tile][row register]: the layer's output

@@ -351,6 +351,10 @@ class OcpProblem:
             raise ValueError('scene_track: a track has at least one time column')
         return np.stack([self.scene(m) for m in moves])
 
+    def context_default(self, select):
+        """[n_ctx]: the context of the shared scene -- :func:`scene_context` of ``row_geometry()``"""
+        return scene_context(self.row_geometry()[None], select)[0]
+
     # per-instance perturbed joint tables for the plant (utils.py:126-171 semantics on the lumped inertias is NOT what
     # the reference does -- it perturbs each URDF link before lumping; see noise.py)
     def joint_table(self):
@@ -362,6 +366,25 @@ class OcpProblem:
             for f in ('mass', 'q_min', 'q_max', 'v_max', 'tau_max'):
                 out[i][f] = getattr(J, f)
         return out
+
+
+def scene_context(geom, select):
+    """[B, n_ctx] from scenes ``geom [B, n_rows, SCENE_ROW]`` (a numpy array, or a ROCm tensor that gives a tensor): the numbers a safe-set network with a context is given about its
+    instance's scene -- entry ``slot`` of row ``row``'s record for every ``(row, slot)`` of ``select``, in
+    that order (``SafeSetNet.ctx_select``)."""
+    on_device = type(geom).__module__.startswith('torch')      # (a ROCm tensor stays one: the device loop holds its scenes there)
+    if not on_device:
+        geom = np.asarray(geom, float)
+    if geom.ndim != 3 or geom.shape[2] != SCENE_ROW:
+        raise ValueError(f'scene_context: expected [B, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+    sel = [(int(r), int(c)) for r, c in select]
+    for r, c in sel:
+        if not (0 <= r < geom.shape[1] and 0 <= c < SCENE_ROW):
+            raise ValueError(f'scene_context: (row {r}, slot {c}) outside a scene of {geom.shape[1]} rows x {SCENE_ROW} slots')
+    if on_device:
+        import torch
+        return torch.stack([geom[:, r, c] for r, c in sel], dim=1).contiguous() if sel else geom.new_zeros((geom.shape[0], 0))
+    return np.ascontiguousarray(np.stack([geom[:, r, c] for r, c in sel], axis=1)) if sel else np.zeros((geom.shape[0], 0))
 
 
 def _row_signature(prob):

@@ -231,7 +231,7 @@ def _label_chunk_device(ctrl, rays_np, n_live, bisect, budget, check_every, opts
 
 
 def label_rays(ctrl, q, d, s_hi, bisect=8, budget=30, check_every=5, batch=None, bookkeeping='auto', sqp_tol=1e-6, armijo=1e-4,
-               alpha_reduction=0.7, alpha_min=0.05):
+               alpha_reduction=0.7, alpha_min=0.05, scenes=None):
     """Labels of the rays ``(q, d)`` [n, nq] by bisection on the speed, on a backup controller (``get_controller`` has none: a
     ``controller.SafeBackupController``).
 
@@ -248,6 +248,10 @@ def label_rays(ctrl, q, d, s_hi, bisect=8, budget=30, check_every=5, batch=None,
     documents.  The controller is resized to the chunk.  ``bookkeeping``: 'device' (``solver.ray_update``), 'statement' (host
     decisions by :func:`ray_update_statement`, any solver) or 'auto' (the device where the solver has ``ray_update``).
 
+    ``scenes`` [n, n_rows, 8]: a scene of its own for every ray (problem.jittered_scenes).  Per chunk, the
+    chunk's scenes, padded like ``q``, are set on the controller's solver (``set_instance_scene``; ValueError for a solver without
+    one) and cleared behind the loop, also when a round raises.  A ray whose ``q`` collides in its own scene comes out DEAD.
+
     Returns a dict: ``label`` [n], ``kind`` [n] (DEAD / SATURATED / BRACKETED), ``lo``, ``hi``, ``trials`` (trials run), ``iters`` (SQP
     iterations of all trials), ``x_cert`` [n, N+1, nx], ``u_cert`` [n, N, nu], ``rounds`` (of all chunks)."""
     if bookkeeping not in ('auto', 'device', 'statement'):
@@ -259,6 +263,12 @@ def label_rays(ctrl, q, d, s_hi, bisect=8, budget=30, check_every=5, batch=None,
     n, nq = q.shape
     if nq != ctrl.nq or d.shape != q.shape or s_hi.shape != (n,):
         raise ValueError(f'label_rays: q, d [n, {ctrl.nq}] and s_hi [n] expected')
+    if scenes is not None:
+        scenes = np.ascontiguousarray(scenes, np.float64)
+        if not hasattr(ctrl.ocp_solver, 'set_instance_scene'):
+            raise ValueError(f'label_rays(scenes=...): {type(ctrl.ocp_solver).__name__} has no set_instance_scene')
+        if scenes.ndim != 3 or scenes.shape[0] != n:
+            raise ValueError(f'label_rays: scenes [n = {n}, n_rows, 8] expected, got {scenes.shape}')
     on_device = hasattr(ctrl.ocp_solver, 'ray_update') if bookkeeping == 'auto' else bookkeeping == 'device'
     if on_device and not hasattr(ctrl.ocp_solver, 'ray_update'):
         raise ValueError(f"label_rays(bookkeeping='device') needs a solver with ray_update; {type(ctrl.ocp_solver).__name__} has none")
@@ -278,7 +288,14 @@ def label_rays(ctrl, q, d, s_hi, bisect=8, budget=30, check_every=5, batch=None,
         rays = new_ray_state(pad(q), pad(d), pad(s_hi), N)
         rays['open'][m:] = 0                                        # padding slots: finished rays, skipped by every kernel
         run = _label_chunk_device if on_device else _label_chunk_statement
-        out['rounds'] += run(ctrl, rays, m, bisect, budget, check_every, opts, mu0)
+        if scenes is None:
+            out['rounds'] += run(ctrl, rays, m, bisect, budget, check_every, opts, mu0)
+        else:
+            try:
+                ctrl.ocp_solver.set_instance_scene(pad(scenes))
+                out['rounds'] += run(ctrl, rays, m, bisect, budget, check_every, opts, mu0)
+            finally:
+                ctrl.ocp_solver.set_instance_scene(None)
         sl = slice(lo, lo + m)
         out['kind'][sl], out['lo'][sl], out['hi'][sl] = rays['kind'][:m], rays['lo'][:m], rays['hi'][:m]
         out['trials'][sl], out['iters'][sl] = rays['trial'][:m], rays['iters_total'][:m]
@@ -288,11 +305,14 @@ def label_rays(ctrl, q, d, s_hi, bisect=8, budget=30, check_every=5, batch=None,
 
 
 # ---- the fit and the checkpoint -----------------------------------------------------------------------------------------------------
-def fit_safe_set(data, params, epochs, seed, hidden=None, device='cpu', lr=3e-3, batch_size=256):
+def fit_safe_set(data, params, epochs, seed, hidden=None, device='cpu', lr=3e-3, batch_size=256, context=None):
     """Fits the reference's network (``NeuralNetwork(*params.net_size, activation(params.act))``; ``hidden`` overrides the width) to
     labelled rays: ``data`` with ``q``, ``d``, ``label`` and ``kind`` (DEAD rays are dropped).  Inputs ``((q - mean) / std, d)`` with
     mean / std per joint from the sampled q, target the label, MSE, Adam, mini-batches in a seeded order; the output bias starts at
     the mean label.  The ``eps`` the reference adds to the first velocity before normalising it (safe_set.py:83) is not modelled.
+    ``context`` [n, n_ctx]: numbers of every ray's scene (problem.scene_context) as extra inputs behind (q, d), normalised by their
+    own mean / std over the kept rays (``info['ctx_mean']``, ``info['ctx_std']``); ``net_size[0]`` must then be ``2 nq + n_ctx``
+    (DESIGN.md section 9j).
     Returns ``(net, mean, std, info)``; the same seed gives the same weights."""
     import torch
     from .safe_set import NeuralNetwork, activation
@@ -306,15 +326,29 @@ def fit_safe_set(data, params, epochs, seed, hidden=None, device='cpu', lr=3e-3,
     size = [int(v) for v in params.net_size]
     if hidden is not None:
         size[1] = int(hidden)
-    if size[0] != 2 * q.shape[1] or size[2] != 1:
-        raise ValueError(f'fit_safe_set: net_size {size} does not take (q, d) of {q.shape[1]} joints to one output')
+    cols = [None, d]
+    extra = {}
+    if context is not None:
+        ctx = np.asarray(context, float)
+        if ctx.ndim != 2 or ctx.shape[0] != len(keep):
+            raise ValueError(f'fit_safe_set: context [n = {len(keep)}, n_ctx] expected, got {ctx.shape}')
+        ctx = ctx[keep]
+        ctx_mean, ctx_std = ctx.mean(0), ctx.std(0)
+        ctx_std = np.where(ctx_std > 0.0, ctx_std, 1.0)
+        cols.append((ctx - ctx_mean) / ctx_std)
+        extra = {'ctx_mean': ctx_mean, 'ctx_std': ctx_std}
+    n_in = 2 * q.shape[1] + (0 if context is None else ctx.shape[1])
+    if size[0] != n_in or size[2] != 1:
+        raise ValueError(f'fit_safe_set: net_size {size} does not take (q, d) of {q.shape[1]} joints'
+                         + ('' if context is None else f' and {ctx.shape[1]} context numbers ({n_in} inputs)') + ' to one output')
     torch.manual_seed(int(seed))
     net = NeuralNetwork(*size, activation(params.act)).float()
     with torch.no_grad():
         net.linear_stack[-1].bias.fill_(float(y.mean()))
     dev = torch.device(device)
     net = net.to(dev)
-    X = torch.as_tensor(np.hstack([(q - mean) / std, d]), dtype=torch.float32, device=dev)
+    cols[0] = (q - mean) / std
+    X = torch.as_tensor(np.hstack(cols), dtype=torch.float32, device=dev)
     Y = torch.as_tensor(y, dtype=torch.float32, device=dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     gen = torch.Generator().manual_seed(int(seed))
@@ -330,25 +364,35 @@ def fit_safe_set(data, params, epochs, seed, hidden=None, device='cpu', lr=3e-3,
     net = net.cpu().eval()
     with torch.no_grad():
         rmse = float(torch.sqrt(torch.mean((net(X.cpu()).reshape(-1) - Y.cpu()) ** 2)))
-    return net, mean, std, {'rays': int(keep.sum()), 'dropped': int((~keep).sum()), 'train_rmse': rmse, 'net_size': size}
+    return net, mean, std, {'rays': int(keep.sum()), 'dropped': int((~keep).sum()), 'train_rmse': rmse, 'net_size': size, **extra}
 
 
-def predict(net, mean, std, q, d):
-    """the fitted network's labels for rays (q, d), numpy"""
+def predict(net, mean, std, q, d, ctx=None):
+    """the fitted network's labels for rays (q, d), numpy; ``ctx`` [n, n_ctx]: the NORMALISED context of a net fitted with one"""
     import torch
-    X = torch.as_tensor(np.hstack([(np.asarray(q, float) - mean) / std, np.asarray(d, float)]), dtype=torch.float32)
+    cols = [(np.asarray(q, float) - mean) / std, np.asarray(d, float)] + ([] if ctx is None else [np.asarray(ctx, float)])
+    X = torch.as_tensor(np.hstack(cols), dtype=torch.float32)
     with torch.no_grad():
         return net(X).reshape(-1).numpy().astype(float)
 
 
-def save_checkpoint(path, net, mean, std):
+def save_checkpoint(path, net, mean, std, ctx_mean=None, ctx_std=None, ctx_select=None):
     """``{'model': state_dict, 'mean', 'std'}``: the reference's checkpoint (safe_set.py:76-85), what ``network_path:`` names and
-    ``SafeSetNet.from_params`` reads"""
+    ``SafeSetNet.from_params`` reads.  A net fitted with a context also carries ``ctx_mean``, ``ctx_std`` and ``ctx_select`` (the
+    ``(row, slot)`` pairs of problem.scene_context); without them the file is the reference's, key for key."""
     import torch
-    torch.save({'model': {k: v.detach().cpu() for k, v in net.state_dict().items()},
-                'mean': torch.as_tensor(np.asarray(mean, np.float64)), 'std': torch.as_tensor(np.asarray(std, np.float64))}, path)
+    ck = {'model': {k: v.detach().cpu() for k, v in net.state_dict().items()},
+          'mean': torch.as_tensor(np.asarray(mean, np.float64)), 'std': torch.as_tensor(np.asarray(std, np.float64))}
+    if ctx_mean is not None:
+        if ctx_std is None or ctx_select is None:
+            raise ValueError('save_checkpoint: ctx_mean, ctx_std and ctx_select go together')
+        ck['ctx_mean'] = torch.as_tensor(np.asarray(ctx_mean, np.float64))
+        ck['ctx_std'] = torch.as_tensor(np.asarray(ctx_std, np.float64))
+        ck['ctx_select'] = torch.as_tensor(np.asarray(ctx_select, np.int64).reshape(-1, 2))
+    torch.save(ck, path)
 
 
-def save_dataset(path, q, d, s_hi, labels):
-    """the dataset as .npz: q, d, s_hi, label, kind, trials"""
-    np.savez(path, q=q, d=d, s_hi=s_hi, label=labels['label'], kind=labels['kind'], trials=labels['trials'])
+def save_dataset(path, q, d, s_hi, labels, ctx=None):
+    """the dataset as .npz: q, d, s_hi, label, kind, trials (and ctx [n, n_ctx], the raw context of every ray, where given)"""
+    extra = {} if ctx is None else {'ctx': np.asarray(ctx, float)}
+    np.savez(path, q=q, d=d, s_hi=s_hi, label=labels['label'], kind=labels['kind'], trials=labels['trials'], **extra)

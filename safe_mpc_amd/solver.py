@@ -103,8 +103,13 @@ class BatchedOcpSolver:
             if not same:
                 cur.wait_stream(self._ext_stream)
 
-    def set_mlp(self, net):
+    def set_mlp(self, net, ctx_default=None):
         """net: SafeSetNet (weights as numpy fp32) -- or anything with .weights/.biases lists of [out, in] / [out].
+
+        A net with a context (``net.n_ctx > 0``): the state columns of ``weights[0]`` go through smpc_set_mlp,
+        the last ``n_ctx`` columns through smpc_set_mlp_context with the net's ``ctx_mean`` / ``ctx_std``.  ``ctx_default [n_ctx]`` is
+        the context of every row while no instance context is set (:meth:`set_instance_context`): unless given, the shared scene's
+        (``problem.context_default(net.ctx_select)``), or ``ctx_mean`` for a net that does not say where its context comes from.
 
         The engine's network kernels take hidden widths that are multiples of 64 (smpc_set_mlp refuses any other).  A net of another
         width -- a small one from safe_set_data.fit_safe_set -- is handed over with ZERO UNITS ADDED up to the next multiple of 256
@@ -114,6 +119,10 @@ class BatchedOcpSolver:
         Ws = [np.ascontiguousarray(w, np.float32) for w in net.weights]
         bs = [np.ascontiguousarray(b, np.float32) for b in net.biases]
         n = len(Ws)
+        n_ctx = int(getattr(net, 'n_ctx', 0))
+        Wc = np.ascontiguousarray(Ws[0][:, Ws[0].shape[1] - n_ctx:]) if n_ctx else None
+        if n_ctx:
+            Ws[0] = np.ascontiguousarray(Ws[0][:, :Ws[0].shape[1] - n_ctx])
         Ws, bs = pad_hidden_units(Ws, bs)
         dims = np.array([Ws[0].shape[1]] + [w.shape[0] for w in Ws], np.int32)
         Wp = (C.c_void_p * n)(*[w.ctypes.data for w in Ws])
@@ -122,7 +131,38 @@ class BatchedOcpSolver:
         act = getattr(net, 'act', 'gelu')
         from .safe_set import SafeSetNet
         self._chk(self.L.smpc_set_mlp_activation(self.h, SafeSetNet.ACT_CODES[act]))      # SMPC_ACT_* (parser.py:95-102)
+        if n_ctx:
+            Wcp = np.zeros((Ws[0].shape[0], n_ctx), np.float32)       # (zero rows for the zero units pad_hidden_units added)
+            Wcp[:Wc.shape[0]] = Wc
+            if ctx_default is None:
+                sel = getattr(net, 'ctx_select', None)
+                ctx_default = self.problem.context_default(sel) if sel else net.ctx_mean
+            cm, cs, cd = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (net.ctx_mean, net.ctx_std, ctx_default))
+            if cm.shape != (n_ctx,) or cs.shape != (n_ctx,) or cd.shape != (n_ctx,):
+                raise ValueError(f'set_mlp: ctx_mean, ctx_std and ctx_default must have {n_ctx} entries')
+            self._chk(self.L.smpc_set_mlp_context(self.h, n_ctx, Wcp.ctypes.data, cm.ctypes.data, cs.ctypes.data, cd.ctypes.data, 0))
         self.net = net
+
+    def set_instance_context(self, ctx=None):
+        """The context of every instance for a net that has one (smpc_set_instance_context): ``ctx [B, n_ctx]`` float64, the raw
+        numbers (``problem.scene_context(geom, net.ctx_select)``), a numpy array or a contiguous ROCm tensor; the engine keeps a
+        normalised fp32 copy.  None clears it: every row then takes the default context again.  While set, every call that runs the
+        network must come with the same B; the parallel policy and :meth:`rollout` refuse it.  The engine does not derive it from
+        :meth:`set_instance_scene`: set and clear the two together."""
+        if ctx is None:
+            self._chk(self.L.smpc_set_instance_context(self.h, 0, None, 0))
+            return
+        if _is_torch(ctx):
+            import torch
+            if ctx.dtype != torch.float64:
+                raise ValueError('set_instance_context: the context must be float64')
+        n_ctx = int(getattr(self.net, 'n_ctx', 0)) if self.net is not None else 0
+        if ctx.ndim != 2 or (n_ctx and ctx.shape[1] != n_ctx):
+            raise ValueError(f'set_instance_context: expected [B, {n_ctx}], got {tuple(ctx.shape)}')
+        B = int(ctx.shape[0])
+        ptrs, dev, keep = self._prep([ctx], [tuple(ctx.shape)])
+        with self._ordered(dev):
+            self._chk(self.L.smpc_set_instance_context(self.h, B, ptrs[0], dev))
 
     QP_MODES = {'auto': -1, 'throughput': 0, 'latency': 1}
 

@@ -6,6 +6,12 @@ host-pointer path carries the arrays), alternating the two in one session, wall 
 smpc_ray_update (events on the engine's stream) and inside ray_update_statement (host clock), and the share of rays per kind.
 
     python scripts/safe_set_bench.py [output file] [--rays 4096] [--reps 2]
+
+SMPC_CONTEXT=1 measures something else with the same tools (profiles/safe_set_context.txt): what the feature
+stage of the network pass costs with a four-number instance context against a network without context columns.  The forward-only
+pass of smpc_check_trajectory(nn_ok) over --rays instances x 1 node (4096 rows: k_mlp_fused) and x 30 nodes (122 880 rows:
+k_mlp_wave), the two networks alternating on one handle, wall clock around a synchronise over 50 calls each; k_check_nodes and
+k_check_nn run in both and are part of both figures.
 """
 import os, sys, time
 import numpy as np
@@ -34,6 +40,46 @@ def say(*a):
 
 par = Parameters({}, 'z1', rti=False)
 par.nq, par.n_dof_safe_set, par.net_size = 6, 6, [12, 256, 1]
+
+def context_bench():
+    from safe_mpc_amd.problem import OcpProblem
+    from safe_mpc_amd.safe_set import SafeSetNet
+    prob = OcpProblem(par, 'st', 'ext', N=30)
+    net = SafeSetNet.synthetic([16, 256, 1], 6, prob.x_min, prob.x_max, 0, par.act)
+    prob.set_normalisation(net.mean, net.std)
+    plain = net.folded(np.zeros(4))
+    sv = BatchedOcpSolver(prob, None)
+    dev = torch.device('cuda', sv.device)
+    rng = np.random.default_rng(0)
+    ctx = torch.as_tensor(rng.standard_normal((B, 4)), device=dev)
+    CALLS = 50
+    say(f'# SMPC_CONTEXT=1 python scripts/safe_set_bench.py -- the forward-only network pass of smpc_check_trajectory(nn_ok), {B} instances, a '
+        f'four-number instance context against a network without context columns; one MI355X, one session, {CALLS} calls per figure')
+    for n_nodes in (1, 30):
+        x = torch.as_tensor(prob.x_min + rng.uniform(size=(B, n_nodes, 12)) * (prob.x_max - prob.x_min), device=dev)
+        times = {'none': [], 'context': []}
+        for rep in range(REPS + 1):                 # (the first round warms both up and is not reported)
+            for mode in ('none', 'context'):
+                sv.set_mlp(plain if mode == 'none' else net)
+                if mode == 'context':
+                    sv.set_instance_context(ctx)
+                sv.check_trajectory(x, want_nn=True)
+                sv.sync(); torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(CALLS):
+                    sv.check_trajectory(x, want_nn=True)
+                sv.sync(); torch.cuda.synchronize()
+                if rep:
+                    times[mode].append((time.perf_counter() - t0) / CALLS * 1e6)
+        for mode in ('none', 'context'):
+            say(f'{B * n_nodes:7d} rows ({"k_mlp_fused" if B * n_nodes < 8192 else "k_mlp_wave"}), {mode:7s}: '
+                f'{min(times[mode]):8.1f} us per call best of {REPS}; all {[round(t, 1) for t in times[mode]]}')
+    OUT.close()
+
+if os.environ.get('SMPC_CONTEXT') == '1':
+    context_bench()
+    sys.exit(0)
+
 BISECT, BUDGET, EVERY = 8, 30, 5
 ctrl = SafeBackupController(par, B)
 sv = ctrl.ocp_solver
