@@ -55,6 +55,47 @@ struct ParamBlock {
     int upload(smpc_handle* h, std::vector<double>& img);
 };
 
+// A device array per instance: valid for exactly the batch size it was set with.  A setter makes room, fills
+// the buffer (upload(), or work of its own on the handle's stream) and commits; readers take for_batch(B).  The members are defined
+// below the handle.
+struct SlotTag {
+    const char *noun, *setter;      // in messages: "instance scene", "smpc_set_instance_scene"
+    int B = 0;                      // the batch size the content is valid for; 0: none
+    void clear() { B = 0; }
+    void commit(int b) { B = b; }
+    // an entry point that reads the slot refuses any other B while it is set, never the shared input instead without a word
+    int guard(smpc_handle* h, int b, const char* who) const;
+};
+template <class T> struct InstSlot : SlotTag {
+    DevBuf<T> d;
+    InstSlot(const char* noun_, const char* setter_) : SlotTag{noun_, setter_} {}
+    const T* held() const { return B ? d.p : nullptr; }                       // for a reader whose entry point has guarded its B
+    const T* for_batch(int b) const { return B == b ? held() : nullptr; }     // for one that falls back to the shared input
+    // Room for n elements, grown only when n grows: the same size is overwritten in place, stream-ordered, and a captured step keeps
+    // seeing this buffer.  A failed growth leaves the slot empty; a refused one (capture) keeps the old content in force.
+    int room(smpc_handle* h, size_t n, bool zero = false);
+    // stream-ordered copy of n elements; a host source may be reused by the caller on return, so the stream is drained for it
+    int upload(smpc_handle* h, const T* src, size_t n, bool on_device, size_t at = 0);
+};
+
+// What smpc_set_mlp, smpc_set_mlp_activation and smpc_set_mlp_context establish.  A handle owns one and reads the network through
+// smpc_handle::net, which names its parent's in a worker of smpc_rollout_batch.
+struct Net {
+    int nlayers = 0;
+    int act = SMPC_ACT_GELU_TANH;
+    int dims[SMPC_MAX_LAYERS + 1] = {0};
+    int H = 0;
+    DevBuf<char> d_weights;         // one block for the three arrays below, 256-byte aligned
+    float* Wfwd[SMPC_MAX_LAYERS] = {nullptr};  // [K][N] = W^T (layer 0 padded to MLP_KPAD rows)
+    float* Wbwd[SMPC_MAX_LAYERS] = {nullptr};  // [out][in] as given (layer 0 padded to MLP_NPAD columns)
+    float* bias[SMPC_MAX_LAYERS] = {nullptr};
+    // the network's context (smpc_set_mlp_context, DESIGN.md section 9j): n_ctx numbers of the instance's scene behind the 2 nn_dof
+    // state features of layer 0's input
+    int n_ctx = 0;                  // 0: a network without context columns
+    double ctx_mean[MLP_KPAD] = {0}, ctx_std[MLP_KPAD] = {0};
+    DevBuf<float> d_default_ctx;    // [MLP_KPAD] the normalised default context
+};
+
 struct smpc_handle {
     smpc_problem_desc desc;
     int device = 0;
@@ -63,34 +104,20 @@ struct smpc_handle {
     smpc_problem_desc* d_desc = nullptr;
     DevBuf<double> d_lo, d_hi;      // [N+1][nx] stage bounds
     DevBuf<double> d_zl;            // [N+1] run-time slack weights of the soft safe-set rows (cost_set); empty: the formulation's
-    DevBuf<double> d_lo_b, d_hi_b;  // [B][N+1][nx] per-instance bounds (RealReceding), valid for inst_B
-    int inst_B = 0;
-    DevBuf<double> d_scene;         // [B][T][n_rows][SMPC_SCENE_ROW] per-instance obstacle geometry along time (smpc_set_instance_scene_track;
-                                    // smpc_set_instance_scene: T = 1), valid for scene_B
-    int scene_B = 0;                // 0: no scene, every launcher takes the shared-scene kernels
-    int64_t scene_T = 1;            // time columns of d_scene
+    // the per-instance inputs (InstSlot).  Unset: every launcher takes the shared input -- the descriptor's scene, the caller's
+    // reference table (or none), the default context row, the shared stage bounds.
+    InstSlot<double> bounds{"per-instance bounds", "smpc_set_instance_bounds"};     // [lo | hi], a half of the buffer each, both
+                                                                                    // [B][N+1][nx] (RealReceding); not guarded
+    InstSlot<double> scene{"instance scene", "smpc_set_instance_scene"};    // [B][T][n_rows][SMPC_SCENE_ROW] obstacle geometry along
+                                                                            // time (smpc_set_instance_scene_track; _scene: T = 1)
+    int64_t scene_T = 1;            // time columns of the scene
     const int64_t* scene_clock = nullptr;   // the caller's device cell of smpc_set_scene_clock; null: time 0
-    DevBuf<double> d_curves;        // [B][3][L] per-instance reference curves (smpc_set_instance_curves), valid for curves_B / curves_L
-    int curves_B = 0;               // 0: no curves, the policy step and the score take the caller's shared table (or none)
+    InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
+    InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][n_ctx] normalised context of the network
     // network
-    int nlayers = 0;
-    int act = SMPC_ACT_GELU_TANH;
-    int dims[SMPC_MAX_LAYERS + 1] = {0};
-    int H = 0;
-    DevBuf<char> d_weights;         // one block for the three arrays below, 256-byte aligned (empty in a worker of smpc_rollout_batch:
-                                    // it borrows its parent's)
-    float* d_Wfwd[SMPC_MAX_LAYERS] = {nullptr};  // [K][N] = W^T (layer 0 padded to MLP_KPAD rows)
-    float* d_Wbwd[SMPC_MAX_LAYERS] = {nullptr};  // [out][in] as given (layer 0 padded to MLP_NPAD columns)
-    float* d_bias[SMPC_MAX_LAYERS] = {nullptr};
-    // the network's context (smpc_set_mlp_context, DESIGN.md section 9j): n_ctx numbers of the instance's scene behind the 2 nn_dof
-    // state features of layer 0's input
-    int n_ctx = 0;                  // 0: a network without context columns
-    double ctx_mean[MLP_KPAD] = {0}, ctx_std[MLP_KPAD] = {0};
-    DevBuf<float> d_ctx_def;        // [MLP_KPAD] the normalised default context (empty in a worker: it borrows its parent's)
-    const float* ctx_def = nullptr; // the default row the kernels read: d_ctx_def.p, or the parent's
-    DevBuf<float> d_ctx;            // [B][n_ctx] normalised per-instance context (smpc_set_instance_context), valid for ctx_B
-    int ctx_B = 0;                  // 0: none, every row takes the default
+    Net own_net;
+    const Net* net = &own_net;      // the network this handle runs: its own, or the parent's in a worker of smpc_rollout_batch
     // per-batch scratch of the solve path (ensure_batch)
     DevBuf<double> d_ev;    // linearisation records of the last call, interleaved tiles of EV_TILE nodes (device_model.hpp)
     DevBuf<double> d_nn;    // value and gradient of the network's row (read by the stage builder): [B][N+1][1 + nx] with the row
@@ -213,7 +240,33 @@ int ParamBlock::upload(smpc_handle* h, std::vector<double>& img) {
     return SMPC_OK;
 }
 
+int SlotTag::guard(smpc_handle* h, int b, const char* who) const {
+    if (B && B != b)
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the %s was set for %d instances (%s: clear it or set one of this size)", who, b,
+                    noun, B, setter);
+    return SMPC_OK;
+}
+template <class T> int InstSlot<T>::room(smpc_handle* h, size_t n, bool zero) {
+    const int rc = d.reserve(h, noun, n * sizeof(T), zero);
+    if (rc && !d.p) clear();
+    return rc;
+}
+template <class T> int InstSlot<T>::upload(smpc_handle* h, const T* src, size_t n, bool on_device, size_t at) {
+    HIPCHK(h, hipMemcpyAsync(d.p + at, src, n * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SMPC_OK;
+}
+
 namespace {
+
+// An entry point that cannot honour per-instance inputs at all refuses each of the given slots while it is set.
+int refuse_slots(smpc_handle* h, const char* who, const char* why, std::initializer_list<const SlotTag*> slots) {
+    for (const SlotTag* s : slots)
+        if (s->B)
+            return fail(h, SMPC_ESTATE, "%s: an %s is set (for %d instances) and %s: clear it (%s with a NULL array)", who, s->noun, s->B,
+                        why, s->setter);
+    return SMPC_OK;
+}
 
 // Bump allocator, 256-byte alignment unless told otherwise: with a null base it only sizes a layout (off), with a buffer's base it
 // places it.
@@ -318,16 +371,16 @@ int upload_bounds(smpc_handle* h, const double* lo, const double* hi) {
 // the network pass's buffers for M rows: level 0 the output alone (k_mlp_fused), 1 also the hidden layers' activation derivatives
 // (k_mlp_wave), 2 every buffer of the layer-by-layer GEMM chain
 int ensure_mlp(smpc_handle* h, size_t M, int level = 2) {
-    const size_t Mp = (M + 127) / 128 * 128, row = sizeof(float) * Mp, H = h->H;
+    const size_t Mp = (M + 127) / 128 * 128, row = sizeof(float) * Mp, H = h->net->H;
     int rc;
     if ((rc = h->d_y.reserve(h, "network output", row))) return rc;
-    for (int l = 0; level >= 1 && l + 1 < h->nlayers; l++)
+    for (int l = 0; level >= 1 && l + 1 < h->net->nlayers; l++)
         if ((rc = h->d_dg[l].reserve(h, "network activation derivatives", row * H))) return rc;
     if (level < 2) return SMPC_OK;
     if ((rc = h->d_S.reserve(h, "network features", row * MLP_KPAD)) || (rc = h->d_GS.reserve(h, "network gradients", row * MLP_NPAD)) ||
         (rc = h->d_dA.reserve(h, "network backward pass", row * H)) || (rc = h->d_dB.reserve(h, "network backward pass", row * H)))
         return rc;
-    for (int l = 0; l + 1 < h->nlayers; l++)
+    for (int l = 0; l + 1 < h->net->nlayers; l++)
         if ((rc = h->d_act[l].reserve(h, "network activations", row * H))) return rc;
     return SMPC_OK;
 }
@@ -359,15 +412,17 @@ CtxSrc rows_step_major(int B, long m0) { CtxSrc c; c.mod = B; c.m0 = (int)(m0 % 
 template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const double* d_x, bool backward, CtxSrc rows,
                               const double* d_p = nullptr, double* d_ev = nullptr, bool* chained = nullptr, int compact = 0) {
     int rc;
-    // the instances' own rows when they are set (every entry point has checked its B against ctx_B: ctx_guard), else the default row
+    // the instances' own rows when they are set (every entry point has checked its B against the slot's: guard), else the default row
     // for all; without context columns the kernels' context loop has no iteration
+    const Net& net = *h->net;
     CtxSrc cx = rows;
-    if (h->n_ctx > 0) {
-        cx.n = h->n_ctx;
-        cx.p = h->ctx_B ? h->d_ctx.p : h->ctx_def;
-        cx.stride = h->ctx_B ? h->n_ctx : 0;
+    if (net.n_ctx > 0) {
+        const float* own = h->ctx.held();
+        cx.n = net.n_ctx;
+        cx.p = own ? own : net.d_default_ctx.p;
+        cx.stride = own ? net.n_ctx : 0;
     }
-    const int Mp = (M + 127) / 128 * 128, H = h->H, L = h->nlayers;
+    const int Mp = (M + 127) / 128 * 128, H = net.H, L = net.nlayers;
     hipStream_t s = h->stream;
     const int32_t* idx = mode == 3 ? h->d_nn_idx.p : nullptr;
     const int32_t* live = mode == 3 ? h->d_nn_cnt : nullptr;
@@ -382,13 +437,13 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         if (!no_fused && rows_all < fused_max && H == MLPF_H && L == 4 && (!backward || (d_p && d_ev))) {
             if ((rc = ensure_mlp(h, (size_t)M, 0))) return rc;
             MlpWeights Wt;
-            for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
+            for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = net.Wfwd[l]; Wt.wb[l] = net.Wbwd[l]; Wt.bias[l] = net.bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(256);
             if (backward)
-                hipLaunchKernelGGL((k_mlp_fused<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
+                hipLaunchKernelGGL((k_mlp_fused<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, net.act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
                                    compact, cx);
             else
-                hipLaunchKernelGGL((k_mlp_fused<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
+                hipLaunchKernelGGL((k_mlp_fused<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, net.act, Wt, d_x, d_p, idx, live, h->d_y.p,
                                    (double*)nullptr, 0, cx);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
@@ -401,13 +456,13 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         if (!no_fused && !large_chain && rows_all >= fused_max && H == MLPF_H && L == 4 && (!backward || (d_p && d_ev))) {
             if ((rc = ensure_mlp(h, (size_t)M, backward ? 1 : 0))) return rc;
             MlpWeights Wt;
-            for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = h->d_Wfwd[l]; Wt.wb[l] = h->d_Wbwd[l]; Wt.bias[l] = h->d_bias[l]; }
+            for (int l = 0; l < SMPC_MAX_LAYERS; l++) { Wt.wf[l] = net.Wfwd[l]; Wt.wb[l] = net.Wbwd[l]; Wt.bias[l] = net.bias[l]; }
             const dim3 grd((M + MLPF_ROWS - 1) / MLPF_ROWS), blk(64);
             if (backward)
-                hipLaunchKernelGGL((k_mlp_wave<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
+                hipLaunchKernelGGL((k_mlp_wave<NQ, true>), grd, blk, 0, s, h->d_desc, M, N, mode, net.act, Wt, d_x, d_p, idx, live, h->d_y.p, d_ev,
                                    compact, h->d_dg[0].p, h->d_dg[1].p, h->d_dg[2].p, cx);
             else
-                hipLaunchKernelGGL((k_mlp_wave<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, h->act, Wt, d_x, d_p, idx, live, h->d_y.p,
+                hipLaunchKernelGGL((k_mlp_wave<NQ, false>), grd, blk, 0, s, h->d_desc, M, N, mode, net.act, Wt, d_x, d_p, idx, live, h->d_y.p,
                                    (double*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, cx);
             HIPCHK(h, hipGetLastError());
             if (chained) *chained = backward;
@@ -423,22 +478,22 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
     // alone on the GPU (90 vs 79 TFLOP/s) but in C4's loop its blocks waited for CUs that QP wavefronts keep refilling: 12-14 ms per
     // solve for 1.9 ms of work (profiles/r04_c4_kernel_summary_by_grid.txt).
     const dim3 blk(64), grd(Mp / 32, H / 64);
-    hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, MLP_KPAD, h->d_S.p, h->d_Wfwd[0], h->d_bias[0],
-                       (const float*)nullptr, h->d_act[0].p, h->d_dg[0].p, live, h->act);
+    hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, MLP_KPAD, h->d_S.p, net.Wfwd[0], net.bias[0],
+                       (const float*)nullptr, h->d_act[0].p, h->d_dg[0].p, live, net.act);
     for (int l = 1; l + 1 < L; l++)
-        hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1].p, h->d_Wfwd[l], h->d_bias[l],
-                           (const float*)nullptr, h->d_act[l].p, h->d_dg[l].p, live, h->act);
+        hipLaunchKernelGGL((k_gemm_f32<EPI_BIAS_GELU>), grd, blk, 0, s, Mp, H, H, h->d_act[l - 1].p, net.Wfwd[l], net.bias[l],
+                           (const float*)nullptr, h->d_act[l].p, h->d_dg[l].p, live, net.act);
     hipLaunchKernelGGL(k_nn_output, dim3((Mp + 3) / 4), dim3(256), 0, s, Mp, H, h->d_act[L - 2].p, h->d_dg[L - 2].p,
-                       h->d_Wbwd[L - 1], h->d_bias[L - 1], h->d_y.p, h->d_dA.p, live);
+                       net.Wbwd[L - 1], net.bias[L - 1], h->d_y.p, h->d_dA.p, live);
     if (backward) {
         float *cur = h->d_dA.p, *nxt = h->d_dB.p;
         for (int l = L - 2; l >= 1; l--) {
-            hipLaunchKernelGGL((k_gemm_f32<EPI_MUL>), grd, blk, 0, s, Mp, H, H, cur, h->d_Wbwd[l], (const float*)nullptr,
-                               h->d_dg[l - 1].p, nxt, (float*)nullptr, live, h->act);
+            hipLaunchKernelGGL((k_gemm_f32<EPI_MUL>), grd, blk, 0, s, Mp, H, H, cur, net.Wbwd[l], (const float*)nullptr,
+                               h->d_dg[l - 1].p, nxt, (float*)nullptr, live, net.act);
             float* t = cur; cur = nxt; nxt = t;
         }
         hipLaunchKernelGGL((k_gemm_f32<EPI_PLAIN>), dim3(Mp / 32, MLP_NPAD / 64), blk, 0, s, Mp, MLP_NPAD, H, cur,
-                           h->d_Wbwd[0], (const float*)nullptr, (const float*)nullptr, h->d_GS.p, (float*)nullptr, live, h->act);
+                           net.Wbwd[0], (const float*)nullptr, (const float*)nullptr, h->d_GS.p, (float*)nullptr, live, net.act);
     }
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
@@ -451,7 +506,7 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
     if (h->desc.nn_mode == SMPC_NN_NONE) return SMPC_OK;
     const int N = h->N;
     hipStream_t s = h->stream;
-    if (h->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_mode != NONE but smpc_set_mlp was not called");
+    if (h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_mode != NONE but smpc_set_mlp was not called");
     // row on every node: only the nodes whose per-node switch is on are evaluated (compacted list, mode 3)
     const int mode = h->desc.nn_mode == SMPC_NN_TERMINAL ? 1 : 3;
     const int M = mode == 1 ? B : B * N;
@@ -470,41 +525,20 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
     return SMPC_OK;
 }
 
-// A scene belongs to its batch size: an entry point that evaluates collision rows refuses any other B while one is set (it would
-// otherwise solve in the descriptor's world without a word).  The launchers below then pick the SCENE instantiation through
-// with_scene.
-int scene_guard(smpc_handle* h, int B, const char* who) {
-    if (h->scene_B && h->scene_B != B)
-        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance scene was set for %d instances (smpc_set_instance_scene: clear "
-                    "it or set one of this size)", who, B, h->scene_B);
-    return SMPC_OK;
-}
 // f(std::true_type{}, sc) with the handle's scene track when it was set for B instances, else f(std::false_type{}, nullptr): a launcher
 // names its kernel and its arguments once, as with with_rows below.  (The SCENE instantiation first: a kernel's place in the code
 // object follows its first mention, see ensure_batch.)  off: added to the clock (smpc_loop_post); clocked = false: the kernel
 // counts time from 0 (smpc_score_rollout).  A single column needs no time, so the clock is not handed on with T = 1.
 template <class F> int with_scene(const smpc_handle* h, int B, F&& f, int64_t off = 0, bool clocked = true) {
-    if (h->scene_B == B)
-        return f(std::true_type{}, SceneSrc{h->d_scene.p, clocked && h->scene_T > 1 ? h->scene_clock : nullptr, h->scene_T, off});
+    if (const double* geom = h->scene.for_batch(B))
+        return f(std::true_type{}, SceneSrc{geom, clocked && h->scene_T > 1 ? h->scene_clock : nullptr, h->scene_T, off});
     return f(std::false_type{}, (const double*)nullptr);
 }
 
-// The instance context belongs to its batch size in the same way: every entry point that runs the network refuses another B while
-// one is set, never the default context instead.
-int ctx_guard(smpc_handle* h, int B, const char* who) {
-    if (h->ctx_B && h->ctx_B != B)
-        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance context was set for %d instances (smpc_set_instance_context: "
-                    "clear it or set one of this size)", who, B, h->ctx_B);
-    return SMPC_OK;
-}
-
-// The curves belong to their batch size in the same way: the two entry points that read them refuse another B while they are set,
-// never the shared reference instead.
-int curves_guard(smpc_handle* h, int B, const char* who) {
-    if (h->curves_B && h->curves_B != B)
-        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance curves were set for %d instances (smpc_set_instance_curves: "
-                    "clear them or set curves of this size)", who, B, h->curves_B);
-    return SMPC_OK;
+// The guards of an entry point that evaluates collision rows and runs the network (SlotTag::guard)
+int guard_scene_and_context(smpc_handle* h, int B, const char* who) {
+    const int rc = h->scene.guard(h, B, who);
+    return rc ? rc : h->ctx.guard(h, B, who);
 }
 
 // The reference table of a policy step: the handle's curves (a table per instance) or the caller's shared one (stride 0), or none.
@@ -514,12 +548,12 @@ struct TrajSrc {
 };
 int policy_traj_src(smpc_handle* h, int B, const smpc_policy_state* st, TrajSrc* out) {
     int rc;
-    if ((rc = curves_guard(h, B, "smpc_policy_step"))) return rc;
-    if (h->curves_B) {
+    if ((rc = h->curves.guard(h, B, "smpc_policy_step"))) return rc;
+    if (const double* own = h->curves.held()) {
         if (st->traj)
             return fail(h, SMPC_EINVAL, "smpc_policy_step: st->traj given (traj_len %lld) while instance curves are set (%d instances, "
-                        "%lld columns): two sources for one input, clear one", (long long)st->traj_len, h->curves_B, (long long)h->curves_L);
-        *out = TrajSrc{h->d_curves.p, (long)h->curves_L, 3 * (long)h->curves_L};
+                        "%lld columns): two sources for one input, clear one", (long long)st->traj_len, h->curves.B, (long long)h->curves_L);
+        *out = TrajSrc{own, (long)h->curves_L, 3 * (long)h->curves_L};
         return SMPC_OK;
     }
     if (st->traj) {
@@ -568,25 +602,19 @@ template <class F> int with_rows(const smpc_handle* h, F&& f) {
     }
 }
 
+// Room for the per-instance bounds of B instances, zeroed when grown if asked: lo in the buffer's first half, hi in its second (a
+// half keeps its place, and what it holds, whatever B a buffer that is large enough serves next)
+int ensure_instance_bounds(smpc_handle* h, int B, bool zero) { return h->bounds.room(h, (size_t)2 * B * (h->N + 1) * 2 * h->desc.nq, zero); }
+double* instance_hi(const smpc_handle* h) { return h->bounds.d.p ? h->bounds.d.p + h->bounds.d.cap / (2 * sizeof(double)) : nullptr; }
+
 // the stage bounds the set-up reads: per instance (RealReceding) when they were given for this batch size, else the shared ones
 struct StageBounds {
     const double *lo, *hi;
     long stride;
 };
 StageBounds stage_bounds(const smpc_handle* h, int B) {
-    if (h->inst_B == B) return {h->d_lo_b.p, h->d_hi_b.p, (long)(h->N + 1) * 2 * h->desc.nq};
+    if (const double* lo = h->bounds.for_batch(B)) return {lo, instance_hi(h), (long)(h->N + 1) * 2 * h->desc.nq};
     return {h->d_lo.p, h->d_hi.p, 0L};
-}
-
-// RealReceding's per-instance bounds for B instances, zeroed when grown if asked.  A failure that freed or replaced either array
-// leaves no per-instance bounds (inst_B = 0); a refused growth keeps the old ones.
-int ensure_instance_bounds(smpc_handle* h, int B, bool zero) {
-    const size_t bytes = sizeof(double) * B * (h->N + 1) * 2 * h->desc.nq;
-    int rc;
-    if ((rc = h->d_lo_b.reserve(h, "per-instance bounds", bytes, zero)) || (rc = h->d_hi_b.reserve(h, "per-instance bounds", bytes, zero))) {
-        if (!h->d_lo_b.p || h->d_lo_b.cap != h->d_hi_b.cap) h->inst_B = 0;
-    }
-    return rc;
 }
 
 // everything of a solve before the interior point: the network pass, then the stage records of the QP workspace by the
@@ -879,7 +907,8 @@ RollScratch roll_layout(char* base, int n, int N, int nq) {
     return r;
 }
 
-// Worker handles of smpc_rollout_batch: same problem, own stream and workspaces, the parent's network weights (borrowed).
+// Worker handles of smpc_rollout_batch: same problem, own stream and workspaces, the parent's network (smpc_handle::net).  What a
+// worker takes from its parent it takes here, on every call: no setter pushes a value to the workers.
 int rollout_workers(smpc_handle* h, int n) {
     while ((int)h->kids.size() < n) {
         smpc_handle* k = nullptr;
@@ -891,14 +920,8 @@ int rollout_workers(smpc_handle* h, int n) {
         smpc_handle* k = h->kids[i];
         int rc;
         if (k->N != h->N && (rc = smpc_set_horizon(k, h->N))) return fail(h, rc, "rollout worker: %s", k->err);
-        k->nlayers = h->nlayers;
-        k->act = h->act;
+        k->net = h->net;                // (with the weights goes the default context; a worker holds no instance context)
         k->qp_mode = h->qp_mode;
-        k->H = h->H;
-        for (int l = 0; l <= SMPC_MAX_LAYERS; l++) k->dims[l] = h->dims[l];
-        for (int l = 0; l < SMPC_MAX_LAYERS; l++) { k->d_Wfwd[l] = h->d_Wfwd[l]; k->d_Wbwd[l] = h->d_Wbwd[l]; k->d_bias[l] = h->d_bias[l]; }
-        k->n_ctx = h->n_ctx;            // (with the weights goes the default context; a worker holds no instance context)
-        k->ctx_def = h->ctx_def;
         // stage bounds and slack weights follow the parent (small; stream-ordered on the worker's stream)
         const size_t nb = (size_t)(h->N + 1) * 2 * h->desc.nq;
         HIPCHK(h, hipMemcpyAsync(k->d_lo.p, h->d_lo.p, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
@@ -1121,7 +1144,7 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
     const long nodes = (long)B * (N + 1);
     const float* y = nullptr;
     if (h->desc.nn_mode != SMPC_NN_NONE) {
-        if (h->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_mode != NONE but smpc_set_mlp was not called");
+        if (h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_mode != NONE but smpc_set_mlp was not called");
         const int terminal = h->desc.nn_mode == SMPC_NN_TERMINAL;
         const int M = terminal ? B : B * N;          // the list's capacity
         int rc;
@@ -1452,24 +1475,25 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
         if (dims[l] != H) return fail(h, SMPC_EINVAL, "hidden layers must share one width");
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers borrow the weight buffers rewritten below)
+    for (smpc_handle* k : h->kids) smpc_destroy(k);      // (workers read the weight block, which may move below)
     h->kids.clear();
-    h->nlayers = 0;     // (no network until every layer is in place)
-    h->n_ctx = 0;       // (new weights mean no context: layer 0's context rows are rewritten as zeros below)
-    h->ctx_B = 0;
+    Net& net = h->own_net;
+    net.nlayers = 0;    // (no network until every layer is in place)
+    net.n_ctx = 0;      // (new weights mean no context: layer 0's context rows are rewritten as zeros below)
+    h->ctx.clear();
     // one block for every layer's W^T (layer 0 padded to MLP_KPAD rows), W (layer 0 padded to MLP_NPAD columns) and b
     const auto layout = [&](char* base) {
         Carve m{base};
         for (int l = 0; l < nlayers; l++) {
-            h->d_Wfwd[l] = m.take<float>((size_t)(l == 0 ? MLP_KPAD : dims[l]) * dims[l + 1]);
-            h->d_Wbwd[l] = m.take<float>((size_t)dims[l + 1] * (l == 0 ? MLP_NPAD : dims[l]));
-            h->d_bias[l] = m.take<float>(dims[l + 1]);
+            net.Wfwd[l] = m.take<float>((size_t)(l == 0 ? MLP_KPAD : dims[l]) * dims[l + 1]);
+            net.Wbwd[l] = m.take<float>((size_t)dims[l + 1] * (l == 0 ? MLP_NPAD : dims[l]));
+            net.bias[l] = m.take<float>(dims[l + 1]);
         }
         return m.off;
     };
     int rc;
-    if ((rc = h->d_weights.reserve(h, "network weights", layout(nullptr)))) return rc;
-    layout(h->d_weights.p);
+    if ((rc = net.d_weights.reserve(h, "network weights", layout(nullptr)))) return rc;
+    layout(net.d_weights.p);
     for (int l = 0; l < nlayers; l++) {
         const int ni = dims[l], no = dims[l + 1];
         std::vector<float> w((size_t)ni * no), bb(no);
@@ -1483,29 +1507,29 @@ int smpc_set_mlp(smpc_handle* h, int nlayers, const int32_t* dims, const float* 
                 wf[(size_t)i * no + o] = w[(size_t)o * ni + i];
                 wb[(size_t)o * nb + i] = w[(size_t)o * ni + i];
             }
-        HIPCHK(h, hipMemcpy(h->d_Wfwd[l], wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->d_Wbwd[l], wb.data(), wb.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->d_bias[l], bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(net.Wfwd[l], wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(net.Wbwd[l], wb.data(), wb.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(net.bias[l], bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    h->nlayers = nlayers;
-    for (int l = 0; l <= nlayers; l++) h->dims[l] = dims[l];
-    h->H = H;
+    net.nlayers = nlayers;
+    for (int l = 0; l <= nlayers; l++) net.dims[l] = dims[l];
+    net.H = H;
     return SMPC_OK;
 }
 
 int smpc_set_mlp_activation(smpc_handle* h, int act) {
     if (!h) return SMPC_EINVAL;
     if (act < SMPC_ACT_GELU_TANH || act > SMPC_ACT_SILU) return fail(h, SMPC_EINVAL, "unknown activation %d", act);
-    h->act = act;
-    for (smpc_handle* k : h->kids) k->act = act;
+    h->own_net.act = act;
     return SMPC_OK;
 }
 
 int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const double* ctx_mean, const double* ctx_std,
                          const double* ctx_default, int on_device) {
     if (!h) return SMPC_EINVAL;
-    if (h->nlayers == 0) return fail(h, SMPC_ESTATE, "smpc_set_mlp_context: smpc_set_mlp was not called");
-    const int nd2 = 2 * h->desc.nn_dof, room = MLP_KPAD - nd2, H = h->dims[1];
+    Net& net = h->own_net;
+    if (net.nlayers == 0) return fail(h, SMPC_ESTATE, "smpc_set_mlp_context: smpc_set_mlp was not called");
+    const int nd2 = 2 * h->desc.nn_dof, room = MLP_KPAD - nd2, H = net.dims[1];
     if (n_ctx < 0 || n_ctx > room)
         return fail(h, SMPC_EINVAL, "smpc_set_mlp_context: n_ctx=%d outside 0..%d: layer 0's input is padded to %d columns and the state "
                     "takes 2*n_dof_safe_set = %d of them", n_ctx, room, MLP_KPAD, nd2);
@@ -1540,32 +1564,28 @@ int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const doubl
         for (int c = 0; c < n_ctx; c++) defn[c] = (float)((def[c] - mean[c]) / std_[c]);
     }
     int rc;
-    if (!clear && (rc = h->d_ctx_def.reserve(h, "default context", sizeof(defn)))) return rc;
+    if (!clear && (rc = net.d_default_ctx.reserve(h, "default context", sizeof(defn)))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (smpc_handle* k : h->kids) HIPCHK(h, hipStreamSynchronize(k->stream));      // (the workers read these weights too)
-    h->n_ctx = 0;
-    h->ctx_B = 0;       // (an instance context belongs to the context columns it was normalised for)
-    if (room > 0) HIPCHK(h, hipMemcpy(h->d_Wfwd[0] + (size_t)nd2 * H, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (clear) {
-        for (smpc_handle* k : h->kids) k->n_ctx = 0;
-        return SMPC_OK;
-    }
-    HIPCHK(h, hipMemcpy(h->d_ctx_def.p, defn, sizeof(defn), hipMemcpyHostToDevice));
-    h->ctx_def = h->d_ctx_def.p;
-    for (int c = 0; c < MLP_KPAD; c++) { h->ctx_mean[c] = mean[c]; h->ctx_std[c] = c < n_ctx ? std_[c] : 1.0; }
-    h->n_ctx = n_ctx;
-    for (smpc_handle* k : h->kids) { k->n_ctx = n_ctx; k->ctx_def = h->ctx_def; }
+    net.n_ctx = 0;
+    h->ctx.clear();     // (an instance context belongs to the context columns it was normalised for)
+    if (room > 0) HIPCHK(h, hipMemcpy(net.Wfwd[0] + (size_t)nd2 * H, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (clear) return SMPC_OK;
+    HIPCHK(h, hipMemcpy(net.d_default_ctx.p, defn, sizeof(defn), hipMemcpyHostToDevice));
+    for (int c = 0; c < MLP_KPAD; c++) { net.ctx_mean[c] = mean[c]; net.ctx_std[c] = c < n_ctx ? std_[c] : 1.0; }
+    net.n_ctx = n_ctx;
     return SMPC_OK;
 }
 
 int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
-    if (!ctx) { h->ctx_B = 0; return SMPC_OK; }
-    if (h->n_ctx == 0)
+    if (!ctx) { h->ctx.clear(); return SMPC_OK; }
+    const Net& net = *h->net;
+    if (net.n_ctx == 0)
         return fail(h, SMPC_EINVAL, "smpc_set_instance_context: the network has no context columns (smpc_set_mlp_context was not called)");
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
-    const int nc = h->n_ctx;
+    const int nc = net.n_ctx;
     const size_t n = (size_t)B * nc;
     std::vector<float> norm;
     if (!on_device) {
@@ -1574,25 +1594,19 @@ int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_d
         for (size_t i = 0; i < n; i++) {
             if (!(ctx[i] - ctx[i] == 0.0))
                 return fail(h, SMPC_EINVAL, "context of instance %zu (of B=%d), number %zu (of %d) is not finite", i / nc, B, i % nc, nc);
-            norm[i] = (float)((ctx[i] - h->ctx_mean[i % nc]) / h->ctx_std[i % nc]);
+            norm[i] = (float)((ctx[i] - net.ctx_mean[i % nc]) / net.ctx_std[i % nc]);
         }
     }
     int rc;
-    // (grown only when the batch grows: the same B is overwritten in place, stream-ordered, and a captured step keeps seeing this buffer)
-    if ((rc = h->d_ctx.reserve(h, "instance context", n * sizeof(float)))) {
-        if (!h->d_ctx.p) h->ctx_B = 0;      // (a failed growth left no buffer; a refused one keeps the old context)
-        return rc;
-    }
+    if ((rc = h->ctx.room(h, n))) return rc;
     if (on_device) {
         CtxNorm nm;
-        for (int c = 0; c < MLP_KPAD; c++) { nm.mean[c] = h->ctx_mean[c]; nm.std[c] = h->ctx_std[c]; }
-        hipLaunchKernelGGL(k_ctx_normalise, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, (long)n, nc, ctx, nm, h->d_ctx.p);
+        for (int c = 0; c < MLP_KPAD; c++) { nm.mean[c] = net.ctx_mean[c]; nm.std[c] = net.ctx_std[c]; }
+        hipLaunchKernelGGL(k_ctx_normalise, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, (long)n, nc, ctx, nm, h->ctx.d.p);
         HIPCHK(h, hipGetLastError());
-    } else {
-        HIPCHK(h, hipMemcpyAsync(h->d_ctx.p, norm.data(), n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
-    }
-    h->ctx_B = B;
+    } else if ((rc = h->ctx.upload(h, norm.data(), n, false)))
+        return rc;
+    h->ctx.commit(B);
     return SMPC_OK;
 }
 
@@ -1600,7 +1614,6 @@ int smpc_set_qp_mode(smpc_handle* h, int mode) {
     if (!h) return SMPC_EINVAL;
     if (mode < SMPC_QP_AUTO || mode > SMPC_QP_LATENCY) return fail(h, SMPC_EINVAL, "qp mode %d (SMPC_QP_AUTO, _THROUGHPUT, _LATENCY)", mode);
     h->qp_mode = mode;
-    for (smpc_handle* k : h->kids) k->qp_mode = mode;
     return SMPC_OK;
 }
 
@@ -1610,10 +1623,10 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->N = N;
-    h->inst_B = 0;
+    h->bounds.clear();      // (the one slot laid out by the horizon)
     h->order_B = 0;
     // every buffer laid out by the horizon starts afresh (zeroed where that is its contract) in the next call that needs it
-    for (DevBuf<double>* buf : {&h->d_zl, &h->d_lo_b, &h->d_hi_b, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
+    for (DevBuf<double>* buf : {&h->d_zl, &h->bounds.d, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
     h->d_par.release();
     h->d_sqp.release();
     h->d_guess.release();
@@ -1647,24 +1660,21 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
     if (!h) return SMPC_EINVAL;
     if ((lo == nullptr) != (hi == nullptr)) return fail(h, SMPC_EINVAL, "lo and hi must both be given or both be NULL");
     (void)hipSetDevice(h->device);
-    if (!lo) { h->inst_B = 0; return SMPC_OK; }
+    if (!lo) { h->bounds.clear(); return SMPC_OK; }
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
     const size_t n = (size_t)B * (h->N + 1) * 2 * h->desc.nq;
     int rc;
-    // (grown only when the tube grows: a per-step caller pays two stream-ordered copies)
-    if ((rc = ensure_instance_bounds(h, B, false))) return rc;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIPCHK(h, hipMemcpyAsync(h->d_lo_b.p, lo, n * sizeof(double), kind, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_hi_b.p, hi, n * sizeof(double), kind, h->stream));
-    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
-    h->inst_B = B;
+    if ((rc = ensure_instance_bounds(h, B, false)) || (rc = h->bounds.upload(h, lo, n, on_device != 0)) ||
+        (rc = h->bounds.upload(h, hi, n, on_device != 0, instance_hi(h) - h->bounds.d.p)))
+        return rc;
+    h->bounds.commit(B);
     return SMPC_OK;
 }
 
 int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
-    if (!geom) { h->scene_B = 0; h->scene_T = 1; return SMPC_OK; }
+    if (!geom) { h->scene.clear(); return SMPC_OK; }
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
     if (T < 1) return fail(h, SMPC_EINVAL, "smpc_set_instance_scene_track: T=%lld: a track has at least one time column", (long long)T);
     const int nr = h->desc.n_rows;
@@ -1687,14 +1697,8 @@ int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double
             }
     }
     int rc;
-    // (grown only when the track grows: a caller that moves its obstacles every step pays one stream-ordered copy)
-    if ((rc = h->d_scene.reserve(h, "instance scene", n * sizeof(double)))) {
-        if (!h->d_scene.p) { h->scene_B = 0; h->scene_T = 1; }      // (a failed growth left no buffer; a refused one keeps the old scene)
-        return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_scene.p, geom, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
-    h->scene_B = B;
+    if ((rc = h->scene.room(h, n)) || (rc = h->scene.upload(h, geom, n, on_device != 0))) return rc;
+    h->scene.commit(B);
     h->scene_T = T;
     return SMPC_OK;
 }
@@ -1713,7 +1717,7 @@ int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock) {
 int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* curves, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
-    if (!curves) { h->curves_B = 0; h->curves_L = 0; return SMPC_OK; }
+    if (!curves) { h->curves.clear(); return SMPC_OK; }
     if (B <= 0 || L < 1) return fail(h, SMPC_EINVAL, "smpc_set_instance_curves: B=%d, L=%lld: need B > 0 and L >= 1", B, (long long)L);
     const size_t n = (size_t)B * 3 * (size_t)L;
     if (!on_device) {
@@ -1724,14 +1728,8 @@ int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* cur
                             (long long)(i / (3 * (size_t)L)), B, (int)(i / (size_t)L % 3), (long long)(i % (size_t)L), (long long)L);
     }
     int rc;
-    // (grown only when the curves grow: the same (B, L) is overwritten in place, and a captured step keeps seeing this buffer)
-    if ((rc = h->d_curves.reserve(h, "instance curves", n * sizeof(double)))) {
-        if (!h->d_curves.p) { h->curves_B = 0; h->curves_L = 0; }      // (a failed growth left no buffer; a refused one keeps the old curves)
-        return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_curves.p, curves, n * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller on return
-    h->curves_B = B;
+    if ((rc = h->curves.room(h, n)) || (rc = h->curves.upload(h, curves, n, on_device != 0))) return rc;
+    h->curves.commit(B);
     h->curves_L = L;
     return SMPC_OK;
 }
@@ -1742,8 +1740,7 @@ int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, 
     if (B <= 0 || !x0 || !xg || !ug || !p || !x_out || !u_out || !status) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_solve_batch"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_solve_batch"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_solve_batch"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
     Stage io{h, on_device != 0};
@@ -1771,8 +1768,7 @@ int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, c
     if (B <= 0 || !xg || !ug || !p || !out) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_eval_nodes"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_eval_nodes"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_eval_nodes"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     hipStream_t s = h->stream;
@@ -1849,13 +1845,12 @@ int smpc_check_trajectory(smpc_handle* h, int B, int n_nodes, const double* x, c
     if (!h) return SMPC_EINVAL;
     if (B <= 0 || n_nodes <= 0 || !x || !x_min || !x_max || !state_ok) return fail(h, SMPC_EINVAL, "bad argument");
     if (h->desc.n_rows > 0 && (!row_lb_chk || !row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
-    if (nn_ok && h->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_ok requested but smpc_set_mlp was not called");
+    if (nn_ok && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "nn_ok requested but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
     const size_t M = (size_t)B * n_nodes;
     // (x_min / x_max / row bounds are host pointers on both paths: small, constant per caller)
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_check_trajectory"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_check_trajectory"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_check_trajectory"))) return rc;
     if ((rc = upload_check_bounds(h, x_min, x_max, row_lb_chk, row_ub_chk))) return rc;
     Stage io{h, on_device != 0};
     const double* dx;
@@ -1907,14 +1902,9 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     if (!h) return SMPC_EINVAL;
     if (B <= 0 || n_steps <= 0 || !x0 || !x_guess || !u_guess || !p || !x_traj || !u_traj || !status_traj)
         return fail(h, SMPC_EINVAL, "bad argument");
-    if (h->scene_B)
-        return fail(h, SMPC_ESTATE, "smpc_rollout_batch: an instance scene is set (for %d instances) and the worker handles of the "
-                    "rollout hold none: clear it with smpc_set_instance_scene(h, 0, NULL, 0), or step the loop through "
-                    "smpc_policy_step / smpc_loop_post", h->scene_B);
-    if (h->ctx_B)
-        return fail(h, SMPC_ESTATE, "smpc_rollout_batch: an instance context is set (for %d instances) and the worker handles of the "
-                    "rollout hold none: clear it with smpc_set_instance_context(h, 0, NULL, 0), or step the loop through "
-                    "smpc_policy_step / smpc_loop_post", h->ctx_B);
+    if (const int rf = refuse_slots(h, "smpc_rollout_batch", "the worker handles of the rollout hold none (step the loop through smpc_policy_step / "
+                                    "smpc_loop_post instead)", {&h->scene, &h->ctx}))
+        return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
@@ -1948,7 +1938,7 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     if (const char* ev = getenv("SMPC_ROLLOUT_STREAMS")) n_sub = atoi(ev);
     if (n_sub < 1) n_sub = 1;
     if (n_sub > B) n_sub = B;
-    if (h->inst_B == B) n_sub = 1;                       // per-instance stage bounds are held by this handle only
+    if (h->bounds.for_batch(B)) n_sub = 1;                      // per-instance stage bounds are held by this handle only
     // (workspaces are allocated by whoever solves: the workers below when the batch is split -- the parent then holds none of
     //  the QP workspace / linearisation records of the full batch -- otherwise this handle)
     rc = SMPC_OK;
@@ -2029,19 +2019,15 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     if (stepping && !u_other) return fail(h, SMPC_EINVAL, "u_other missing");
     if (kind != SMPC_POLICY_NAIVE && (!par->x_min || !par->x_max || (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk))))
         return fail(h, SMPC_EINVAL, "check bounds missing");
-    if ((receding || parallel) && h->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
-    if (parallel && h->scene_B)
-        return fail(h, SMPC_ESTATE, "smpc_policy_step: an instance scene is set (for %d instances) and the parallel policy's candidate "
-                    "slots are not instances: clear it with smpc_set_instance_scene(h, 0, NULL, 0)", h->scene_B);
-    if (parallel && h->ctx_B)
-        return fail(h, SMPC_ESTATE, "smpc_policy_step: an instance context is set (for %d instances) and the parallel policy's candidate "
-                    "slots are not instances: clear it with smpc_set_instance_context(h, 0, NULL, 0)", h->ctx_B);
+    if ((receding || parallel) && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
+    if (parallel)
+        if (const int rf = refuse_slots(h, "smpc_policy_step", "the parallel policy's candidate slots are not instances", {&h->scene, &h->ctx}))
+            return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_policy_step"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_policy_step"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_policy_step"))) return rc;
     TrajSrc tr;
     if (!parallel && (rc = policy_traj_src(h, B, st, &tr))) return rc;     // (before anything is enqueued; the parallel step asks itself)
     if ((rc = ensure_batch(h, B))) return rc;
@@ -2061,10 +2047,10 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
         if (kind == SMPC_POLICY_REAL_RECEDING) {
             // (zeroed when grown: instances that never step keep valid bounds)
             if ((rc = ensure_instance_bounds(h, B, true))) return rc;
-            h->inst_B = B;
+            h->bounds.commit(B);
         }
         hipLaunchKernelGGL(k_policy_pre, dim3((unsigned)(((size_t)B * (N + 1) + 63) / 64)), dim3(64), 0, s, B, N, nx, kind,
-                           stepping, st->r, st->p, st->x_guess, par->stage_lo, par->stage_hi, par->tube, h->d_lo_b.p, h->d_hi_b.p,
+                           stepping, st->r, st->p, st->x_guess, par->stage_lo, par->stage_hi, par->tube, h->bounds.d.p, instance_hi(h),
                            kind == SMPC_POLICY_REAL_RECEDING ? any_abort : (int32_t*)nullptr,
                            kind == SMPC_POLICY_REAL_RECEDING ? d_ok : (int32_t*)nullptr);
     }
@@ -2162,7 +2148,7 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     const int nq = h->desc.nq;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_loop_post"))) return rc;
+    if ((rc = h->scene.guard(h, B, "smpc_loop_post"))) return rc;
     PolScratch w;       // (its x_next [B][nx] and ok [B] lie behind smpc_policy_step's part)
     if ((rc = policy_scratch(h, B, &w))) return rc;
     if ((rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
@@ -2187,8 +2173,7 @@ int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, c
     const int N = h->N, nq = h->desc.nq;
     const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_merit_terms"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_merit_terms"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_merit_terms"))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, false, &w))) return rc;
     Stage io{h, on_device != 0};
@@ -2226,8 +2211,7 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
     const size_t nX = (size_t)B * nX1, nU = (size_t)B * nU1;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_sqp_batch"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_sqp_batch"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_sqp_batch"))) return rc;
     if ((rc = ensure_batch(h, B, false))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, true, &w))) return rc;
@@ -2302,12 +2286,11 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
     if (!par->x_min || !par->x_max || !par->tau_min || !par->tau_max) return fail(h, SMPC_EINVAL, "state or torque bounds missing");
     if (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
     if (par->safe_node > h->N) return fail(h, SMPC_EINVAL, "safe_node=%d beyond the horizon N=%d", (int)par->safe_node, h->N);
-    if (par->safe_node >= 0 && h->nlayers == 0) return fail(h, SMPC_ESTATE, "safe_node given but smpc_set_mlp was not called");
+    if (par->safe_node >= 0 && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "safe_node given but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_check_guess"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_check_guess"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_check_guess"))) return rc;
     if ((rc = upload_guess_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du;
@@ -2394,7 +2377,7 @@ int smpc_ik_batch(smpc_handle* h, int B, int S, const double* target, const doub
     (void)hipSetDevice(h->device);
     const int nq = h->desc.nq;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_ik_batch"))) return rc;
+    if ((rc = h->scene.guard(h, B, "smpc_ik_batch"))) return rc;
     if ((rc = upload_ik_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dt, *dq;
@@ -2424,15 +2407,14 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
     if (h->desc.n_rows > 0 && (!par->row_lb_chk || !par->row_ub_chk)) return fail(h, SMPC_EINVAL, "row check bounds missing");
     if (par->traj && par->traj_len < 1) return fail(h, SMPC_EINVAL, "traj given with traj_len=%lld", (long long)par->traj_len);
     // neither pointer: the reference of instance b is its own curve (smpc_set_instance_curves), if the handle holds curves
-    const bool own = !par->traj && !par->ee_ref && h->curves_B;
+    const bool own = !par->traj && !par->ee_ref && h->curves.B;
     if (!par->traj && !par->ee_ref && !own) return fail(h, SMPC_EINVAL, "neither ee_ref nor traj given");
-    if (par->want_safe && h->nlayers == 0) return fail(h, SMPC_ESTATE, "want_safe given but smpc_set_mlp was not called");
+    if (par->want_safe && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "want_safe given but smpc_set_mlp was not called");
     (void)hipSetDevice(h->device);
     const int nq = h->desc.nq;
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_score_rollout"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_score_rollout"))) return rc;
-    if (own && (rc = curves_guard(h, B, "smpc_score_rollout"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_score_rollout"))) return rc;
+    if (own && (rc = h->curves.guard(h, B, "smpc_score_rollout"))) return rc;
     if ((rc = upload_score_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du, *dtraj;
@@ -2451,7 +2433,7 @@ int smpc_score_rollout(smpc_handle* h, int B, int n_steps, const double* x_log, 
              douti = v.inout(outi, (size_t)B * SCORE_NI);
          })))
         return rc;
-    const double* ref = own ? h->d_curves.p : dtraj;
+    const double* ref = own ? h->curves.held() : dtraj;
     const long ref_len = own ? (long)h->curves_L : (long)par->traj_len, ref_stride = own ? 3 * (long)h->curves_L : 0L;
     if ((rc = with_nq(h, [&](auto NQ) { return launch_score<NQ>(h, B, n_steps, dx, du, dlx, dlu, par, ref, ref_len, ref_stride, dmask, dout, douti); })))
         return rc;
@@ -2557,8 +2539,7 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = scene_guard(h, B, "smpc_debug_stage_records"))) return rc;
-    if ((rc = ctx_guard(h, B, "smpc_debug_stage_records"))) return rc;
+    if ((rc = guard_scene_and_context(h, B, "smpc_debug_stage_records"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     Stage io{h, false};

@@ -149,20 +149,10 @@ class BatchedOcpSolver:
         normalised fp32 copy.  None clears it: every row then takes the default context again.  While set, every call that runs the
         network must come with the same B; the parallel policy and :meth:`rollout` refuse it.  The engine does not derive it from
         :meth:`set_instance_scene`: set and clear the two together."""
-        if ctx is None:
-            self._chk(self.L.smpc_set_instance_context(self.h, 0, None, 0))
-            return
-        if _is_torch(ctx):
-            import torch
-            if ctx.dtype != torch.float64:
-                raise ValueError('set_instance_context: the context must be float64')
         n_ctx = int(getattr(self.net, 'n_ctx', 0)) if self.net is not None else 0
-        if ctx.ndim != 2 or (n_ctx and ctx.shape[1] != n_ctx):
+        if ctx is not None and (ctx.ndim != 2 or (n_ctx and ctx.shape[1] != n_ctx)):
             raise ValueError(f'set_instance_context: expected [B, {n_ctx}], got {tuple(ctx.shape)}')
-        B = int(ctx.shape[0])
-        ptrs, dev, keep = self._prep([ctx], [tuple(ctx.shape)])
-        with self._ordered(dev):
-            self._chk(self.L.smpc_set_instance_context(self.h, B, ptrs[0], dev))
+        self._set_instance(self.L.smpc_set_instance_context, 'set_instance_context', [ctx], None if ctx is None else ctx.shape[1:])
 
     QP_MODES = {'auto': -1, 'throughput': 0, 'latency': 1}
 
@@ -195,30 +185,15 @@ class BatchedOcpSolver:
 
     def set_instance_bounds(self, lo=None, hi=None):
         """Per-instance stage bounds [B, N+1, nx] (RealReceding's state tube, controller.py:530-536); None clears."""
-        if lo is None:
-            self._chk(self.L.smpc_set_instance_bounds(self.h, 0, None, None, 0))
-            return
-        B = lo.shape[0]
-        ptrs, dev, keep = self._prep([lo, hi], [(B, self.N + 1, self.nx)] * 2)
-        with self._ordered(dev):
-            self._chk(self.L.smpc_set_instance_bounds(self.h, B, ptrs[0], ptrs[1], dev))
+        self._set_instance(self.L.smpc_set_instance_bounds, 'set_instance_bounds', [None, None] if lo is None else [lo, hi],
+                           (self.N + 1, self.nx))
 
     def set_instance_scene(self, geom=None):
         """A scene of its own for every instance (smpc_set_instance_scene): ``geom [B, n_rows, 8]`` -- per (instance, row) the
         world-fixed element's C[3], D[3], offset, 0, as ``OcpProblem.row_geometry`` / ``scene`` / ``jittered_scenes`` lay it out --
         as a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy.  None clears it.  While set, every call that
         evaluates collision rows uses it and must come with the same B; the parallel policy and :meth:`rollout` refuse it."""
-        if geom is None:
-            self._chk(self.L.smpc_set_instance_scene(self.h, 0, None, 0))
-            return
-        if _is_torch(geom):
-            import torch
-            if geom.dtype != torch.float64:
-                raise ValueError('set_instance_scene: the scene must be float64')
-        B = int(geom.shape[0])
-        ptrs, dev, keep = self._prep([geom], [(B, len(self.problem.rows), SCENE_ROW)])
-        with self._ordered(dev):
-            self._chk(self.L.smpc_set_instance_scene(self.h, B, ptrs[0], dev))
+        self._set_instance(self.L.smpc_set_instance_scene, 'set_instance_scene', [geom], (len(self.problem.rows), SCENE_ROW))
 
     def set_instance_scene_track(self, geom=None):
         """Obstacles that move along the horizon (smpc_set_instance_scene_track): ``geom [B, T, n_rows, 8]``, one scene of
@@ -227,21 +202,15 @@ class BatchedOcpSolver:
         formed in column ``clip(t + k, 0, T - 1)``, t = the scene clock (:meth:`set_scene_clock`; 0 without one); the table of
         include/smpc.h says it for every entry point.  A track and a scene are one slot: setting one replaces the other, and None
         (here or in ``set_instance_scene``) clears both."""
-        if geom is None:
-            self._chk(self.L.smpc_set_instance_scene_track(self.h, 0, 1, None, 0))
-            return
-        if _is_torch(geom):
-            import torch
-            if geom.dtype != torch.float64:
-                raise ValueError('set_instance_scene_track: the track must be float64')
-        if geom.ndim != 4:
-            raise ValueError(f'set_instance_scene_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
-        B, T = int(geom.shape[0]), int(geom.shape[1])
-        if T < 1:
-            raise ValueError('set_instance_scene_track: a track has at least one time column')
-        ptrs, dev, keep = self._prep([geom], [(B, T, len(self.problem.rows), SCENE_ROW)])
-        with self._ordered(dev):
-            self._chk(self.L.smpc_set_instance_scene_track(self.h, B, T, ptrs[0], dev))
+        T = 1
+        if geom is not None:
+            if geom.ndim != 4:
+                raise ValueError(f'set_instance_scene_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+            T = int(geom.shape[1])
+            if T < 1:
+                raise ValueError('set_instance_scene_track: a track has at least one time column')
+        self._set_instance(self.L.smpc_set_instance_scene_track, 'set_instance_scene_track', [geom],
+                           (T, len(self.problem.rows), SCENE_ROW), T)
 
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on
@@ -264,23 +233,13 @@ class BatchedOcpSolver:
         (tracking.tracking_curves / jittered_curves), a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy
         (24 B x L x B).  None clears them.  While set, :meth:`policy_step` feeds instance b the columns of ``curves[b]`` (and
         refuses a shared table), ``score_rollout(traj='instance')`` scores against them, and both must come with the same B."""
-        if curves is None:
-            self._chk(self.L.smpc_set_instance_curves(self.h, 0, 0, None, 0))
-            self._curves_src = self._curves_host = None
-            return
-        if _is_torch(curves):
-            import torch
-            if curves.dtype != torch.float64:
-                raise ValueError('set_instance_curves: the curves must be float64')
-        if curves.ndim != 3 or curves.shape[1] != 3:
+        if curves is not None and (curves.ndim != 3 or curves.shape[1] != 3):
             raise ValueError(f'set_instance_curves: expected [B, 3, L], got {tuple(curves.shape)}')
-        B, L = int(curves.shape[0]), int(curves.shape[2])
-        ptrs, dev, keep = self._prep([curves], [(B, 3, L)])
-        with self._ordered(dev):
-            self._chk(self.L.smpc_set_instance_curves(self.h, B, L, ptrs[0], dev))
+        L = 0 if curves is None else int(curves.shape[2])
+        self._set_instance(self.L.smpc_set_instance_curves, 'set_instance_curves', [curves], (3, L), L)
         # what the handle holds: the tensor it was copied from (its owner says when it changes), or a copy of the host array
-        self._curves_src = curves if dev else None
-        self._curves_host = None if dev else np.array(curves, np.float64)
+        self._curves_src = curves if _is_torch(curves) else None
+        self._curves_host = None if curves is None or _is_torch(curves) else np.array(curves, np.float64)
 
     def _holds_curves(self, curves):
         if _is_torch(curves):
@@ -350,6 +309,22 @@ class BatchedOcpSolver:
                 ptrs.append(b.ctypes.data)
                 keep.append(b)
         return ptrs, int(dev), keep
+
+    def _set_instance(self, fn, name, arrs, tail, *ints):
+        """The steps every per-instance input shares, for ``fn(h, B, *ints, *arrays, on_device)``: None clears the
+        slot; a tensor must be float64; every array is ``[B, *tail]``, B read off the first; the engine's stream is ordered against
+        torch's around the call."""
+        if arrs[0] is None:
+            self._chk(fn(self.h, 0, *ints, *[None] * len(arrs), 0))
+            return
+        if _is_torch(arrs[0]):
+            import torch
+            if any(_is_torch(a) and a.dtype != torch.float64 for a in arrs):
+                raise ValueError(f'{name}: a tensor argument must be float64')
+        B = int(arrs[0].shape[0])
+        ptrs, dev, keep = self._prep(arrs, [(B, *tail)] * len(arrs))
+        with self._ordered(dev):
+            self._chk(fn(self.h, B, *ints, *ptrs, dev))
 
     def _state_pointers(self, what, d, fields, shapes, B, dev):
         """pointers of the per-instance arrays ``d[k]`` of a ctypes struct of arrays (``fields``: (name, dtype); ``shapes``: the
