@@ -289,6 +289,31 @@ int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
  * (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* curves, int on_device);
 
+/* A controller model of its own for every instance: the link inertials the OCP's dynamics are formed with.  joints is [B][nq]
+ * smpc_joint, the records smpc_plant_step takes as joints_noisy; of every record the engine reads mass, com[3] and inertia[6] and
+ * nothing else.  Kinematics (R0, p0, axis) and the limits (q_min, q_max, v_max, tau_max) stay the descriptor's, and with them the EE
+ * point, the collision rows, inverse kinematics, the bounds and the torque limits.
+ * The handle keeps the 232-byte records as they are -- the caller's inertials with the descriptor's other seven fields in every
+ * record -- so that a record stands wherever the kernels read a joint of the descriptor; 232 x nq x B bytes (1392 per instance at
+ * nq = 6, 5.7 MB at 4096), of which the kernels touch the 80 bytes of inertials per joint (and the torque kernels of the
+ * thread-per-node path the kinematics beside them).  The copy is stream-ordered; with host pointers the call checks that the seven
+ * fields equal the descriptor's bit for bit, that mass is finite and >= 0 and that com and inertia are finite, and waits for the
+ * copy; device pointers are taken as they are (the seven fields are then not read at all: the handle's records get the
+ * descriptor's).  joints == NULL clears the table.  A call with the same B overwrites the handle's buffer in place, so a step
+ * captured in a hipGraph keeps seeing it; smpc_set_horizon does not drop it.
+ * While a table is set, these form the torque row, its Jacobians, the merit's torque term and the torque margin with instance b's
+ * inertials: smpc_solve_batch, smpc_eval_nodes, smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_policy_step (kinds 0-4)
+ * and smpc_debug_stage_records (both paths).  The table belongs to ITS batch size: a call of these with another B returns
+ * SMPC_EINVAL and names both sizes -- it never falls back to the descriptor's robot.  SMPC_POLICY_PARALLEL and smpc_rollout_batch
+ * return SMPC_ESTATE while a table is set, for the reasons they refuse a scene.  Not read by: smpc_plant_step and the plant inside
+ * smpc_loop_post (their own joints_noisy argument), smpc_check_trajectory, smpc_score_rollout, smpc_ik_batch (no dynamics),
+ * smpc_ray_update.  Without a table every entry point launches exactly the kernels it launched before the table existed.
+ * SMPC_EINVAL: B <= 0, or (host pointers only) a record that fails the checks above; the message names instance, joint and field
+ * and the previous table stays in force.
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured (the old contents stay).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_models(smpc_handle* h, int B, const smpc_joint* joints, int on_device);
+
 /* A safe-set network that knows its scene: n_ctx extra inputs (a CONTEXT, numbers of the instance's scene) behind the 2 n_dof_safe_set
  * state features.  The network's first layer is W0 = [Ws | Wc], Ws [H][2 nd] handed over by smpc_set_mlp and Wc [H][n_ctx] (row-major,
  * H = dims[1]) here; for an instance with context c the row's value and gradient are those of the plain network with first-layer

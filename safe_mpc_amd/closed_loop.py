@@ -29,10 +29,15 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
             f'_q_collision_margins_{params.q_margin}_{params.collision_margin}_guess.pkl')
 
 
-def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm):
+def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal'):
+    """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
+    before ``_mpc.pkl``; the default gives the reference's name"""
+    if controller_model not in ('nominal', 'plant'):
+        raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
     track = 'traj_track' if params.track_traj else ''
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
-            f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}_mpc.pkl')
+            f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
+            f"{'_cmplant' if controller_model == 'plant' else ''}_mpc.pkl")
 
 
 def tracking_from_cli(params, argv, n=None):
@@ -356,6 +361,33 @@ def _clear_scene(solver):
         solver.set_scene_clock(None)
 
 
+def _check_models(models, B, noise, cont_name):
+    """run_mpc's ``models`` before anything is built: None, 'plant' (needs plant tables, so noise > 0) or a JOINT_DTYPE table
+    [B, nq]; not with the parallel policy.  Returns None, 'plant' or the contiguous table."""
+    if models is None:
+        return None
+    if cont_name == 'parallel':
+        raise ValueError("models: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
+                         "the engine refuses a model table there)")
+    if isinstance(models, str):
+        if models != 'plant':
+            raise ValueError(f"models: {models!r}: expected None, 'plant' or a joint table [{B}, nq]")
+        if not noise > 0:
+            raise ValueError("models='plant': the plant has a model of its own per instance only with noise > 0")
+        return models
+    models = np.ascontiguousarray(models)
+    if models.dtype != JOINT_DTYPE or models.ndim != 2 or models.shape[0] != B:
+        raise ValueError(f'models: expected a JOINT_DTYPE table [{B}, nq], got {models.dtype} {models.shape}')
+    return models
+
+
+def _set_models(solver, table):
+    """the controller models [B, nq] of a batch onto the solver (None clears them)"""
+    if not hasattr(solver, 'set_instance_models'):
+        raise ValueError(f'models: {type(solver).__name__} has no set_instance_models')
+    solver.set_instance_models(table)
+
+
 def _new_scene_clock(solver):
     """a one-element int64 cell for ``solver.set_scene_clock`` on a host loop: in HBM for an engine handle (the kernels read it
     there), a numpy array for a CPU double"""
@@ -508,7 +540,7 @@ def sqp_host_advance(ctrl, x0, state, max_iter, sqp_tol=1e-6, armijo=1e-4, alpha
 
 
 def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7,
-                   alpha_min=0.05, history=None, on_device=False, scenes=None, traj=None):
+                   alpha_min=0.05, history=None, on_device=False, scenes=None, traj=None, models=None):
     """guess_acados.py:98-158: Halton q0 in the joint box, collision filter, constant guess, SQP to convergence, checkGuess.
 
     SQP with merit backtracking (the reference runs acados with nlp_solver_type SQP, globalization MERIT_BACKTRACKING,
@@ -538,9 +570,19 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     returned mask (one per requested instance) is False and the result's ``'ik_failed'`` lists it.
     ``traj`` [n, 3, L] (tracking.tracking_curves / jittered_curves): a curve of its own for every instance -- instance i starts from
     an IK solution at ``traj[i, :, 0]`` and follows ``traj[i]`` (p[i, k, :3] = traj[i, :, k]); the result gains ``'curves'``, the
-    curves of the accepted instances."""
+    curves of the accepted instances.
+
+    ``models`` (``JOINT_DTYPE`` [n, nq], ``perturbed_joint_tables``): a warm start for the robot it will run on -- instance i is
+    solved and tested with the link inertials of ``models[i]`` (solver.set_instance_models; the start states do not depend on them).
+    The result gains ``'models'``, the tables of the accepted instances; the solver is left without a table."""
     make_controller = make_controller or (lambda name, batch: get_controller(name, params, batch))
+    if models is not None:
+        models = np.ascontiguousarray(models)
+        if models.dtype != JOINT_DTYPE or models.ndim != 2 or models.shape[0] != n:
+            raise ValueError(f'models: expected a JOINT_DTYPE table [{n}, nq], got {models.dtype} {models.shape}')
     ctrl = make_controller(cont_name, n)
+    if models is not None and not hasattr(ctrl.ocp_solver, 'set_instance_models'):
+        raise ValueError(f'models: {type(ctrl.ocp_solver).__name__} has no set_instance_models')
     curves = traj is not None and np.ndim(traj) == 3
     if traj is not None:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -580,6 +622,10 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
         if traj is not None:
             ctrl.setTrajectory(traj)
     B = len(x0)
+    if models is not None:
+        models = models[filled] if filled is not None else models[:B]      # (instance k of B is the k-th start that was found)
+        if B:
+            _set_models(ctrl.ocp_solver, models)
     if scenes is not None and B:
         _set_scene(ctrl.ocp_solver, scenes)
         if hasattr(ctrl.ocp_solver, 'set_scene_clock'):
@@ -587,6 +633,9 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
 
     def result(good):
         out = {'xg': ctrl.x_guess[good], 'ug': ctrl.u_guess[good]}
+        if models is not None:
+            out['models'] = models[good]
+            _set_models(ctrl.ocp_solver, None)
         if ik_failed is not None:
             out['ik_failed'] = ik_failed
         if filled is None:
@@ -704,7 +753,8 @@ class _FreeStarts:
 
 
 def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accept='final', max_samples=None, make_controller=None,
-                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, scenes=None, traj=None):
+                         sqp_tol=1e-6, verbose=False, armijo=1e-4, alpha_reduction=0.7, alpha_min=0.05, scenes=None, traj=None,
+                         models=None):
     """guess_acados.py:98-158 with its ``while succ < num_ics``: sample, solve and test warm starts until ``n`` are ACCEPTED, on
     the device.  Returns ``(guess, info)``: ``guess['xg'] [n, N+1, nx]``, ``guess['ug'] [n, N, nu]`` in sampling order.
 
@@ -740,6 +790,9 @@ def generate_guess_until(params, cont_name, n, batch=None, check_every=50, accep
     if traj is not None and np.ndim(traj) == 3:
         raise ValueError('generate_guess_until: per-instance curves are not supported (a refilled slot would need a curve for its '
                          'new sample); use generate_guess(traj=[n, 3, L])')
+    if models is not None:
+        raise ValueError('generate_guess_until: per-instance models are not supported (a refilled slot would be a new sample in an old '
+                         'robot); use generate_guess(models=[n, nq])')
     if accept not in ('final', 'first'):
         raise ValueError("accept must be 'final' or 'first'")
     check_every = int(check_every)
@@ -1007,7 +1060,7 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None):
+                 scenes=None, models=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -1034,6 +1087,13 @@ class _Group:
         self._Nb = backup.N
         seeds = np.arange(first, first + B)
         self._joints_noisy = perturbed_joint_tables(params, nq, noise, seeds) if noise > 0 else None          # mpc.py:106-107
+        # a controller model per instance (run_mpc(models=...)): 'plant' or the group's rows of a table; the subclasses hand it to the
+        # handles once the tables are where the loop keeps them (_hand_over_models)
+        self._models_arg, self._models = models, None
+        if models is not None:
+            for sv in (ctrl.ocp_solver, backup.ocp_solver):
+                if not hasattr(sv, 'set_instance_models'):
+                    raise ValueError(f'models: {type(sv).__name__} has no set_instance_models')
         # model.reset_seed(i) is called at EVERY step (mpc.py:126): each instance sees the same torque-noise draw each step
         self._tau_noise = None
         if control_noise > 0:
@@ -1066,6 +1126,19 @@ class _Group:
         order of the compact batch, onto the backup handle"""
         if self._scenes is not None:
             _set_scene(self._backup.ocp_solver, self._scenes[rows])
+
+    def _hand_over_models(self, table=None):
+        """the group's controller models onto the controller's handle: ``table`` (the subclass's form of the rows it was given), or
+        with 'plant' the very tables -- on the device the very tensor -- the plant steps with"""
+        if self._models_arg is None:
+            return
+        self._models = self._joints_noisy if isinstance(self._models_arg, str) else table
+        _set_models(self._ctrl.ocp_solver, self._models)
+
+    def _backup_models(self, rows):
+        """... and the backup OCP of an abort event is solved with the models of the aborting instances, like its scenes"""
+        if self._models is not None:
+            _set_models(self._backup.ocp_solver, self._models[rows])
 
     def _progress(self, j):
         xp = self._xp
@@ -1122,6 +1195,9 @@ class _Group:
             extra['scenes'] = xp.host(self._scenes)
             _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
             _clear_scene(self._backup.ocp_solver)
+        if self._models is not None:               # (nor a model table)
+            _set_models(solver, None)
+            _set_models(self._backup.ocp_solver, None)
         if getattr(ctrl, 'traj', None) is not None and ctrl.traj.ndim == 3 and hasattr(solver, 'set_instance_curves'):
             solver.set_instance_curves(None)       # (nor curves: the controller hands them over again should it step once more)
         return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
@@ -1150,6 +1226,7 @@ class _HostGroup(_Group):
             self._backup_clock = _new_scene_clock(self._backup.ocp_solver)
             self._ctrl.ocp_solver.set_scene_clock(self._clock)
             self._backup.ocp_solver.set_scene_clock(self._backup_clock)
+        self._hand_over_models(self._models_arg)
 
     # ---- first half: everything up to the controller's verdict ---------------------------------------------------------------
     def part_a(self):
@@ -1210,6 +1287,7 @@ class _HostGroup(_Group):
         xv_c = ctrl.getLastViableState()[rows]
         xg_c = np.repeat(xv_c[:, None, :], Nb + 1, axis=1)
         self._backup_scene(rows)
+        self._backup_models(rows)
         _write_scene_clock(self._backup_clock, j)
         xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(np.ascontiguousarray(xv_c), xg_c, np.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
         self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))
@@ -1272,8 +1350,10 @@ class _DeviceGroup(_Group):
         super().__init__(*args, **kw)
         import torch
         xp, ctrl, B, nu = self._xp, self._ctrl, self._B, self._ctrl.nu
-        if self._joints_noisy is not None:            # [B, nq] smpc_joint records as a float64 tensor (33 doubles each)
-            self._joints_noisy = xp.asarray(np.ascontiguousarray(self._joints_noisy).view(np.float64).reshape(B, ctrl.nq, -1), xp.f64)
+        as_tensor = lambda t: xp.asarray(np.ascontiguousarray(t).view(np.float64).reshape(B, ctrl.nq, -1), xp.f64)
+        if self._joints_noisy is not None:            # [B, nq] smpc_joint records as a float64 tensor (29 doubles each)
+            self._joints_noisy = as_tensor(self._joints_noisy)
+        self._hand_over_models(None if self._models_arg is None or isinstance(self._models_arg, str) else as_tensor(self._models_arg))
         if self._tau_noise is not None:
             self._tau_noise = xp.asarray(self._tau_noise, xp.f64)
         self._jt = xp.step_index(0)               # the step counter, a device tensor: smpc_loop_post advances it, graphs replay it
@@ -1345,6 +1425,7 @@ class _DeviceGroup(_Group):
             self._side.wait_event(ev0)
             xg_c = xp.repeat_nodes(xv_c, Nb + 1)
             self._backup_scene(rows_b)
+            self._backup_models(rows_b)
             xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
             ev = torch.cuda.Event()
             ev.record(self._side)
@@ -1443,7 +1524,7 @@ def _check_state_kind(ctrl, backup, on_device):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False, scenes=None, traj=None):
+            score=False, scenes=None, traj=None, models=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1477,9 +1558,16 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
     jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle
     holds the curves, solver.set_instance_curves), the score uses each instance's own curve, the backup OCP has zero cost and needs
-    none, and the handles are left without curves when the run ends."""
+    none, and the handles are left without curves when the run ends.
+    ``models``: the link inertials the CONTROLLER forms its dynamics with, per instance (solver.set_instance_models; kinematics and
+    limits stay the problem's).  ``'plant'``: every group's controller gets the very tables the loop draws for its plant
+    (``perturbed_joint_tables`` with the instances' seeds; on the device the same tensor) -- the matched-model arm of the model-noise
+    study, which needs ``noise > 0`` --; a ``JOINT_DTYPE`` table [B, nq]: each group gets its rows.  The backup OCP of an abort
+    event is solved with the aborting instances' models, and both handles are left without a table when the run ends.  Not with the
+    parallel policy (ValueError), and the plant keeps stepping with its own tables whatever the controller is given."""
     import time
     B = x_guess.shape[0]
+    models = _check_models(models, B, noise, cont_name)
     if scenes is not None:
         if cont_name == 'parallel':
             raise ValueError("scenes: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
@@ -1508,6 +1596,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     gens, grps, streams = [], [], []
     for lo, hi in spans:
         ctrl = make_controller(cont_name, hi - lo)
+        if models is not None and not hasattr(ctrl.ocp_solver, 'set_instance_models'):
+            raise ValueError(f'models: {type(ctrl.ocp_solver).__name__} has no set_instance_models')
         backup = make_backup(hi - lo)
         _check_state_kind(ctrl, backup, on_device)
         if traj is not None:
@@ -1518,10 +1608,12 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
             sv = ctrl.ocp_solver
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
-                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs)
+                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs,
+                                   models=models if models is None or isinstance(models, str) else models[lo:hi])
         else:
             streams.append(None)
-            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi])
+            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi],
+                             models=models if models is None or isinstance(models, str) else models[lo:hi])
         grps.append(grp)
         gens.append(grp.run())
 

@@ -323,6 +323,29 @@ __device__ __forceinline__ int64_t scene_time(const SceneSrc& sc) {
 __device__ __forceinline__ const double* scene_block(const SceneSrc& sc, long b, int64_t c, int n_rows) {
     return sc.geom + ((size_t)b * (size_t)sc.T + (size_t)scene_col(c, sc.T)) * n_rows * SMPC_SCENE_ROW;
 }
+// Whose link inertials the controller's dynamics take: the descriptor's (MODEL = false: the same loads as before the table
+// existed) or instance b's own records of smpc_set_instance_models (MODEL = true), joints = the handle's [B][NQ] smpc_joint
+// table.  Its setter has written the descriptor's kinematics and limits into every record, so a record serves wherever a
+// const smpc_joint* of the descriptor did (rnea_world, rnea_with_derivatives) and only mass, com and inertia differ.  The kernels
+// take the table behind the scene as a parameter pack `const MJ* __restrict__... md` that holds ONE pointer (MJ = smpc_joint)
+// when MODEL is true and NOTHING when it is false (ModelArg below; even an empty record would take a byte of the kernel's
+// argument segment): the shared-model instantiations keep their argument lists, and with them their code.  A pointer of its
+// own, not a member of a record like SceneSrc, because only a kernel argument can be `const __restrict__`: that is what lets
+// a block whose lanes share the instance (k_merit, k_check_guess) read its records with scalar loads, as it reads the
+// descriptor's -- through a record's member the same kernels held the 29 doubles per joint in vector registers and lost
+// a wavefront of occupancy (profiles/instance_models.txt).
+using ModelSrc = const smpc_joint*;     // what the launchers hand over (with_model, engine.hip): the handle's table
+// the pack a kernel with the flag MODEL accepts: static_assert(ModelArg<MODEL, MJ...>) in its first line
+template <bool MODEL, class... MJ>
+constexpr bool ModelArg = MODEL ? (sizeof...(MJ) == 1 && (std::is_same_v<MJ, smpc_joint> && ...)) : sizeof...(MJ) == 0;
+// instance b's NQ joint records: model_joints<NQ>(D, b, md...).  A kernel must only ask for an instance the table was set for
+// (the entry points' B guard).
+template <int NQ> __device__ __forceinline__ const smpc_joint* model_joints(const smpc_problem_desc* __restrict__ D, long) { return D->joints; }
+template <int NQ>
+__device__ __forceinline__ const smpc_joint* model_joints(const smpc_problem_desc* __restrict__, long b, const smpc_joint* __restrict__ table) {
+    return table + (size_t)b * NQ;
+}
+
 template <bool SCENE>
 __device__ __forceinline__ RowGeom<SCENE> row_geom(const smpc_row& row, const double* __restrict__ geom_b, int r) {
     if constexpr (SCENE) {

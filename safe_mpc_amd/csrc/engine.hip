@@ -115,6 +115,8 @@ struct smpc_handle {
     InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
     InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][n_ctx] normalised context of the network
+    InstSlot<smpc_joint> models{"instance model table", "smpc_set_instance_models"};    // [B][nq] the controller's joint records:
+                                                                                        // the caller's inertials, the descriptor's rest
     // network
     Net own_net;
     const Net* net = &own_net;      // the network this handle runs: its own, or the parent's in a worker of smpc_rollout_batch
@@ -535,10 +537,24 @@ template <class F> int with_scene(const smpc_handle* h, int B, F&& f, int64_t of
     return f(std::false_type{}, (const double*)nullptr);
 }
 
+// f(std::true_type{}, md) with the handle's table of instance models when it was set for B instances, else f(std::false_type{}) --
+// no argument at all, so that a shared-model kernel is launched with the argument list it always had (ModelSrc, device_model.hpp);
+// a launcher takes `auto... md` and hands `md...` on.  The launchers of the kernels that form the controller's dynamics nest it
+// inside with_scene.
+template <class F> int with_model(const smpc_handle* h, int B, F&& f) {
+    if (const ModelSrc table = h->models.for_batch(B)) return f(std::true_type{}, table);
+    return f(std::false_type{});
+}
+
 // The guards of an entry point that evaluates collision rows and runs the network (SlotTag::guard)
 int guard_scene_and_context(smpc_handle* h, int B, const char* who) {
     const int rc = h->scene.guard(h, B, who);
     return rc ? rc : h->ctx.guard(h, B, who);
+}
+// ... and forms the controller's dynamics as well
+int guard_scene_context_and_models(smpc_handle* h, int B, const char* who) {
+    const int rc = guard_scene_and_context(h, B, who);
+    return rc ? rc : h->models.guard(h, B, who);
 }
 
 // The reference table of a policy step: the handle's curves (a table per instance) or the caller's shared one (stride 0), or none.
@@ -571,9 +587,11 @@ int launch_eval(smpc_handle* h, int B, const double* d_xg, const double* d_ug, c
     hipStream_t s = h->stream;
     const long n1 = (long)B * (N + 1);
     with_scene(h, B, [&](auto SCENE, auto sc) {
-        hipLaunchKernelGGL((k_node_linearise<NQ, SCENE>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg, d_ug,
-                           d_p, d_ev, sc);
-        return SMPC_OK;
+        return with_model(h, B, [&](auto MODEL, auto... md) {
+            hipLaunchKernelGGL((k_node_linearise<NQ, SCENE, MODEL>), dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, h->d_desc, B, N, d_xg,
+                               d_ug, d_p, d_ev, sc, md...);
+            return SMPC_OK;
+        });
     });
     HIPCHK(h, hipGetLastError());
     int rc;
@@ -631,9 +649,11 @@ int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* 
     int32_t* const zero_cnt = h->desc.nn_mode == SMPC_NN_ALL ? h->d_nn_cnt : nullptr;     // (the builder hands the list's counter back at zero)
     with_rows(h, [&](auto MR) {
         return with_scene(h, B, [&](auto SCENE, auto sc) {
-            hipLaunchKernelGGL((k_stage_build<NQ, MR, SCENE>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo, bd.hi,
-                               h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, sc);
-            return SMPC_OK;
+            return with_model(h, B, [&](auto MODEL, auto... md) {
+                hipLaunchKernelGGL((k_stage_build<NQ, MR, SCENE, MODEL>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
+                                   bd.hi, h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, sc, md...);
+                return SMPC_OK;
+            });
         });
     });
     HIPCHK(h, hipGetLastError());
@@ -1162,8 +1182,11 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
         y = h->d_y.p;
     }
     with_scene(h, B, [&](auto SCENE, auto sc) {
-        hipLaunchKernelGGL((k_merit<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos, out, sc);
-        return SMPC_OK;
+        return with_model(h, B, [&](auto MODEL, auto... md) {
+            hipLaunchKernelGGL((k_merit<NQ, SCENE, MODEL>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos,
+                               out, sc, md...);
+            return SMPC_OK;
+        });
     });
     HIPCHK(h, hipGetLastError());
     if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
@@ -1218,10 +1241,12 @@ int launch_check_guess(smpc_handle* h, int B, const double* x, const double* u, 
     }
     const GchkBlock c = gchk_block(h->gchk.d.p, NQ);
     with_scene(h, B, [&](auto SCENE, auto sc) {
-        hipLaunchKernelGGL((k_check_guess<NQ, SCENE>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau, par->tol_dyn,
-                           par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, c.x_min, c.x_max, c.tau_min, c.tau_max,
-                           c.row_lb, c.row_ub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, sc);
-        return SMPC_OK;
+        return with_model(h, B, [&](auto MODEL, auto... md) {
+            hipLaunchKernelGGL((k_check_guess<NQ, SCENE, MODEL>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x, u, par->tol_x, par->tol_tau,
+                               par->tol_dyn, par->tol_safe, par->alpha, (int)par->collision_first_node, (int)par->safe_node, c.x_min, c.x_max,
+                               c.tau_min, c.tau_max, c.row_lb, c.row_ub, mask, y, (const int32_t*)h->d_guess.p, flags, worst, sc, md...);
+            return SMPC_OK;
+        });
     });
     HIPCHK(h, hipGetLastError());
     if (y) HIPCHK(h, hipMemsetAsync(h->d_nn_cnt, 0, sizeof(int32_t), s));
@@ -1734,13 +1759,59 @@ int smpc_set_instance_curves(smpc_handle* h, int B, int64_t L, const double* cur
     return SMPC_OK;
 }
 
+int smpc_set_instance_models(smpc_handle* h, int B, const smpc_joint* joints, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!joints) { h->models.clear(); return SMPC_OK; }
+    if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    const int nq = h->desc.nq;
+    const size_t n = (size_t)B * nq;
+    if (!on_device) {
+        // Kinematics and limits are the descriptor's, bit for bit: a table that moves one of them asks for something the engine does
+        // not do.  (Device pointers are taken as they are -- reading them back would synchronise -- and k_model_table takes those
+        // fields from the descriptor.)
+        const auto same = [](const double* a, const double* b, int m) { return memcmp(a, b, sizeof(double) * m) == 0; };
+        const auto finite = [](const double* a, int m) {
+            for (int i = 0; i < m; i++)
+                if (!(a[i] - a[i] == 0.0)) return false;
+            return true;
+        };
+        for (size_t t = 0; t < n; t++) {
+            const smpc_joint &J = joints[t], &Dj = h->desc.joints[t % nq];
+            const char* bad = !same(J.R0, Dj.R0, 9)             ? "R0 differs from the descriptor's"
+                              : !same(J.p0, Dj.p0, 3)           ? "p0 differs from the descriptor's"
+                              : !same(J.axis, Dj.axis, 3)       ? "axis differs from the descriptor's"
+                              : !same(&J.q_min, &Dj.q_min, 1)   ? "q_min differs from the descriptor's"
+                              : !same(&J.q_max, &Dj.q_max, 1)   ? "q_max differs from the descriptor's"
+                              : !same(&J.v_max, &Dj.v_max, 1)   ? "v_max differs from the descriptor's"
+                              : !same(&J.tau_max, &Dj.tau_max, 1) ? "tau_max differs from the descriptor's"
+                              : !(finite(&J.mass, 1) && J.mass >= 0.0) ? "mass is negative or not finite"
+                              : !finite(J.com, 3)               ? "com is not finite"
+                              : !finite(J.inertia, 6)           ? "inertia is not finite"
+                                                                : nullptr;
+            if (bad)
+                return fail(h, SMPC_EINVAL, "smpc_set_instance_models: instance %zu (of B=%d), joint %d: %s (only mass, com and inertia are "
+                            "per instance)", t / nq, B, (int)(t % nq), bad);
+        }
+    }
+    int rc;
+    if ((rc = h->models.room(h, n))) return rc;
+    if (on_device) {
+        hipLaunchKernelGGL(k_model_table, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_desc, (long)n, nq, joints, h->models.d.p);
+        HIPCHK(h, hipGetLastError());
+    } else if ((rc = h->models.upload(h, joints, n, false)))
+        return rc;      // (the records as they came: their other fields have just been found equal to the descriptor's)
+    h->models.commit(B);
+    return SMPC_OK;
+}
+
 int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, const double* ug, const double* p,
                      double* x_out, double* u_out, int32_t* status, int32_t* qp_iter, int on_device) {
     if (!h) return SMPC_EINVAL;
     if (B <= 0 || !x0 || !xg || !ug || !p || !x_out || !u_out || !status) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_solve_batch"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_solve_batch"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
     Stage io{h, on_device != 0};
@@ -1768,7 +1839,7 @@ int smpc_eval_nodes(smpc_handle* h, int B, const double* xg, const double* ug, c
     if (B <= 0 || !xg || !ug || !p || !out) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_eval_nodes"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_eval_nodes"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     hipStream_t s = h->stream;
@@ -1903,7 +1974,7 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     if (B <= 0 || n_steps <= 0 || !x0 || !x_guess || !u_guess || !p || !x_traj || !u_traj || !status_traj)
         return fail(h, SMPC_EINVAL, "bad argument");
     if (const int rf = refuse_slots(h, "smpc_rollout_batch", "the worker handles of the rollout hold none (step the loop through smpc_policy_step / "
-                                    "smpc_loop_post instead)", {&h->scene, &h->ctx}))
+                                    "smpc_loop_post instead)", {&h->scene, &h->ctx, &h->models}))
         return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
@@ -2021,13 +2092,14 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
         return fail(h, SMPC_EINVAL, "check bounds missing");
     if ((receding || parallel) && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
     if (parallel)
-        if (const int rf = refuse_slots(h, "smpc_policy_step", "the parallel policy's candidate slots are not instances", {&h->scene, &h->ctx}))
+        if (const int rf = refuse_slots(h, "smpc_policy_step", "the parallel policy's candidate slots are not instances",
+                                            {&h->scene, &h->ctx, &h->models}))
             return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_policy_step"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_policy_step"))) return rc;
     TrajSrc tr;
     if (!parallel && (rc = policy_traj_src(h, B, st, &tr))) return rc;     // (before anything is enqueued; the parallel step asks itself)
     if ((rc = ensure_batch(h, B))) return rc;
@@ -2173,7 +2245,7 @@ int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, c
     const int N = h->N, nq = h->desc.nq;
     const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_merit_terms"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_merit_terms"))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, false, &w))) return rc;
     Stage io{h, on_device != 0};
@@ -2211,7 +2283,7 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
     const size_t nX = (size_t)B * nX1, nU = (size_t)B * nU1;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_sqp_batch"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_sqp_batch"))) return rc;
     if ((rc = ensure_batch(h, B, false))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, true, &w))) return rc;
@@ -2290,7 +2362,7 @@ int smpc_check_guess(smpc_handle* h, int B, const double* x, const double* u, co
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq;
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_check_guess"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_check_guess"))) return rc;
     if ((rc = upload_guess_bounds(h, par))) return rc;
     Stage io{h, on_device != 0};
     const double *dx, *du;
@@ -2539,7 +2611,7 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = guard_scene_and_context(h, B, "smpc_debug_stage_records"))) return rc;
+    if ((rc = guard_scene_context_and_models(h, B, "smpc_debug_stage_records"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     Stage io{h, false};

@@ -90,14 +90,16 @@ __device__ __forceinline__ double grp_max(double v) {
 // One node.  Every lane of the wavefront calls this (cross-lane steps inside); `valid` = this group has a node.  L = the group's
 // LDS block.  ws = the stage's record.  g = lane within the group.  SCENE: the fixed obstacles of the collision rows come from
 // geom_b, the instance's [n_rows][SMPC_SCENE_ROW] block of smpc_set_instance_scene, instead of the descriptor (the record of the
-// lane's row, eight doubles, then sits in the lane's registers where the shared scene has scalar loads).
-template <int NQ, int MRT, bool SCENE = false>
+// lane's row, eight doubles, then sits in the lane's registers where the shared scene has scalar loads).  MODEL: the lane that
+// owns joint g takes mass, com and inertia from Jb[g], the instance's records of smpc_set_instance_models, instead of the
+// descriptor's joint g (ten doubles in the lane's registers where the shared model has scalar loads); the kinematics stay D's.
+template <int NQ, int MRT, bool SCENE = false, bool MODEL = false>
 __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict__ D, const QpLayout<NQ>& Ly, const int N, const int k,
                                             const bool valid, const int g, double* __restrict__ L, const double* __restrict__ x0b,
                                             const double* __restrict__ xk, const double* __restrict__ uk, const double* __restrict__ pk,
                                             const double* __restrict__ lo_k, const double* __restrict__ hi_k,
                                             const double* __restrict__ zl_st, const double* __restrict__ nnk, double* __restrict__ w,
-                                            const double* __restrict__ geom_b = nullptr) {
+                                            const double* __restrict__ geom_b = nullptr, const smpc_joint* __restrict__ Jb = nullptr) {
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NQP = QpLayout<NQ>::NQP, NZP = QpLayout<NQ>::NZP;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     constexpr int NSLOT = (MR_MAX + SB_G - 1) / SB_G;      // collision rows per lane (row g + 8 s on lane g)
@@ -172,7 +174,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
     rd::V3 Pl;
     rd::SV F;
     {
-        const smpc_joint& Jg = D->joints[gj];
+        const smpc_joint& Jg = MODEL ? Jb[gj] : D->joints[gj];
         const rd::V3 c = pj + rd::rot(R, Jg.com);
         const double* I = Jg.inertia;
         double T[9];
@@ -660,13 +662,15 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
 
 // Standalone launch: one wavefront = 8 nodes.  Node index t over (instance, stage); instances the policy layer masks out are skipped.
 // SCENE: sc = the handle's scene track; stage k reads column scene_col(time + k) of its instance (unused otherwise).
-template <int NQ, int MRT, bool SCENE = false>
+// MODEL: md = the handle's table of instance models; the nodes of instance b read its NQ records (unused otherwise).
+template <int NQ, int MRT, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB_WAVES))) void k_stage_build(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                                     const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ pp,
                                                     const double* __restrict__ lo_st, const double* __restrict__ hi_st,
                                                     const double* __restrict__ zl_st, const double* __restrict__ nn, double* __restrict__ ws_all,
                                                     long bnd_stride, const uint8_t* __restrict__ active, int32_t* __restrict__ zero_cnt,
-                                                    const SceneArg<SCENE> sc = {}) {
+                                                    const SceneArg<SCENE> sc = {}, const MJ* __restrict__... md) {
+    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
     constexpr int NX = 2 * NQ, NU = NQ;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     using LD = SbLds<NQ, MR_MAX>;
@@ -691,9 +695,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB
     const size_t bo = (size_t)b * bnd_stride + (size_t)k * NX;
     const double* geom_b = nullptr;
     if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc) + k, Ly.MR);
-    stage_build<NQ, MRT, SCENE>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
+    const smpc_joint* Jb = nullptr;
+    if constexpr (MODEL) Jb = model_joints<NQ>(D, b, md...);
+    stage_build<NQ, MRT, SCENE, MODEL>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
                                 nn ? nn + (D->nn_mode == SMPC_NN_TERMINAL ? (size_t)b : (size_t)b * (N + 1) + k) * (1 + NX) : nullptr, w,
-                                geom_b);
+                                geom_b, Jb);
 }
 
 }  // namespace smpc

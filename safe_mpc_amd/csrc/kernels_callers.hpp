@@ -149,6 +149,21 @@ __global__ void k_accept(int B, const int32_t* __restrict__ status, int32_t* __r
     accept[b] = f == 0;
 }
 
+// smpc_set_instance_models: the handle's table from the caller's records, one thread per (instance, joint).  Of src it reads
+// mass, com and inertia and nothing else; kinematics and limits of every record are the descriptor's, so that the record can stand
+// wherever the descriptor's joint did.  n = B * nq records; dst is the handle's buffer of at least n records.
+__global__ void k_model_table(const smpc_problem_desc* __restrict__ D, long n, int nq, const smpc_joint* __restrict__ src,
+                              smpc_joint* __restrict__ dst) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    smpc_joint J = D->joints[t % nq];
+    const smpc_joint& S = src[t];
+    J.mass = S.mass;
+    for (int i = 0; i < 3; i++) J.com[i] = S.com[i];
+    for (int i = 0; i < 6; i++) J.inertia[i] = S.inertia[i];
+    dst[t] = J;
+}
+
 // plant step AdamModel.integrate (env_model.py:192-206).  NQ + 2 lanes per instance, one inverse-dynamics call each: lane 0
 // tau(q, qd, u), lane 1 the bias h(q, qd), lanes 2.. the columns of M (unit accelerations, no velocity, no gravity) -- the
 // same code with different inputs, so the wavefront does not diverge; lane 0 then solves M a = clamp(tau + noise) - h.

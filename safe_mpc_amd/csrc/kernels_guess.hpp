@@ -39,7 +39,8 @@ __global__ void k_guess_nn_list(int B, int N, int safe_node, const uint8_t* __re
 //                                                                        passes when g >= -tol_safe && g <= 1e6 + tol_safe
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
 // SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
-template <int NQ, bool SCENE = false>
+// MODEL: the torque margin's link inertials from instance b's own records (md, smpc_set_instance_models) instead of the descriptor's.
+template <int NQ, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
                                                     const double* __restrict__ ug, double tol_x, double tol_tau, double tol_dyn,
                                                     double tol_safe, double alpha, int coll_first, int safe_node,
@@ -48,7 +49,9 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
                                                     const double* __restrict__ row_lb, const double* __restrict__ row_ub,
                                                     const uint8_t* __restrict__ mask, const float* __restrict__ y,
                                                     const int32_t* __restrict__ pos, int32_t* __restrict__ flags,
-                                                    double* __restrict__ worst, const SceneArg<SCENE> sc = {}) {
+                                                    double* __restrict__ worst, const SceneArg<SCENE> sc = {},
+                                                    const MJ* __restrict__... md) {
+    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     __shared__ double s_sim[(SMPC_MAX_N + 1) * NX];
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(64) void k_check_guess(const smpc_problem_desc* __r
             double u[NQ], tau[NQ];
 #pragma unroll
             for (int i = 0; i < NQ; i++) u[i] = uk[i];
-            rnea_world<NQ, double>(D->joints, D->gravity, q, v, u, tau);
+            rnea_world<NQ, double>(model_joints<NQ>(D, b, md...), D->gravity, q, v, u, tau);
 #pragma unroll
             for (int i = 0; i < NQ; i++) w_tau = nanmax(w_tau, nanmax(tau_min[i] - tau[i], tau[i] - tau_max[i]));
         }

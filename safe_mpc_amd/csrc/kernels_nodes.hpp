@@ -102,9 +102,10 @@ __device__ __forceinline__ void node_geometry(const smpc_problem_desc* __restric
 // entry is stored once, straight from the recursion into the node's (interleaved) record.  The thread index runs over ALL nodes,
 // so that EV_TILE neighbouring lanes always belong to one tile; the terminal nodes (no torque row) idle.  (Round 1 ran 3 NQ
 // single-tangent dual-number passes per node in 3 NQ threads: 0.48 ms per 4096 x 30 nodes.)
-template <int NQ>
+// md (the model table or nothing, device_model.hpp): the link inertials of instance b's own records instead of the descriptor's
+template <int NQ, class... MJ>
 __device__ __forceinline__ void node_torque(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ xg,
-                                            const double* __restrict__ ug, double* __restrict__ out, const long t) {
+                                            const double* __restrict__ ug, double* __restrict__ out, const long t, const MJ* __restrict__... md) {
     if (t >= (long)B * (N + 1)) return;
     constexpr int NX = 2 * NQ;
     const long b = t / (N + 1);
@@ -120,21 +121,22 @@ __device__ __forceinline__ void node_torque(const smpc_problem_desc* __restrict_
         qd[i] = x[NQ + i];
         qdd[i] = u[i];
     }
-    rd::rnea_with_derivatives<NQ>(D->joints, D->gravity, q, qd, qdd, o + SMPC_EV_OFF(tau) * EV_TILE, o + SMPC_EV_OFF(M) * EV_TILE,
+    rd::rnea_with_derivatives<NQ>(model_joints<NQ>(D, b, md...), D->gravity, q, qd, qdd, o + SMPC_EV_OFF(tau) * EV_TILE, o + SMPC_EV_OFF(M) * EV_TILE,
                                   o + SMPC_EV_OFF(dtau_dq) * EV_TILE, o + SMPC_EV_OFF(dtau_dv) * EV_TILE, (long)EV_TILE);
 }
 
 // The linearisation kernel: geometry + cost, then torque row and Jacobians, one thread per node, ONE launch.  As two kernels
 // (rounds 1-2) each of them waited for SIMD room of its own in the three-stream closed loop -- a wavefront of either needs a
 // SIMD that holds no QP wavefront (310 / 512 registers per lane) -- about 0.13 ms per wait against 0.04 / 0.05 ms of work.
-template <int NQ, bool SCENE = false>
+template <int NQ, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) void k_node_linearise(const smpc_problem_desc* __restrict__ D, int B, int N,
                                                        const double* __restrict__ xg, const double* __restrict__ ug,
                                                        const double* __restrict__ p, double* __restrict__ out,
-                                                       const SceneArg<SCENE> sc = {}) {
+                                                       const SceneArg<SCENE> sc = {}, const MJ* __restrict__... md) {
+    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     node_geometry<NQ, SCENE>(D, B, N, xg, p, out, t, sc);
-    node_torque<NQ>(D, B, N, xg, ug, out, t);
+    node_torque<NQ>(D, B, N, xg, ug, out, t, md...);
 }
 
 // smpc_eval_nodes: the interleaved tiles back into plain records, one thread per (node, element)

@@ -87,13 +87,15 @@ __global__ void k_sqp_trial_states(int B, int per, const double* __restrict__ x,
 // geometric Jacobian columns (which the forward kinematics has already paid for) against the lane's dq.
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
 // SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
-template <int NQ, bool SCENE = false>
+// MODEL: the torque term's link inertials from instance b's own records (md, smpc_set_instance_models) instead of the descriptor's.
+template <int NQ, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                               const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ p,
                                               const double* __restrict__ dxg, const double* __restrict__ dug,
                                               const double* __restrict__ alpha, const uint8_t* __restrict__ mask,
                                               const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out,
-                                              const SceneArg<SCENE> sc = {}) {
+                                              const SceneArg<SCENE> sc = {}, const MJ* __restrict__... md) {
+    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x, k = threadIdx.x;
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
                 f += cs * D->R * uu;
                 if (want_gd) gd += cs * 2.0 * D->R * ud;
             }
-            rnea_world<NQ, double>(D->joints, D->gravity, q, v, u, tau);
+            rnea_world<NQ, double>(model_joints<NQ>(D, b, md...), D->gravity, q, v, u, tau);
 #pragma unroll
             for (int i = 0; i < NQ; i++) viol += fmax(fabs(tau[i]) - D->joints[i].tau_max, 0.0);
         }

@@ -241,6 +241,23 @@ class BatchedOcpSolver:
         self._curves_src = curves if _is_torch(curves) else None
         self._curves_host = None if curves is None or _is_torch(curves) else np.array(curves, np.float64)
 
+    def set_instance_models(self, joints=None):
+        """A controller model of its own for every instance (smpc_set_instance_models): ``joints [B, nq]`` of ``JOINT_DTYPE``
+        (``closed_loop.perturbed_joint_tables``, the records ``plant_step`` takes as ``joints_noisy``), or the same records as a
+        contiguous ROCm float64 tensor ``[B, nq, 29]``; the engine keeps a copy (232 B x nq x B).  Only mass, com and inertia are
+        per instance: a numpy table that moves a kinematic field or a limit is refused, a tensor's are not read.  None clears it.
+        While set, every call that forms the controller's dynamics (solve, eval_nodes, merit_terms, sqp, check_guess, policy_step)
+        uses instance b's inertials and must come with the same B; the parallel policy and :meth:`rollout` refuse it."""
+        words = JOINT_DTYPE.itemsize // 8
+        if joints is not None and not _is_torch(joints):
+            joints = np.ascontiguousarray(joints)
+            if joints.dtype != JOINT_DTYPE or joints.ndim != 2 or joints.shape[1] != self.nq:
+                raise ValueError(f'set_instance_models: expected JOINT_DTYPE [B, {self.nq}], got {joints.dtype} {tuple(joints.shape)}')
+            joints = joints.view(np.float64).reshape(joints.shape[0], self.nq, words)
+        elif joints is not None and (joints.ndim != 3 or tuple(joints.shape[1:]) != (self.nq, words)):
+            raise ValueError(f'set_instance_models: expected [B, {self.nq}, {words}], got {tuple(joints.shape)}')
+        self._set_instance(self.L.smpc_set_instance_models, 'set_instance_models', [joints], (self.nq, words))
+
     def _holds_curves(self, curves):
         if _is_torch(curves):
             return getattr(self, '_curves_src', None) is curves

@@ -14,6 +14,9 @@ jittered by --scene-jitter if that is given too).
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
 the curves stored with the guesses (guess_acados.py --track-jitter) if there are any, else tracking.jittered_curves.
+--controller-model nominal|plant (default nominal): with ``plant`` (needs --noise > 0) every instance's controller forms its dynamics
+with the perturbed link inertials its plant is simulated with -- the matched-model arm of the model-noise study -- and the result
+file's name gets the suffix ``_cmplant`` before ``_mpc.pkl``.
 Exit code = number of failed instances, as in the reference (mpc.py:317).
 """
 import os
@@ -59,11 +62,15 @@ def main(argv=None):
             opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
             scenes = moving_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], T, opt('--scene-velocity', 0.0, float),
                                    opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
+    cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
+    if cmodel not in ('nominal', 'plant'):
+        raise SystemExit(f'--controller-model {cmodel}: expected nominal or plant')
     tm = {}
     # all loop state in HBM (policy automaton, abort handling, logs); SMPC_HOST_STATE=1 keeps it in numpy arrays instead
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],
                      callback=True, on_device=os.environ.get('SMPC_HOST_STATE', '0') != '1', timing=tm,
-                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes, traj=traj)
+                     collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes, traj=traj,
+                     models='plant' if cmodel == 'plant' else None)
     with_stats = os.environ.get('SMPC_NO_TIME_STATS', '0') != '1'
     print(f"{tm['ms_per_step']:.3f} ms per closed-loop step of {x_guess.shape[0]} instances"
           + (' (eager launches with per-solve HIP events for the time statistics below; SMPC_NO_TIME_STATS=1 replays the step halves as '
@@ -76,7 +83,7 @@ def main(argv=None):
     print(f"Completed task: {len(res['conv_idx'])}\nCollisions: {len(res['collisions_idx'])}"
           f"\nViable states: {len(res['viable_idx'])}\nNot converged: {n - len(res['conv_idx']) - len(res['collisions_idx'])}")
     cl.save_pickle(cl.result_file(params, model_name, cont_name, params.N, use_net, args['noise'], args['control_noise'],
-                                  args['joint_bounds_margin'], args['collision_margin']), res)
+                                  args['joint_bounds_margin'], args['collision_margin'], controller_model=cmodel), res)
     return len(res['collisions_idx'])
 
 
