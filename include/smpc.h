@@ -264,8 +264,10 @@ int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double
 
 /* The time of node 0, for a track: d_clock is a DEVICE pointer to ONE int64 that the caller owns and keeps alive; NULL = time 0.
  * The cell is read on the device when a kernel runs -- no host synchronisation, and a captured graph replays with whatever the cell
- * holds then; smpc_loop_state.step is the intended cell.  Without a track, or with T = 1, the clock is not read.  The clock stays
- * set across smpc_set_instance_scene / _track calls until it is replaced or cleared here. */
+ * holds then; smpc_loop_state.step is the intended cell.  It is read by the kernels that read a scene track with T > 1 and by the
+ * network pass of a context track with T > 1 (smpc_set_instance_context_track); without either, or with T = 1, the clock is not
+ * read.  The clock stays set across smpc_set_instance_scene / _track and smpc_set_instance_context / _track calls until it is
+ * replaced or cleared here. */
 int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
 
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
@@ -341,6 +343,29 @@ int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const doubl
  * SMPC_ESTATE: the copy would have to grow while the stream is being captured (the old contents stay).
  * (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device);
+
+/* A context that follows a scene track: ctx is [B][T][n_ctx] doubles, the raw numbers of instance b's scene in time column j; the
+ * handle keeps a normalised fp32 copy of 4 * n_ctx * T * B bytes.  The meaning is quasi-static: the network is one trained on
+ * standing scenes, and at node k it is asked about the scene as it will stand at time t + k.
+ * The column rule is THE column rule of smpc_set_instance_scene_track above and its table, not restated here: t = the cell of
+ * smpc_set_scene_clock (0 without one), and col(.) clamps with THIS table's T, which may differ from the scene track's (each
+ * table clamps by its own).  Which network row reads which column:
+ *   smpc_solve_batch, smpc_eval_nodes, smpc_merit_terms, smpc_sqp_batch, smpc_check_guess (its safe_node included),
+ *   smpc_debug_stage_records, and the solve and the x_temp / viable-state tests of smpc_policy_step (kinds 0-4):
+ *                                                              the network row of node k of the [B][N+1] arrays: col(t + k)
+ *   smpc_check_trajectory:                                     node k of the [B][n_nodes] arrays: col(t + k)
+ *   smpc_score_rollout (the clock is not read):                state j of the log: col(j)
+ * A context and a context track are ONE slot of the handle, as a scene and a scene track are: setting one replaces the other,
+ * smpc_set_instance_context(h, B, ctx, ..) is exactly a track with T = 1, and ctx == NULL in either setter clears both.  Everything
+ * said of the instance context holds: the copy is stream-ordered; a call with host pointers checks for non-finite values (the message
+ * names instance, column and number, and the previous table stays in force) and waits, device pointers go through the normalising
+ * kernel; the table belongs to its batch size (another B: SMPC_EINVAL naming both); the same (B, T) overwrites the buffer in place, so
+ * a captured step keeps seeing it; smpc_set_mlp and smpc_set_mlp_context drop it; SMPC_POLICY_PARALLEL and smpc_rollout_batch return
+ * SMPC_ESTATE while it is set.  With T = 1 the clock is not read.
+ * SMPC_EINVAL: no context columns, B <= 0, T < 1, or (host pointers only) a non-finite entry.
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured (the old contents stay).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_context_track(smpc_handle* h, int B, int64_t T, const double* ctx, int on_device);
 
 /* replaces ocp_solver.cost_set(k,'zl'/'zu',v) (controller.py:455-468, 526-527): L1 penalty of the slack on the safe-set row of
  * node k, for the nodes where the formulation made that row soft (nn_soft_e / nn_soft_run >= 0; a hard row has no slack and

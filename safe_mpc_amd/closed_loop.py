@@ -331,16 +331,21 @@ def _context_select(solver):
 
 def _set_scene(solver, geom):
     """the scenes [B, n_rows, 8], or the scene track [B, T, n_rows, 8], of a batch onto the solver (None clears either).  Where the
-    solver's safe-set net has a context, the instances' contexts go on and off with the scenes."""
+    solver's safe-set net has a context, the instances' contexts go on and off with the scenes: a track of T > 1 columns brings a
+    context track of the same T (solver.set_instance_context_track), so that the network row of node k is asked
+    about the scene its collision rows see."""
     if not hasattr(solver, 'set_instance_scene'):
         raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene')
     select = _context_select(solver)
     if select is not None:
-        if geom is not None and geom.ndim == 4 and geom.shape[1] > 1:
-            raise ValueError(f'scenes: a track of T = {geom.shape[1]} time columns with a safe-set network that has a context: the '
-                             f'context is a constant of the instance, one that moves along a track is not supported')
         from .problem import scene_context
-        solver.set_instance_context(None if geom is None else scene_context(geom.reshape((geom.shape[0],) + geom.shape[-2:]), select))
+        if geom is not None and geom.ndim == 4 and geom.shape[1] > 1:
+            if not hasattr(solver, 'set_instance_context_track'):
+                raise ValueError(f'scenes: a track of T = {geom.shape[1]} time columns with a safe-set network that has a context: the '
+                                 f'context is a constant of the instance, one that moves along a track is not supported')
+            solver.set_instance_context_track(scene_context(geom, select))
+        else:
+            solver.set_instance_context(None if geom is None else scene_context(geom.reshape((geom.shape[0],) + geom.shape[-2:]), select))
     if geom is not None and geom.ndim == 4:
         if not hasattr(solver, 'set_instance_scene_track'):
             raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene_track')
@@ -561,7 +566,8 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
     (solver.set_instance_scene): the Halton candidates are walked in order and each is tested against the scene of the instance it
     would start, so a candidate that collides there is skipped (:func:`_free_starts_per_scene`).  The result gains ``'scenes'``, the
     geometry of the accepted instances, and the returned mask has one entry per requested instance (False too where the
-    candidates ran out).
+    candidates ran out).  A track [n, T, n_rows, 8] with a safe-set network that has a context (``ctx_select``): the network row
+    of node k is given the context of the column its collision rows read (solver.set_instance_context_track).
 
     ``traj`` ([3, L], tracking.tracking_trajectory): the tracking branch, guess_acados.py:167-226.  The controller follows the curve
     (setTrajectory: p[:, i, :3] = traj[:, i]) and every start state comes from :func:`ik_starts` at ``traj[:, 0]`` -- instance i in
@@ -1553,7 +1559,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     time column (solver.set_instance_scene_track).  The loop's step counter j is the scene clock of both handles: node k of
     step j's solve and tests is formed in column min(j + k, T - 1), the plant's new state is tested in column min(j + 1, T - 1),
     state j of the log is scored there, and the backup OCP of an abort event at step j is solved at clock j in the aborting
-    instances' tracks.  Both handles are left without a track and without a clock when the run ends.
+    instances' tracks.  Both handles are left without a track and without a clock when the run ends.  A safe-set network with a
+    context (``ctx_select``) follows the track: both handles get the context of every (instance, column)
+    (solver.set_instance_context_track), the network row of node k reads the column its collision rows read, and the handles are
+    left without it.  The meaning is quasi-static: a network trained on standing scenes, asked at node k
+    about the scene as it will stand at time j + k.
     ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
     task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
     jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle

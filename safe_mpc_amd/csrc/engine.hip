@@ -114,7 +114,9 @@ struct smpc_handle {
     const int64_t* scene_clock = nullptr;   // the caller's device cell of smpc_set_scene_clock; null: time 0
     InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
-    InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][n_ctx] normalised context of the network
+    InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][T][n_ctx] normalised context of the network along
+                                                                            // time (smpc_set_instance_context_track; _context: T = 1)
+    int64_t ctx_T = 1;              // time columns of the context
     InstSlot<smpc_joint> models{"instance model table", "smpc_set_instance_models"};    // [B][nq] the controller's joint records:
                                                                                         // the caller's inertials, the descriptor's rest
     // network
@@ -400,9 +402,10 @@ int ensure_nn_idx(smpc_handle* h, size_t M) {
 }
 
 // Which instance a network row belongs to (CtxSrc, kernels_mlp.hpp): node / per on instance-major node arrays with `per` nodes per
-// instance; (m0 + m) % B on a step-major log read from flat row m0.
+// instance, the node of its instance being the node-time index of a context track; (m0 + m) % B on a step-major log read from flat
+// row m0, whose state index (m0 + m) / B counts time from 0 (run_mlp hands the kernels no clock cell there).
 CtxSrc rows_of_nodes(int per) { CtxSrc c; c.per = per; return c; }
-CtxSrc rows_step_major(int B, long m0) { CtxSrc c; c.mod = B; c.m0 = (int)(m0 % B); return c; }
+CtxSrc rows_step_major(int B, long m0) { CtxSrc c; c.mod = B; c.m0 = (int)(m0 % B); c.j0 = (int)(m0 / B); return c; }
 
 // forward (and optionally backward) pass of the network over M rows whose states are found through (mode, N) in x.
 // mode 3: the rows are the compacted list h->d_nn_idx of live nodes; their count is only known on the device (h->d_nn_cnt), so
@@ -423,6 +426,10 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         cx.n = net.n_ctx;
         cx.p = own ? own : net.d_default_ctx.p;
         cx.stride = own ? net.n_ctx : 0;
+        // a track: the column of a row follows the scene clock on the node arrays, the state index alone on the log (rows_step_major);
+        // a single column needs no time, so the clock is not handed on with T = 1 (as with_scene)
+        cx.T = own ? (int)h->ctx_T : 1;
+        cx.clock = cx.T > 1 && cx.mod == 0 ? h->scene_clock : nullptr;
     }
     const int Mp = (M + 127) / 128 * 128, H = net.H, L = net.nlayers;
     hipStream_t s = h->stream;
@@ -1602,7 +1609,7 @@ int smpc_set_mlp_context(smpc_handle* h, int n_ctx, const float* Wc, const doubl
     return SMPC_OK;
 }
 
-int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device) {
+int smpc_set_instance_context_track(smpc_handle* h, int B, int64_t T, const double* ctx, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     if (!ctx) { h->ctx.clear(); return SMPC_OK; }
@@ -1610,15 +1617,22 @@ int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_d
     if (net.n_ctx == 0)
         return fail(h, SMPC_EINVAL, "smpc_set_instance_context: the network has no context columns (smpc_set_mlp_context was not called)");
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    if (T < 1 || T > INT32_MAX)
+        return fail(h, SMPC_EINVAL, "smpc_set_instance_context_track: T=%lld: a track has at least one time column (and fewer than 2^31)",
+                    (long long)T);
     const int nc = net.n_ctx;
-    const size_t n = (size_t)B * nc;
+    const size_t n = (size_t)B * (size_t)T * nc;
     std::vector<float> norm;
     if (!on_device) {
         // (device pointers are taken as they are: reading them back would synchronise)
         norm.resize(n);
         for (size_t i = 0; i < n; i++) {
-            if (!(ctx[i] - ctx[i] == 0.0))
-                return fail(h, SMPC_EINVAL, "context of instance %zu (of B=%d), number %zu (of %d) is not finite", i / nc, B, i % nc, nc);
+            if (!(ctx[i] - ctx[i] == 0.0)) {
+                const size_t bt = i / nc;
+                if (T == 1) return fail(h, SMPC_EINVAL, "context of instance %zu (of B=%d), number %zu (of %d) is not finite", bt, B, i % nc, nc);
+                return fail(h, SMPC_EINVAL, "context track of instance %zu (of B=%d), column %zu (of T=%lld), number %zu (of %d) is not finite",
+                            bt / (size_t)T, B, bt % (size_t)T, (long long)T, i % nc, nc);
+            }
             norm[i] = (float)((ctx[i] - net.ctx_mean[i % nc]) / net.ctx_std[i % nc]);
         }
     }
@@ -1632,7 +1646,12 @@ int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_d
     } else if ((rc = h->ctx.upload(h, norm.data(), n, false)))
         return rc;
     h->ctx.commit(B);
+    h->ctx_T = T;
     return SMPC_OK;
+}
+
+int smpc_set_instance_context(smpc_handle* h, int B, const double* ctx, int on_device) {
+    return smpc_set_instance_context_track(h, B, 1, ctx, on_device);
 }
 
 int smpc_set_qp_mode(smpc_handle* h, int mode) {

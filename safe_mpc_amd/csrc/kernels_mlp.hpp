@@ -152,14 +152,24 @@ __global__ void k_nn_compact(int M, int N, const double* __restrict__ p, int32_t
 //         n_nodes for the lists of check_nodes_dev;
 //   mod:  > 0, a step-major log read in chunks that start at flat row m0 (launch_score): instance = (m0 + m) % mod.
 // stride = 0: the one default row serves every instance.  n = 0: a network without context, and nothing below is executed.
+// A context that moves along a track (smpc_set_instance_context_track): p = [instances][T][stride], one row per
+// (instance, time column), and the row of instance b at node-time index k is column scene_col(time + k) -- THE column rule of the scene
+// track (include/smpc.h), with this table's own T.  k = node - instance * per on the node arrays, read from the clock cell; the state
+// index (m0 + m) / mod on the step-major log, which starts at time 0 whatever the clock says (the launcher hands no clock over).
+// T = 1: one row per instance, no clock (the launcher passes null), and the index arithmetic below is not executed.
 struct CtxSrc {
-    const float* p = nullptr;   // [instances][stride] normalised context (stride = 0: one row)
+    const float* p = nullptr;   // [instances][T][stride] normalised context (stride = 0: one row)
     int n = 0;                  // context numbers per row, <= MLP_KPAD - 2 nn_dof
     int stride = 0;
     int per = 1;
     int mod = 0;
     int m0 = 0;                 // (m0 of the chunk) % mod
+    int j0 = 0;                 // (m0 of the chunk) / mod: the state index of the chunk's first row's step
+    int T = 1;                  // time columns of the table
+    const int64_t* clock = nullptr;     // the device cell of smpc_set_scene_clock (null: time 0)
 };
+// the time of a kernel's node 0, as scene_time reads it: one uniform load per kernel, held to +-2^62
+__device__ __forceinline__ int64_t ctx_time(const CtxSrc& cx) { return scene_time(SceneSrc{nullptr, cx.clock, cx.T, 0}); }
 
 // One row of layer 0's input, s[MLP_KPAD] (safe_set.py:82-87): s = [(q - mean)/std ; v/|v| ; context ; 0 ..], v = qd with eps on v_0.
 // A row past the live count is all-zero.  One thread per row.
@@ -187,8 +197,15 @@ __device__ __forceinline__ void nn_feature_row(const smpc_problem_desc* __restri
         }
     }
     if (cx.n > 0) {
-        const unsigned inst = cx.mod > 0 ? (unsigned)(cx.m0 + m) % (unsigned)cx.mod : (unsigned)node / (unsigned)cx.per;
-        const float* c = cx.p + (size_t)inst * cx.stride;
+        const unsigned flat = cx.mod > 0 ? (unsigned)(cx.m0 + m) : (unsigned)node, div = cx.mod > 0 ? (unsigned)cx.mod : (unsigned)cx.per;
+        const unsigned inst = cx.mod > 0 ? flat % div : flat / div;
+        size_t row = inst;
+        if (cx.T > 1) {
+            // (log: state j0 + flat / mod, no clock; node arrays: node flat - inst * per of its instance, at the clock's time)
+            const unsigned k = cx.mod > 0 ? flat / div : flat - inst * div;
+            row = (size_t)inst * (size_t)cx.T + (size_t)scene_col(ctx_time(cx) + cx.j0 + (int64_t)k, cx.T);
+        }
+        const float* c = cx.p + row * cx.stride;
         for (int i = 0; i < cx.n; i++) s[2 * nd + i] = c[i];
     }
 }

@@ -371,10 +371,15 @@ class OcpProblem:
 def scene_context(geom, select):
     """[B, n_ctx] from scenes ``geom [B, n_rows, SCENE_ROW]`` (a numpy array, or a ROCm tensor that gives a tensor): the numbers a safe-set network with a context is given about its
     instance's scene -- entry ``slot`` of row ``row``'s record for every ``(row, slot)`` of ``select``, in
-    that order (``SafeSetNet.ctx_select``)."""
+    that order (``SafeSetNet.ctx_select``).  A track ``[B, T, n_rows, SCENE_ROW]`` gives ``[B, T, n_ctx]``, the context of every
+    (instance, time column) (smpc_set_instance_context_track)."""
     on_device = type(geom).__module__.startswith('torch')      # (a ROCm tensor stays one: the device loop holds its scenes there)
     if not on_device:
         geom = np.asarray(geom, float)
+    if geom.ndim == 4 and geom.shape[3] == SCENE_ROW:
+        B, T = int(geom.shape[0]), int(geom.shape[1])
+        flat = scene_context(geom.reshape((B * T,) + tuple(geom.shape[2:])), select)
+        return flat.reshape((B, T, flat.shape[1]))
     if geom.ndim != 3 or geom.shape[2] != SCENE_ROW:
         raise ValueError(f'scene_context: expected [B, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
     sel = [(int(r), int(c)) for r, c in select]

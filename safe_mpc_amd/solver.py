@@ -154,6 +154,24 @@ class BatchedOcpSolver:
             raise ValueError(f'set_instance_context: expected [B, {n_ctx}], got {tuple(ctx.shape)}')
         self._set_instance(self.L.smpc_set_instance_context, 'set_instance_context', [ctx], None if ctx is None else ctx.shape[1:])
 
+    def set_instance_context_track(self, ctx=None):
+        """A context that follows a scene track (smpc_set_instance_context_track): ``ctx [B, T, n_ctx]`` float64,
+        the raw numbers of every (instance, time column) -- ``problem.scene_context(track, net.ctx_select)`` -- a numpy array or a
+        contiguous ROCm tensor; the engine keeps a normalised fp32 copy (4 B x n_ctx x T x B).  The network row of node k reads
+        column ``clip(t + k, 0, T - 1)``, t = the scene clock (:meth:`set_scene_clock`; 0 without one), state j of a score_rollout
+        log column ``clip(j, 0, T - 1)``: the scene track's rule with this table's own T.  A context and a context track are one
+        slot: setting one replaces the other, and None (here or in :meth:`set_instance_context`) clears both."""
+        n_ctx = int(getattr(self.net, 'n_ctx', 0)) if self.net is not None else 0
+        T = 1
+        if ctx is not None:
+            if ctx.ndim != 3 or (n_ctx and ctx.shape[2] != n_ctx):
+                raise ValueError(f'set_instance_context_track: expected [B, T, {n_ctx}], got {tuple(ctx.shape)}')
+            T = int(ctx.shape[1])
+            if T < 1:
+                raise ValueError('set_instance_context_track: a track has at least one time column')
+        self._set_instance(self.L.smpc_set_instance_context_track, 'set_instance_context_track', [ctx],
+                           None if ctx is None else ctx.shape[1:], T)
+
     QP_MODES = {'auto': -1, 'throughput': 0, 'latency': 1}
 
     def set_qp_mode(self, mode):

@@ -13,7 +13,8 @@ draw per axis (problem.jittered_scenes); the scenes of the accepted guesses are 
 --scene-velocity SIGMA: obstacles that move -- every guess is generated in a constant-velocity track of scenes, horizon + 1 time
 columns long, every obstacle with its own N(0, SIGMA^2) velocity draw per axis (problem.moving_scenes; it shares --scene-seed, and
 --scene-jitter moves the start positions); the tracks of the accepted guesses are stored as 'scenes' [n, T, n_rows, 8], which
-scripts/mpc.py --scene-velocity continues.  Not with --until-accepted.
+scripts/mpc.py --scene-velocity continues.  A safe-set network with a context (``ctx_select`` in its checkpoint) follows the track
+column by column.  Not with --until-accepted.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): warm starts of the trajectory-tracking task
 (guess_acados.py:167-226 of the reference) -- every start state is an inverse-kinematics solution at the curve's first point
 (closed_loop.ik_starts, smpc_ik_batch) and the OCP follows the curve.

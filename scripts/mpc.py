@@ -9,7 +9,8 @@ seed --scene-seed, default 0).
 --scene-velocity SIGMA: obstacles that move -- every instance gets a constant-velocity track of scenes, n_steps + 1 + horizon time
 columns long: the tracks stored with the guesses (guess_acados.py --scene-velocity) continued at their velocity if there are any,
 else every obstacle with its own N(0, SIGMA^2) velocity draw per axis (problem.moving_scenes; seed --scene-seed, start positions
-jittered by --scene-jitter if that is given too).
+jittered by --scene-jitter if that is given too).  A safe-set network with a context (``ctx_select`` in its checkpoint) follows the
+track column by column.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --

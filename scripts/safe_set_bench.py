@@ -12,6 +12,8 @@ stage of the network pass costs with a four-number instance context against a ne
 pass of smpc_check_trajectory(nn_ok) over --rays instances x 1 node (4096 rows: k_mlp_fused) and x 30 nodes (122 880 rows:
 k_mlp_wave), the two networks alternating on one handle, wall clock around a synchronise over 50 calls each; k_check_nodes and
 k_check_nn run in both and are part of both figures.
+SMPC_CONTEXT_TRACK=T beside it (profiles/context_tracks.txt): the instance context is a track of T time
+columns (smpc_set_instance_context_track) read through a scene clock cell that holds 3, so every row looks its column up.
 """
 import os, sys, time
 import numpy as np
@@ -52,9 +54,17 @@ def context_bench():
     dev = torch.device('cuda', sv.device)
     rng = np.random.default_rng(0)
     ctx = torch.as_tensor(rng.standard_normal((B, 4)), device=dev)
+    T = int(os.environ.get('SMPC_CONTEXT_TRACK', '1'))
+    if T > 1:
+        ctx = torch.as_tensor(rng.standard_normal((B, T, 4)), device=dev)
+        cell = torch.full((1,), 3, dtype=torch.int64, device=dev)
+        sv.set_scene_clock(cell)
+    set_ctx = sv.set_instance_context_track if T > 1 else sv.set_instance_context
     CALLS = 50
     say(f'# SMPC_CONTEXT=1 python scripts/safe_set_bench.py -- the forward-only network pass of smpc_check_trajectory(nn_ok), {B} instances, a '
         f'four-number instance context against a network without context columns; one MI355X, one session, {CALLS} calls per figure')
+    if T > 1:
+        say(f'# SMPC_CONTEXT_TRACK={T}: the context is a track of {T} time columns, the scene clock cell holds 3')
     for n_nodes in (1, 30):
         x = torch.as_tensor(prob.x_min + rng.uniform(size=(B, n_nodes, 12)) * (prob.x_max - prob.x_min), device=dev)
         times = {'none': [], 'context': []}
@@ -62,7 +72,7 @@ def context_bench():
             for mode in ('none', 'context'):
                 sv.set_mlp(plain if mode == 'none' else net)
                 if mode == 'context':
-                    sv.set_instance_context(ctx)
+                    set_ctx(ctx)
                 sv.check_trajectory(x, want_nn=True)
                 sv.sync(); torch.cuda.synchronize()
                 t0 = time.perf_counter()
