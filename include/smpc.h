@@ -251,6 +251,7 @@ int smpc_set_instance_scene(smpc_handle* h, int B, const double* geom, int on_de
  *   smpc_solve_batch, smpc_eval_nodes, smpc_merit_terms, smpc_sqp_batch, smpc_check_guess, smpc_check_trajectory,
  *   smpc_debug_stage_records, and the solve and the x_temp test of smpc_policy_step (kinds 0-4):   node k in column col(t + k)
  *   smpc_loop_post (its one node is the plant's NEXT state):                                       column col(t + 1)
+ *     (of the WORLD, with the world's T, while one is set: smpc_set_instance_world_track below)
  *   smpc_ik_batch:                                                                                 column col(t)
  *   smpc_score_rollout (the log starts at time 0, the clock is not read):                          state j of the log in col(j)
  * A track and a scene are ONE slot of the handle: setting one replaces the other, smpc_set_instance_scene(h, B, geom, ..) is exactly
@@ -269,6 +270,48 @@ int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double
  * read.  The clock stays set across smpc_set_instance_scene / _track and smpc_set_instance_context / _track calls until it is
  * replaced or cleared here. */
 int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
+
+/* The WORLD: a track that only the plant meets.  geom is [B][T][n_rows][SMPC_SCENE_ROW], exactly a scene
+ * track's layout and validation (host pointers are checked for non-finite values in the fields the row kinds read and the call
+ * waits for the copy, device pointers are taken as they are).  It is a slot of the handle under the one slot rule: it belongs to its
+ * batch size, the same (B, T) is overwritten in place, growth while the stream is being captured is SMPC_ESTATE with the old contents
+ * kept, and geom == NULL clears it.  Clearing the world also clears a scene slot that holds a forecast and a context the forecast
+ * wrote: a forecast without its world is stale.
+ * Who reads the world: smpc_forecast_scene (below), and smpc_loop_post, whose one node -- the plant's NEXT state -- is tested in
+ * column col(t + 1) of the WORLD instead of the scene slot while a world is set (col with the world's T, t the scene clock).
+ * smpc_loop_post with another B: SMPC_EINVAL naming both sizes.  Nothing else reads it; in particular the x_temp test of
+ * smpc_policy_step keeps reading the scene slot, which is what the controller believes.
+ * SMPC_EINVAL: B <= 0, T < 1, a descriptor without rows, or (host pointers only) a non-finite value in a field that is read.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_world_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device);
+
+/* A FORECAST of the horizon's N + 1 scenes, formed on the device from what the world has shown up to the clock, into the scene
+ * slot.  Enqueue-only on the handle's stream once its buffers exist.  With W the world, T its columns, t the scene clock's cell when
+ * the kernel runs (0 without a clock, held to +-2^62), col THE column rule with W's T, c0 = col(t), c1 = col(t - 1) and N the
+ * handle's horizon, for every instance b, row r and all eight slots s of the record:
+ *   SMPC_FORECAST_HOLD  F[b][k][r][s] = W[b][c0][r][s], k = 0..N                      (the frozen world)
+ *   SMPC_FORECAST_CV    d = W[b][c0][r][s] - W[b][c1][r][s];  F[b][0] = W[b][c0],  F[b][k] = F[b][k-1] + d, k = 1..N
+ *                       -- repeated addition in this order, no multiplication; c0 == c1 (t <= 0, t >= T, T = 1) gives d = 0
+ *   SMPC_FORECAST_TRUE  F[b][k] = W[b][col(t + k)]                                    (the clairvoyant arm of a study)
+ * F replaces whatever the scene slot held, as a track of N + 1 columns for B instances.  While the slot holds a forecast it is read
+ * FROM TIME 0, whatever the clock says (the launchers hand the kernels no clock, as for T = 1): node k of the solves and tests of
+ * the scene track's table reads column clamp(k, 0, N), smpc_ik_batch column 0, smpc_score_rollout column col(j) as for any track
+ * (re-set the slot to the world before scoring a log).  smpc_set_instance_scene / _track replace the forecast and return the slot to
+ * clocked reading; smpc_set_horizon drops a forecast (it is laid out by N); SMPC_POLICY_PARALLEL and smpc_rollout_batch refuse
+ * the slot as they refuse any scene.
+ * Context rows: select is n_sel HOST pairs (row, slot) -- which number of the scene each context input of the network is.  With
+ * n_sel > 0 the call also writes the context slot, [B][N+1][n_ctx] fp32, from the same F:
+ *   ctx[b][k][i] = (float)((F[b][k][row_i][slot_i] - ctx_mean[i]) / ctx_std[i])
+ * read from time 0 like the forecast scene, replaced and re-clocked by smpc_set_instance_context / _track, dropped with the
+ * forecast.  The pairs travel with the launch (no device copy is kept, so a captured call carries its own).  With n_sel == 0 the
+ * context slot is left alone.
+ * SMPC_EINVAL (the message names the call and, where sizes disagree, both): B differs from the world's; unknown mode; n_sel > 0 with
+ * a network without context columns or with n_sel != n_ctx; a pair outside n_rows x SMPC_SCENE_ROW; n_sel > 0 with select == NULL.
+ * SMPC_ESTATE: no world set, or the scene or context buffer would have to grow while the stream is being captured.
+ * A refused call leaves the slot contents in force.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+enum { SMPC_FORECAST_HOLD = 0, SMPC_FORECAST_CV = 1, SMPC_FORECAST_TRUE = 2 };
+int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_t* select);
 
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle

@@ -29,15 +29,16 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
             f'_q_collision_margins_{params.q_margin}_{params.collision_margin}_guess.pkl')
 
 
-def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal'):
+def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
-    before ``_mpc.pkl``; the default gives the reference's name"""
+    before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
+    it; the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
     track = 'traj_track' if params.track_traj else ''
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
-            f"{'_cmplant' if controller_model == 'plant' else ''}_mpc.pkl")
+            f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}_mpc.pkl")
 
 
 def tracking_from_cli(params, argv, n=None):
@@ -1066,7 +1067,7 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None, models=None):
+                 scenes=None, models=None, forecast=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -1074,11 +1075,15 @@ class _Group:
         # a scene per instance (run_mpc(scenes=...)): the controller's handle holds the group's [B, n_rows, 8]; the backup handle gets
         # the rows of the aborting instances before each of its compact solves (_backup_scene).  A track [B, T, n_rows, 8] goes the
         # same way; the loop's step counter is then the scene clock of both handles (the subclasses say where the cell lives)
-        self._scenes, self._track = None, False
+        # A forecast (run_mpc(forecast=...)): the track is the WORLD, which only the plant meets; the scene slot
+        # of either handle holds what the controller forecasts at the head of every step (the subclasses say how), so the track
+        # itself does not go onto the scene slot until the run is scored.
+        self._scenes, self._track, self._forecast = None, False, forecast
         if scenes is not None:
             self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
             self._track = self._scenes.ndim == 4
-            _set_scene(ctrl.ocp_solver, self._scenes)
+            if forecast is None:
+                _set_scene(ctrl.ocp_solver, self._scenes)
             if self._track:
                 for sv in (ctrl.ocp_solver, backup.ocp_solver):
                     if not hasattr(sv, 'set_scene_clock'):
@@ -1130,8 +1135,12 @@ class _Group:
     def _backup_scene(self, rows):
         """the backup OCP of an abort event is solved in the scenes of the aborting instances: their geometry rows, gathered in the
         order of the compact batch, onto the backup handle"""
-        if self._scenes is not None:
+        if self._scenes is None:
+            return
+        if self._forecast is None:
             _set_scene(self._backup.ocp_solver, self._scenes[rows])
+        else:       # (what the controller knows of these instances' world at the event, over the backup's own horizon)
+            self._backup_forecast(rows)
 
     def _hand_over_models(self, table=None):
         """the group's controller models onto the controller's handle: ``table`` (the subclass's form of the rows it was given), or
@@ -1170,6 +1179,11 @@ class _Group:
         xp, ctrl, params, B, n_steps = self._xp, self._ctrl, self._params, self._B, self._n_steps
         solver, pr = ctrl.ocp_solver, ctrl.problem
         scored = None
+        if self._forecast is not None:
+            # the run is scored in the TRUE world: the track replaces the last forecast in the scene slot (with its context track
+            # where the net has one), read by the loop's clock again
+            _set_scene(solver, self._scenes)
+            solver.set_scene_clock(self._clock)
         if score:
             # the run's scores: on the device from the logs where they are (one enqueue on the group's stream, ahead of the wait
             # below), on the host by the statement; the safe-set score where the formulation has a safe-set row
@@ -1201,6 +1215,10 @@ class _Group:
             extra['scenes'] = xp.host(self._scenes)
             _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
             _clear_scene(self._backup.ocp_solver)
+            if self._forecast is not None:         # (nor a world)
+                for sv in (solver, self._backup.ocp_solver):
+                    if hasattr(sv, 'set_instance_world_track'):
+                        sv.set_instance_world_track(None)
         if self._models is not None:               # (nor a model table)
             _set_models(solver, None)
             _set_models(self._backup.ocp_solver, None)
@@ -1264,7 +1282,10 @@ class _HostGroup(_Group):
         stepping = self.alive & ~self.sa
         if hasattr(ctrl, 'r'):
             self.r_log[self._jt] = np.where(stepping, ctrl.r, -1)
-        _write_scene_clock(self._clock, self._jt)           # node k of this step's solve and tests: time j + k
+        if self._forecast is None:
+            _write_scene_clock(self._clock, self._jt)       # node k of this step's solve and tests: time j + k
+        else:                                               # ... in the scenes forecast at time j, read from node 0 on
+            self._forecast_onto(ctrl.ocp_solver, self._scenes, self._jt, ctrl.N)
         # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
         #  read again, so they may step along)
         if self._ever_aborted:
@@ -1280,6 +1301,16 @@ class _HostGroup(_Group):
             again = self.new_abort & self.resumed
             self.sa = self.sa | again
             self.new_abort = self.new_abort & ~again
+
+    def _forecast_onto(self, sv, world, t, N):
+        """the statement of smpc_forecast_scene: the N + 1 scenes forecast from ``world`` at time t onto ``sv``'s scene slot (and
+        their context rows, _set_scene), with no clock -- node k reads column k"""
+        from .problem import forecast_statement
+        sv.set_scene_clock(None)
+        _set_scene(sv, forecast_statement(world, t, N, self._forecast))
+
+    def _backup_forecast(self, rows):
+        self._forecast_onto(self._backup.ocp_solver, self._scenes[rows], self._jt, self._Nb)
 
     # ---- the step's decision: abort events (mpc.py:161-190) ----------------------------------------------------------------------
     def handle_aborts(self):
@@ -1322,7 +1353,10 @@ class _HostGroup(_Group):
         x_next, _ = solver.plant_step(self.x_cur, self.u, self._joints_noisy, self._tau_noise)
         # outcome tests on the new state (mpc.py:246-264): one node per instance, so the engine's box + collision test
         # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints; the new state is
-        # the state of time j + 1, which is where a scene track is read
+        # the state of time j + 1, which is where a scene track is read -- with a forecast the WORLD's track, not the controller's
+        if self._forecast is not None:
+            _set_scene(solver, self._scenes)
+            solver.set_scene_clock(self._clock)
         _write_scene_clock(self._clock, j + 1)
         okn = np.asarray(solver.check_trajectory(x_next[:, None, :]))
         self.x_log[j + 1] = x_next
@@ -1371,6 +1405,15 @@ class _DeviceGroup(_Group):
             self._clock, self._backup_clock = self._jt, xp.step_index(0)
             ctrl.ocp_solver.set_scene_clock(self._clock)
             self._backup.ocp_solver.set_scene_clock(self._backup_clock)
+        # a forecast: the world goes on once; smpc_forecast_scene at the head of every step (inside the captured half) fills the
+        # scene slot from it at the counter's value, and smpc_loop_post tests the plant's next state in the world
+        self._select = self._backup_select = None
+        if self._forecast is not None:
+            for sv in (ctrl.ocp_solver, self._backup.ocp_solver):
+                if not hasattr(sv, 'forecast_scene'):
+                    raise ValueError(f'forecast: {type(sv).__name__} has no forecast_scene')
+            self._select, self._backup_select = _context_select(ctrl.ocp_solver), _context_select(self._backup.ocp_solver)
+            ctrl.ocp_solver.set_instance_world_track(self._scenes)
         self._use_graphs = bool(use_graphs)
         self._graphs = {}                         # half -> captured graph
         self._u_other = xp.zeros((B, nu))
@@ -1390,6 +1433,8 @@ class _DeviceGroup(_Group):
 
     def part_a(self):
         ctrl, sv = self._ctrl, self._ctrl.ocp_solver
+        if self._forecast is not None:
+            sv.forecast_scene(self._forecast, self._select)
         sv.loop_pre(self, getattr(ctrl, 'r', None), self._pending, self._u_other, self._stepping)
         ctrl.step_on_device(self.x_cur, self._stepping, self._u_other, u_out=self.u)
         if ctrl.can_abort:
@@ -1440,6 +1485,13 @@ class _DeviceGroup(_Group):
         #  event recorded on the main stream after that.  torch's record_stream is not usable here -- on this ROCm build it
         #  faults on an ExternalStream.)
         self._inflight = (rows_b, xv_c, xo_c, uo_c, st_c, ev)
+
+    def _backup_forecast(self, rows):
+        """the aborting instances' world rows onto the backup handle and one forecast over ITS horizon, at its own clock cell (which
+        holds the counter's value at the event: handle_aborts)"""
+        sv = self._backup.ocp_solver
+        sv.set_instance_world_track(self._scenes[rows])
+        sv.forecast_scene(self._forecast, self._backup_select)
 
     def part_b(self):
         self._ctrl.ocp_solver.loop_post(self, self.u, self._joints_noisy, self._tau_noise)
@@ -1530,7 +1582,7 @@ def _check_state_kind(ctrl, backup, on_device):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False, scenes=None, traj=None, models=None):
+            score=False, scenes=None, traj=None, models=None, forecast=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1564,6 +1616,15 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     (solver.set_instance_context_track), the network row of node k reads the column its collision rows read, and the handles are
     left without it.  The meaning is quasi-static: a network trained on standing scenes, asked at node k
     about the scene as it will stand at time j + k.
+    ``forecast`` ('hold', 'cv', 'true'; needs a track): the track is the WORLD, which only the plant meets, and the controller plans
+    against a forecast of it (``problem.forecast_statement``): at the head of step j the scene slot gets the
+    horizon's N + 1 scenes as forecast from the world's columns up to j -- 'hold' the frozen world, 'cv' constant velocity from
+    the last two columns, 'true' the world itself (the clairvoyant controller that ``forecast=None`` is) -- and, for a net with a
+    context, their context rows; the plant's new state is tested in column j + 1 of the world.  On the device that is one
+    smpc_forecast_scene per step inside the captured half and smpc_loop_post reading the world; on the host the statement.  The
+    backup OCP of an abort event gets the aborting instances' world rows and one forecast over its own horizon at the event's
+    clock.  The run is scored in the true world, both handles end without world, forecast, context and clock, and the result
+    gains ``'forecast'``.  None: the calls of a run without the argument, one for one.
     ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
     task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
     jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle
@@ -1585,6 +1646,13 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         scenes = np.ascontiguousarray(scenes, np.float64)
         if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
             raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
+    if forecast is not None:
+        from .problem import FORECAST_MODES
+        if forecast not in FORECAST_MODES:
+            raise ValueError(f'forecast: {forecast!r}: expected None or one of {sorted(FORECAST_MODES)}')
+        if scenes is None or scenes.ndim != 4:
+            raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
+                             + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1618,11 +1686,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
             sv = ctrl.ocp_solver
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
-                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs,
+                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs, forecast=forecast,
                                    models=models if models is None or isinstance(models, str) else models[lo:hi])
         else:
             streams.append(None)
-            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi],
+            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi], forecast=forecast,
                              models=models if models is None or isinstance(models, str) else models[lo:hi])
         grps.append(grp)
         gens.append(grp.run())
@@ -1703,6 +1771,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra['score'] = {k: np.concatenate([o['score'][k] for o in outs]) for k in outs[0]['score']}
     if scenes is not None:
         extra['scenes'] = np.concatenate([o['scenes'] for o in outs], axis=0)
+    if forecast is not None:
+        extra['forecast'] = forecast
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -22,6 +22,7 @@
 #include "kernels_score.hpp"
 #include "kernels_ik.hpp"
 #include "kernels_rays.hpp"
+#include "kernels_forecast.hpp"
 
 using namespace smpc;
 
@@ -112,11 +113,17 @@ struct smpc_handle {
                                                                             // time (smpc_set_instance_scene_track; _scene: T = 1)
     int64_t scene_T = 1;            // time columns of the scene
     const int64_t* scene_clock = nullptr;   // the caller's device cell of smpc_set_scene_clock; null: time 0
+    bool scene_fc = false;          // the scene holds a forecast (smpc_forecast_scene): N + 1 columns read from time 0, no clock.
+                                    // Assigned with every commit of the slot, so it means something only while the slot is set
+    InstSlot<double> world{"instance world track", "smpc_set_instance_world_track"};    // [B][T][n_rows][SMPC_SCENE_ROW] the track the
+                                    // plant meets: read by smpc_forecast_scene and smpc_loop_post alone
+    int64_t world_T = 1;
     InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
     InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][T][n_ctx] normalised context of the network along
                                                                             // time (smpc_set_instance_context_track; _context: T = 1)
     int64_t ctx_T = 1;              // time columns of the context
+    bool ctx_fc = false;            // the context was written by smpc_forecast_scene: read from time 0 (as scene_fc)
     InstSlot<smpc_joint> models{"instance model table", "smpc_set_instance_models"};    // [B][nq] the controller's joint records:
                                                                                         // the caller's inertials, the descriptor's rest
     // network
@@ -429,7 +436,7 @@ template <int NQ> int run_mlp(smpc_handle* h, int M, int mode, int N, const doub
         // a track: the column of a row follows the scene clock on the node arrays, the state index alone on the log (rows_step_major);
         // a single column needs no time, so the clock is not handed on with T = 1 (as with_scene)
         cx.T = own ? (int)h->ctx_T : 1;
-        cx.clock = cx.T > 1 && cx.mod == 0 ? h->scene_clock : nullptr;
+        cx.clock = cx.T > 1 && cx.mod == 0 && !(own && h->ctx_fc) ? h->scene_clock : nullptr;     // (a forecast: from time 0)
     }
     const int Mp = (M + 127) / 128 * 128, H = net.H, L = net.nlayers;
     hipStream_t s = h->stream;
@@ -537,10 +544,13 @@ int launch_nn(smpc_handle* h, int B, const double* d_xg, const double* d_p, doub
 // f(std::true_type{}, sc) with the handle's scene track when it was set for B instances, else f(std::false_type{}, nullptr): a launcher
 // names its kernel and its arguments once, as with with_rows below.  (The SCENE instantiation first: a kernel's place in the code
 // object follows its first mention, see ensure_batch.)  off: added to the clock (smpc_loop_post); clocked = false: the kernel
-// counts time from 0 (smpc_score_rollout).  A single column needs no time, so the clock is not handed on with T = 1.
+// counts time from 0 (smpc_score_rollout).  A single column needs no time, so the clock is not handed on with T = 1; a forecast
+// (smpc_forecast_scene) is laid out from the clock's time on, so it is read from time 0 as well, `off` included.
 template <class F> int with_scene(const smpc_handle* h, int B, F&& f, int64_t off = 0, bool clocked = true) {
-    if (const double* geom = h->scene.for_batch(B))
+    if (const double* geom = h->scene.for_batch(B)) {
+        if (h->scene_fc) return f(std::true_type{}, SceneSrc{geom, nullptr, h->scene_T, 0});
         return f(std::true_type{}, SceneSrc{geom, clocked && h->scene_T > 1 ? h->scene_clock : nullptr, h->scene_T, off});
+    }
     return f(std::false_type{}, (const double*)nullptr);
 }
 
@@ -562,6 +572,14 @@ int guard_scene_and_context(smpc_handle* h, int B, const char* who) {
 int guard_scene_context_and_models(smpc_handle* h, int B, const char* who) {
     const int rc = guard_scene_and_context(h, B, who);
     return rc ? rc : h->models.guard(h, B, who);
+}
+
+// A forecast goes when its world or its horizon does (smpc_forecast_scene): the scene slot if it holds one, and the context if a
+// forecast wrote it.  Slots that a setter filled are not touched.
+void drop_forecast(smpc_handle* h) {
+    if (h->scene_fc) h->scene.clear();
+    if (h->ctx_fc) h->ctx.clear();
+    h->scene_fc = h->ctx_fc = false;
 }
 
 // The reference table of a policy step: the handle's curves (a table per instance) or the caller's shared one (stride 0), or none.
@@ -861,13 +879,18 @@ int check_nodes_dev(smpc_handle* h, int B, int n_nodes, const double* d_x, doubl
     //  millisecond: k_policy_post, six blocks of four waves, averaged 131 us in the three-stream loop; rocprofv3, round 3)
     const dim3 grd((unsigned)((M + 63) / 64)), blk(64);
     int rc;
-    if ((rc = with_scene(h, B, [&](auto SCENE, auto sc) {
-             return with_nq(h, [&](auto NQ) {
-                 hipLaunchKernelGGL((k_check_nodes<NQ, SCENE>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, c.x_min, c.x_max, tol_x, c.row_lb,
-                                    c.row_ub, d_ok, coll_nodes, sc);
-                 return SMPC_OK;
-             });
-         }, scene_off)))
+    const auto launch = [&](auto SCENE, auto sc) {
+        return with_nq(h, [&](auto NQ) {
+            hipLaunchKernelGGL((k_check_nodes<NQ, SCENE>), grd, blk, 0, s, h->d_desc, B, n_nodes, d_x, c.x_min, c.x_max, tol_x, c.row_lb,
+                               c.row_ub, d_ok, coll_nodes, sc);
+            return SMPC_OK;
+        });
+    };
+    // the plant's next state (smpc_loop_post: scene_off = 1) meets the WORLD while one is set (its caller has guarded B), clocked
+    // like a scene track; every other test reads the scene slot, which is what the controller believes
+    const double* world = scene_off == 1 ? h->world.held() : nullptr;
+    if ((rc = world ? launch(std::true_type{}, SceneSrc{world, h->world_T > 1 ? h->scene_clock : nullptr, h->world_T, scene_off})
+                    : with_scene(h, B, launch, scene_off)))
         return rc;
     HIPCHK(h, hipGetLastError());
     if (d_nn) {
@@ -1647,6 +1670,7 @@ int smpc_set_instance_context_track(smpc_handle* h, int B, int64_t T, const doub
         return rc;
     h->ctx.commit(B);
     h->ctx_T = T;
+    h->ctx_fc = false;      // (a context of the caller's replaces one that a forecast wrote: read by the clock again)
     return SMPC_OK;
 }
 
@@ -1667,7 +1691,8 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->N = N;
-    h->bounds.clear();      // (the one slot laid out by the horizon)
+    h->bounds.clear();      // (the one slot laid out by the horizon ...
+    drop_forecast(h);       //  ... and a forecast, N + 1 columns of it; the world it was made from stays)
     h->order_B = 0;
     // every buffer laid out by the horizon starts afresh (zeroed where that is its contract) in the next call that needs it
     for (DevBuf<double>* buf : {&h->d_zl, &h->bounds.d, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
@@ -1715,12 +1740,12 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
     return SMPC_OK;
 }
 
-int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
-    if (!h) return SMPC_EINVAL;
-    (void)hipSetDevice(h->device);
-    if (!geom) { h->scene.clear(); return SMPC_OK; }
+// The one setter of a table of scene records [B][T][n_rows][SMPC_SCENE_ROW]: the scene slot (smpc_set_instance_scene_track) and the
+// world (smpc_set_instance_world_track) share layout, validation and the slot rule.
+static int set_scene_table(smpc_handle* h, InstSlot<double>& slot, int64_t& slot_T, const char* who, int B, int64_t T, const double* geom,
+                           int on_device) {
     if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
-    if (T < 1) return fail(h, SMPC_EINVAL, "smpc_set_instance_scene_track: T=%lld: a track has at least one time column", (long long)T);
+    if (T < 1) return fail(h, SMPC_EINVAL, "%s: T=%lld: a track has at least one time column", who, (long long)T);
     const int nr = h->desc.n_rows;
     if (nr == 0) return fail(h, SMPC_EINVAL, "the problem has no collision rows: there is no scene to set");
     const size_t n = (size_t)B * (size_t)T * nr * SMPC_SCENE_ROW;
@@ -1741,9 +1766,101 @@ int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double
             }
     }
     int rc;
-    if ((rc = h->scene.room(h, n)) || (rc = h->scene.upload(h, geom, n, on_device != 0))) return rc;
+    if ((rc = slot.room(h, n)) || (rc = slot.upload(h, geom, n, on_device != 0))) return rc;
+    slot.commit(B);
+    slot_T = T;
+    return SMPC_OK;
+}
+
+int smpc_set_instance_scene_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!geom) { h->scene.clear(); h->scene_fc = false; return SMPC_OK; }
+    const int rc = set_scene_table(h, h->scene, h->scene_T, "smpc_set_instance_scene_track", B, T, geom, on_device);
+    if (rc) return rc;
+    // a scene of the caller's replaces a forecast: the slot is read by the clock again, and a context that the forecast wrote goes
+    // with it (a setter's own context stays)
+    h->scene_fc = false;
+    if (h->ctx_fc) { h->ctx.clear(); h->ctx_fc = false; }
+    return SMPC_OK;
+}
+
+int smpc_set_instance_world_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!geom) {
+        h->world.clear();
+        drop_forecast(h);       // (a forecast without its world is stale)
+        return SMPC_OK;
+    }
+    return set_scene_table(h, h->world, h->world_T, "smpc_set_instance_world_track", B, T, geom, on_device);
+}
+
+int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_t* select) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!h->world.B) return fail(h, SMPC_ESTATE, "smpc_forecast_scene: no world is set (smpc_set_instance_world_track)");
+    if (B != h->world.B)
+        return fail(h, SMPC_EINVAL, "smpc_forecast_scene: batch size %d, but the instance world track was set for %d instances "
+                    "(smpc_set_instance_world_track: clear it or set one of this size)", B, h->world.B);
+    if (mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
+        return fail(h, SMPC_EINVAL, "smpc_forecast_scene: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", mode);
+    const Net& net = *h->net;
+    const int nr = h->desc.n_rows, N = h->N, nc = net.n_ctx;
+    if (n_sel < 0) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d", n_sel);
+    ForecastSel sel{};
+    CtxNorm nm{};
+    if (n_sel > 0) {
+        if (!select) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d with select == NULL", n_sel);
+        if (nc == 0)
+            return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d, but the network has no context columns (smpc_set_mlp_context was "
+                        "not called)", n_sel);
+        if (n_sel != nc) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d, but the network has n_ctx=%d context columns", n_sel, nc);
+        for (int i = 0; i < n_sel; i++) {
+            const int r = select[2 * i], s = select[2 * i + 1];
+            if (r < 0 || r >= nr || s < 0 || s >= SMPC_SCENE_ROW)
+                return fail(h, SMPC_EINVAL, "smpc_forecast_scene: select[%d] = (row %d, slot %d) outside %d rows x %d slots", i, r, s, nr,
+                            SMPC_SCENE_ROW);
+            sel.row[i] = r;
+            sel.slot[i] = s;
+        }
+        for (int c = 0; c < MLP_KPAD; c++) { nm.mean[c] = net.ctx_mean[c]; nm.std[c] = net.ctx_std[c]; }
+    }
+    // room first, launches last: a call refused for growth under capture has changed nothing.  A buffer that did grow lost its old
+    // content with its old allocation, so the slot is empty until the commit below.
+    const size_t n = (size_t)B * (N + 1) * nr * SMPC_SCENE_ROW, n_ctx_el = (size_t)B * (N + 1) * n_sel;
+    const bool scene_grows = n * sizeof(double) > h->scene.d.cap, ctx_grows = n_ctx_el * sizeof(float) > h->ctx.d.cap;
+    if ((scene_grows || ctx_grows) && capturing(h))
+        return fail(h, SMPC_ESTATE, "smpc_forecast_scene: the %s must grow to %zu bytes while the stream is being captured: run one eager "
+                    "call of this size first", scene_grows ? h->scene.noun : h->ctx.noun,
+                    scene_grows ? n * sizeof(double) : n_ctx_el * sizeof(float));
+    int rc;
+    if (scene_grows) h->scene.clear();
+    if ((rc = h->scene.room(h, n))) return rc;
+    if (ctx_grows) h->ctx.clear();
+    if (n_sel > 0 && (rc = h->ctx.room(h, n_ctx_el))) return rc;
+    const SceneSrc world{h->world.d.p, h->world_T > 1 ? h->scene_clock : nullptr, h->world_T, 0};
+    const int n_rec = B * nr;
+    // (one-wavefront blocks, as for every small kernel of the policy step: see check_nodes_dev)
+    const dim3 grd((unsigned)((n_rec + 63) / 64)), blk(64);
+    if (mode == SMPC_FORECAST_HOLD)
+        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_HOLD>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
+    else if (mode == SMPC_FORECAST_CV)
+        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_CV>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
+    else
+        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_TRUE>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
+    HIPCHK(h, hipGetLastError());
     h->scene.commit(B);
-    h->scene_T = T;
+    h->scene_T = N + 1;
+    h->scene_fc = true;
+    if (n_sel > 0) {
+        hipLaunchKernelGGL(k_forecast_context, dim3((unsigned)((n_ctx_el + 63) / 64)), blk, 0, h->stream, (long)n_ctx_el, nc, nr,
+                           h->scene.d.p, sel, nm, h->ctx.d.p);
+        HIPCHK(h, hipGetLastError());
+        h->ctx.commit(B);
+        h->ctx_T = N + 1;
+        h->ctx_fc = true;
+    }
     return SMPC_OK;
 }
 
@@ -2239,7 +2356,7 @@ int smpc_loop_post(smpc_handle* h, int B, const smpc_policy_params* par, const s
     const int nq = h->desc.nq;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = h->scene.guard(h, B, "smpc_loop_post"))) return rc;
+    if ((rc = h->scene.guard(h, B, "smpc_loop_post")) || (rc = h->world.guard(h, B, "smpc_loop_post"))) return rc;
     PolScratch w;       // (its x_next [B][nx] and ok [B] lie behind smpc_policy_step's part)
     if ((rc = policy_scratch(h, B, &w))) return rc;
     if ((rc = upload_check_bounds(h, par->x_min, par->x_max, par->row_lb_chk, par->row_ub_chk))) return rc;
@@ -2619,6 +2736,29 @@ int smpc_get_qp_wave_stats(smpc_handle* h, double* out3) {
 }
 
 }  // extern "C"
+
+// Test hook (not part of include/smpc.h): what the scene slot and the context slot hold, copied to the host after the stream has
+// drained -- tests/test_forecast_gpu.py holds smpc_forecast_scene's table against its numpy statement with it.  info[6] = {scene B,
+// scene T, scene holds a forecast, context B, context T, context written by a forecast} (B = 0: the slot is empty); scene_out /
+// ctx_out (either may be NULL) receive at most scene_cap doubles / ctx_cap floats.  Host pointers.
+extern "C" int smpc_debug_scene_slots(smpc_handle* h, double* scene_out, size_t scene_cap, float* ctx_out, size_t ctx_cap, int64_t* info) {
+    if (!h || !info) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t ns = (size_t)h->scene.B * (size_t)h->scene_T * h->desc.n_rows * SMPC_SCENE_ROW;
+    const size_t nc = (size_t)h->ctx.B * (size_t)h->ctx_T * h->net->n_ctx;
+    const int64_t inf[6] = {h->scene.B, h->scene_T, h->scene.B && h->scene_fc, h->ctx.B, h->ctx_T, h->ctx.B && h->ctx_fc};
+    memcpy(info, inf, sizeof(inf));
+    if (scene_out && ns) {
+        if (ns > scene_cap) return fail(h, SMPC_EINVAL, "smpc_debug_scene_slots: the scene holds %zu doubles, room for %zu", ns, scene_cap);
+        HIPCHK(h, hipMemcpy(scene_out, h->scene.d.p, ns * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (ctx_out && nc) {
+        if (nc > ctx_cap) return fail(h, SMPC_EINVAL, "smpc_debug_scene_slots: the context holds %zu floats, room for %zu", nc, ctx_cap);
+        HIPCHK(h, hipMemcpy(ctx_out, h->ctx.d.p, nc * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return SMPC_OK;
+}
 
 // Test hook (not part of include/smpc.h): the stage records of the QP workspace as the solve path builds them (path 1: MLP ->
 // k_stage_build) or as the thread-per-node kernels of rounds 1-3 do (path 0: k_node_linearise -> MLP -> k_qp_setup, off the solve

@@ -441,8 +441,15 @@ def moving_scenes(prob, B, T, sigma_v, seed=0, sigma=0.0):
     d0 = np.stack([rng0.normal(0.0, float(sigma), (len(names), 3)) for _ in range(B)]).reshape(B, len(names), 3)
     v = np.stack([rngv.normal(0.0, float(sigma_v), (len(names), 3)) for _ in range(B)]).reshape(B, len(names), 3)
     move = d0[:, None] + v[:, None] * (float(prob.desc.dt) * np.arange(T))[None, :, None, None]      # [B, T, obstacle, axis]
+    return _moved_tracks(prob, names, move)
+
+
+def _moved_tracks(prob, names, move):
+    """[B, T, n_rows, SCENE_ROW] from ``move [B, T, obstacle, axis]``, the translation of every obstacle of ``names`` in every
+    (instance, column): OcpProblem.scene, for all of them at once"""
+    B, T = move.shape[:2]
     out = np.broadcast_to(prob.row_geometry(), (B, T, len(prob.rows), SCENE_ROW)).copy()
-    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):          # OcpProblem.scene, for all (instance, column) at once
+    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):
         if name is None:
             continue
         d = move[:, :, names.index(name)]
@@ -453,6 +460,65 @@ def moving_scenes(prob, B, T, sigma_v, seed=0, sigma=0.0):
             if r.kind == ROW_SEG_FIXEDSEG:
                 out[:, :, i, 3:6] += d
     return out
+
+
+def turning_scenes(prob, B, T, sigma_v, sigma_a, seed=0, sigma=0.0):
+    """[B, T, n_rows, SCENE_ROW]: :func:`moving_scenes` with obstacles that change course -- the velocity random-walks,
+    ``p_{j+1} = p_j + v_j dt``, ``v_{j+1} = v_j + a_j dt``, ``a_j ~ N(0, sigma_a^2)`` per obstacle and axis, one draw per (instance,
+    obstacle, column) shared by all the rows the obstacle appears in (plane rows take their axis).  Column 0 and ``v_0`` are the
+    draws of ``moving_scenes(prob, B, T, sigma_v, seed, sigma)``, so ``sigma_a = 0`` is that constant-velocity track (up to the
+    rounding of a running sum), and the tracks are reproducible per seed.  What a constant-velocity forecast gets wrong on these
+    tracks is the obstacle's turning."""
+    B, T = int(B), int(T)
+    if T < 1:
+        raise ValueError('turning_scenes: a track has at least one time column')
+    names = sorted({n for n in prob.row_obstacle if n is not None})
+    rng0, rngv, rnga = np.random.default_rng(seed), np.random.default_rng([int(seed), 1]), np.random.default_rng([int(seed), 2])
+    n, dt = len(names), float(prob.desc.dt)
+    d0 = np.stack([rng0.normal(0.0, float(sigma), (n, 3)) for _ in range(B)]).reshape(B, n, 3)
+    v0 = np.stack([rngv.normal(0.0, float(sigma_v), (n, 3)) for _ in range(B)]).reshape(B, n, 3)
+    a = np.stack([rnga.normal(0.0, float(sigma_a), (T - 1, n, 3)) for _ in range(B)]).reshape(B, T - 1, n, 3)
+    vel = v0[:, None] + dt * np.concatenate([np.zeros((B, 1, n, 3)), np.cumsum(a, axis=1)], axis=1)             # v_j, j = 0..T-1
+    move = d0[:, None] + dt * np.concatenate([np.zeros((B, 1, n, 3)), np.cumsum(vel[:, :-1], axis=1)], axis=1)  # p_j - p_0's base
+    return _moved_tracks(prob, names, move)
+
+
+FORECAST_MODES = {'hold': 0, 'cv': 1, 'true': 2}      # SMPC_FORECAST_* of include/smpc.h
+
+
+def scene_column(c, T):
+    """THE column rule of a scene track (include/smpc.h): the scene at time c is column clamp(c, 0, T - 1)"""
+    return min(max(int(c), 0), int(T) - 1)
+
+
+def forecast_statement(world, t, N, mode):
+    """[B, N + 1, n_rows, SCENE_ROW]: the horizon's scenes as a controller forecasts them at time ``t`` from what the world track
+    ``world [B, T, n_rows, SCENE_ROW]`` has shown up to then -- the numpy statement of smpc_forecast_scene and its readable definition
+    (DESIGN.md section 9n).  ``t``: the scene clock (None: 0; held to +-2^62 as the kernels hold it).  With ``col`` the column rule
+    with the world's T:
+
+    ``'hold'``  every node sees the world as it stands now, column col(t): the frozen world.
+    ``'cv'``    constant velocity: d = W[col(t)] - W[col(t - 1)], F[0] = W[col(t)], F[k] = F[k-1] + d -- repeated addition in this
+                order for all eight slots of a record, which the kernel repeats bit for bit; d = 0 where col(t) = col(t - 1).
+    ``'true'``  F[k] = W[col(t + k)]: the clairvoyant controller of run_mpc(scenes=track) without a forecast."""
+    W = np.asarray(world, float)
+    if W.ndim != 4 or W.shape[3] != SCENE_ROW:
+        raise ValueError(f'forecast_statement: expected a world track [B, T, n_rows, {SCENE_ROW}], got {W.shape}')
+    mode = FORECAST_MODES[mode] if isinstance(mode, str) else int(mode)
+    if mode not in FORECAST_MODES.values():
+        raise ValueError(f'forecast_statement: mode {mode}: expected one of {sorted(FORECAST_MODES)}')
+    T, N = W.shape[1], int(N)
+    t = 0 if t is None else min(max(int(t), -2 ** 62), 2 ** 62)
+    F = np.empty((W.shape[0], N + 1) + W.shape[2:])
+    if mode == FORECAST_MODES['true']:
+        for k in range(N + 1):
+            F[:, k] = W[:, scene_column(t + k, T)]
+        return F
+    F[:, 0] = W[:, scene_column(t, T)]
+    d = W[:, scene_column(t, T)] - W[:, scene_column(t - 1, T)] if mode == FORECAST_MODES['cv'] else None
+    for k in range(1, N + 1):
+        F[:, k] = F[:, k - 1] + d if d is not None else F[:, 0]
+    return F
 
 
 def extend_tracks(tracks, T):

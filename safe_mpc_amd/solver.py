@@ -9,11 +9,12 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import sys
 
 import numpy as np
 
 from . import _lib
-from .problem import JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem
+from .problem import FORECAST_MODES, JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem     # noqa: F401 (FORECAST_MODES: re-exported)
 
 
 # columns of BatchedOcpSolver.score_rollout's two results (SMPC_SCORE_ND doubles, SMPC_SCORE_NI int32 of include/smpc.h)
@@ -229,6 +230,40 @@ class BatchedOcpSolver:
                 raise ValueError('set_instance_scene_track: a track has at least one time column')
         self._set_instance(self.L.smpc_set_instance_scene_track, 'set_instance_scene_track', [geom],
                            (T, len(self.problem.rows), SCENE_ROW), T)
+
+    def set_instance_world_track(self, geom=None):
+        """The WORLD of every instance (smpc_set_instance_world_track): ``geom [B, T, n_rows, 8]``, a scene
+        track's layout, as a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy.  Only :meth:`forecast_scene`
+        and the plant's outcome test of :meth:`loop_post` read it -- the controller plans in the scene slot, which a forecast
+        fills.  None clears it, and with it a forecast in the scene slot and a context that the forecast wrote."""
+        T = 1
+        if geom is not None:
+            if geom.ndim != 4:
+                raise ValueError(f'set_instance_world_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+            T = int(geom.shape[1])
+            if T < 1:
+                raise ValueError('set_instance_world_track: a track has at least one time column')
+        self._set_instance(self.L.smpc_set_instance_world_track, 'set_instance_world_track', [geom],
+                           (T, len(self.problem.rows), SCENE_ROW), T)
+        self._world_B = 0 if geom is None else int(geom.shape[0])
+
+    def forecast_scene(self, mode, select=None, B=None):
+        """The horizon's N + 1 scenes as forecast from the world at the scene clock, into the scene slot (smpc_forecast_scene;
+        ``problem.forecast_statement`` is its definition): ``mode`` 'hold', 'cv' or 'true' (``FORECAST_MODES``).  Enqueue-only.
+        ``select``: the ``(row, slot)`` pairs of a safe-set net with a context (``SafeSetNet.ctx_select``) -- the context rows of
+        the N + 1 forecast scenes are then written as well; None or empty leaves the context slot alone.  While the slot holds a
+        forecast it is read from time 0: node k in column min(k, N).  ``B``: the batch size handed to the engine, the world's unless
+        given (the engine refuses any other)."""
+        if isinstance(mode, str):
+            if mode not in FORECAST_MODES:
+                raise ValueError(f'forecast_scene: mode {mode!r}: expected one of {sorted(FORECAST_MODES)}')
+            mode = FORECAST_MODES[mode]
+        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
+        B = int(getattr(self, '_world_B', 0) if B is None else B)
+        # (ordered like a device-path call wherever torch is in play: the clock cell is the caller's to write on torch's stream, and a
+        #  capture on torch's stream must see the launch)
+        with self._ordered('torch' in sys.modules):
+            self._chk(self.L.smpc_forecast_scene(self.h, B, int(mode), len(sel), sel.ctypes.data if len(sel) else None))
 
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""What a forecast costs and what it changes (smpc_forecast_scene, run_mpc(forecast=...); profiles/scene_forecast.txt).
+
+1. k_scene_forecast alone (+ nothing else on the stream): B = 4096 (SMPC_B), N = 30, the problem's six rows, a world of T = 131
+   columns read at clock 50, each mode: 3 warm-up and 10 timed calls between HIP events on the handle's stream.
+2. The closed loop: 'htwa', B = 4096, N = 30, SMPC_STEPS (default 60) steps on turning tracks (problem.turning_scenes, sigma_v = 0.3,
+   sigma_a = 3.0), the four arms none / true / hold / cv in alternation, SMPC_ROUNDS (default 2) rounds: ms per closed-loop step
+   (run_mpc's own timing) and the lengths of conv_idx, collisions_idx, viable_idx, unconv_idx per arm.
+A measurement tool, not a test; it reads nothing outside the repository.
+
+    python scripts/forecast_bench.py [kernel|loop]"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench                                                   # noqa: E402
+from safe_mpc_amd import closed_loop as cl                     # noqa: E402
+from safe_mpc_amd.problem import FORECAST_MODES, turning_scenes   # noqa: E402
+from safe_mpc_amd.solver import BatchedOcpSolver               # noqa: E402
+
+
+def kernel_times(B):
+    import torch
+    par, prob, net = bench.build_problem()
+    s = BatchedOcpSolver(prob, net)
+    N, T, clock = prob.N, 131, 50
+    device = torch.device('cuda', s.device)
+    world = torch.tensor(turning_scenes(prob, B, T, 0.3, 3.0, seed=0), dtype=torch.float64, device=device)
+    cell = torch.full((1,), clock, dtype=torch.int64, device=device)
+    s.set_instance_world_track(world)
+    s.set_scene_clock(cell)
+    stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
+    wrote = B * (N + 1) * len(prob.rows) * 64 / 1e6
+    with torch.cuda.stream(stream):
+        for mode in FORECAST_MODES:
+            for _ in range(3):
+                s.forecast_scene(mode)
+            ms = []
+            for _ in range(10):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(stream)
+                s.forecast_scene(mode)
+                b.record(stream)
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            ms = np.array(ms)
+            print(f'k_scene_forecast {mode:>4}: mean {1e3 * ms.mean():.1f} us, min {1e3 * ms.min():.1f}, max {1e3 * ms.max():.1f} (10 calls between '
+                  f'HIP events); writes {wrote:.1f} MB: {wrote / ms.mean() / 1e3:.2f} TB/s of stores at the mean; B = {B}, N = {N}, '
+                  f'{len(prob.rows)} rows, T = {T}, clock {clock}', flush=True)
+    s.set_instance_world_track(None)
+    s.set_scene_clock(None)
+    s.close()
+
+
+def loop_times(B):
+    from safe_mpc_amd import controller as C
+    par, prob, net = bench.build_problem()
+    par.N = prob.N
+    steps, rounds = int(os.environ.get('SMPC_STEPS', '60')), int(os.environ.get('SMPC_ROUNDS', '2'))
+    probe = BatchedOcpSolver(prob, net)
+    x0 = bench.initial_states(probe, prob, B, 0)
+    probe.close()
+    N = prob.N
+    xg, ug = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((B, N, prob.nu))
+    world = turning_scenes(C.OcpProblem(par, 'htwa', 'ext', N=N), B, steps + 1 + N, 0.3, 3.0, seed=0)
+    arms = [None, 'true', 'hold', 'cv']
+    res = {a: [] for a in arms}
+    for r in range(rounds + 1):                                 # (round 0 warms everything up)
+        for arm in arms:
+            tm = {}
+            out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, timing=tm,
+                             **({} if arm is None else {'forecast': arm}))
+            counts = tuple(len(out[k]) for k in ('conv_idx', 'collisions_idx', 'viable_idx', 'unconv_idx'))
+            if r:
+                res[arm].append((tm['ms_per_step'],) + counts)
+            print(f'round {r} forecast={arm}: {tm["ms_per_step"]:.3f} ms per step; conv / collisions / viable / unconv = {counts}', flush=True)
+    for arm in arms:
+        a = np.array(res[arm])
+        print(f'forecast={str(arm):>4}: {a[:, 0].mean():.3f} ms per closed-loop step (rounds {a[:, 0].min():.3f} .. {a[:, 0].max():.3f}); '
+              f'conv {int(a[0, 1])}, collisions {int(a[0, 2])}, viable {int(a[0, 3])}, unconv {int(a[0, 4])}; B = {B}, N = {N}, {steps} steps')
+
+
+def main(argv=None):
+    what = (sys.argv[1:] if argv is None else argv) or ['kernel', 'loop']
+    B = int(os.environ.get('SMPC_B', '4096'))
+    if 'kernel' in what:
+        kernel_times(B)
+    if 'loop' in what:
+        loop_times(B)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

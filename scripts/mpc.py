@@ -11,6 +11,11 @@ columns long: the tracks stored with the guesses (guess_acados.py --scene-veloci
 else every obstacle with its own N(0, SIGMA^2) velocity draw per axis (problem.moving_scenes; seed --scene-seed, start positions
 jittered by --scene-jitter if that is given too).  A safe-set network with a context (``ctx_select`` in its checkpoint) follows the
 track column by column.
+--scene-accel SIGMA (needs --scene-velocity): obstacles that change course -- the tracks are drawn by problem.turning_scenes, whose
+velocities random-walk with N(0, SIGMA^2) accelerations per obstacle and axis (stored tracks are not continued: they are drawn).
+--scene-forecast hold|cv|true (needs --scene-velocity): the track is the WORLD, which only the plant meets; the controller plans
+against a forecast of it formed every step from the columns the world has shown (run_mpc(forecast=...)) -- the
+frozen world, a constant-velocity extrapolation, or the world itself.  The result file's name gets the suffix ``_fc<mode>``.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -54,13 +59,22 @@ def main(argv=None):
             from safe_mpc_amd.problem import OcpProblem, jittered_scenes
             seed = int(raw[raw.index('--scene-seed') + 1]) if '--scene-seed' in raw else 0
             scenes = jittered_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], float(raw[raw.index('--scene-jitter') + 1]), seed)
+    opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
+    forecast = opt('--scene-forecast', None, str)
+    if forecast is not None and forecast not in ('hold', 'cv', 'true'):
+        raise SystemExit(f'--scene-forecast {forecast}: expected hold, cv or true')
+    for flag in ('--scene-forecast', '--scene-accel'):
+        if flag in raw and '--scene-velocity' not in raw:
+            raise SystemExit(f'{flag} needs --scene-velocity: there is no track to forecast or to turn')
     if '--scene-velocity' in raw:
-        from safe_mpc_amd.problem import OcpProblem, extend_tracks, moving_scenes
+        from safe_mpc_amd.problem import OcpProblem, extend_tracks, moving_scenes, turning_scenes
         T = int(params.n_steps) + 1 + int(params.N)
-        if 'scenes' in data and data['scenes'].ndim == 4:
+        if '--scene-accel' in raw:
+            scenes = turning_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], T, opt('--scene-velocity', 0.0, float),
+                                    opt('--scene-accel', 0.0, float), opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
+        elif 'scenes' in data and data['scenes'].ndim == 4:
             scenes = extend_tracks(data['scenes'][:params.test_num], T)
         else:
-            opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
             scenes = moving_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], T, opt('--scene-velocity', 0.0, float),
                                    opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
     cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
@@ -71,7 +85,7 @@ def main(argv=None):
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],
                      callback=True, on_device=os.environ.get('SMPC_HOST_STATE', '0') != '1', timing=tm,
                      collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes, traj=traj,
-                     models='plant' if cmodel == 'plant' else None)
+                     models='plant' if cmodel == 'plant' else None, **({} if forecast is None else {'forecast': forecast}))
     with_stats = os.environ.get('SMPC_NO_TIME_STATS', '0') != '1'
     print(f"{tm['ms_per_step']:.3f} ms per closed-loop step of {x_guess.shape[0]} instances"
           + (' (eager launches with per-solve HIP events for the time statistics below; SMPC_NO_TIME_STATS=1 replays the step halves as '
@@ -84,7 +98,8 @@ def main(argv=None):
     print(f"Completed task: {len(res['conv_idx'])}\nCollisions: {len(res['collisions_idx'])}"
           f"\nViable states: {len(res['viable_idx'])}\nNot converged: {n - len(res['conv_idx']) - len(res['collisions_idx'])}")
     cl.save_pickle(cl.result_file(params, model_name, cont_name, params.N, use_net, args['noise'], args['control_noise'],
-                                  args['joint_bounds_margin'], args['collision_margin'], controller_model=cmodel), res)
+                                  args['joint_bounds_margin'], args['collision_margin'], controller_model=cmodel,
+                                  **({} if forecast is None else {'forecast': forecast})), res)
     return len(res['collisions_idx'])
 
 
