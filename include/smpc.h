@@ -276,9 +276,11 @@ int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
  * waits for the copy, device pointers are taken as they are).  It is a slot of the handle under the one slot rule: it belongs to its
  * batch size, the same (B, T) is overwritten in place, growth while the stream is being captured is SMPC_ESTATE with the old contents
  * kept, and geom == NULL clears it.  Clearing the world also clears a scene slot that holds a forecast and a context the forecast
- * wrote: a forecast without its world is stale.
- * Who reads the world: smpc_forecast_scene (below), and smpc_loop_post, whose one node -- the plant's NEXT state -- is tested in
- * column col(t + 1) of the WORLD instead of the scene slot while a world is set (col with the world's T, t the scene clock).
+ * wrote, and the observed track (below): a forecast or an observation without its world is stale.
+ * Who reads the world: smpc_forecast_scene and smpc_forecast_scene_fit (below; in the modes HOLD and CV and in the fit only while
+ * no observed track is set, see smpc_set_instance_observed_track), and smpc_loop_post, whose one node -- the plant's NEXT state --
+ * is tested in column col(t + 1) of the WORLD instead of the scene slot while a world is set (col with the world's T, t the scene
+ * clock).
  * smpc_loop_post with another B: SMPC_EINVAL naming both sizes.  Nothing else reads it; in particular the x_temp test of
  * smpc_policy_step keeps reading the scene slot, which is what the controller believes.
  * SMPC_EINVAL: B <= 0, T < 1, a descriptor without rows, or (host pointers only) a non-finite value in a field that is read.
@@ -286,7 +288,8 @@ int smpc_set_scene_clock(smpc_handle* h, const int64_t* d_clock);
 int smpc_set_instance_world_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device);
 
 /* A FORECAST of the horizon's N + 1 scenes, formed on the device from what the world has shown up to the clock, into the scene
- * slot.  Enqueue-only on the handle's stream once its buffers exist.  With W the world, T its columns, t the scene clock's cell when
+ * slot.  Enqueue-only on the handle's stream once its buffers exist.  With W the world (in the modes HOLD and CV: the observed
+ * track of smpc_set_instance_observed_track while one is set -- what the controller has seen of the world), T its columns, t the scene clock's cell when
  * the kernel runs (0 without a clock, held to +-2^62), col THE column rule with W's T, c0 = col(t), c1 = col(t - 1) and N the
  * handle's horizon, for every instance b, row r and all eight slots s of the record:
  *   SMPC_FORECAST_HOLD  F[b][k][r][s] = W[b][c0][r][s], k = 0..N                      (the frozen world)
@@ -305,13 +308,43 @@ int smpc_set_instance_world_track(smpc_handle* h, int B, int64_t T, const double
  * read from time 0 like the forecast scene, replaced and re-clocked by smpc_set_instance_context / _track, dropped with the
  * forecast.  The pairs travel with the launch (no device copy is kept, so a captured call carries its own).  With n_sel == 0 the
  * context slot is left alone.
- * SMPC_EINVAL (the message names the call and, where sizes disagree, both): B differs from the world's; unknown mode; n_sel > 0 with
+ * SMPC_EINVAL (the message names the call and, where sizes disagree, both): B differs from the world's; unknown mode; an observed
+ * track whose (B, T) is not the world's; n_sel > 0 with
  * a network without context columns or with n_sel != n_ctx; a pair outside n_rows x SMPC_SCENE_ROW; n_sel > 0 with select == NULL.
  * SMPC_ESTATE: no world set, or the scene or context buffer would have to grow while the stream is being captured.
  * A refused call leaves the slot contents in force.
  * (ABI version unchanged: no existing entry point or structure changed) */
 enum { SMPC_FORECAST_HOLD = 0, SMPC_FORECAST_CV = 1, SMPC_FORECAST_TRUE = 2 };
 int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_t* select);
+
+/* What the controller OBSERVES of the world: geom is [B][T][n_rows][SMPC_SCENE_ROW], and layout, validation,
+ * the slot rule, host and device pointers and growth under capture (SMPC_ESTATE, the old contents kept) are exactly the world
+ * track's.  A slot of its own; geom == NULL clears it, and so does clearing the world (an observation without its world is stale).
+ * Who reads it, while it is set: smpc_forecast_scene in the modes HOLD and CV, INSTEAD of the world (same column rule, same clock),
+ * and smpc_forecast_scene_fit.  SMPC_FORECAST_TRUE and smpc_loop_post keep reading the world; nothing else reads the observed track.
+ * Call the table those forecasts read S, "what was seen": the observed track while one is set, else the world.
+ * A forecast call while an observed track is set needs its (B, T) to equal the world's: SMPC_EINVAL naming both otherwise.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_observed_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device);
+
+/* A forecast by a LINE FIT over the last `window` samples of S.  Every rule of smpc_forecast_scene holds (enqueue-only once its
+ * buffers exist; needs a world, of B instances; F replaces the scene slot as a track of N + 1 columns read from time 0; n_sel and
+ * select mean and are refused the same, and write the context rows; the slot then "holds a forecast" exactly as after
+ * smpc_forecast_scene; a refused call changes nothing), and SMPC_EINVAL also for window < 1 or window > SMPC_FIT_MAX, naming it.
+ * With t the scene clock's cell when the kernel runs (0 without a clock, held to +-2^62), col THE column rule with S's T,
+ * m = min(window, max(t, 0) + 1) -- nothing has been seen before time 0 -- and y_j = S[b][col(t - j)][r][s], j = 0..m-1, for every
+ * instance b, row r and all eight slots s:
+ *   u_j = (double)(4m - 2 - 6j)    / (double)(m (m + 1))
+ *   w_j = (double)(6(m - 1) - 12j) / (double)(m (m^2 - 1))                               (m = 1: w_0 = 0)
+ *   a = u_0 y_0;  a = a + u_j y_j   (j = 1..m-1, in this order, every product rounded before its sum)
+ *   d = w_0 y_0;  d = d + w_j y_j   (likewise)
+ *   F[b][0] = a,  F[b][k] = F[b][k-1] + d,  k = 1..N                                     (repeated addition, as SMPC_FORECAST_CV)
+ * a is the least-squares line's value now and d its slope per column.  window = 1 is SMPC_FORECAST_HOLD; window = 2 gives
+ * u = (1, 0), w = (1, -1), hence a = y_0, d = y_0 - y_1: SMPC_FORECAST_CV bit for bit at every clock.  Behind the track's last
+ * column the clamped samples make the slope decay to zero within `window` steps.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+#define SMPC_FIT_MAX 32
+int smpc_forecast_scene_fit(smpc_handle* h, int B, int window, int n_sel, const int32_t* select);
 
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle

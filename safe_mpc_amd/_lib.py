@@ -22,7 +22,8 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
            'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves',
            'smpc_set_instance_scene_track', 'smpc_set_scene_clock', 'smpc_set_mlp_context', 'smpc_set_instance_context',
-           'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene']
+           'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene',
+           'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit']
 
 
 class EngineError(RuntimeError):
@@ -140,6 +141,8 @@ def lib():
     L.smpc_set_scene_clock.argtypes = [vp, dp]
     L.smpc_set_instance_world_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_forecast_scene.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    L.smpc_set_instance_observed_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
+    L.smpc_forecast_scene_fit.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     L.smpc_set_instance_curves.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_solve_batch.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_eval_nodes.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int]

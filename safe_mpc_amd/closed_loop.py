@@ -29,16 +29,19 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
             f'_q_collision_margins_{params.q_margin}_{params.collision_margin}_guess.pkl')
 
 
-def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None):
+def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None,
+                forecast_window=None, obs_noise=0.0):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
     before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
-    it; the defaults give the reference's name"""
+    it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns; ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
+    that; the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
     track = 'traj_track' if params.track_traj else ''
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
-            f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}_mpc.pkl")
+            f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}"
+            f"{f'_w{int(forecast_window)}' if forecast == 'fit' else ''}{f'_on{obs_noise}' if obs_noise > 0 else ''}_mpc.pkl")
 
 
 def tracking_from_cli(params, argv, n=None):
@@ -1067,7 +1070,7 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None, models=None, forecast=None):
+                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -1078,9 +1081,13 @@ class _Group:
         # A forecast (run_mpc(forecast=...)): the track is the WORLD, which only the plant meets; the scene slot
         # of either handle holds what the controller forecasts at the head of every step (the subclasses say how), so the track
         # itself does not go onto the scene slot until the run is scored.
-        self._scenes, self._track, self._forecast = None, False, forecast
+        # 'fit' forecasts by a line through the last forecast_window columns; with ``observed`` (the world's shape: what a sensor
+        # shows of it) 'hold', 'cv' and 'fit' are formed from that table instead of the world.
+        self._scenes, self._track, self._forecast, self._window, self._observed = None, False, forecast, forecast_window, None
         if scenes is not None:
             self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
+            if observed is not None:
+                self._observed = xp.asarray(_check_scenes(observed, B, ctrl.problem), xp.f64)
             self._track = self._scenes.ndim == 4
             if forecast is None:
                 _set_scene(ctrl.ocp_solver, self._scenes)
@@ -1215,8 +1222,10 @@ class _Group:
             extra['scenes'] = xp.host(self._scenes)
             _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
             _clear_scene(self._backup.ocp_solver)
-            if self._forecast is not None:         # (nor a world)
+            if self._forecast is not None:         # (nor a world, nor what was observed of it)
                 for sv in (solver, self._backup.ocp_solver):
+                    if self._observed is not None and hasattr(sv, 'set_instance_observed_track'):
+                        sv.set_instance_observed_track(None)
                     if hasattr(sv, 'set_instance_world_track'):
                         sv.set_instance_world_track(None)
         if self._models is not None:               # (nor a model table)
@@ -1285,7 +1294,7 @@ class _HostGroup(_Group):
         if self._forecast is None:
             _write_scene_clock(self._clock, self._jt)       # node k of this step's solve and tests: time j + k
         else:                                               # ... in the scenes forecast at time j, read from node 0 on
-            self._forecast_onto(ctrl.ocp_solver, self._scenes, self._jt, ctrl.N)
+            self._forecast_onto(ctrl.ocp_solver, slice(None), self._jt, ctrl.N)
         # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
         #  read again, so they may step along)
         if self._ever_aborted:
@@ -1302,15 +1311,18 @@ class _HostGroup(_Group):
             self.sa = self.sa | again
             self.new_abort = self.new_abort & ~again
 
-    def _forecast_onto(self, sv, world, t, N):
-        """the statement of smpc_forecast_scene: the N + 1 scenes forecast from ``world`` at time t onto ``sv``'s scene slot (and
-        their context rows, _set_scene), with no clock -- node k reads column k"""
-        from .problem import forecast_statement
+    def _forecast_onto(self, sv, rows, t, N):
+        """the statement of smpc_forecast_scene / smpc_forecast_scene_fit: the N + 1 scenes forecast at time t for the instances
+        ``rows`` onto ``sv``'s scene slot (and their context rows, _set_scene), with no clock -- node k reads column k.  'hold', 'cv'
+        and 'fit' are formed from what was seen, the observed track where the run has one; 'true' from the world"""
+        from .problem import fit_forecast_statement, forecast_statement
+        seen = self._scenes if self._observed is None or self._forecast == 'true' else self._observed
         sv.set_scene_clock(None)
-        _set_scene(sv, forecast_statement(world, t, N, self._forecast))
+        _set_scene(sv, fit_forecast_statement(seen[rows], t, N, self._window) if self._forecast == 'fit'
+                   else forecast_statement(seen[rows], t, N, self._forecast))
 
     def _backup_forecast(self, rows):
-        self._forecast_onto(self._backup.ocp_solver, self._scenes[rows], self._jt, self._Nb)
+        self._forecast_onto(self._backup.ocp_solver, rows, self._jt, self._Nb)
 
     # ---- the step's decision: abort events (mpc.py:161-190) ----------------------------------------------------------------------
     def handle_aborts(self):
@@ -1412,8 +1424,14 @@ class _DeviceGroup(_Group):
             for sv in (ctrl.ocp_solver, self._backup.ocp_solver):
                 if not hasattr(sv, 'forecast_scene'):
                     raise ValueError(f'forecast: {type(sv).__name__} has no forecast_scene')
+                if self._forecast == 'fit' and not hasattr(sv, 'forecast_scene_fit'):
+                    raise ValueError(f"forecast: {type(sv).__name__} has no forecast_scene_fit")
+                if self._observed is not None and not hasattr(sv, 'set_instance_observed_track'):
+                    raise ValueError(f'observed: {type(sv).__name__} has no set_instance_observed_track')
             self._select, self._backup_select = _context_select(ctrl.ocp_solver), _context_select(self._backup.ocp_solver)
             ctrl.ocp_solver.set_instance_world_track(self._scenes)
+            if self._observed is not None:          # (what HOLD, CV and the fit then read instead of the world)
+                ctrl.ocp_solver.set_instance_observed_track(self._observed)
         self._use_graphs = bool(use_graphs)
         self._graphs = {}                         # half -> captured graph
         self._u_other = xp.zeros((B, nu))
@@ -1434,7 +1452,7 @@ class _DeviceGroup(_Group):
     def part_a(self):
         ctrl, sv = self._ctrl, self._ctrl.ocp_solver
         if self._forecast is not None:
-            sv.forecast_scene(self._forecast, self._select)
+            self._enqueue_forecast(sv, self._select)
         sv.loop_pre(self, getattr(ctrl, 'r', None), self._pending, self._u_other, self._stepping)
         ctrl.step_on_device(self.x_cur, self._stepping, self._u_other, u_out=self.u)
         if ctrl.can_abort:
@@ -1491,7 +1509,16 @@ class _DeviceGroup(_Group):
         holds the counter's value at the event: handle_aborts)"""
         sv = self._backup.ocp_solver
         sv.set_instance_world_track(self._scenes[rows])
-        sv.forecast_scene(self._forecast, self._backup_select)
+        if self._observed is not None:
+            sv.set_instance_observed_track(self._observed[rows])
+        self._enqueue_forecast(sv, self._backup_select)
+
+    def _enqueue_forecast(self, sv, select):
+        """one forecast of the run's kind from ``sv``'s world (and observed track) at its clock cell, into its scene slot"""
+        if self._forecast == 'fit':
+            sv.forecast_scene_fit(self._window, select)
+        else:
+            sv.forecast_scene(self._forecast, select)
 
     def part_b(self):
         self._ctrl.ocp_solver.loop_post(self, self.u, self._joints_noisy, self._tau_noise)
@@ -1582,7 +1609,7 @@ def _check_state_kind(ctrl, backup, on_device):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False, scenes=None, traj=None, models=None, forecast=None):
+            score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1625,6 +1652,15 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     backup OCP of an abort event gets the aborting instances' world rows and one forecast over its own horizon at the event's
     clock.  The run is scored in the true world, both handles end without world, forecast, context and clock, and the result
     gains ``'forecast'``.  None: the calls of a run without the argument, one for one.
+    ``forecast='fit'`` with ``forecast_window`` (1..``problem.FIT_MAX``, default 8): the forecast is a
+    least-squares line through the last ``forecast_window`` columns seen (``problem.fit_forecast_statement``; window 1 is 'hold',
+    window 2 'cv') -- on the device one smpc_forecast_scene_fit per step where 'hold' and 'cv' enqueue smpc_forecast_scene.
+    ``observed`` ([B, T, n_rows, 8], the world's shape; ``problem.observe_tracks`` draws one): what the controller observes of the
+    world.  'hold', 'cv' and 'fit' are then formed from it instead of the world (smpc_set_instance_observed_track on the device,
+    the statement on it on the host), the plant still meets the world, and the backup handle of an abort event gets the aborting
+    instances' observed rows with their world rows.  ValueError with ``forecast`` None or 'true', which do not read it.  The
+    result gains ``'forecast_window'`` (with 'fit') and ``'observed'`` (bool, with any forecast); both handles end without an
+    observed track.  Without ``observed``, None, 'hold', 'cv' and 'true' make the calls of before, one for one.
     ``traj`` ([3, L], tracking.tracking_trajectory): every group's controller follows this curve (``setTrajectory``), the tracking
     task of the reference's Tracking8* / TrackingMovingCircle* costs.  ``traj`` [B, 3, L] (tracking.tracking_curves /
     jittered_curves): a curve of its own for every instance -- every group's controller gets its slice (on the device its handle
@@ -1647,12 +1683,20 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
             raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
     if forecast is not None:
-        from .problem import FORECAST_MODES
-        if forecast not in FORECAST_MODES:
-            raise ValueError(f'forecast: {forecast!r}: expected None or one of {sorted(FORECAST_MODES)}')
+        from .problem import FIT_MAX, FORECAST_MODES
+        if forecast != 'fit' and forecast not in FORECAST_MODES:
+            raise ValueError(f"forecast: {forecast!r}: expected None, 'fit' or one of {sorted(FORECAST_MODES)}")
+        if forecast == 'fit' and not (isinstance(forecast_window, (int, np.integer)) and 1 <= forecast_window <= FIT_MAX):
+            raise ValueError(f'forecast_window: {forecast_window!r}: a fit takes 1 to {FIT_MAX} columns')
         if scenes is None or scenes.ndim != 4:
             raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
                              + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
+    if observed is not None:
+        if forecast is None or forecast == 'true':
+            raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
+        observed = np.ascontiguousarray(observed, np.float64)
+        if observed.shape != scenes.shape:
+            raise ValueError(f'observed: expected the world\'s shape {scenes.shape}, got {observed.shape}')
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1681,16 +1725,18 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         if traj is not None:
             ctrl.setTrajectory(traj[lo:hi] if curves else traj)
         args = (params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, collect_times)
+        fit_kw = dict(forecast_window=int(forecast_window) if forecast == 'fit' else None,
+                      observed=None if observed is None else observed[lo:hi])
         if on_device:
             import torch
             sv = ctrl.ocp_solver
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
-                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs, forecast=forecast,
+                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs, forecast=forecast, **fit_kw,
                                    models=models if models is None or isinstance(models, str) else models[lo:hi])
         else:
             streams.append(None)
-            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi], forecast=forecast,
+            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi], forecast=forecast, **fit_kw,
                              models=models if models is None or isinstance(models, str) else models[lo:hi])
         grps.append(grp)
         gens.append(grp.run())
@@ -1773,6 +1819,9 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra['scenes'] = np.concatenate([o['scenes'] for o in outs], axis=0)
     if forecast is not None:
         extra['forecast'] = forecast
+        extra['observed'] = observed is not None
+        if forecast == 'fit':
+            extra['forecast_window'] = int(forecast_window)
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

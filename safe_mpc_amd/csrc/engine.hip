@@ -118,6 +118,10 @@ struct smpc_handle {
     InstSlot<double> world{"instance world track", "smpc_set_instance_world_track"};    // [B][T][n_rows][SMPC_SCENE_ROW] the track the
                                     // plant meets: read by smpc_forecast_scene and smpc_loop_post alone
     int64_t world_T = 1;
+    InstSlot<double> seen{"instance observed track", "smpc_set_instance_observed_track"};   // the world's layout: what the controller
+                                    // observes of it.  While set, smpc_forecast_scene (HOLD, CV) and
+                                    // smpc_forecast_scene_fit read it instead of the world; nothing else reads it
+    int64_t seen_T = 1;
     InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
     InstSlot<float> ctx{"instance context", "smpc_set_instance_context"};   // [B][T][n_ctx] normalised context of the network along
@@ -1790,37 +1794,52 @@ int smpc_set_instance_world_track(smpc_handle* h, int B, int64_t T, const double
     (void)hipSetDevice(h->device);
     if (!geom) {
         h->world.clear();
-        drop_forecast(h);       // (a forecast without its world is stale)
+        h->seen.clear();        // (an observation without its world is stale ...
+        drop_forecast(h);       //  ... and so is a forecast)
         return SMPC_OK;
     }
     return set_scene_table(h, h->world, h->world_T, "smpc_set_instance_world_track", B, T, geom, on_device);
 }
 
-int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_t* select) {
+int smpc_set_instance_observed_track(smpc_handle* h, int B, int64_t T, const double* geom, int on_device) {
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
-    if (!h->world.B) return fail(h, SMPC_ESTATE, "smpc_forecast_scene: no world is set (smpc_set_instance_world_track)");
+    if (!geom) { h->seen.clear(); return SMPC_OK; }
+    return set_scene_table(h, h->seen, h->seen_T, "smpc_set_instance_observed_track", B, T, geom, on_device);
+}
+
+// The one body of smpc_forecast_scene (fit = false: `what` is its mode) and smpc_forecast_scene_fit (fit = true: `what` is its
+// window); `who` names the entry point in every message.  S, "what was seen", is the observed track while one is set and the world
+// otherwise; SMPC_FORECAST_TRUE reads the world whatever was observed.
+static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit, int what, int n_sel, const int32_t* select) {
+    const int mode = what, window = what;
+    if (!h->world.B) return fail(h, SMPC_ESTATE, "%s: no world is set (smpc_set_instance_world_track)", who);
     if (B != h->world.B)
-        return fail(h, SMPC_EINVAL, "smpc_forecast_scene: batch size %d, but the instance world track was set for %d instances "
-                    "(smpc_set_instance_world_track: clear it or set one of this size)", B, h->world.B);
-    if (mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
-        return fail(h, SMPC_EINVAL, "smpc_forecast_scene: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", mode);
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance world track was set for %d instances "
+                    "(smpc_set_instance_world_track: clear it or set one of this size)", who, B, h->world.B);
+    if (!fit && mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
+        return fail(h, SMPC_EINVAL, "%s: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", who, mode);
+    if (fit && (window < 1 || window > SMPC_FIT_MAX))
+        return fail(h, SMPC_EINVAL, "%s: window %d: a fit takes 1 to SMPC_FIT_MAX = %d samples", who, window, SMPC_FIT_MAX);
+    if (h->seen.B && (h->seen.B != h->world.B || h->seen_T != h->world_T))
+        return fail(h, SMPC_EINVAL, "%s: the instance observed track was set for %d instances and %lld columns, but the instance world "
+                    "track for %d instances and %lld columns (smpc_set_instance_observed_track: clear it or set one of the world's "
+                    "shape)", who, h->seen.B, (long long)h->seen_T, h->world.B, (long long)h->world_T);
     const Net& net = *h->net;
     const int nr = h->desc.n_rows, N = h->N, nc = net.n_ctx;
-    if (n_sel < 0) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d", n_sel);
+    if (n_sel < 0) return fail(h, SMPC_EINVAL, "%s: n_sel=%d", who, n_sel);
     ForecastSel sel{};
     CtxNorm nm{};
     if (n_sel > 0) {
-        if (!select) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d with select == NULL", n_sel);
+        if (!select) return fail(h, SMPC_EINVAL, "%s: n_sel=%d with select == NULL", who, n_sel);
         if (nc == 0)
-            return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d, but the network has no context columns (smpc_set_mlp_context was "
-                        "not called)", n_sel);
-        if (n_sel != nc) return fail(h, SMPC_EINVAL, "smpc_forecast_scene: n_sel=%d, but the network has n_ctx=%d context columns", n_sel, nc);
+            return fail(h, SMPC_EINVAL, "%s: n_sel=%d, but the network has no context columns (smpc_set_mlp_context was not called)", who,
+                        n_sel);
+        if (n_sel != nc) return fail(h, SMPC_EINVAL, "%s: n_sel=%d, but the network has n_ctx=%d context columns", who, n_sel, nc);
         for (int i = 0; i < n_sel; i++) {
             const int r = select[2 * i], s = select[2 * i + 1];
             if (r < 0 || r >= nr || s < 0 || s >= SMPC_SCENE_ROW)
-                return fail(h, SMPC_EINVAL, "smpc_forecast_scene: select[%d] = (row %d, slot %d) outside %d rows x %d slots", i, r, s, nr,
-                            SMPC_SCENE_ROW);
+                return fail(h, SMPC_EINVAL, "%s: select[%d] = (row %d, slot %d) outside %d rows x %d slots", who, i, r, s, nr, SMPC_SCENE_ROW);
             sel.row[i] = r;
             sel.slot[i] = s;
         }
@@ -1831,24 +1850,30 @@ int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_
     const size_t n = (size_t)B * (N + 1) * nr * SMPC_SCENE_ROW, n_ctx_el = (size_t)B * (N + 1) * n_sel;
     const bool scene_grows = n * sizeof(double) > h->scene.d.cap, ctx_grows = n_ctx_el * sizeof(float) > h->ctx.d.cap;
     if ((scene_grows || ctx_grows) && capturing(h))
-        return fail(h, SMPC_ESTATE, "smpc_forecast_scene: the %s must grow to %zu bytes while the stream is being captured: run one eager "
-                    "call of this size first", scene_grows ? h->scene.noun : h->ctx.noun,
-                    scene_grows ? n * sizeof(double) : n_ctx_el * sizeof(float));
+        return fail(h, SMPC_ESTATE, "%s: the %s must grow to %zu bytes while the stream is being captured: run one eager call of this size "
+                    "first", who, scene_grows ? h->scene.noun : h->ctx.noun, scene_grows ? n * sizeof(double) : n_ctx_el * sizeof(float));
     int rc;
     if (scene_grows) h->scene.clear();
     if ((rc = h->scene.room(h, n))) return rc;
     if (ctx_grows) h->ctx.clear();
     if (n_sel > 0 && (rc = h->ctx.room(h, n_ctx_el))) return rc;
     const SceneSrc world{h->world.d.p, h->world_T > 1 ? h->scene_clock : nullptr, h->world_T, 0};
+    SceneSrc seen = world;      // (its (B, T) are the world's: checked above)
+    if (h->seen.B) seen.geom = h->seen.d.p;
+    if (fit) seen.clock = h->scene_clock;       // (the fit's window grows with the clock even where T = 1 leaves one column to read)
     const int n_rec = B * nr;
     // (one-wavefront blocks, as for every small kernel of the policy step: see check_nodes_dev)
     const dim3 grd((unsigned)((n_rec + 63) / 64)), blk(64);
-    if (mode == SMPC_FORECAST_HOLD)
-        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_HOLD>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
-    else if (mode == SMPC_FORECAST_CV)
-        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_CV>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
-    else
+    // (the fit last: a kernel's place in the code object follows its first mention, and the three older ones keep theirs)
+    if (!fit && mode == SMPC_FORECAST_HOLD)
+        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_HOLD>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
+    else if (!fit && mode == SMPC_FORECAST_CV)
+        hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_CV>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
+    else if (!fit)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_TRUE>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
+    else            // four lanes to a record: see k_scene_fit
+        hipLaunchKernelGGL(k_scene_fit, dim3((unsigned)((4 * (size_t)n_rec + 63) / 64)), blk, 0, h->stream, 4 * n_rec, nr, N, window, seen,
+                           h->scene.d.p);
     HIPCHK(h, hipGetLastError());
     h->scene.commit(B);
     h->scene_T = N + 1;
@@ -1862,6 +1887,18 @@ int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_
         h->ctx_fc = true;
     }
     return SMPC_OK;
+}
+
+int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_t* select) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    return forecast_into_scene(h, "smpc_forecast_scene", B, false, mode, n_sel, select);
+}
+
+int smpc_forecast_scene_fit(smpc_handle* h, int B, int window, int n_sel, const int32_t* select) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    return forecast_into_scene(h, "smpc_forecast_scene_fit", B, true, window, n_sel, select);
 }
 
 // a scene that stands still: the track of one column

@@ -64,6 +64,91 @@ __global__ __launch_bounds__(64) void k_scene_forecast(int n_rec, int n_rows, in
     }
 }
 
+// The weights of a least-squares line through m equally spaced samples, ages j = 0..m-1 (j = 0 the newest), for m = 1..SMPC_FIT_MAX:
+//   u_j = (4m - 2 - 6j) / (m (m + 1))           the line's value now    is sum u_j y_j
+//   w_j = (6(m - 1) - 12j) / (m (m^2 - 1))      its step per column     is sum w_j y_j        (m = 1: w_0 = 0)
+// Numerators and denominators are small integers, so every weight is ONE correctly rounded division -- done by the compiler, which
+// divides as IEEE 754 says, so the table holds the bits of problem.fit_weights.  Row m starts at m (m - 1) / 2.  In the code
+// object's constant data: no upload, and a captured launch carries nothing but its arguments.
+struct FitWeights {
+    double u[SMPC_FIT_MAX * (SMPC_FIT_MAX + 1) / 2], w[SMPC_FIT_MAX * (SMPC_FIT_MAX + 1) / 2];
+    constexpr FitWeights() : u{}, w{} {
+        for (int m = 1; m <= SMPC_FIT_MAX; m++)
+            for (int j = 0; j < m; j++) {
+                u[m * (m - 1) / 2 + j] = (double)(4 * m - 2 - 6 * j) / (double)(m * (m + 1));
+                w[m * (m - 1) / 2 + j] = m == 1 ? 0.0 : (double)(6 * (m - 1) - 12 * j) / (double)(m * (m * m - 1));
+            }
+    }
+};
+__constant__ constexpr FitWeights FIT_WEIGHTS{};
+
+// a product rounded BEFORE it is summed: the build contracts a * b + c into one fma (-ffp-contract=fast), and `#pragma clang fp
+// contract(off)` did not stop it on gfx950; an empty register barrier on the product does (v_mul_f64, then v_add_f64)
+__device__ __forceinline__ double rounded_product(double a, double b) {
+    double p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
+// k_scene_fit: F [B][N+1][n_rows][SMPC_SCENE_ROW] from S = seen.geom [B][T][n_rows][SMPC_SCENE_ROW], what the controller has seen of
+// the world (the observed track, or the world itself).  With t the scene clock's cell (scene_time), col = scene_col with S's T,
+// m = min(window, max(t, 0) + 1) -- nothing was seen before time 0 -- and y_j = S[b][col(t - j)][r][s], for all eight slots
+//   a = u_0 y_0;  a = a + u_j y_j  (j = 1..m-1);   d = w_0 y_0;  d = d + w_j y_j       -- every product rounded before its sum
+//   F[b][0] = a,  F[b][k] = F[b][k-1] + d                                              -- repeated addition, as SMPC_FORECAST_CV
+// which is problem.fit_forecast_statement operation for operation, so the kernel equals it bit for bit; window 1 is HOLD and
+// window 2 (u = (1, 0), w = (1, -1)) is SMPC_FORECAST_CV.
+// A thread owns ONE 16-byte piece of a record, so four neighbouring lanes load and store a whole 64-byte record and a wavefront's
+// access covers 16 whole records (k_scene_forecast's thread owns a record: four accesses of 16 bytes at a stride of 64).  The live
+// set is the two accumulators of the piece and FIT_AHEAD samples in flight, not the window.  m comes from one clock cell, so it is
+// wave-uniform: the age loop has a scalar bound and the weights are uniform reads of the constant table.  The age loads are
+// independent; FIT_AHEAD of them are issued before the first is used (ages past m - 1 are loaded where age m - 1 lies and not
+// used).  Nothing is shared between threads: an instance's result depends neither on B nor on its neighbours.  No atomics, no LDS.
+constexpr int FIT_AHEAD = 4;
+__global__ __launch_bounds__(64) void k_scene_fit(int n_piece, int n_rows, int N, int window, SceneSrc seen, double* __restrict__ F) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_piece) return;
+    const int rec_i = i / (SMPC_SCENE_ROW / 2), q = i % (SMPC_SCENE_ROW / 2);
+    const int b = rec_i / n_rows, r = rec_i % n_rows;
+    const int64_t t = scene_time(seen);
+    const int64_t shown = (t < 0 ? 0 : t) + 1;
+    const int m = shown < window ? (int)shown : window;
+    const double* __restrict__ u = FIT_WEIGHTS.u + m * (m - 1) / 2;
+    const double* __restrict__ w = FIT_WEIGHTS.w + m * (m - 1) / 2;
+    const size_t piece = (size_t)r * SMPC_SCENE_ROW + 2 * q;
+    const auto sample = [&](int j) {
+        const int age = j < m ? j : m - 1;
+        return *static_cast<const ScenePiece*>(__builtin_assume_aligned(scene_block(seen, b, t - age, n_rows) + piece, 16));
+    };
+    ScenePiece a{0.0, 0.0}, d{0.0, 0.0};
+    for (int j0 = 0; j0 < m; j0 += FIT_AHEAD) {
+        ScenePiece y[FIT_AHEAD];
+#pragma unroll
+        for (int e = 0; e < FIT_AHEAD; e++) y[e] = sample(j0 + e);
+#pragma unroll
+        for (int e = 0; e < FIT_AHEAD; e++) {
+            const int j = j0 + e;
+            if (j >= m) break;
+            const ScenePiece pa{rounded_product(u[j], y[e].a), rounded_product(u[j], y[e].b)};
+            const ScenePiece pd{rounded_product(w[j], y[e].a), rounded_product(w[j], y[e].b)};
+            if (j == 0) {       // (a = u_0 y_0, not 0 + u_0 y_0: a -0.0 stays one)
+                a = pa;
+                d = pd;
+            } else {
+                a.a = a.a + pa.a; a.b = a.b + pa.b;
+                d.a = d.a + pd.a; d.b = d.b + pd.b;
+            }
+        }
+    }
+    ScenePiece* out = static_cast<ScenePiece*>(__builtin_assume_aligned(F + (size_t)b * (size_t)(N + 1) * n_rows * SMPC_SCENE_ROW + piece, 16));
+    const size_t step = (size_t)n_rows * (SMPC_SCENE_ROW / 2);      // in pieces
+    *out = a;
+    for (int k = 1; k <= N; k++) {
+        a.a = a.a + d.a;
+        a.b = a.b + d.b;
+        out[k * step] = a;
+    }
+}
+
 // k_forecast_context: the context rows of a scene-aware safe-set network from the same F, one thread per number:
 //   ctx[b][k][i] = (float)((F[b][k][row_i][slot_i] - mean[i]) / std[i])       -- the expression of k_ctx_normalise
 // sel: which (row, slot) of the scene context number i is, by value like nm (at most MLP_KPAD pairs: no device block to keep, and a

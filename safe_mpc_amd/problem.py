@@ -521,6 +521,88 @@ def forecast_statement(world, t, N, mode):
     return F
 
 
+FIT_MAX = 32                                           # SMPC_FIT_MAX of include/smpc.h: the longest window of a line fit
+
+
+def fit_weights(m):
+    """(u, w), two float64 arrays of length m: the weights of a least-squares line through m equally spaced samples y_j of ages
+    j = 0..m-1 (j = 0 the newest).  ``sum u_j y_j`` is the line's value now and ``sum w_j y_j`` its step per column:
+    ``u_j = (4m - 2 - 6j) / (m (m + 1))``, ``w_j = (6(m - 1) - 12j) / (m (m^2 - 1))`` (m = 1: w_0 = 0).  Numerators and denominators
+    are small integers, so each weight is one correctly rounded division -- the bits of the engine's table (FIT_WEIGHTS,
+    kernels_forecast.hpp)."""
+    m = int(m)
+    if not 1 <= m <= FIT_MAX:
+        raise ValueError(f'fit_weights: m={m}: expected 1..{FIT_MAX}')
+    j = np.arange(m)
+    u = (4 * m - 2 - 6 * j).astype(float) / float(m * (m + 1))
+    w = np.zeros(1) if m == 1 else (6 * (m - 1) - 12 * j).astype(float) / float(m * (m * m - 1))
+    return u, w
+
+
+def fit_forecast_statement(seen, t, N, window):
+    """[B, N + 1, n_rows, SCENE_ROW]: the horizon's scenes forecast at time ``t`` by a least-squares line through the last ``window``
+    columns of ``seen [B, T, n_rows, SCENE_ROW]``, what the controller has seen of the world (the observed track, or the world) --
+    the numpy statement of smpc_forecast_scene_fit and its readable definition.  ``t``: the scene clock
+    (None: 0; held to +-2^62).  With ``col`` the column rule with T, ``m = min(window, max(t, 0) + 1)`` (nothing was seen before
+    time 0), ``y_j = S[col(t - j)]`` and ``(u, w) = fit_weights(m)``, for all eight slots of a record:
+
+    ``a = u_0 y_0; a = a + u_j y_j`` (j = 1..m-1, in this order, every product rounded before its sum), ``d`` likewise with ``w``;
+    ``F[0] = a, F[k] = F[k-1] + d`` -- repeated addition, as 'cv'.  The kernel repeats it bit for bit.  ``window = 1`` is 'hold',
+    ``window = 2`` is 'cv' (u = (1, 0), w = (1, -1))."""
+    S = np.asarray(seen, float)
+    if S.ndim != 4 or S.shape[3] != SCENE_ROW:
+        raise ValueError(f'fit_forecast_statement: expected a world track [B, T, n_rows, {SCENE_ROW}], got {S.shape}')
+    window = int(window)
+    if not 1 <= window <= FIT_MAX:
+        raise ValueError(f'fit_forecast_statement: window {window}: expected 1..{FIT_MAX}')
+    T, N = S.shape[1], int(N)
+    t = 0 if t is None else min(max(int(t), -2 ** 62), 2 ** 62)
+    m = min(window, max(t, 0) + 1)
+    u, w = fit_weights(m)
+    y = S[:, scene_column(t, T)]
+    a, d = u[0] * y, w[0] * y
+    for j in range(1, m):
+        y = S[:, scene_column(t - j, T)]
+        a = a + u[j] * y
+        d = d + w[j] * y
+    F = np.empty((S.shape[0], N + 1) + S.shape[2:])
+    F[:, 0] = a
+    for k in range(1, N + 1):
+        F[:, k] = F[:, k - 1] + d
+    return F
+
+
+def observe_tracks(prob, world, sigma, seed=0):
+    """[B, T, n_rows, SCENE_ROW]: ``world`` as a sensor with independent noise shows it -- every obstacle's position in every
+    (instance, column) off by its own N(0, sigma^2) draw per axis, one draw per (instance, obstacle, column) shared by all the rows
+    the obstacle appears in (plane rows take their axis in slot 6, capsule rows move both end points, as ``_moved_tracks`` does).
+    The draws come instance by instance, so instance b's do not depend on B; reproducible per seed; ``sigma = 0`` returns the
+    world's bits.  What run_mpc(observed=...) and smpc_set_instance_observed_track take."""
+    W = np.asarray(world, float)
+    if W.ndim != 4 or W.shape[2:] != (len(prob.rows), SCENE_ROW):
+        raise ValueError(f'observe_tracks: expected a world track [B, T, {len(prob.rows)}, {SCENE_ROW}], got {W.shape}')
+    if float(sigma) < 0:
+        raise ValueError(f'observe_tracks: sigma={sigma}: a standard deviation is not negative')
+    out = W.copy()
+    if float(sigma) == 0.0:
+        return out
+    B, T = W.shape[:2]
+    names = sorted({n for n in prob.row_obstacle if n is not None})
+    rng = np.random.default_rng([int(seed), 3])
+    e = np.stack([rng.normal(0.0, float(sigma), (T, len(names), 3)) for _ in range(B)]).reshape(B, T, len(names), 3)
+    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):
+        if name is None:
+            continue
+        d = e[:, :, names.index(name)]
+        if r.kind == ROW_COORD:
+            out[:, :, i, 6] += d[:, :, r.axis]
+        else:
+            out[:, :, i, 0:3] += d
+            if r.kind == ROW_SEG_FIXEDSEG:
+                out[:, :, i, 3:6] += d
+    return out
+
+
 def extend_tracks(tracks, T):
     """Scene tracks [B, T0, n_rows, SCENE_ROW] continued to T columns at constant velocity -- the step between their last two
     columns (none for T0 = 1) -- or cut to T columns: what turns the tracks stored with warm starts (one horizon long) into the

@@ -253,7 +253,8 @@ class BatchedOcpSolver:
         ``select``: the ``(row, slot)`` pairs of a safe-set net with a context (``SafeSetNet.ctx_select``) -- the context rows of
         the N + 1 forecast scenes are then written as well; None or empty leaves the context slot alone.  While the slot holds a
         forecast it is read from time 0: node k in column min(k, N).  ``B``: the batch size handed to the engine, the world's unless
-        given (the engine refuses any other)."""
+        given (the engine refuses any other).  While an observed track is set (:meth:`set_instance_observed_track`) 'hold' and 'cv'
+        are formed from it instead of the world; 'true' always reads the world."""
         if isinstance(mode, str):
             if mode not in FORECAST_MODES:
                 raise ValueError(f'forecast_scene: mode {mode!r}: expected one of {sorted(FORECAST_MODES)}')
@@ -264,6 +265,32 @@ class BatchedOcpSolver:
         #  capture on torch's stream must see the launch)
         with self._ordered('torch' in sys.modules):
             self._chk(self.L.smpc_forecast_scene(self.h, B, int(mode), len(sel), sel.ctypes.data if len(sel) else None))
+
+    def set_instance_observed_track(self, geom=None):
+        """What the controller OBSERVES of the world (smpc_set_instance_observed_track): ``geom [B, T, n_rows,
+        8]``, the world's shape, as a numpy array or a contiguous ROCm float64 tensor (``problem.observe_tracks`` draws one); the
+        engine keeps a copy.  While it is set, :meth:`forecast_scene` ('hold', 'cv') and :meth:`forecast_scene_fit` read it instead
+        of the world; 'true' and the plant's outcome test of :meth:`loop_post` keep reading the world.  None clears it, and so does
+        clearing the world."""
+        T = 1
+        if geom is not None:
+            if geom.ndim != 4:
+                raise ValueError(f'set_instance_observed_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+            T = int(geom.shape[1])
+            if T < 1:
+                raise ValueError('set_instance_observed_track: a track has at least one time column')
+        self._set_instance(self.L.smpc_set_instance_observed_track, 'set_instance_observed_track', [geom],
+                           (T, len(self.problem.rows), SCENE_ROW), T)
+
+    def forecast_scene_fit(self, window, select=None, B=None):
+        """The horizon's N + 1 scenes forecast by a least-squares line through the last ``window`` (1..``problem.FIT_MAX``) columns of
+        what was seen -- the observed track, or the world without one -- at the scene clock, into the scene slot
+        (smpc_forecast_scene_fit; ``problem.fit_forecast_statement`` is its definition).  Enqueue-only; ``select`` and ``B`` as for
+        :meth:`forecast_scene`, and the slot is read from time 0 in the same way.  Window 1 is 'hold', window 2 is 'cv'."""
+        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
+        B = int(getattr(self, '_world_B', 0) if B is None else B)
+        with self._ordered('torch' in sys.modules):         # (as forecast_scene)
+            self._chk(self.L.smpc_forecast_scene_fit(self.h, B, int(window), len(sel), sel.ctypes.data if len(sel) else None))
 
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on

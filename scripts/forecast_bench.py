@@ -6,9 +6,13 @@
 2. The closed loop: 'htwa', B = 4096, N = 30, SMPC_STEPS (default 60) steps on turning tracks (problem.turning_scenes, sigma_v = 0.3,
    sigma_a = 3.0), the four arms none / true / hold / cv in alternation, SMPC_ROUNDS (default 2) rounds: ms per closed-loop step
    (run_mpc's own timing) and the lengths of conv_idx, collisions_idx, viable_idx, unconv_idx per arm.
+3. k_scene_fit alone beside the CV kernel (profiles/scene_forecast_fit.txt): the shapes of 1, an observed track set, windows 2, 4, 8,
+   16, 32 at clock 50 (every window full), the same 3 + 10 calls between HIP events.
+4. The closed loop under observation noise: the tracks of 2 seen through observe_tracks (sigma SMPC_OBS_NOISE, default 0.005), the arms
+   true (the clairvoyant reference, which observes nothing), cv and fit with windows 4, 8, 16 -- noise against lag by window length.
 A measurement tool, not a test; it reads nothing outside the repository.
 
-    python scripts/forecast_bench.py [kernel|loop]"""
+    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop]"""
 import os
 import sys
 
@@ -18,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench                                                   # noqa: E402
 from safe_mpc_amd import closed_loop as cl                     # noqa: E402
-from safe_mpc_amd.problem import FORECAST_MODES, turning_scenes   # noqa: E402
+from safe_mpc_amd.problem import FORECAST_MODES, observe_tracks, turning_scenes   # noqa: E402
 from safe_mpc_amd.solver import BatchedOcpSolver               # noqa: E402
 
 
@@ -55,7 +59,42 @@ def kernel_times(B):
     s.close()
 
 
-def loop_times(B):
+def fit_kernel_times(B):
+    import torch
+    par, prob, net = bench.build_problem()
+    s = BatchedOcpSolver(prob, net)
+    N, T, clock = prob.N, 131, 50
+    device = torch.device('cuda', s.device)
+    world = turning_scenes(prob, B, T, 0.3, 3.0, seed=0)
+    s.set_instance_world_track(torch.tensor(world, dtype=torch.float64, device=device))
+    s.set_instance_observed_track(torch.tensor(observe_tracks(prob, world, 0.005), dtype=torch.float64, device=device))
+    cell = torch.full((1,), clock, dtype=torch.int64, device=device)
+    s.set_scene_clock(cell)
+    stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
+    rec = B * len(prob.rows) * 64 / 1e6                         # MB per column of the table
+    with torch.cuda.stream(stream):
+        for name, call, cols in [('k_scene_forecast cv', lambda: s.forecast_scene('cv'), 2)] + \
+                [(f'k_scene_fit window {m:2d}', (lambda m=m: s.forecast_scene_fit(m)), m) for m in (2, 4, 8, 16, 32)]:
+            for _ in range(3):
+                call()
+            ms = []
+            for _ in range(10):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(stream)
+                call()
+                b.record(stream)
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            ms = np.array(ms)
+            print(f'{name}: mean {1e3 * ms.mean():.1f} us, min {1e3 * ms.min():.1f}, max {1e3 * ms.max():.1f} (10 calls between HIP events); '
+                  f'reads {cols * rec:.1f} MB, writes {(N + 1) * rec:.1f} MB: {(cols + N + 1) * rec / ms.mean() / 1e3:.2f} TB/s at the mean; '
+                  f'B = {B}, N = {N}, {len(prob.rows)} rows, T = {T}, clock {clock}', flush=True)
+    s.set_instance_world_track(None)
+    s.set_scene_clock(None)
+    s.close()
+
+
+def loop_times(B, noisy=False):
     from safe_mpc_amd import controller as C
     par, prob, net = bench.build_problem()
     par.N = prob.N
@@ -67,12 +106,19 @@ def loop_times(B):
     xg, ug = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((B, N, prob.nu))
     world = turning_scenes(C.OcpProblem(par, 'htwa', 'ext', N=N), B, steps + 1 + N, 0.3, 3.0, seed=0)
     arms = [None, 'true', 'hold', 'cv']
+    kwargs = {a: ({} if a is None else {'forecast': a}) for a in arms}
+    if noisy:           # what the controller sees: the world through a sensor; 'true' observes nothing and is the reference
+        sigma = float(os.environ.get('SMPC_OBS_NOISE', '0.005'))
+        seen = observe_tracks(C.OcpProblem(par, 'htwa', 'ext', N=N), world, sigma, seed=0)
+        arms = ['true', 'cv', 'fit4', 'fit8', 'fit16']
+        kwargs = {'true': {'forecast': 'true'}, 'cv': {'forecast': 'cv', 'observed': seen}}
+        kwargs.update({f'fit{m}': {'forecast': 'fit', 'forecast_window': m, 'observed': seen} for m in (4, 8, 16)})
+        print(f'observation noise sigma = {sigma}')
     res = {a: [] for a in arms}
     for r in range(rounds + 1):                                 # (round 0 warms everything up)
         for arm in arms:
             tm = {}
-            out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, timing=tm,
-                             **({} if arm is None else {'forecast': arm}))
+            out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, timing=tm, **kwargs[arm])
             counts = tuple(len(out[k]) for k in ('conv_idx', 'collisions_idx', 'viable_idx', 'unconv_idx'))
             if r:
                 res[arm].append((tm['ms_per_step'],) + counts)
@@ -90,6 +136,10 @@ def main(argv=None):
         kernel_times(B)
     if 'loop' in what:
         loop_times(B)
+    if 'fit-kernel' in what:
+        fit_kernel_times(B)
+    if 'fit-loop' in what:
+        loop_times(B, noisy=True)
     return 0
 
 

@@ -16,6 +16,11 @@ velocities random-walk with N(0, SIGMA^2) accelerations per obstacle and axis (s
 --scene-forecast hold|cv|true (needs --scene-velocity): the track is the WORLD, which only the plant meets; the controller plans
 against a forecast of it formed every step from the columns the world has shown (run_mpc(forecast=...)) -- the
 frozen world, a constant-velocity extrapolation, or the world itself.  The result file's name gets the suffix ``_fc<mode>``.
+--scene-forecast fit [--forecast-window M] (M = 1..32, default 8): the forecast is a least-squares line through the last M columns seen
+(run_mpc(forecast='fit', forecast_window=M)); suffix ``_fcfit_w<M>``.
+--scene-obs-noise SIGMA [--scene-obs-seed S] (needs --scene-forecast hold, cv or fit): the controller sees the world through a sensor --
+every obstacle's position in every column off by its own N(0, SIGMA^2) draw per axis (problem.observe_tracks, seed S, default 0), and
+the forecast is formed from that (run_mpc(observed=...)); the plant meets the true world.  Suffix ``_on<SIGMA>`` for SIGMA > 0.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -61,8 +66,18 @@ def main(argv=None):
             scenes = jittered_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], float(raw[raw.index('--scene-jitter') + 1]), seed)
     opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
     forecast = opt('--scene-forecast', None, str)
-    if forecast is not None and forecast not in ('hold', 'cv', 'true'):
-        raise SystemExit(f'--scene-forecast {forecast}: expected hold, cv or true')
+    if forecast is not None and forecast not in ('hold', 'cv', 'true', 'fit'):
+        raise SystemExit(f'--scene-forecast {forecast}: expected hold, cv or true, or fit')
+    window, obs_noise = opt('--forecast-window', 8, int), opt('--scene-obs-noise', 0.0, float)
+    if '--forecast-window' in raw and forecast != 'fit':
+        raise SystemExit('--forecast-window needs --scene-forecast fit: no other forecast has a window')
+    if forecast == 'fit' and not 1 <= window <= 32:
+        raise SystemExit(f'--forecast-window {window}: expected 1..32')
+    for flag in ('--scene-obs-noise', '--scene-obs-seed'):
+        if flag in raw and forecast not in ('hold', 'cv', 'fit'):
+            raise SystemExit(f'{flag} needs --scene-forecast hold, cv or fit: nothing else reads what was observed')
+    if obs_noise < 0:
+        raise SystemExit(f'--scene-obs-noise {obs_noise}: a standard deviation is not negative')
     for flag in ('--scene-forecast', '--scene-accel'):
         if flag in raw and '--scene-velocity' not in raw:
             raise SystemExit(f'{flag} needs --scene-velocity: there is no track to forecast or to turn')
@@ -77,6 +92,13 @@ def main(argv=None):
         else:
             scenes = moving_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], T, opt('--scene-velocity', 0.0, float),
                                    opt('--scene-seed', 0, int), sigma=opt('--scene-jitter', 0.0, float))
+    fc_kw, name_kw = ({} if forecast is None else {'forecast': forecast}), ({} if forecast is None else {'forecast': forecast})
+    if forecast == 'fit':
+        fc_kw['forecast_window'] = name_kw['forecast_window'] = window
+    if '--scene-obs-noise' in raw:
+        from safe_mpc_amd.problem import OcpProblem, observe_tracks
+        fc_kw['observed'] = observe_tracks(OcpProblem(params, 'naive'), scenes, obs_noise, opt('--scene-obs-seed', 0, int))
+        name_kw['obs_noise'] = obs_noise
     cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
     if cmodel not in ('nominal', 'plant'):
         raise SystemExit(f'--controller-model {cmodel}: expected nominal or plant')
@@ -85,7 +107,7 @@ def main(argv=None):
     res = cl.run_mpc(params, cont_name, x_guess, u_guess, noise=args['noise'], control_noise=args['control_noise'],
                      callback=True, on_device=os.environ.get('SMPC_HOST_STATE', '0') != '1', timing=tm,
                      collect_times=os.environ.get('SMPC_NO_TIME_STATS', '0') != '1', scenes=scenes, traj=traj,
-                     models='plant' if cmodel == 'plant' else None, **({} if forecast is None else {'forecast': forecast}))
+                     models='plant' if cmodel == 'plant' else None, **fc_kw)
     with_stats = os.environ.get('SMPC_NO_TIME_STATS', '0') != '1'
     print(f"{tm['ms_per_step']:.3f} ms per closed-loop step of {x_guess.shape[0]} instances"
           + (' (eager launches with per-solve HIP events for the time statistics below; SMPC_NO_TIME_STATS=1 replays the step halves as '
@@ -99,7 +121,7 @@ def main(argv=None):
           f"\nViable states: {len(res['viable_idx'])}\nNot converged: {n - len(res['conv_idx']) - len(res['collisions_idx'])}")
     cl.save_pickle(cl.result_file(params, model_name, cont_name, params.N, use_net, args['noise'], args['control_noise'],
                                   args['joint_bounds_margin'], args['collision_margin'], controller_model=cmodel,
-                                  **({} if forecast is None else {'forecast': forecast})), res)
+                                  **name_kw), res)
     return len(res['collisions_idx'])
 
 
