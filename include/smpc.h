@@ -212,6 +212,12 @@ int smpc_set_horizon(smpc_handle* h, int N);
 enum { SMPC_QP_AUTO = -1, SMPC_QP_THROUGHPUT = 0, SMPC_QP_LATENCY = 1 };
 int smpc_set_qp_mode(smpc_handle* h, int mode);
 
+/* The crew of the throughput form: a k_qp_ipm launch over P = ceil(B / 2) pairs of instances runs G = ceil(fraction * P) wavefronts,
+ * which take the pairs longest-expected-first from a ticket -- the first G at once, the others as wavefronts come free.  fraction = 1
+ * is a wavefront per pair.  waves > 0 fixes G itself (clamped to P) and fraction is ignored.  Scheduling only: every instance's
+ * arithmetic, and so every result, is the same for every crew.  The latency form is not affected. */
+int smpc_set_qp_crew(smpc_handle* h, double fraction, int waves);
+
 /* replaces ocp_solver.constraints_set(k,'lbx'/'ubx',v) for k >= 1 (controller.py:531-536).  lo/hi are [N+1][nx]
  * shared by all instances, or NULL to restore the descriptor's bounds. */
 int smpc_set_stage_bounds(smpc_handle* h, const double* lo, const double* hi);

@@ -19,7 +19,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_provide_control', 'smpc_check_trajectory', 'smpc_plant_step', 'smpc_rollout_batch', 'smpc_sync', 'smpc_stream',
            'smpc_enable_timing', 'smpc_get_timing', 'smpc_get_qp_timing', 'smpc_get_qp_wave_stats', 'smpc_policy_step', 'smpc_loop_pre',
            'smpc_loop_post', 'smpc_loop_apply_backup', 'smpc_loop_classify_aborts', 'smpc_get_timing_history',
-           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
+           'smpc_accumulate_stats', 'smpc_set_mlp_activation', 'smpc_set_qp_mode', 'smpc_set_qp_crew', 'smpc_merit_terms', 'smpc_sqp_batch', 'smpc_check_guess',
            'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves',
            'smpc_set_instance_scene_track', 'smpc_set_scene_clock', 'smpc_set_mlp_context', 'smpc_set_instance_context',
            'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene',
@@ -172,6 +172,8 @@ def lib():
     L.smpc_set_instance_context_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_set_instance_models.argtypes = [vp, C.c_int, dp, C.c_int]
     L.smpc_set_qp_mode.argtypes = [vp, C.c_int]
+    if hasattr(L, 'smpc_set_qp_crew'):      # (an older build named by SMPC_HIP_LIB, in an A/B run: a wavefront per pair, no setter)
+        L.smpc_set_qp_crew.argtypes = [vp, C.c_double, C.c_int]
     L.smpc_merit_terms.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_sqp_batch.argtypes = [vp, C.c_int, C.POINTER(SqpOpts), dp, dp, dp, dp, C.POINTER(SqpState), C.c_int]
     L.smpc_check_guess.argtypes = [vp, C.c_int, dp, dp, C.POINTER(GuessCheck), dp, dp, dp, C.c_int]

@@ -145,8 +145,10 @@ struct smpc_handle {
     bool wg_lds_raised[2] = {false, false};   // dynamic-LDS limit raised for this handle's instantiation of k_qp_ipm_wg (8 / 4 half-waves)
     DevBuf<int32_t> d_order, d_last_it;       // longest-first dispatch order from the previous call's iterations
     int order_B = 0;                          // batch size d_last_it is valid for (0 = none yet)
-    DevBuf<int32_t> d_ord_hist;   // [256] histogram of d_last_it (k_qp_ipm) | [256] bin cursors | ticket (k_order_by_iters); zeroed
-                                  // when allocated
+    DevBuf<int32_t> d_ord_hist;   // [256] histogram of d_last_it (k_qp_ipm) | [256] bin cursors | ticket (k_order_by_iters) | pair
+                                  // ticket (k_qp_ipm's crew); zeroed when allocated
+    double qp_crew = -1.0;        // smpc_set_qp_crew: wavefronts of a k_qp_ipm launch as a fraction of its pairs; < 0 = not set (the
+    int qp_crew_waves = 0;        // process default, SMPC_QP_CREW) | > 0: that many wavefronts whatever the batch
     // MLP activations (ensure_mlp)
     DevBuf<float> d_S, d_y, d_GS, d_dA, d_dB;
     DevBuf<int32_t> d_nn_idx;     // compacted list of the nodes whose safe-set row is on, followed by its length d_nn_cnt
@@ -638,6 +640,26 @@ static int qp_nt_mode() {
     return v;
 }
 
+// k_qp_ipm's crew: the wavefronts of a launch as a fraction f of its pairs of instances, G = ceil(f pairs); the G wavefronts take
+// the pairs longest-first from a ticket (kernel_qp.hpp).  f = 1 is a wavefront per pair.  Per handle by smpc_set_qp_crew, for the
+// process by SMPC_QP_CREW (A/B runs).  The default is the measured one: profiles/qp_crew.txt, DESIGN.md section 4, point 4c.
+constexpr double QP_CREW_DEFAULT = 1.0;
+static double qp_crew_default() {
+    static const double v = [] {
+        const char* e = getenv("SMPC_QP_CREW");
+        const double f = e ? atof(e) : QP_CREW_DEFAULT;
+        return f > 0.0 && f <= 1.0 ? f : QP_CREW_DEFAULT;
+    }();
+    return v;
+}
+static int qp_crew_waves(const smpc_handle* h, int B) {
+    const int pairs = (B + 1) / 2;
+    if (h->qp_crew_waves > 0) return h->qp_crew_waves < pairs ? h->qp_crew_waves : pairs;
+    const double f = h->qp_crew > 0.0 ? h->qp_crew : qp_crew_default();
+    const int g = (int)ceil(f * pairs);
+    return g < 1 ? 1 : (g > pairs ? pairs : g);
+}
+
 // f(std::integral_constant<int, MR>{}) with the handle's row count as the kernels' compile-time constant: the shipped geometries
 // have 6 rows (the reference's six capsule pairs, config.yaml:205-216) or 4 (config_fr7.yaml); any other count takes the
 // runtime-row-count instantiation, MR = -1
@@ -825,8 +847,9 @@ int launch_solve(smpc_handle* h, int B, const double* x0, const double* xg, cons
         const bool nt = qp_nt_mode() < 0 ? ws_doubles_per_instance(h, h->N) * sizeof(double) * (size_t)B >= qp_nt_threshold : qp_nt_mode() > 0;
         with_rows(h, [&](auto MR) {
             const auto launch = [&](auto NT) {
-                hipLaunchKernelGGL((k_qp_ipm<NQ, MR, NT>), dim3((B + 1) / 2), dim3(64), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, h->d_ws.p,
-                                   xo, uo, st, it, order, h->d_last_it.p, wstat, h->d_active, h->d_ord_hist.p);
+                // (the pair ticket is zero here: cleared with the histogram, by k_order_by_iters or the memset above)
+                hipLaunchKernelGGL((k_qp_ipm<NQ, MR, NT>), dim3(qp_crew_form<NQ, MR>() ? qp_crew_waves(h, B) : (B + 1) / 2), dim3(64), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug,
+                                   h->d_ws.p, xo, uo, st, it, order, h->d_last_it.p, wstat, h->d_active, h->d_ord_hist.p, h->d_ord_hist.p + 513);
                 return SMPC_OK;
             };
             if constexpr (MR < 0) return launch(std::false_type{});      // (the runtime-row-count instantiation is not built twice)
@@ -976,6 +999,8 @@ int rollout_workers(smpc_handle* h, int n) {
         if (k->N != h->N && (rc = smpc_set_horizon(k, h->N))) return fail(h, rc, "rollout worker: %s", k->err);
         k->net = h->net;                // (with the weights goes the default context; a worker holds no instance context)
         k->qp_mode = h->qp_mode;
+        k->qp_crew = h->qp_crew;
+        k->qp_crew_waves = h->qp_crew_waves;
         // stage bounds and slack weights follow the parent (small; stream-ordered on the worker's stream)
         const size_t nb = (size_t)(h->N + 1) * 2 * h->desc.nq;
         HIPCHK(h, hipMemcpyAsync(k->d_lo.p, h->d_lo.p, nb * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
@@ -1686,6 +1711,15 @@ int smpc_set_qp_mode(smpc_handle* h, int mode) {
     if (!h) return SMPC_EINVAL;
     if (mode < SMPC_QP_AUTO || mode > SMPC_QP_LATENCY) return fail(h, SMPC_EINVAL, "qp mode %d (SMPC_QP_AUTO, _THROUGHPUT, _LATENCY)", mode);
     h->qp_mode = mode;
+    return SMPC_OK;
+}
+
+int smpc_set_qp_crew(smpc_handle* h, double fraction, int waves) {
+    if (!h) return SMPC_EINVAL;
+    if (waves < 0 || (waves == 0 && !(fraction > 0.0 && fraction <= 1.0)))
+        return fail(h, SMPC_EINVAL, "qp crew: fraction %g outside (0, 1], or %d wavefronts", fraction, waves);
+    h->qp_crew = waves > 0 ? -1.0 : fraction;
+    h->qp_crew_waves = waves;
     return SMPC_OK;
 }
 
@@ -2794,6 +2828,18 @@ extern "C" int smpc_debug_scene_slots(smpc_handle* h, double* scene_out, size_t 
         if (nc > ctx_cap) return fail(h, SMPC_EINVAL, "smpc_debug_scene_slots: the context holds %zu floats, room for %zu", nc, ctx_cap);
         HIPCHK(h, hipMemcpy(ctx_out, h->ctx.d.p, nc * sizeof(float), hipMemcpyDeviceToHost));
     }
+    return SMPC_OK;
+}
+
+// Test hook (not part of include/smpc.h): the dispatch state a solve leaves behind, once the handle's stream has drained -- out[520] =
+// [256] histogram of the solve's iteration counts (every instance of the launch adds itself once) | [256] bin cursors | the ticket of
+// k_order_by_iters | the pair ticket of k_qp_ipm's crew | 6 unused.  Host pointer.
+extern "C" int smpc_debug_qp_dispatch(smpc_handle* h, int32_t* out) {
+    if (!h || !out) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    if (!h->d_ord_hist.p) return fail(h, SMPC_ESTATE, "smpc_debug_qp_dispatch: no solve yet");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out, h->d_ord_hist.p, 520 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return SMPC_OK;
 }
 

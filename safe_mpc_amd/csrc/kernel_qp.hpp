@@ -10,7 +10,8 @@
 //   k_qp_ipm   : ONE WAVEFRONT PER PAIR OF OCP INSTANCES -- lanes 0-31 own one instance, lanes 32-63 another, each with its
 //                own LDS region, workspace and iteration state.  The halves never exchange data, so every branch is
 //                half-uniform and the SIMT exec mask does the rest (a converged half idles until its twin is done;
-//                longest-first dispatch pairs instances with similar iteration counts).
+//                longest-first dispatch pairs instances with similar iteration counts).  A launch may hold fewer wavefronts
+//                than pairs (a crew: each takes its next pair from a ticket); by default it holds one per pair.
 // Per IPM iteration a half-wave walks the horizon four times
 //   B1  backward: apply the previous step, barrier weights, the u rows of H + C^T D C, Cholesky, W = L^-1 [G | rho], L^-1,
 //                 P_k (its x-x block of H + C^T D C assembled element by element inside the P update), predictor costate
@@ -563,6 +564,12 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
 // =========================================================================================================================
 // k_qp_ipm
 // =========================================================================================================================
+// Which instantiations take the crew shell (below: a wavefront works through several pairs).  All but the 6-DoF kernel with a run-time
+// row count: that one spills inside its stage bodies as it is, and the shell adds to it (76 -> 104 scratch accesses, those of the B2
+// bodies 21 -> 46: the known failure mode, DESIGN.md section 4 point 6), so it keeps a wavefront per pair and the engine launches it
+// that way whatever the crew setting.
+template <int NQ, int MRT> constexpr bool qp_crew_form() { return !(NQ == 6 && MRT < 0); }
+
 // NT: the wide accesses of the stage workspace -- 16-byte loads of every sweep, the factorisation sweep's wide stores -- are
 // non-temporal.  The workspace is a stream (every block is touched once per sweep by one wavefront and comes round again long after
 // its XCD's 4 MB L2 has turned over), so for a workspace far larger than the 256 MB Infinity Cache `nt` is a plain win: C1's loop at
@@ -576,7 +583,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     const double* __restrict__ ug, double* __restrict__ ws_all, double* __restrict__ x_out, double* __restrict__ u_out,
     int32_t* __restrict__ status, int32_t* __restrict__ qp_iter, const int32_t* __restrict__ order,
     int32_t* __restrict__ last_iter, unsigned long long* __restrict__ wstat, const uint8_t* __restrict__ active,
-    int32_t* __restrict__ it_hist) {
+    int32_t* __restrict__ it_hist, int32_t* __restrict__ ticket) {
     using LyT = QpLayout<NQ>;
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NZP = LyT::NZP, NQP = LyT::NQP, WS2 = LyT::WS2, NL = 32,
                   LC0 = LyT::LC0, KS = LyT::KS, NWP = LyT::NWP;
@@ -589,10 +596,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         if constexpr (NT) __builtin_nontemporal_store(v, p);
         else *p = v;
     };
-    // load-balance probe (smpc_get_qp_wave_stats): two reads of the constant 100 MHz clock per half-wave; the first one is
-    // parked in LDS (the kernel has no register to spare)
+    // load-balance probe (smpc_get_qp_wave_stats): two reads of the constant 100 MHz clock per half-wave and pair; the first one
+    // is parked in LDS (the kernel has no register to spare)
     __shared__ unsigned long long s_tbegin[2];
-    if (wstat && (threadIdx.x & 31) == 0) s_tbegin[threadIdx.x >> 5] = __builtin_amdgcn_s_memrealtime();
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS, MRP_MAX = qp_even_c(MR_MAX);
     constexpr int NRC_MAX = NQ + MR_MAX + 1;
     static_assert(MRT < 0 || NX + NRC_MAX <= NL, "one lane per constraint row");
@@ -608,27 +614,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
     unsigned long long tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev = __builtin_readcyclecounter();
 #endif
-    const int hl = threadIdx.x & 31, half = threadIdx.x >> 5;
-    const int slot = 2 * (int)blockIdx.x + half;
-    if (slot >= B) return;  // odd batch: the last half-wave has no instance
-    // longest-expected-first dispatch: slot i takes the instance with the i-th largest iteration count of the previous
-    // call (instances are independent, so the order only changes the makespan, never a result)
-    const int b = order ? order[slot] : slot;
-    if (active && !active[b]) {
-        // the policy layer masks out instances that do not step their controller (dead, or following a backup trajectory):
-        // their state can be anywhere, and an infeasible QP running to its iteration cap would set the launch time
-        if (hl == 0) {
-            status[b] = SMPC_STATUS_SUCCESS;
-            if (qp_iter) qp_iter[b] = 0;
-            if (last_iter) last_iter[b] = 0;
-            if (it_hist) atomicAdd(&it_hist[0], 1);
-        }
-        return;
+    // ---- the crew: this wavefront solves pair blockIdx.x, then whatever pair the launch's ticket hands it next -------------
+    // A launch of G <= (B + 1) / 2 wavefronts works through all pairs: the first G -- with a longest-first order the ones expected to
+    // take longest -- start at once, the others follow as wavefronts come free (list scheduling; DESIGN.md section 4, point 4c).  The ticket
+    // is the only word the wavefronts share, nobody waits for anybody, and a full crew never touches it.  A pair belongs to the
+    // WAVEFRONT: a half whose instance is done, masked out or absent (odd batch) sits the pair out, as it idled to the kernel's end
+    // before -- two halves at different points of the program would take turns.  The pair index is wave-uniform (scalar registers).
+    // The loop encloses the WHOLE kernel, and what a pair starts from -- the lane index, the descriptor, the horizon -- is opaque to
+    // the optimiser at its top: were a pair's set-up and write-back loop-invariant, their lane roles, offsets and descriptor fields
+    // would be hoisted out of the loop and held across the sweeps, which have no register to spare.  A later pair rebuilds the
+    // index tables: microseconds.  (Without the shell -- qp_crew_form -- the loop ends after its first pass and compiles away.)
+    constexpr bool CREW = qp_crew_form<NQ, MRT>();
+    const smpc_problem_desc* __restrict__ const D_arg = D;
+    const int N_arg = N, n_pairs = (B + 1) >> 1;
+    int pair = (int)blockIdx.x;
+#pragma unroll 1
+    for (;;) {
+    int tid = (int)threadIdx.x, zero = 0;
+    if constexpr (CREW) {
+        asm volatile("" : "+v"(tid));
+        asm volatile("" : "+s"(zero));
     }
+    const smpc_problem_desc* const D = D_arg + zero;
+    const int N = N_arg + zero;
+    const int hl = tid & 31, half = tid >> 5;
     const LyT Ly(MRT >= 0 ? MRT : D->n_rows);
     const int MR = Ly.MR, MRP = Ly.MRP, NRC = Ly.NRC, NRT = Ly.NRT;
     const int rT0 = NX, rC0 = NX + NQ, rNN = NX + NQ + MR;
-    double* const ws = ws_all + (size_t)b * Ly.per_instance(N);
     const double dt = D->dt, cB = 0.5 * dt * dt;
     const int img_n2 = Ly.nIMG >> 1;   // 16-byte pieces of the image
     const int c_n2 = Ly.nF >> 1;            // ... and of its part [Tt | Gt | gn | b | scalars] (what the forward sweeps fetch)
@@ -748,6 +760,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         else return reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off);
     };
 
+    const int slot = 2 * pair + half;
+    bool live = slot < B;   // odd batch: the last half-wave has no instance
+    // longest-expected-first dispatch: slot i takes the instance with the i-th largest iteration count of the previous
+    // call (instances are independent, so the order only changes the makespan, never a result)
+    const int b = live ? (order ? order[slot] : slot) : 0;
+    if (live && active && !active[b]) {
+        // the policy layer masks out instances that do not step their controller (dead, or following a backup trajectory):
+        // their state can be anywhere, and an infeasible QP running to its iteration cap would set the launch time
+        if (hl == 0) {
+            status[b] = SMPC_STATUS_SUCCESS;
+            if (qp_iter) qp_iter[b] = 0;
+            if (last_iter) last_iter[b] = 0;
+            if (it_hist) atomicAdd(&it_hist[0], 1);
+        }
+        live = false;
+    }
+    if (live) {
+    if (wstat && hl == 0) s_tbegin[half] = __builtin_amdgcn_s_memrealtime();
+    double* const ws = ws_all + (size_t)b * Ly.per_instance(N);
     const double* xb0 = xg + (size_t)b * (N + 1) * NX;
     const double* ub0 = ug + (size_t)b * N * NU;
     const double dx0_reg = hl < NX ? x0[(size_t)b * NX + hl] - xb0[hl] : 0.0;
@@ -1712,6 +1743,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QP_WAVES_PER
         if (last_iter) last_iter[b] = it;
         if (it_hist) atomicAdd(&it_hist[min(it, 255)], 1);   // next solve's longest-first order (k_order_by_iters)
     }
+    }   // (live)
+    // the next pair: the first one not yet taken.  The ticket is zero when the launch starts -- cleared where the histogram is,
+    // by the memset or the k_order_by_iters that precedes every launch on the handle's stream (engine.hip: launch_solve).
+    if constexpr (!CREW) break;
+    if ((int)gridDim.x >= n_pairs) break;
+    int nxt = 0;
+    if (tid == 0) nxt = atomicAdd(ticket, 1);
+    pair = (int)gridDim.x + __builtin_amdgcn_readfirstlane(nxt);
+    if (pair >= n_pairs) break;
+    lds_fence();   // (the pair's last LDS reads before the next one's first writes)
+    }
 }
 
 
@@ -1762,7 +1804,7 @@ __global__ __launch_bounds__(64) void k_order_by_iters(int B, const int32_t* __r
     if (offs[0] == (int)gridDim.x - 1) {
 #pragma unroll
         for (int j = 0; j < 4; j++) { hist[4 * t + j] = 0; cur[4 * t + j] = 0; }
-        if (t == 0) *ticket = 0;
+        if (t == 0) { ticket[0] = 0; ticket[1] = 0; }   // (ticket[1]: the pair ticket of k_qp_ipm's crew, left by the previous solve)
     }
 }
 

@@ -180,6 +180,11 @@ class BatchedOcpSolver:
         wavefront per two instances) or 'latency' (k_qp_ipm_wg, a workgroup per instance).  Same result to rounding."""
         self._chk(self.L.smpc_set_qp_mode(self.h, self.QP_MODES[mode] if isinstance(mode, str) else int(mode)))
 
+    def set_qp_crew(self, fraction=1.0, waves=0):
+        """Wavefronts of a k_qp_ipm launch (smpc_set_qp_crew): ``fraction`` of its pairs of instances, or exactly ``waves`` of them.
+        The crew takes the pairs longest-first from a ticket; results do not depend on it."""
+        self._chk(self.L.smpc_set_qp_crew(self.h, float(fraction), int(waves)))
+
     def set_horizon(self, N):
         self._chk(self.L.smpc_set_horizon(self.h, int(N)))
         self.N = int(N)
