@@ -327,7 +327,8 @@ int smpc_forecast_scene(smpc_handle* h, int B, int mode, int n_sel, const int32_
  * the slot rule, host and device pointers and growth under capture (SMPC_ESTATE, the old contents kept) are exactly the world
  * track's.  A slot of its own; geom == NULL clears it, and so does clearing the world (an observation without its world is stale).
  * Who reads it, while it is set: smpc_forecast_scene in the modes HOLD and CV, INSTEAD of the world (same column rule, same clock),
- * and smpc_forecast_scene_fit.  SMPC_FORECAST_TRUE and smpc_loop_post keep reading the world; nothing else reads the observed track.
+ * smpc_forecast_scene_fit and smpc_forecast_scene_poly.  SMPC_FORECAST_TRUE and smpc_loop_post keep reading the world; nothing else
+ * reads the observed track.
  * Call the table those forecasts read S, "what was seen": the observed track while one is set, else the world.
  * A forecast call while an observed track is set needs its (B, T) to equal the world's: SMPC_EINVAL naming both otherwise.
  * (ABI version unchanged: no existing entry point or structure changed) */
@@ -351,6 +352,25 @@ int smpc_set_instance_observed_track(smpc_handle* h, int B, int64_t T, const dou
  * (ABI version unchanged: no existing entry point or structure changed) */
 #define SMPC_FIT_MAX 32
 int smpc_forecast_scene_fit(smpc_handle* h, int B, int window, int n_sel, const int32_t* select);
+
+/* A forecast by a least-squares POLYNOMIAL of degree 0, 1 or 2 over the last `window` samples of S.  Every
+ * rule, refusal, flag and state of smpc_forecast_scene_fit holds -- it is the same code, with this call's name in the message -- and
+ * SMPC_EINVAL also for degree < 0 or degree > 2, naming it.  t, col, m = min(window, max(t, 0) + 1) and y_j = S[b][col(t - j)][r][s]
+ * as there; the effective degree is p = min(degree, m - 1): nothing was seen before time 0, so one sample gives a constant and two
+ * give a line.  The model is y(tau) = a + b tau + c tau^2 at tau = -j.  For every instance b, row r and all eight slots s:
+ *   p = 0   u_j = 1.0 / (double)m;  a = u_0 y_0;  a = a + u_j y_j  (j = 1..m-1, every product rounded before its sum)
+ *           F[b][k] = a, k = 0..N                 (stored, not added: a -0.0 stays one).  The window mean; m = 1: SMPC_FORECAST_HOLD
+ *   p = 1   smpc_forecast_scene_fit with window m, bit for bit: degree == 1 launches that call's kernel
+ *   p = 2   ua_j = (double)(3(3m^2 - 3m + 2) - 18(2m - 1) j + 30 j^2)                         / (double)(m (m + 1)(m + 2))
+ *           uv_j = (double)((36m^3 - 96m^2 + 36m + 24) + (-192m^2 + 180m + 48) j + 180 m j^2) / (double)(m (m^2 - 1)(m^2 - 4))
+ *           ue_j = (double)(60 ((m - 1)(m - 2) - 6(m - 1) j + 6 j^2))                         / (double)(m (m^2 - 1)(m^2 - 4))
+ *           (integers formed in 64 bits, ONE correctly rounded division each; m = 3: ua = (1, 0, 0), uv = (2, -3, 1), ue = (1, -2, 1))
+ *           a, v, e each  x = u_0 y_0;  x = x + u_j y_j   (in increasing j, every product rounded before its sum)
+ *           F[b][0] = a;  for k = 1..N:  F[b][k] = F[b][k-1] + v;  v = v + e              (in that order; repeated addition)
+ * a is the parabola's value now, v = b + c its first step F[1] - F[0] and e = 2c the step of the step: a constant-acceleration
+ * model.  degree 2 with window 2 is SMPC_FORECAST_CV and degree 0 with window 1 SMPC_FORECAST_HOLD, bit for bit at every clock.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int n_sel, const int32_t* select);
 
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle

@@ -30,10 +30,11 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
 
 
 def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None,
-                forecast_window=None, obs_noise=0.0):
+                forecast_window=None, obs_noise=0.0, forecast_degree=1):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
     before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
-    it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns; ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
+    it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns, ``_d<p>`` behind that for ``forecast_degree = p`` other than 1
+    (a polynomial fit, --forecast-degree); ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
     that; the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
@@ -41,7 +42,9 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
             f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}"
-            f"{f'_w{int(forecast_window)}' if forecast == 'fit' else ''}{f'_on{obs_noise}' if obs_noise > 0 else ''}_mpc.pkl")
+            f"{f'_w{int(forecast_window)}' if forecast == 'fit' else ''}"
+            f"{f'_d{int(forecast_degree)}' if forecast == 'fit' and int(forecast_degree) != 1 else ''}"
+            f"{f'_on{obs_noise}' if obs_noise > 0 else ''}_mpc.pkl")
 
 
 def tracking_from_cli(params, argv, n=None):
@@ -1070,7 +1073,7 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None):
+                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None, forecast_degree=1):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -1083,7 +1086,9 @@ class _Group:
         # itself does not go onto the scene slot until the run is scored.
         # 'fit' forecasts by a line through the last forecast_window columns; with ``observed`` (the world's shape: what a sensor
         # shows of it) 'hold', 'cv' and 'fit' are formed from that table instead of the world.
+        # forecast_degree other than 1 makes the fit a window mean (0) or a parabola (2), DESIGN.md section 9p.
         self._scenes, self._track, self._forecast, self._window, self._observed = None, False, forecast, forecast_window, None
+        self._degree = int(forecast_degree)
         if scenes is not None:
             self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
             if observed is not None:
@@ -1312,14 +1317,20 @@ class _HostGroup(_Group):
             self.new_abort = self.new_abort & ~again
 
     def _forecast_onto(self, sv, rows, t, N):
-        """the statement of smpc_forecast_scene / smpc_forecast_scene_fit: the N + 1 scenes forecast at time t for the instances
-        ``rows`` onto ``sv``'s scene slot (and their context rows, _set_scene), with no clock -- node k reads column k.  'hold', 'cv'
-        and 'fit' are formed from what was seen, the observed track where the run has one; 'true' from the world"""
-        from .problem import fit_forecast_statement, forecast_statement
+        """the statement of smpc_forecast_scene / smpc_forecast_scene_fit / smpc_forecast_scene_poly: the N + 1 scenes forecast at
+        time t for the instances ``rows`` onto ``sv``'s scene slot (and their context rows, _set_scene), with no clock -- node k reads
+        column k.  'hold', 'cv' and 'fit' (of any degree) are formed from what was seen, the observed track where the run has one;
+        'true' from the world"""
+        from .problem import fit_forecast_statement, forecast_statement, poly_forecast_statement
         seen = self._scenes if self._observed is None or self._forecast == 'true' else self._observed
         sv.set_scene_clock(None)
-        _set_scene(sv, fit_forecast_statement(seen[rows], t, N, self._window) if self._forecast == 'fit'
-                   else forecast_statement(seen[rows], t, N, self._forecast))
+        if self._forecast != 'fit':
+            F = forecast_statement(seen[rows], t, N, self._forecast)
+        elif self._degree == 1:
+            F = fit_forecast_statement(seen[rows], t, N, self._window)
+        else:
+            F = poly_forecast_statement(seen[rows], t, N, self._window, self._degree)
+        _set_scene(sv, F)
 
     def _backup_forecast(self, rows):
         self._forecast_onto(self._backup.ocp_solver, rows, self._jt, self._Nb)
@@ -1426,6 +1437,8 @@ class _DeviceGroup(_Group):
                     raise ValueError(f'forecast: {type(sv).__name__} has no forecast_scene')
                 if self._forecast == 'fit' and not hasattr(sv, 'forecast_scene_fit'):
                     raise ValueError(f"forecast: {type(sv).__name__} has no forecast_scene_fit")
+                if self._forecast == 'fit' and self._degree != 1 and not hasattr(sv, 'forecast_scene_poly'):
+                    raise ValueError(f"forecast_degree: {type(sv).__name__} has no forecast_scene_poly")
                 if self._observed is not None and not hasattr(sv, 'set_instance_observed_track'):
                     raise ValueError(f'observed: {type(sv).__name__} has no set_instance_observed_track')
             self._select, self._backup_select = _context_select(ctrl.ocp_solver), _context_select(self._backup.ocp_solver)
@@ -1515,7 +1528,9 @@ class _DeviceGroup(_Group):
 
     def _enqueue_forecast(self, sv, select):
         """one forecast of the run's kind from ``sv``'s world (and observed track) at its clock cell, into its scene slot"""
-        if self._forecast == 'fit':
+        if self._forecast == 'fit' and self._degree != 1:
+            sv.forecast_scene_poly(self._window, self._degree, select)
+        elif self._forecast == 'fit':
             sv.forecast_scene_fit(self._window, select)
         else:
             sv.forecast_scene(self._forecast, select)
@@ -1609,7 +1624,8 @@ def _check_state_kind(ctrl, backup, on_device):
 
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
-            score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None):
+            score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None,
+            forecast_degree=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1655,6 +1671,11 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     ``forecast='fit'`` with ``forecast_window`` (1..``problem.FIT_MAX``, default 8): the forecast is a
     least-squares line through the last ``forecast_window`` columns seen (``problem.fit_forecast_statement``; window 1 is 'hold',
     window 2 'cv') -- on the device one smpc_forecast_scene_fit per step where 'hold' and 'cv' enqueue smpc_forecast_scene.
+    ``forecast_degree`` (0, 1 or 2, only with ``forecast='fit'``; None: 1): the fit is a least-squares
+    polynomial of that degree (``problem.poly_forecast_statement``) -- 0 the window mean, 2 a constant-acceleration model.  Degree 1
+    makes exactly the calls of a run without the argument; degrees 0 and 2 apply the statement on the host path and enqueue one
+    smpc_forecast_scene_poly per step on the device, the backup handle of an abort event included.  ValueError with any other
+    ``forecast`` or outside 0..2.  The result gains ``'forecast_degree'`` only when the degree is not 1.
     ``observed`` ([B, T, n_rows, 8], the world's shape; ``problem.observe_tracks`` draws one): what the controller observes of the
     world.  'hold', 'cv' and 'fit' are then formed from it instead of the world (smpc_set_instance_observed_track on the device,
     the statement on it on the host), the plant still meets the world, and the backup handle of an abort event gets the aborting
@@ -1691,6 +1712,12 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         if scenes is None or scenes.ndim != 4:
             raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
                              + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
+    if forecast_degree is not None:
+        if forecast != 'fit':
+            raise ValueError(f"forecast_degree: forecast={forecast!r} has no degree: it goes with forecast='fit'")
+        if not (isinstance(forecast_degree, (int, np.integer)) and 0 <= forecast_degree <= 2):
+            raise ValueError(f'forecast_degree: {forecast_degree!r}: a polynomial fit has degree 0, 1 or 2')
+    degree = 1 if forecast_degree is None else int(forecast_degree)
     if observed is not None:
         if forecast is None or forecast == 'true':
             raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
@@ -1725,7 +1752,7 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         if traj is not None:
             ctrl.setTrajectory(traj[lo:hi] if curves else traj)
         args = (params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, collect_times)
-        fit_kw = dict(forecast_window=int(forecast_window) if forecast == 'fit' else None,
+        fit_kw = dict(forecast_window=int(forecast_window) if forecast == 'fit' else None, forecast_degree=degree,
                       observed=None if observed is None else observed[lo:hi])
         if on_device:
             import torch
@@ -1822,6 +1849,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra['observed'] = observed is not None
         if forecast == 'fit':
             extra['forecast_window'] = int(forecast_window)
+            if degree != 1:
+                extra['forecast_degree'] = degree
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -120,7 +120,7 @@ struct smpc_handle {
     int64_t world_T = 1;
     InstSlot<double> seen{"instance observed track", "smpc_set_instance_observed_track"};   // the world's layout: what the controller
                                     // observes of it.  While set, smpc_forecast_scene (HOLD, CV) and
-                                    // smpc_forecast_scene_fit read it instead of the world; nothing else reads it
+                                    // smpc_forecast_scene_fit / _poly read it instead of the world; nothing else reads it
     int64_t seen_T = 1;
     InstSlot<double> curves{"instance curve table", "smpc_set_instance_curves"};    // [B][3][L] reference curves
     int64_t curves_L = 0;
@@ -1842,10 +1842,11 @@ int smpc_set_instance_observed_track(smpc_handle* h, int B, int64_t T, const dou
     return set_scene_table(h, h->seen, h->seen_T, "smpc_set_instance_observed_track", B, T, geom, on_device);
 }
 
-// The one body of smpc_forecast_scene (fit = false: `what` is its mode) and smpc_forecast_scene_fit (fit = true: `what` is its
-// window); `who` names the entry point in every message.  S, "what was seen", is the observed track while one is set and the world
+// The one body of smpc_forecast_scene (fit = false: `what` is its mode), smpc_forecast_scene_fit (fit = true: `what` is its window,
+// degree 1) and smpc_forecast_scene_poly (fit = true with its degree); `who` names the entry point in every message.  S, "what was seen", is the observed track while one is set and the world
 // otherwise; SMPC_FORECAST_TRUE reads the world whatever was observed.
-static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit, int what, int n_sel, const int32_t* select) {
+static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit, int what, int n_sel, const int32_t* select,
+                               int degree = 1) {
     const int mode = what, window = what;
     if (!h->world.B) return fail(h, SMPC_ESTATE, "%s: no world is set (smpc_set_instance_world_track)", who);
     if (B != h->world.B)
@@ -1855,6 +1856,8 @@ static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit,
         return fail(h, SMPC_EINVAL, "%s: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", who, mode);
     if (fit && (window < 1 || window > SMPC_FIT_MAX))
         return fail(h, SMPC_EINVAL, "%s: window %d: a fit takes 1 to SMPC_FIT_MAX = %d samples", who, window, SMPC_FIT_MAX);
+    if (fit && (degree < 0 || degree > 2))
+        return fail(h, SMPC_EINVAL, "%s: degree %d: a polynomial of degree 0, 1 or 2", who, degree);
     if (h->seen.B && (h->seen.B != h->world.B || h->seen_T != h->world_T))
         return fail(h, SMPC_EINVAL, "%s: the instance observed track was set for %d instances and %lld columns, but the instance world "
                     "track for %d instances and %lld columns (smpc_set_instance_observed_track: clear it or set one of the world's "
@@ -1898,16 +1901,19 @@ static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit,
     const int n_rec = B * nr;
     // (one-wavefront blocks, as for every small kernel of the policy step: see check_nodes_dev)
     const dim3 grd((unsigned)((n_rec + 63) / 64)), blk(64);
-    // (the fit last: a kernel's place in the code object follows its first mention, and the three older ones keep theirs)
+    // (the fit and the polynomial last: a kernel's place in the code object follows its first mention, and the older ones keep theirs)
     if (!fit && mode == SMPC_FORECAST_HOLD)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_HOLD>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
     else if (!fit && mode == SMPC_FORECAST_CV)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_CV>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
     else if (!fit)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_TRUE>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
-    else            // four lanes to a record: see k_scene_fit
+    else if (degree == 1)       // four lanes to a record: see k_scene_fit
         hipLaunchKernelGGL(k_scene_fit, dim3((unsigned)((4 * (size_t)n_rec + 63) / 64)), blk, 0, h->stream, 4 * n_rec, nr, N, window, seen,
                            h->scene.d.p);
+    else                        // degrees 0 and 2: the same mapping
+        hipLaunchKernelGGL(k_scene_poly, dim3((unsigned)((4 * (size_t)n_rec + 63) / 64)), blk, 0, h->stream, 4 * n_rec, nr, N, window, degree,
+                           seen, h->scene.d.p);
     HIPCHK(h, hipGetLastError());
     h->scene.commit(B);
     h->scene_T = N + 1;
@@ -1933,6 +1939,12 @@ int smpc_forecast_scene_fit(smpc_handle* h, int B, int window, int n_sel, const 
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     return forecast_into_scene(h, "smpc_forecast_scene_fit", B, true, window, n_sel, select);
+}
+
+int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int n_sel, const int32_t* select) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    return forecast_into_scene(h, "smpc_forecast_scene_poly", B, true, window, n_sel, select, degree);
 }
 
 // a scene that stands still: the track of one column

@@ -149,6 +149,119 @@ __global__ __launch_bounds__(64) void k_scene_fit(int n_piece, int n_rows, int N
     }
 }
 
+// The weights of a least-squares parabola y(tau) = a + b tau + c tau^2 through m equally spaced samples at tau = -j, ages j = 0..m-1,
+// for m = 3..SMPC_FIT_MAX (rows 1 and 2 stay zero and are not read), and the weight of the window mean, 1 / m:
+//   ua_j = (3(3m^2 - 3m + 2) - 18(2m - 1) j + 30 j^2)                        / (m (m + 1)(m + 2))      a, the value now
+//   uv_j = ((36m^3 - 96m^2 + 36m + 24) + (-192m^2 + 180m + 48) j + 180 m j^2) / (m (m^2 - 1)(m^2 - 4))  v = b + c, the first step
+//   ue_j = (60 ((m - 1)(m - 2) - 6(m - 1) j + 6 j^2))                        / (m (m^2 - 1)(m^2 - 4))  e = 2c, the step of the step
+// Numerators stay below 2^31 and denominators reach 33 390 720 at m = 32, so the integers are formed in 64 bits; every weight is ONE
+// correctly rounded division, done by the compiler: the bits of problem.poly_weights.  Row m starts at m (m - 1) / 2, as in
+// FIT_WEIGHTS, and like it the table lies in the code object's constant data: no upload.
+struct PolyWeights {
+    double ua[SMPC_FIT_MAX * (SMPC_FIT_MAX + 1) / 2], uv[SMPC_FIT_MAX * (SMPC_FIT_MAX + 1) / 2], ue[SMPC_FIT_MAX * (SMPC_FIT_MAX + 1) / 2];
+    double mean[SMPC_FIT_MAX + 1];
+    constexpr PolyWeights() : ua{}, uv{}, ue{}, mean{} {
+        for (long long m = 1; m <= SMPC_FIT_MAX; m++) {
+            mean[m] = 1.0 / (double)m;
+            if (m < 3) continue;
+            const long long da = m * (m + 1) * (m + 2), dv = m * (m * m - 1) * (m * m - 4);
+            for (long long j = 0; j < m; j++) {
+                ua[m * (m - 1) / 2 + j] = (double)(3 * (3 * m * m - 3 * m + 2) - 18 * (2 * m - 1) * j + 30 * j * j) / (double)da;
+                uv[m * (m - 1) / 2 + j] =
+                    (double)((36 * m * m * m - 96 * m * m + 36 * m + 24) + (-192 * m * m + 180 * m + 48) * j + 180 * m * j * j) / (double)dv;
+                ue[m * (m - 1) / 2 + j] = (double)(60 * ((m - 1) * (m - 2) - 6 * (m - 1) * j + 6 * j * j)) / (double)dv;
+            }
+        }
+    }
+};
+__constant__ constexpr PolyWeights POLY_WEIGHTS{};
+
+// k_scene_poly: F [B][N+1][n_rows][SMPC_SCENE_ROW] from S = seen.geom by a least-squares polynomial of degree 0 or 2 through the last
+// `window` columns seen (degree 1 is k_scene_fit itself: the engine launches that).  With t, col, m and y_j as in k_scene_fit and the
+// effective degree p = min(degree, m - 1) -- one sample gives a constant, two give a line -- for all eight slots
+//   p = 0   a = u y_0;  a = a + u y_j,  u = 1 / m;                      F[b][k] = a, k = 0..N          -- stored, not added
+//   p = 1   a and d of k_scene_fit with FIT_WEIGHTS (m = 2 only);       F[b][0] = a, F[b][k] = F[b][k-1] + d
+//   p = 2   a, v, e each x = u_0 y_0;  x = x + u_j y_j  with ua, uv, ue;  F[b][0] = a,  F[b][k] = F[b][k-1] + v;  v = v + e
+// every product rounded before its sum (rounded_product): problem.poly_forecast_statement operation for operation, so the kernel
+// equals it bit for bit.  The mapping is k_scene_fit's and for its reasons: a thread owns ONE 16-byte piece of a record, four
+// neighbouring lanes a whole 64-byte record, a wavefront's access 16 whole records; FIT_AHEAD age loads are issued before the first
+// is used.  m and p come from one clock cell, so they are wave-uniform: the age loop has a scalar bound, the weights are uniform reads
+// of the constant tables, and the branches on p are scalar -- the line's tail adds no zero e (-0.0 + 0.0 is not -0.0) and the
+// constant's adds nothing.  The live set is three accumulators of the piece and FIT_AHEAD samples in flight.  Nothing is shared
+// between threads: an instance's result depends neither on B nor on its neighbours.  No atomics, no LDS.
+__global__ __launch_bounds__(64) void k_scene_poly(int n_piece, int n_rows, int N, int window, int degree, SceneSrc seen,
+                                                   double* __restrict__ F) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_piece) return;
+    const int rec_i = i / (SMPC_SCENE_ROW / 2), q = i % (SMPC_SCENE_ROW / 2);
+    const int b = rec_i / n_rows, r = rec_i % n_rows;
+    const int64_t t = scene_time(seen);
+    const int64_t shown = (t < 0 ? 0 : t) + 1;
+    const int m = shown < window ? (int)shown : window;
+    const int p = degree < m - 1 ? degree : m - 1;
+    const int row = m * (m - 1) / 2;
+    const double* __restrict__ ua = p == 2 ? POLY_WEIGHTS.ua + row : FIT_WEIGHTS.u + row;
+    const double* __restrict__ uv = p == 2 ? POLY_WEIGHTS.uv + row : FIT_WEIGHTS.w + row;
+    const double* __restrict__ ue = POLY_WEIGHTS.ue + row;
+    const double mean = POLY_WEIGHTS.mean[m];
+    const size_t piece = (size_t)r * SMPC_SCENE_ROW + 2 * q;
+    const auto sample = [&](int j) {
+        const int age = j < m ? j : m - 1;
+        return *static_cast<const ScenePiece*>(__builtin_assume_aligned(scene_block(seen, b, t - age, n_rows) + piece, 16));
+    };
+    ScenePiece a{0.0, 0.0}, v{0.0, 0.0}, e{0.0, 0.0};
+    for (int j0 = 0; j0 < m; j0 += FIT_AHEAD) {
+        ScenePiece y[FIT_AHEAD];
+#pragma unroll
+        for (int l = 0; l < FIT_AHEAD; l++) y[l] = sample(j0 + l);
+#pragma unroll
+        for (int l = 0; l < FIT_AHEAD; l++) {
+            const int j = j0 + l;
+            if (j >= m) break;
+            const double wa = p == 0 ? mean : ua[j];
+            const ScenePiece pa{rounded_product(wa, y[l].a), rounded_product(wa, y[l].b)};
+            if (j == 0) {       // (x = u_0 y_0, not 0 + u_0 y_0: a -0.0 stays one)
+                a = pa;
+            } else {
+                a.a = a.a + pa.a; a.b = a.b + pa.b;
+            }
+            if (p >= 1) {
+                const ScenePiece pv{rounded_product(uv[j], y[l].a), rounded_product(uv[j], y[l].b)};
+                if (j == 0) {
+                    v = pv;
+                } else {
+                    v.a = v.a + pv.a; v.b = v.b + pv.b;
+                }
+            }
+            if (p == 2) {
+                const ScenePiece pe{rounded_product(ue[j], y[l].a), rounded_product(ue[j], y[l].b)};
+                if (j == 0) {
+                    e = pe;
+                } else {
+                    e.a = e.a + pe.a; e.b = e.b + pe.b;
+                }
+            }
+        }
+    }
+    ScenePiece* out = static_cast<ScenePiece*>(__builtin_assume_aligned(F + (size_t)b * (size_t)(N + 1) * n_rows * SMPC_SCENE_ROW + piece, 16));
+    const size_t step = (size_t)n_rows * (SMPC_SCENE_ROW / 2);      // in pieces
+    *out = a;
+    if (p == 2) {
+        for (int k = 1; k <= N; k++) {
+            a.a = a.a + v.a; a.b = a.b + v.b;
+            v.a = v.a + e.a; v.b = v.b + e.b;
+            out[k * step] = a;
+        }
+    } else if (p == 1) {
+        for (int k = 1; k <= N; k++) {
+            a.a = a.a + v.a; a.b = a.b + v.b;
+            out[k * step] = a;
+        }
+    } else {
+        for (int k = 1; k <= N; k++) out[k * step] = a;
+    }
+}
+
 // k_forecast_context: the context rows of a scene-aware safe-set network from the same F, one thread per number:
 //   ctx[b][k][i] = (float)((F[b][k][row_i][slot_i] - mean[i]) / std[i])       -- the expression of k_ctx_normalise
 // sel: which (row, slot) of the scene context number i is, by value like nm (at most MLP_KPAD pairs: no device block to keep, and a

@@ -572,6 +572,86 @@ def fit_forecast_statement(seen, t, N, window):
     return F
 
 
+def poly_weights(m, degree):
+    """The weights of a least-squares polynomial of degree ``p = min(degree, m - 1)`` through m equally spaced samples y_j of ages
+    j = 0..m-1 (j = 0 the newest; the model is y(tau) = a + b tau + c tau^2 at tau = -j), a tuple of float64 arrays of length m:
+
+    ``p = 0``  ``(u,)`` with ``u_j = 1.0 / float(m)``: the window mean.
+    ``p = 1``  ``fit_weights(m)``: the line's value now and its step per column.
+    ``p = 2``  ``(ua, uv, ue)``: ``sum ua_j y_j`` is a, the value now; ``sum uv_j y_j`` is v = b + c, the first step F[1] - F[0];
+               ``sum ue_j y_j`` is e = 2c, the step of the step:
+               ``ua_j = (3(3m^2 - 3m + 2) - 18(2m - 1) j + 30 j^2) / (m (m + 1)(m + 2))``
+               ``uv_j = ((36m^3 - 96m^2 + 36m + 24) + (-192m^2 + 180m + 48) j + 180 m j^2) / (m (m^2 - 1)(m^2 - 4))``
+               ``ue_j = (60 ((m - 1)(m - 2) - 6(m - 1) j + 6 j^2)) / (m (m^2 - 1)(m^2 - 4))``
+               At m = 3 they are integers, ua = (1, 0, 0), uv = (2, -3, 1), ue = (1, -2, 1): the parabola through three columns.
+
+    Numerators and denominators are integers (below 2^31 and up to 33 390 720 at m = 32), so each weight is one correctly rounded
+    division -- the bits of the engine's table (POLY_WEIGHTS, kernels_forecast.hpp)."""
+    m, degree = int(m), int(degree)
+    if not 1 <= m <= FIT_MAX:
+        raise ValueError(f'poly_weights: m={m}: expected 1..{FIT_MAX}')
+    if not 0 <= degree <= 2:
+        raise ValueError(f'poly_weights: degree={degree}: expected 0, 1 or 2')
+    p = min(degree, m - 1)
+    if p == 0:
+        return (np.full(m, 1.0 / float(m)),)
+    if p == 1:
+        return fit_weights(m)
+    j = np.arange(m, dtype=np.int64)
+    da, dv = m * (m + 1) * (m + 2), m * (m * m - 1) * (m * m - 4)
+    ua = (3 * (3 * m * m - 3 * m + 2) - 18 * (2 * m - 1) * j + 30 * j * j).astype(float) / float(da)
+    uv = ((36 * m ** 3 - 96 * m * m + 36 * m + 24) + (-192 * m * m + 180 * m + 48) * j + 180 * m * j * j).astype(float) / float(dv)
+    ue = (60 * ((m - 1) * (m - 2) - 6 * (m - 1) * j + 6 * j * j)).astype(float) / float(dv)
+    return ua, uv, ue
+
+
+def poly_forecast_statement(seen, t, N, window, degree):
+    """[B, N + 1, n_rows, SCENE_ROW]: the horizon's scenes forecast at time ``t`` by a least-squares polynomial of degree 0, 1 or 2
+    through the last ``window`` columns of ``seen [B, T, n_rows, SCENE_ROW]``, what the controller has seen of the world -- the numpy
+    statement of smpc_forecast_scene_poly and its readable definition.  ``t``, ``col``,
+    ``m = min(window, max(t, 0) + 1)`` and ``y_j = S[col(t - j)]`` as in :func:`fit_forecast_statement`; the effective degree is
+    ``p = min(degree, m - 1)`` -- nothing was seen before time 0, so one sample gives a constant and two give a line.  With
+    ``poly_weights(m, p)``, for all eight slots of a record:
+
+    ``p = 0``  ``a = u_0 y_0; a = a + u_j y_j`` (j = 1..m-1, every product rounded before its sum); ``F[k] = a`` for every k --
+               stored, not added, so a -0.0 stays one.  The window mean; with m = 1 it is 'hold' bit for bit.
+    ``p = 1``  ``fit_forecast_statement(seen, t, N, m)``: today's line, bit for bit.
+    ``p = 2``  ``a``, ``v``, ``e`` each as ``x = u_0 y_0; x = x + u_j y_j`` in increasing j, every product rounded before its sum;
+               ``F[0] = a``, then for k = 1..N: ``F[k] = F[k-1] + v; v = v + e``, in that order -- repeated addition, as 'cv' and the
+               fit: a constant-acceleration model.  The kernel repeats it bit for bit."""
+    S = np.asarray(seen, float)
+    if S.ndim != 4 or S.shape[3] != SCENE_ROW:
+        raise ValueError(f'poly_forecast_statement: expected a world track [B, T, n_rows, {SCENE_ROW}], got {S.shape}')
+    window, degree = int(window), int(degree)
+    if not 1 <= window <= FIT_MAX:
+        raise ValueError(f'poly_forecast_statement: window {window}: expected 1..{FIT_MAX}')
+    if not 0 <= degree <= 2:
+        raise ValueError(f'poly_forecast_statement: degree {degree}: expected 0, 1 or 2')
+    T, N = S.shape[1], int(N)
+    t = 0 if t is None else min(max(int(t), -2 ** 62), 2 ** 62)
+    m = min(window, max(t, 0) + 1)
+    p = min(degree, m - 1)
+    if p == 1:
+        return fit_forecast_statement(S, t, N, m)
+    us = poly_weights(m, p)
+    y = S[:, scene_column(t, T)]
+    acc = [u[0] * y for u in us]
+    for j in range(1, m):
+        y = S[:, scene_column(t - j, T)]
+        acc = [x + u[j] * y for x, u in zip(acc, us)]
+    F = np.empty((S.shape[0], N + 1) + S.shape[2:])
+    F[:, 0] = acc[0]
+    if p == 0:
+        for k in range(1, N + 1):
+            F[:, k] = acc[0]
+        return F
+    v, e = acc[1], acc[2]
+    for k in range(1, N + 1):
+        F[:, k] = F[:, k - 1] + v
+        v = v + e
+    return F
+
+
 def observe_tracks(prob, world, sigma, seed=0):
     """[B, T, n_rows, SCENE_ROW]: ``world`` as a sensor with independent noise shows it -- every obstacle's position in every
     (instance, column) off by its own N(0, sigma^2) draw per axis, one draw per (instance, obstacle, column) shared by all the rows

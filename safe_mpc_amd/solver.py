@@ -297,6 +297,16 @@ class BatchedOcpSolver:
         with self._ordered('torch' in sys.modules):         # (as forecast_scene)
             self._chk(self.L.smpc_forecast_scene_fit(self.h, B, int(window), len(sel), sel.ctypes.data if len(sel) else None))
 
+    def forecast_scene_poly(self, window, degree, select=None, B=None):
+        """The horizon's N + 1 scenes forecast by a least-squares polynomial of degree 0, 1 or 2 through the last ``window``
+        (1..``problem.FIT_MAX``) columns of what was seen, at the scene clock, into the scene slot (smpc_forecast_scene_poly;
+        ``problem.poly_forecast_statement`` is its definition).  Enqueue-only; ``select`` and ``B`` as for :meth:`forecast_scene`.
+        Degree 1 is :meth:`forecast_scene_fit`, degree 0 the window mean, degree 2 a constant-acceleration model."""
+        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
+        B = int(getattr(self, '_world_B', 0) if B is None else B)
+        with self._ordered('torch' in sys.modules):         # (as forecast_scene)
+            self._chk(self.L.smpc_forecast_scene_poly(self.h, B, int(window), int(degree), len(sel), sel.ctypes.data if len(sel) else None))
+
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on
         the device whenever a kernel runs -- write to it between calls (stream-ordered, no synchronisation), or hand over the

@@ -10,9 +10,13 @@
    16, 32 at clock 50 (every window full), the same 3 + 10 calls between HIP events.
 4. The closed loop under observation noise: the tracks of 2 seen through observe_tracks (sigma SMPC_OBS_NOISE, default 0.005), the arms
    true (the clairvoyant reference, which observes nothing), cv and fit with windows 4, 8, 16 -- noise against lag by window length.
+5. k_scene_poly alone beside k_scene_fit (profiles/scene_forecast_poly.txt): the shapes and the observed track of 3, windows 4, 8, 16,
+   32, the line (smpc_forecast_scene_fit) and degrees 0 and 2 (smpc_forecast_scene_poly) window by window.
+6. The closed loop on the turning tracks of 2, without observation noise (the controller sees the world) and with it (as 4): the arms
+   true, cv, and the polynomial fit of degrees 1, 0 and 2 with windows 4, 8, 16, 32 -- lag against noise by window length and degree.
 A measurement tool, not a test; it reads nothing outside the repository.
 
-    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop]"""
+    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop]"""
 import os
 import sys
 
@@ -59,7 +63,7 @@ def kernel_times(B):
     s.close()
 
 
-def fit_kernel_times(B):
+def fit_kernel_times(B, poly=False):
     import torch
     par, prob, net = bench.build_problem()
     s = BatchedOcpSolver(prob, net)
@@ -73,8 +77,13 @@ def fit_kernel_times(B):
     stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
     rec = B * len(prob.rows) * 64 / 1e6                         # MB per column of the table
     with torch.cuda.stream(stream):
-        for name, call, cols in [('k_scene_forecast cv', lambda: s.forecast_scene('cv'), 2)] + \
-                [(f'k_scene_fit window {m:2d}', (lambda m=m: s.forecast_scene_fit(m)), m) for m in (2, 4, 8, 16, 32)]:
+        calls = [('k_scene_forecast cv', lambda: s.forecast_scene('cv'), 2)] + \
+            [(f'k_scene_fit window {m:2d}', (lambda m=m: s.forecast_scene_fit(m)), m) for m in (2, 4, 8, 16, 32)]
+        if poly:        # the line and the two new degrees side by side, window by window
+            calls = [c for m in (4, 8, 16, 32) for c in
+                     [(f'k_scene_fit window {m:2d}', (lambda m=m: s.forecast_scene_fit(m)), m)] +
+                     [(f'k_scene_poly window {m:2d} degree {p}', (lambda m=m, p=p: s.forecast_scene_poly(m, p)), m) for p in (0, 2)]]
+        for name, call, cols in calls:
             for _ in range(3):
                 call()
             ms = []
@@ -94,7 +103,7 @@ def fit_kernel_times(B):
     s.close()
 
 
-def loop_times(B, noisy=False):
+def loop_times(B, noisy=False, poly=False):
     from safe_mpc_amd import controller as C
     par, prob, net = bench.build_problem()
     par.N = prob.N
@@ -114,6 +123,14 @@ def loop_times(B, noisy=False):
         kwargs = {'true': {'forecast': 'true'}, 'cv': {'forecast': 'cv', 'observed': seen}}
         kwargs.update({f'fit{m}': {'forecast': 'fit', 'forecast_window': m, 'observed': seen} for m in (4, 8, 16)})
         print(f'observation noise sigma = {sigma}')
+    elif poly:          # the controller sees the world itself: what is left is the lag
+        kwargs = {'true': {'forecast': 'true'}, 'cv': {'forecast': 'cv'}}
+        print('no observation noise')
+    if poly:            # every window with the line, the mean and the parabola
+        what = {} if not noisy else {'observed': seen}
+        arms = ['true', 'cv'] + [f'fit{m}d{p}' for m in (4, 8, 16, 32) for p in (1, 0, 2)]
+        kwargs.update({f'fit{m}d{p}': {'forecast': 'fit', 'forecast_window': m, 'forecast_degree': p, **what}
+                       for m in (4, 8, 16, 32) for p in (1, 0, 2)})
     res = {a: [] for a in arms}
     for r in range(rounds + 1):                                 # (round 0 warms everything up)
         for arm in arms:
@@ -125,7 +142,7 @@ def loop_times(B, noisy=False):
             print(f'round {r} forecast={arm}: {tm["ms_per_step"]:.3f} ms per step; conv / collisions / viable / unconv = {counts}', flush=True)
     for arm in arms:
         a = np.array(res[arm])
-        print(f'forecast={str(arm):>4}: {a[:, 0].mean():.3f} ms per closed-loop step (rounds {a[:, 0].min():.3f} .. {a[:, 0].max():.3f}); '
+        print(f'forecast={str(arm):>8}: {a[:, 0].mean():.3f} ms per closed-loop step (rounds {a[:, 0].min():.3f} .. {a[:, 0].max():.3f}); '
               f'conv {int(a[0, 1])}, collisions {int(a[0, 2])}, viable {int(a[0, 3])}, unconv {int(a[0, 4])}; B = {B}, N = {N}, {steps} steps')
 
 
@@ -140,6 +157,11 @@ def main(argv=None):
         fit_kernel_times(B)
     if 'fit-loop' in what:
         loop_times(B, noisy=True)
+    if 'poly-kernel' in what:
+        fit_kernel_times(B, poly=True)
+    if 'poly-loop' in what:
+        loop_times(B, poly=True)
+        loop_times(B, noisy=True, poly=True)
     return 0
 
 

@@ -18,6 +18,9 @@ against a forecast of it formed every step from the columns the world has shown 
 frozen world, a constant-velocity extrapolation, or the world itself.  The result file's name gets the suffix ``_fc<mode>``.
 --scene-forecast fit [--forecast-window M] (M = 1..32, default 8): the forecast is a least-squares line through the last M columns seen
 (run_mpc(forecast='fit', forecast_window=M)); suffix ``_fcfit_w<M>``.
+--forecast-degree P (P = 0, 1 or 2, default 1; needs --scene-forecast fit): the fit is a least-squares polynomial of degree P through
+those columns (run_mpc(forecast_degree=P)) -- 0 the window mean, 2 a constant-acceleration model; suffix ``_d<P>``
+behind ``_w<M>`` for P other than 1.
 --scene-obs-noise SIGMA [--scene-obs-seed S] (needs --scene-forecast hold, cv or fit): the controller sees the world through a sensor --
 every obstacle's position in every column off by its own N(0, SIGMA^2) draw per axis (problem.observe_tracks, seed S, default 0), and
 the forecast is formed from that (run_mpc(observed=...)); the plant meets the true world.  Suffix ``_on<SIGMA>`` for SIGMA > 0.
@@ -73,6 +76,11 @@ def main(argv=None):
         raise SystemExit('--forecast-window needs --scene-forecast fit: no other forecast has a window')
     if forecast == 'fit' and not 1 <= window <= 32:
         raise SystemExit(f'--forecast-window {window}: expected 1..32')
+    degree = opt('--forecast-degree', 1, int)
+    if '--forecast-degree' in raw and forecast != 'fit':
+        raise SystemExit('--forecast-degree needs --scene-forecast fit: no other forecast has a degree')
+    if not 0 <= degree <= 2:
+        raise SystemExit(f'--forecast-degree {degree}: expected 0, 1 or 2')
     for flag in ('--scene-obs-noise', '--scene-obs-seed'):
         if flag in raw and forecast not in ('hold', 'cv', 'fit'):
             raise SystemExit(f'{flag} needs --scene-forecast hold, cv or fit: nothing else reads what was observed')
@@ -95,6 +103,8 @@ def main(argv=None):
     fc_kw, name_kw = ({} if forecast is None else {'forecast': forecast}), ({} if forecast is None else {'forecast': forecast})
     if forecast == 'fit':
         fc_kw['forecast_window'] = name_kw['forecast_window'] = window
+    if degree != 1:             # (degree 1 is the fit of before: its call and its file name)
+        fc_kw['forecast_degree'] = name_kw['forecast_degree'] = degree
     if '--scene-obs-noise' in raw:
         from safe_mpc_amd.problem import OcpProblem, observe_tracks
         fc_kw['observed'] = observe_tracks(OcpProblem(params, 'naive'), scenes, obs_noise, opt('--scene-obs-seed', 0, int))
