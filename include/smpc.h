@@ -228,7 +228,8 @@ int smpc_set_stage_bounds(smpc_handle* h, const double* lo, const double* hi);
 int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const double* hi, int on_device);
 
 /* A scene of its own for every instance: where each collision row's FIXED obstacle sits in the world, per instance.  Geometry only:
- * the rows themselves stay shared -- kinds, robot points, len2, bounds lb / ub and every check bound come from the descriptor.
+ * the rows themselves stay shared -- kinds, robot points, len2, bounds lb / ub and every check bound come from the descriptor
+ * (the bounds lb / ub have a slot of their own: smpc_set_instance_row_bounds).
  * geom is [B][n_rows][SMPC_SCENE_ROW] doubles, one 64-byte record {C[3], D[3], offset, 0} per (instance, row), of which a row
  * reads by kind
  *   SMPC_ROW_SEG_FIXEDSEG  C, D (the fixed capsule's end points)      SMPC_ROW_SEG_POINT, _POINT_POINT  C (the fixed point)
@@ -371,6 +372,26 @@ int smpc_forecast_scene_fit(smpc_handle* h, int B, int window, int n_sel, const 
  * model.  degree 2 with window 2 is SMPC_FORECAST_CV and degree 0 with window 1 SMPC_FORECAST_HOLD, bit for bit at every clock.
  * (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int n_sel, const int32_t* select);
+
+/* Row bounds per instance and node: how much room a collision row leaves, along the horizon (obstacle inflation).  lo and hi are
+ * [B][N+1][n_rows] doubles, N the handle's horizon at the call; entry (b, k, r) REPLACES rows[r].lb / .ub of the descriptor for node k
+ * of instance b wherever the OCP's own row bounds are read: the row's lo = lb - v and hi = ub - v of the QP, the rows_at_node0
+ * infeasibility test (the only reader of node 0) and the rows' l1 violation of the merit.  A value with |v| >= SMPC_INF is an
+ * absent side, as in the descriptor.  The table is read along the horizon from node 0, like a forecast in the scene slot: it needs no
+ * clock, and it is independent of the scene, world, observed and context slots (smpc_forecast_scene leaves it in force).
+ *   reads it, and guards its B (another B: SMPC_EINVAL naming the call, both sizes and this setter):
+ *       smpc_solve_batch, smpc_sqp_batch, smpc_merit_terms, smpc_policy_step kinds 0-4 (the solve only), smpc_debug_stage_records
+ *   does not read it -- what counts as a collision stays physical, the caller's check bounds:
+ *       smpc_check_trajectory, smpc_check_guess, smpc_score_rollout, smpc_loop_post, smpc_ik_batch, the x_temp test of smpc_policy_step
+ *   refuses it (SMPC_ESTATE while it is set, whatever its B): SMPC_POLICY_PARALLEL and smpc_rollout_batch
+ * The handle keeps a copy (stream-ordered; with host pointers the call waits for it, device pointers are taken as they are).  The
+ * same B is overwritten in place, so a captured solve keeps seeing the buffer and replays with the new table; lo == hi == NULL clears
+ * it; smpc_set_horizon drops it (it is laid out by N), as it drops the instance bounds.  A refused call changes nothing.
+ * SMPC_EINVAL: B <= 0, a descriptor without rows, exactly one of the two pointers NULL, or (host pointers only) a NaN, or lo > hi
+ * where both sides are present -- the message names (b, k, r).
+ * SMPC_ESTATE: the copy would have to grow while the stream is being captured (the old table stays in force).
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_set_instance_row_bounds(smpc_handle* h, int B, const double* lo, const double* hi, int on_device);
 
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle

@@ -23,7 +23,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves',
            'smpc_set_instance_scene_track', 'smpc_set_scene_clock', 'smpc_set_mlp_context', 'smpc_set_instance_context',
            'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene',
-           'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit', 'smpc_forecast_scene_poly']
+           'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit', 'smpc_forecast_scene_poly', 'smpc_set_instance_row_bounds']
 
 
 class EngineError(RuntimeError):
@@ -136,6 +136,7 @@ def lib():
     L.smpc_set_stage_bounds.argtypes = [vp, dp, dp]
     L.smpc_set_slack_weights.argtypes = [vp, dp]
     L.smpc_set_instance_bounds.argtypes = [vp, C.c_int, dp, dp, C.c_int]
+    L.smpc_set_instance_row_bounds.argtypes = [vp, C.c_int, dp, dp, C.c_int]
     L.smpc_set_instance_scene.argtypes = [vp, C.c_int, dp, C.c_int]
     L.smpc_set_instance_scene_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_set_scene_clock.argtypes = [vp, dp]

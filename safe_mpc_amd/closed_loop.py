@@ -30,12 +30,13 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
 
 
 def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None,
-                forecast_window=None, obs_noise=0.0, forecast_degree=1):
+                forecast_window=None, obs_noise=0.0, forecast_degree=1, row_margin=None):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
     before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
     it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns, ``_d<p>`` behind that for ``forecast_degree = p`` other than 1
     (a polynomial fit, --forecast-degree); ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
-    that; the defaults give the reference's name"""
+    that; ``row_margin = (a, b)`` (--row-margin, run_mpc(row_margin=...)): ``_rm<a>`` behind that, and ``_g<b>`` for b other than 0;
+    the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
     track = 'traj_track' if params.track_traj else ''
@@ -44,7 +45,9 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
             f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}"
             f"{f'_w{int(forecast_window)}' if forecast == 'fit' else ''}"
             f"{f'_d{int(forecast_degree)}' if forecast == 'fit' and int(forecast_degree) != 1 else ''}"
-            f"{f'_on{obs_noise}' if obs_noise > 0 else ''}_mpc.pkl")
+            f"{f'_on{obs_noise}' if obs_noise > 0 else ''}"
+            f"{'' if row_margin is None else f'_rm{float(row_margin[0])}' + (f'_g{float(row_margin[1])}' if float(row_margin[1]) != 0.0 else '')}"
+            "_mpc.pkl")
 
 
 def tracking_from_cli(params, argv, n=None):
@@ -1073,7 +1076,7 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None, forecast_degree=1):
+                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None, forecast_degree=1, row_margin=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
@@ -1100,6 +1103,19 @@ class _Group:
                 for sv in (ctrl.ocp_solver, backup.ocp_solver):
                     if not hasattr(sv, 'set_scene_clock'):
                         raise ValueError(f'scenes: {type(sv).__name__} has no set_scene_clock')
+        # row bounds that leave more room along the horizon (run_mpc(row_margin=(a, b))): d_k = a + b k metres at
+        # node k, the same for every instance.  The controller's handle gets its table once, here; the backup handle gets the rows of
+        # the aborting instances, over its own horizon, before each of its compact solves (_backup_row_bounds).
+        self._row_bounds = None
+        if row_margin is not None:
+            from .problem import inflated_row_bounds
+            for sv in (ctrl.ocp_solver, backup.ocp_solver):
+                if not hasattr(sv, 'set_instance_row_bounds'):
+                    raise ValueError(f'row_margin: {type(sv).__name__} has no set_instance_row_bounds')
+            a, g = (float(v) for v in row_margin)
+            lo, hi = inflated_row_bounds(ctrl.problem, B, a + g * np.arange(ctrl.N + 1))
+            ctrl.ocp_solver.set_instance_row_bounds(xp.asarray(lo, xp.f64), xp.asarray(hi, xp.f64))
+            self._row_bounds = tuple(xp.asarray(v, xp.f64) for v in inflated_row_bounds(backup.problem, B, a + g * np.arange(backup.N + 1)))
         # stats.append(controller.getTime()) of scripts/mpc.py:239: one row of the seven time_fields per step of this group's
         # controller (host: read when step() returns; device: _DeviceGroup._read_times)
         self._collect_times = bool(collect_times) and hasattr(ctrl.ocp_solver, 'timing_history')
@@ -1153,6 +1169,11 @@ class _Group:
             _set_scene(self._backup.ocp_solver, self._scenes[rows])
         else:       # (what the controller knows of these instances' world at the event, over the backup's own horizon)
             self._backup_forecast(rows)
+
+    def _backup_row_bounds(self, rows):
+        """... and with the aborting instances' rows of the inflated row bounds, over the backup's own horizon"""
+        if self._row_bounds is not None:
+            self._backup.ocp_solver.set_instance_row_bounds(self._row_bounds[0][rows], self._row_bounds[1][rows])
 
     def _hand_over_models(self, table=None):
         """the group's controller models onto the controller's handle: ``table`` (the subclass's form of the rows it was given), or
@@ -1233,6 +1254,9 @@ class _Group:
                         sv.set_instance_observed_track(None)
                     if hasattr(sv, 'set_instance_world_track'):
                         sv.set_instance_world_track(None)
+        if self._row_bounds is not None:           # (nor a row-bounds table)
+            solver.set_instance_row_bounds(None)
+            self._backup.ocp_solver.set_instance_row_bounds(None)
         if self._models is not None:               # (nor a model table)
             _set_models(solver, None)
             _set_models(self._backup.ocp_solver, None)
@@ -1347,6 +1371,7 @@ class _HostGroup(_Group):
         xv_c = ctrl.getLastViableState()[rows]
         xg_c = np.repeat(xv_c[:, None, :], Nb + 1, axis=1)
         self._backup_scene(rows)
+        self._backup_row_bounds(rows)
         self._backup_models(rows)
         _write_scene_clock(self._backup_clock, j)
         xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(np.ascontiguousarray(xv_c), xg_c, np.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
@@ -1507,6 +1532,7 @@ class _DeviceGroup(_Group):
             self._side.wait_event(ev0)
             xg_c = xp.repeat_nodes(xv_c, Nb + 1)
             self._backup_scene(rows_b)
+            self._backup_row_bounds(rows_b)
             self._backup_models(rows_b)
             xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
             ev = torch.cuda.Event()
@@ -1625,7 +1651,7 @@ def _check_state_kind(ctrl, backup, on_device):
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
             score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None,
-            forecast_degree=None):
+            forecast_degree=None, row_margin=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1692,7 +1718,13 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     (``perturbed_joint_tables`` with the instances' seeds; on the device the same tensor) -- the matched-model arm of the model-noise
     study, which needs ``noise > 0`` --; a ``JOINT_DTYPE`` table [B, nq]: each group gets its rows.  The backup OCP of an abort
     event is solved with the aborting instances' models, and both handles are left without a table when the run ends.  Not with the
-    parallel policy (ValueError), and the plant keeps stepping with its own tables whatever the controller is given."""
+    parallel policy (ValueError), and the plant keeps stepping with its own tables whatever the controller is given.
+    ``row_margin`` ``(a, b)``: obstacle inflation along the horizon -- node k of every solve leaves
+    ``d_k = a + b k`` metres of extra room around the world-fixed obstacles (``problem.inflated_row_bounds``,
+    solver.set_instance_row_bounds), set once per group on the controller's handle before the loop, and on the backup handle, over its
+    own horizon, for the aborting instances of an abort event.  The outcome tests and the scores keep the physical check bounds.  With
+    or without ``scenes`` and ``forecast``; both handles are left without a table when the run ends and the result gains
+    ``'row_margin'``.  Not with the parallel policy (ValueError).  None: the calls of a run without the argument, one for one."""
     import time
     B = x_guess.shape[0]
     models = _check_models(models, B, noise, cont_name)
@@ -1703,6 +1735,13 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         scenes = np.ascontiguousarray(scenes, np.float64)
         if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
             raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
+    if row_margin is not None:
+        if cont_name == 'parallel':
+            raise ValueError("row_margin: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
+                             "the engine refuses a row-bounds table there)")
+        row_margin = tuple(float(v) for v in np.asarray(row_margin, float).reshape(-1))
+        if len(row_margin) != 2 or not all(np.isfinite(row_margin)):
+            raise ValueError(f'row_margin: expected (a, b), the margin a + b k metres at node k, got {row_margin}')
     if forecast is not None:
         from .problem import FIT_MAX, FORECAST_MODES
         if forecast != 'fit' and forecast not in FORECAST_MODES:
@@ -1754,6 +1793,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         args = (params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, collect_times)
         fit_kw = dict(forecast_window=int(forecast_window) if forecast == 'fit' else None, forecast_degree=degree,
                       observed=None if observed is None else observed[lo:hi])
+        if row_margin is not None:          # (a run without it constructs its groups with the arguments of before)
+            fit_kw['row_margin'] = row_margin
         if on_device:
             import torch
             sv = ctrl.ocp_solver
@@ -1851,6 +1892,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
             extra['forecast_window'] = int(forecast_window)
             if degree != 1:
                 extra['forecast_degree'] = degree
+    if row_margin is not None:
+        extra['row_margin'] = row_margin
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

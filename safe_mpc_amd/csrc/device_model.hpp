@@ -345,6 +345,31 @@ template <int NQ>
 __device__ __forceinline__ const smpc_joint* model_joints(const smpc_problem_desc* __restrict__, long b, const smpc_joint* __restrict__ table) {
     return table + (size_t)b * NQ;
 }
+// Whose bounds a collision row takes where the OCP's own row bounds are read (the stage builders and k_merit; never the tests
+// against a caller's check bounds): the descriptor's rows[r].lb / .ub, shared by every instance and node, or entry (b, k, r) of the
+// handle's table of smpc_set_instance_row_bounds, [lo | hi] with each half [B][N+1][n_rows].  The table rides in the same pack,
+// behind the model table, as ONE more pointer (a `const double*`): a kernel that was not handed it keeps its argument list, its
+// name and its code.  RowBounds<MJ...> says whether the pack holds it; ModelRowArg is ModelArg for a kernel that accepts it.
+template <class... MJ> constexpr bool RowBounds = (false || ... || std::is_same_v<MJ, double>);
+template <bool MODEL, class... MJ>
+constexpr bool ModelRowArg = sizeof...(MJ) == (MODEL ? 1 : 0) + (RowBounds<MJ...> ? 1 : 0) &&
+                             ((0 + ... + (std::is_same_v<MJ, smpc_joint> ? 1 : 0)) == (MODEL ? 1 : 0));
+template <int NQ> __device__ __forceinline__ const smpc_joint* model_joints(const smpc_problem_desc* __restrict__ D, long, const double* __restrict__) {
+    return D->joints;
+}
+template <int NQ>
+__device__ __forceinline__ const smpc_joint* model_joints(const smpc_problem_desc* __restrict__, long b, const smpc_joint* __restrict__ table,
+                                                          const double* __restrict__) {
+    return table + (size_t)b * NQ;
+}
+__device__ __forceinline__ const double* row_bounds_table(const double* __restrict__ t) { return t; }
+__device__ __forceinline__ const double* row_bounds_table(const smpc_joint* __restrict__, const double* __restrict__ t) { return t; }
+// {lb, ub} of row r at node k of instance b; n_rows is the table's row count, the descriptor's
+struct RowLbUb { double lb, ub; };
+__device__ __forceinline__ RowLbUb row_bounds_at(const double* __restrict__ t, long B, int N, int n_rows, long b, int k, int r) {
+    const size_t at = ((size_t)b * (N + 1) + k) * n_rows + r;
+    return {t[at], t[(size_t)B * (N + 1) * n_rows + at]};
+}
 
 template <bool SCENE>
 __device__ __forceinline__ RowGeom<SCENE> row_geom(const smpc_row& row, const double* __restrict__ geom_b, int r) {

@@ -130,6 +130,9 @@ struct smpc_handle {
     bool ctx_fc = false;            // the context was written by smpc_forecast_scene: read from time 0 (as scene_fc)
     InstSlot<smpc_joint> models{"instance model table", "smpc_set_instance_models"};    // [B][nq] the controller's joint records:
                                                                                         // the caller's inertials, the descriptor's rest
+    InstSlot<double> rowb{"instance row-bounds table", "smpc_set_instance_row_bounds"};   // [lo | hi], each [B][N+1][n_rows]: the
+                                    // collision rows' bounds per instance and node, read from node 0 without a
+                                    // clock by the stage builders and k_merit alone; laid out by the horizon, like `bounds`
     // network
     Net own_net;
     const Net* net = &own_net;      // the network this handle runs: its own, or the parent's in a worker of smpc_rollout_batch
@@ -569,6 +572,15 @@ template <class F> int with_model(const smpc_handle* h, int B, F&& f) {
     return f(std::false_type{});
 }
 
+// f(rb) with the handle's row-bounds table when it was set for B instances, else f() -- no argument at all, as with_model: the
+// launchers of the kernels that read the OCP's row bounds nest it innermost, take `auto... rb` and hand `md..., rb...` on.  (The
+// call without the table first: a kernel's place in the code object follows its first mention, and the older ones keep theirs.)
+template <class F> int with_row_bounds(const smpc_handle* h, int B, F&& f) {
+    const double* table = h->rowb.for_batch(B);
+    if (!table) return f();
+    return f(table);
+}
+
 // The guards of an entry point that evaluates collision rows and runs the network (SlotTag::guard)
 int guard_scene_and_context(smpc_handle* h, int B, const char* who) {
     const int rc = h->scene.guard(h, B, who);
@@ -578,6 +590,12 @@ int guard_scene_and_context(smpc_handle* h, int B, const char* who) {
 int guard_scene_context_and_models(smpc_handle* h, int B, const char* who) {
     const int rc = guard_scene_and_context(h, B, who);
     return rc ? rc : h->models.guard(h, B, who);
+}
+
+// ... and reads the OCP's own row bounds: the entry points that solve, or state the QP or its merit
+int guard_solve_slots(smpc_handle* h, int B, const char* who) {
+    const int rc = guard_scene_context_and_models(h, B, who);
+    return rc ? rc : h->rowb.guard(h, B, who);
 }
 
 // A forecast goes when its world or its horizon does (smpc_forecast_scene): the scene slot if it holds one, and the context if a
@@ -701,9 +719,11 @@ int launch_stage_records(smpc_handle* h, int B, const double* x0, const double* 
     with_rows(h, [&](auto MR) {
         return with_scene(h, B, [&](auto SCENE, auto sc) {
             return with_model(h, B, [&](auto MODEL, auto... md) {
-                hipLaunchKernelGGL((k_stage_build<NQ, MR, SCENE, MODEL>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
-                                   bd.hi, h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, sc, md...);
-                return SMPC_OK;
+                return with_row_bounds(h, B, [&](auto... rb) {
+                    hipLaunchKernelGGL((k_stage_build<NQ, MR, SCENE, MODEL>), grd, blk, 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
+                                       bd.hi, h->d_zl.p, nn, h->d_ws.p, bd.stride, h->d_active, zero_cnt, sc, md..., rb...);
+                    return SMPC_OK;
+                });
             });
         });
     });
@@ -722,9 +742,11 @@ int launch_stage_records_per_node(smpc_handle* h, int B, const double* x0, const
     const StageBounds bd = stage_bounds(h, B);
     const int tiles = (int)ev_tiles((size_t)B * (h->N + 1));
     with_rows(h, [&](auto MR) {
-        hipLaunchKernelGGL((k_qp_setup<NQ, MR>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
-                           bd.hi, h->d_zl.p, h->d_ev.p, h->d_ws.p, bd.stride, h->d_active);
-        return SMPC_OK;
+        return with_row_bounds(h, B, [&](auto... rb) {
+            hipLaunchKernelGGL((k_qp_setup<NQ, MR>), dim3(tiles), dim3(32 * EV_TILE), 0, h->stream, h->d_desc, B, h->N, x0, xg, ug, p, bd.lo,
+                               bd.hi, h->d_zl.p, h->d_ev.p, h->d_ws.p, bd.stride, h->d_active, rb...);
+            return SMPC_OK;
+        });
     });
     HIPCHK(h, hipGetLastError());
     return SMPC_OK;
@@ -1242,9 +1264,11 @@ int launch_merit(smpc_handle* h, int B, const SqpScratch& w, const double* x0, c
     }
     with_scene(h, B, [&](auto SCENE, auto sc) {
         return with_model(h, B, [&](auto MODEL, auto... md) {
-            hipLaunchKernelGGL((k_merit<NQ, SCENE, MODEL>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y, w.pos,
-                               out, sc, md...);
-            return SMPC_OK;
+            return with_row_bounds(h, B, [&](auto... rb) {
+                hipLaunchKernelGGL((k_merit<NQ, SCENE, MODEL>), dim3(B), dim3(64), 0, s, h->d_desc, B, N, x0, x, u, p, dx, du, alpha, mask, y,
+                                   w.pos, out, sc, md..., rb...);
+                return SMPC_OK;
+            });
         });
     });
     HIPCHK(h, hipGetLastError());
@@ -1729,11 +1753,12 @@ int smpc_set_horizon(smpc_handle* h, int N) {
     (void)hipSetDevice(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->N = N;
-    h->bounds.clear();      // (the one slot laid out by the horizon ...
+    h->bounds.clear();      // (the slots laid out by the horizon ...
+    h->rowb.clear();
     drop_forecast(h);       //  ... and a forecast, N + 1 columns of it; the world it was made from stays)
     h->order_B = 0;
     // every buffer laid out by the horizon starts afresh (zeroed where that is its contract) in the next call that needs it
-    for (DevBuf<double>* buf : {&h->d_zl, &h->bounds.d, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
+    for (DevBuf<double>* buf : {&h->d_zl, &h->bounds.d, &h->rowb.d, &h->d_ev, &h->d_nn, &h->d_ws, &h->d_hrec}) buf->release();
     h->d_par.release();
     h->d_sqp.release();
     h->d_guess.release();
@@ -1775,6 +1800,34 @@ int smpc_set_instance_bounds(smpc_handle* h, int B, const double* lo, const doub
         (rc = h->bounds.upload(h, hi, n, on_device != 0, instance_hi(h) - h->bounds.d.p)))
         return rc;
     h->bounds.commit(B);
+    return SMPC_OK;
+}
+
+int smpc_set_instance_row_bounds(smpc_handle* h, int B, const double* lo, const double* hi, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    if ((lo == nullptr) != (hi == nullptr))
+        return fail(h, SMPC_EINVAL, "smpc_set_instance_row_bounds: lo and hi must both be given or both be NULL");
+    (void)hipSetDevice(h->device);
+    if (!lo) { h->rowb.clear(); return SMPC_OK; }
+    if (B <= 0) return fail(h, SMPC_EINVAL, "bad batch size");
+    const int nr = h->desc.n_rows;
+    if (nr == 0) return fail(h, SMPC_EINVAL, "the problem has no collision rows: there are no row bounds to set");
+    const size_t n = (size_t)B * (h->N + 1) * nr;
+    if (!on_device) {
+        // (device pointers are taken as they are: reading them back would synchronise)
+        for (size_t i = 0; i < n; i++) {
+            const int b = (int)(i / ((size_t)(h->N + 1) * nr)), k = (int)(i / nr % (h->N + 1)), r = (int)(i % nr);
+            if (lo[i] != lo[i] || hi[i] != hi[i])
+                return fail(h, SMPC_EINVAL, "row bounds of instance %d, node %d, row %d: NaN", b, k, r);
+            if (fabs(lo[i]) < SMPC_INF && fabs(hi[i]) < SMPC_INF && lo[i] > hi[i])
+                return fail(h, SMPC_EINVAL, "row bounds of instance %d, node %d, row %d: lo %g > hi %g", b, k, r, lo[i], hi[i]);
+        }
+    }
+    // [lo | hi]: the same B finds both halves where they were, so a captured solve keeps seeing them
+    int rc;
+    if ((rc = h->rowb.room(h, 2 * n)) || (rc = h->rowb.upload(h, lo, n, on_device != 0)) || (rc = h->rowb.upload(h, hi, n, on_device != 0, n)))
+        return rc;
+    h->rowb.commit(B);
     return SMPC_OK;
 }
 
@@ -2030,7 +2083,7 @@ int smpc_solve_batch(smpc_handle* h, int B, const double* x0, const double* xg, 
     if (B <= 0 || !x0 || !xg || !ug || !p || !x_out || !u_out || !status) return fail(h, SMPC_EINVAL, "bad argument");
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = guard_scene_context_and_models(h, B, "smpc_solve_batch"))) return rc;
+    if ((rc = guard_solve_slots(h, B, "smpc_solve_batch"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const size_t nX = (size_t)B * (h->N + 1) * 2 * h->desc.nq, nU = (size_t)B * h->N * h->desc.nq;
     Stage io{h, on_device != 0};
@@ -2193,7 +2246,7 @@ int smpc_rollout_batch(smpc_handle* h, int B, int n_steps, const double* x0, dou
     if (B <= 0 || n_steps <= 0 || !x0 || !x_guess || !u_guess || !p || !x_traj || !u_traj || !status_traj)
         return fail(h, SMPC_EINVAL, "bad argument");
     if (const int rf = refuse_slots(h, "smpc_rollout_batch", "the worker handles of the rollout hold none (step the loop through smpc_policy_step / "
-                                    "smpc_loop_post instead)", {&h->scene, &h->ctx, &h->models}))
+                                    "smpc_loop_post instead)", {&h->scene, &h->ctx, &h->models, &h->rowb}))
         return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
@@ -2312,13 +2365,13 @@ int smpc_policy_step(smpc_handle* h, int B, const smpc_policy_params* par, const
     if ((receding || parallel) && h->net->nlayers == 0) return fail(h, SMPC_ESTATE, "receding policy but smpc_set_mlp was not called");
     if (parallel)
         if (const int rf = refuse_slots(h, "smpc_policy_step", "the parallel policy's candidate slots are not instances",
-                                            {&h->scene, &h->ctx, &h->models}))
+                                            {&h->scene, &h->ctx, &h->models, &h->rowb}))
             return rf;
     (void)hipSetDevice(h->device);
     const int N = h->N, nq = h->desc.nq, nx = 2 * nq;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = guard_scene_context_and_models(h, B, "smpc_policy_step"))) return rc;
+    if ((rc = guard_solve_slots(h, B, "smpc_policy_step"))) return rc;
     TrajSrc tr;
     if (!parallel && (rc = policy_traj_src(h, B, st, &tr))) return rc;     // (before anything is enqueued; the parallel step asks itself)
     if ((rc = ensure_batch(h, B))) return rc;
@@ -2464,7 +2517,7 @@ int smpc_merit_terms(smpc_handle* h, int B, const double* x0, const double* x, c
     const int N = h->N, nq = h->desc.nq;
     const size_t nX = (size_t)B * (N + 1) * 2 * nq, nU = (size_t)B * N * nq;
     int rc;
-    if ((rc = guard_scene_context_and_models(h, B, "smpc_merit_terms"))) return rc;
+    if ((rc = guard_solve_slots(h, B, "smpc_merit_terms"))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, false, &w))) return rc;
     Stage io{h, on_device != 0};
@@ -2502,7 +2555,7 @@ int smpc_sqp_batch(smpc_handle* h, int B, const smpc_sqp_opts* opts, const doubl
     const size_t nX = (size_t)B * nX1, nU = (size_t)B * nU1;
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = guard_scene_context_and_models(h, B, "smpc_sqp_batch"))) return rc;
+    if ((rc = guard_solve_slots(h, B, "smpc_sqp_batch"))) return rc;
     if ((rc = ensure_batch(h, B, false))) return rc;
     SqpScratch w;
     if ((rc = sqp_scratch(h, B, true, &w))) return rc;
@@ -2865,7 +2918,7 @@ extern "C" int smpc_debug_stage_records(smpc_handle* h, int B, const double* x0,
     if (!h || B <= 0 || !x0 || !xg || !ug || !p || !ws_out || !layout) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     int rc;
-    if ((rc = guard_scene_context_and_models(h, B, "smpc_debug_stage_records"))) return rc;
+    if ((rc = guard_solve_slots(h, B, "smpc_debug_stage_records"))) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
     const int N = h->N, nx = 2 * h->desc.nq, nu = h->desc.nq;
     Stage io{h, false};

@@ -93,13 +93,17 @@ __device__ __forceinline__ double grp_max(double v) {
 // lane's row, eight doubles, then sits in the lane's registers where the shared scene has scalar loads).  MODEL: the lane that
 // owns joint g takes mass, com and inertia from Jb[g], the instance's records of smpc_set_instance_models, instead of the
 // descriptor's joint g (ten doubles in the lane's registers where the shared model has scalar loads); the kinematics stay D's.
-template <int NQ, int MRT, bool SCENE = false, bool MODEL = false>
+// ROWB: the bounds of the lane's collision rows come from rb_k, this node's [n_rows] block of the lower half of the table of
+// smpc_set_instance_row_bounds (the upper half rb_half doubles behind it), instead of the descriptor's rows[r].lb / .ub: two loads
+// in phase S where the descriptor's two were, and the same subtraction.
+template <int NQ, int MRT, bool SCENE = false, bool MODEL = false, bool ROWB = false>
 __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict__ D, const QpLayout<NQ>& Ly, const int N, const int k,
                                             const bool valid, const int g, double* __restrict__ L, const double* __restrict__ x0b,
                                             const double* __restrict__ xk, const double* __restrict__ uk, const double* __restrict__ pk,
                                             const double* __restrict__ lo_k, const double* __restrict__ hi_k,
                                             const double* __restrict__ zl_st, const double* __restrict__ nnk, double* __restrict__ w,
-                                            const double* __restrict__ geom_b = nullptr, const smpc_joint* __restrict__ Jb = nullptr) {
+                                            const double* __restrict__ geom_b = nullptr, const smpc_joint* __restrict__ Jb = nullptr,
+                                            const double* __restrict__ rb_k = nullptr, const size_t rb_half = 0) {
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NQP = QpLayout<NQ>::NQP, NZP = QpLayout<NQ>::NZP;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     constexpr int NSLOT = (MR_MAX + SB_G - 1) / SB_G;      // collision rows per lane (row g + 8 s on lane g)
@@ -570,8 +574,17 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
         const bool have = r < MR;
         const smpc_row& row = D->rows[have ? r : 0];
         double lo = -QP_ABSENT, hi = QP_ABSENT, cz = 0.0, cn = 0.0;
-        if (k >= 1 && fabs(row.lb) < SMPC_INF) lo = row.lb - growv[sl];
-        if (k >= 1 && fabs(row.ub) < SMPC_INF) hi = row.ub - growv[sl];
+        // (the two branches state one rule on two sources; the descriptor's keeps the very expressions it had, and so its code)
+        double lb = 0.0, ub = 0.0;
+        if constexpr (ROWB) {
+            lb = rb_k[have ? r : 0];
+            ub = rb_k[rb_half + (have ? r : 0)];
+            if (k >= 1 && fabs(lb) < SMPC_INF) lo = lb - growv[sl];
+            if (k >= 1 && fabs(ub) < SMPC_INF) hi = ub - growv[sl];
+        } else {
+            if (k >= 1 && fabs(row.lb) < SMPC_INF) lo = row.lb - growv[sl];
+            if (k >= 1 && fabs(row.ub) < SMPC_INF) hi = row.ub - growv[sl];
+        }
 #pragma unroll
         for (int j = 0; j < NQ; j++) cn = fmax(cn, fabs(grow[sl][j]));
         if (k == 0) {
@@ -583,7 +596,11 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
         // collision rows at node 0 (controller.py:77-79): constants of the QP; a violated one = QP infeasible
         if (have && k == 0 && D->rows_at_node0) {
             const double v = growv[sl] + cz;
-            if ((fabs(row.lb) < SMPC_INF && v < row.lb - D->qp_tol) || (fabs(row.ub) < SMPC_INF && v > row.ub + D->qp_tol)) inf0 = 1.0;
+            if constexpr (ROWB) {
+                if ((fabs(lb) < SMPC_INF && v < lb - D->qp_tol) || (fabs(ub) < SMPC_INF && v > ub + D->qp_tol)) inf0 = 1.0;
+            } else {
+                if ((fabs(row.lb) < SMPC_INF && v < row.lb - D->qp_tol) || (fabs(row.ub) < SMPC_INF && v > row.ub + D->qp_tol)) inf0 = 1.0;
+            }
         }
     }
     // the network's row: lane NNL
@@ -663,6 +680,7 @@ __device__ __forceinline__ void stage_build(const smpc_problem_desc* __restrict_
 // Standalone launch: one wavefront = 8 nodes.  Node index t over (instance, stage); instances the policy layer masks out are skipped.
 // SCENE: sc = the handle's scene track; stage k reads column scene_col(time + k) of its instance (unused otherwise).
 // MODEL: md = the handle's table of instance models; the nodes of instance b read its NQ records (unused otherwise).
+// A pack that ends in the table of smpc_set_instance_row_bounds (RowBounds, device_model.hpp): node (b, k) reads its rows' bounds there.
 template <int NQ, int MRT, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB_WAVES))) void k_stage_build(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                                     const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ pp,
@@ -670,7 +688,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB
                                                     const double* __restrict__ zl_st, const double* __restrict__ nn, double* __restrict__ ws_all,
                                                     long bnd_stride, const uint8_t* __restrict__ active, int32_t* __restrict__ zero_cnt,
                                                     const SceneArg<SCENE> sc = {}, const MJ* __restrict__... md) {
-    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
+    static_assert(ModelRowArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, then the row-bounds table or nothing");
+    constexpr bool ROWB = RowBounds<MJ...>;
     constexpr int NX = 2 * NQ, NU = NQ;
     constexpr int MR_MAX = MRT >= 0 ? MRT : SMPC_MAX_ROWS;
     using LD = SbLds<NQ, MR_MAX>;
@@ -697,9 +716,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SB_WAVES, SB
     if constexpr (SCENE) geom_b = scene_block(sc, b, scene_time(sc) + k, Ly.MR);
     const smpc_joint* Jb = nullptr;
     if constexpr (MODEL) Jb = model_joints<NQ>(D, b, md...);
-    stage_build<NQ, MRT, SCENE, MODEL>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
+    const double* rb_k = nullptr;
+    size_t rb_half = 0;
+    if constexpr (ROWB) {
+        rb_k = row_bounds_table(md...) + ((size_t)b * (N + 1) + k) * Ly.MR;
+        rb_half = (size_t)B * (N + 1) * Ly.MR;
+    }
+    stage_build<NQ, MRT, SCENE, MODEL, ROWB>(D, Ly, N, k, valid, g, smem + grp * LD::SIZE, x0 + (size_t)b * NX, xk, uk, pk, lo_st + bo, hi_st + bo, zl_st,
                                 nn ? nn + (D->nn_mode == SMPC_NN_TERMINAL ? (size_t)b : (size_t)b * (N + 1) + k) * (1 + NX) : nullptr, w,
-                                geom_b, Jb);
+                                geom_b, Jb, rb_k, rb_half);
 }
 
 }  // namespace smpc

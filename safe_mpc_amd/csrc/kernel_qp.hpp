@@ -329,13 +329,16 @@ __device__ unsigned long long g_qp_prof[16];
 // k_qp_setup: stage records + initial interior point, one half-wave per (instance, stage); a block = the EV_TILE nodes of one
 // interleaved tile of linearisation records (device_model.hpp), loaded by all its threads and taken apart in LDS
 // =========================================================================================================================
-template <int NQ, int MRT>
+// RB: nothing, or the table of smpc_set_instance_row_bounds as one `const double*` (RowBounds, device_model.hpp): the collision rows'
+// bounds of node (b, k) then come from it instead of the descriptor.
+template <int NQ, int MRT, class... RB>
 __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_desc* __restrict__ D, int B, int N,
                                                   const double* __restrict__ x0, const double* __restrict__ xg,
                                                   const double* __restrict__ ug, const double* __restrict__ pp,
                                                   const double* __restrict__ lo_st, const double* __restrict__ hi_st,
                                                   const double* __restrict__ zl_st, const double* __restrict__ ev, double* __restrict__ ws_all,
-                                                  long bnd_stride, const uint8_t* __restrict__ active) {
+                                                  long bnd_stride, const uint8_t* __restrict__ active, const RB* __restrict__... rb) {
+    static_assert(ModelRowArg<false, RB...>, "rb: the row-bounds table or nothing");
     using LyT = QpLayout<NQ>;
     constexpr int NX = 2 * NQ, NU = NQ, NZ = 3 * NQ, NZP = LyT::NZP, NQP = LyT::NQP, NL = 32;
     constexpr int MAXRC = NQ + (MRT >= 0 ? MRT : SMPC_MAX_ROWS) + 1;
@@ -442,8 +445,15 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
             if (!last && tm < SMPC_INF) { lo = -tm - e.tau[r - rT0]; hi = tm - e.tau[r - rT0]; }
         } else if (r < rNN) {
             const smpc_row& row = D->rows[r - rC0];
-            if (k >= 1 && fabs(row.lb) < SMPC_INF) lo = row.lb - e.row_val[r - rC0];
-            if (k >= 1 && fabs(row.ub) < SMPC_INF) hi = row.ub - e.row_val[r - rC0];
+            // (the two branches state one rule on two sources; the descriptor's keeps the very expressions it had, and so its code)
+            if constexpr (RowBounds<RB...>) {
+                const RowLbUb own = row_bounds_at(row_bounds_table(rb...), B, N, MR, b, k, r - rC0);
+                if (k >= 1 && fabs(own.lb) < SMPC_INF) lo = own.lb - e.row_val[r - rC0];
+                if (k >= 1 && fabs(own.ub) < SMPC_INF) hi = own.ub - e.row_val[r - rC0];
+            } else {
+                if (k >= 1 && fabs(row.lb) < SMPC_INF) lo = row.lb - e.row_val[r - rC0];
+                if (k >= 1 && fabs(row.ub) < SMPC_INF) hi = row.ub - e.row_val[r - rC0];
+            }
         } else if (r == rNN) {
             if (nn_on) lo = 0.0 - e.nn_val;
         }
@@ -551,7 +561,12 @@ __global__ __launch_bounds__(32 * EV_TILE) void k_qp_setup(const smpc_problem_de
         const smpc_row& row = D->rows[hl - rC0];
         double v = e.row_val[hl - rC0];
         for (int c = 0; c < NZ; c++) v = fma(sC[(hl - NX) * NZP + c], sZ0[c], v);
-        if ((fabs(row.lb) < SMPC_INF && v < row.lb - D->qp_tol) || (fabs(row.ub) < SMPC_INF && v > row.ub + D->qp_tol)) inf0 = 1.0;
+        if constexpr (RowBounds<RB...>) {
+            const RowLbUb own = row_bounds_at(row_bounds_table(rb...), B, N, MR, b, k, hl - rC0);
+            if ((fabs(own.lb) < SMPC_INF && v < own.lb - D->qp_tol) || (fabs(own.ub) < SMPC_INF && v > own.ub + D->qp_tol)) inf0 = 1.0;
+        } else {
+            if ((fabs(row.lb) < SMPC_INF && v < row.lb - D->qp_tol) || (fabs(row.ub) < SMPC_INF && v > row.ub + D->qp_tol)) inf0 = 1.0;
+        }
     }
     const double R0 = half_max(r0_loc), musum = half_sum(mu_acc), cntsum = half_sum((double)cnt), infs = half_max(inf0);
     if (hl < 4) w[Ly.oPART + hl] = hl == 0 ? R0 : (hl == 1 ? musum : (hl == 2 ? cntsum : infs));

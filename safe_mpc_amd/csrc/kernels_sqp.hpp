@@ -88,6 +88,8 @@ __global__ void k_sqp_trial_states(int B, int per, const double* __restrict__ x,
 // Instances whose mask byte is 0 are skipped and their outputs left as they are.
 // SCENE: the rows' fixed obstacles from the scene track sc (node k in column scene_col(time + k)) instead of the descriptor.
 // MODEL: the torque term's link inertials from instance b's own records (md, smpc_set_instance_models) instead of the descriptor's.
+// A pack that ends in the table of smpc_set_instance_row_bounds (RowBounds, device_model.hpp): the rows' l1 violation at node k is
+// taken against entry (b, k, r) of it instead of the descriptor's bounds.
 template <int NQ, bool SCENE = false, bool MODEL = false, class... MJ>
 __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restrict__ D, int B, int N, const double* __restrict__ x0,
                                               const double* __restrict__ xg, const double* __restrict__ ug, const double* __restrict__ p,
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
                                               const double* __restrict__ alpha, const uint8_t* __restrict__ mask,
                                               const float* __restrict__ y, const int32_t* __restrict__ pos, double* __restrict__ out,
                                               const SceneArg<SCENE> sc = {}, const MJ* __restrict__... md) {
-    static_assert(ModelArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, nothing otherwise");
+    static_assert(ModelRowArg<MODEL, MJ...>, "md: the table of smpc_joint records when MODEL is set, then the row-bounds table or nothing");
     constexpr int NX = 2 * NQ;
     __shared__ double s_pts[PT_COL_DOUBLES];
     const int b = blockIdx.x, k = threadIdx.x;
@@ -181,8 +183,15 @@ __global__ __launch_bounds__(64) void k_merit(const smpc_problem_desc* __restric
             for (int r = 0; r < nrows; r++) {
                 const smpc_row& row = D->rows[r];
                 const double rv = sqp_row_value<SCENE>(row, spt, row_geom<SCENE>(row, geom_b, r));
-                if (fabs(row.lb) < SMPC_INF) viol += fmax(row.lb - rv, 0.0);
-                if (fabs(row.ub) < SMPC_INF) viol += fmax(rv - row.ub, 0.0);
+                // (the two branches state one rule on two sources; the descriptor's keeps the very expressions it had, and so its code)
+                if constexpr (RowBounds<MJ...>) {
+                    const RowLbUb own = row_bounds_at(row_bounds_table(md...), B, N, nrows, b, k, r);
+                    if (fabs(own.lb) < SMPC_INF) viol += fmax(own.lb - rv, 0.0);
+                    if (fabs(own.ub) < SMPC_INF) viol += fmax(rv - own.ub, 0.0);
+                } else {
+                    if (fabs(row.lb) < SMPC_INF) viol += fmax(row.lb - rv, 0.0);
+                    if (fabs(row.ub) < SMPC_INF) viol += fmax(rv - row.ub, 0.0);
+                }
             }
             // safe-set row: max(-g, 0) with g = y (100 - alpha) / 100 - |v| (safe_set.py:94), where the formulation has the row
             const int mode = D->nn_mode;

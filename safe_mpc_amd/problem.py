@@ -694,3 +694,40 @@ def extend_tracks(tracks, T):
     step = tracks[:, -1] - tracks[:, -2] if T0 > 1 else np.zeros_like(tracks[:, -1])
     more = tracks[:, -1:, :, :] + step[:, None] * np.arange(1, T - T0 + 1)[None, :, None, None]
     return np.concatenate([tracks, more], axis=1)
+
+
+def inflated_row_bounds(prob, B, margin):
+    """``(lo, hi)``, each ``[B, N+1, n_rows]``: the collision rows' bounds with ``margin`` metres of extra room around every
+    world-fixed element, per instance, node and row -- what smpc_set_instance_row_bounds takes.  ``margin`` is
+    ``[N+1]`` (a profile along the horizon for every instance and row), ``[B, N+1]`` or ``[B, N+1, n_rows]``, finite and >= 0.
+    Rows without a world-fixed element (``row_obstacle`` None: robot against robot) keep their bounds.  A squared-distance row
+    (fixed capsule, sphere, fixed point) gets ``lb' = (sqrt(lb) + d)^2``; a plane row ``lb' = lb + d`` and ``ub' = ub - d``; a side
+    that is absent (``|v| >= INF``) stays absent.  Where ``d == 0.0`` the descriptor's own doubles come back, bit for bit.  With
+    ``d = 2 c`` this is what ``collision_margin = c`` does to a problem built without one."""
+    N, nr, B = int(prob.N), len(prob.rows), int(B)
+    m = np.asarray(margin, float)
+    shapes = {1: (N + 1,), 2: (B, N + 1), 3: (B, N + 1, nr)}
+    if B < 1 or m.ndim not in shapes or m.shape != shapes[m.ndim]:
+        raise ValueError(f'inflated_row_bounds: margin of shape {m.shape}: expected [{N + 1}], [{B}, {N + 1}] or [{B}, {N + 1}, {nr}]')
+    if not np.all(np.isfinite(m)) or np.any(m < 0.0):
+        raise ValueError('inflated_row_bounds: a margin is finite and not negative')
+    d = np.broadcast_to(m if m.ndim == 3 else (m[:, :, None] if m.ndim == 2 else m[None, :, None]), (B, N + 1, nr))
+    lo = np.broadcast_to(np.asarray(prob.row_lb, float), (B, N + 1, nr)).copy()
+    hi = np.broadcast_to(np.asarray(prob.row_ub, float), (B, N + 1, nr)).copy()
+    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):
+        di = d[:, :, i]
+        on = di != 0.0
+        if name is None or not on.any():
+            continue
+        if r.kind == ROW_COORD:
+            if abs(r.lb) < INF:
+                lo[:, :, i] = np.where(on, r.lb + di, r.lb)
+            if abs(r.ub) < INF:
+                hi[:, :, i] = np.where(on, r.ub - di, r.ub)
+            if abs(r.lb) < INF and abs(r.ub) < INF and np.any(lo[:, :, i] > hi[:, :, i]):
+                b, k = np.argwhere(lo[:, :, i] > hi[:, :, i])[0]
+                raise ValueError(f'inflated_row_bounds: row {i} ({prob.row_names[i]}): a margin of {di[b, k]:g} m at instance {b}, '
+                                 f'node {k} makes its sides cross ({lo[b, k, i]:g} > {hi[b, k, i]:g})')
+        elif abs(r.lb) < INF:
+            lo[:, :, i] = np.where(on, (np.sqrt(r.lb) + di) ** 2, r.lb)
+    return lo, hi

@@ -212,6 +212,17 @@ class BatchedOcpSolver:
         self._set_instance(self.L.smpc_set_instance_bounds, 'set_instance_bounds', [None, None] if lo is None else [lo, hi],
                            (self.N + 1, self.nx))
 
+    def set_instance_row_bounds(self, lo=None, hi=None):
+        """The collision rows' bounds per instance and node (smpc_set_instance_row_bounds): ``lo``, ``hi``
+        ``[B, N+1, n_rows]`` -- ``problem.inflated_row_bounds`` forms them from a margin in metres -- as numpy arrays or contiguous
+        ROCm float64 tensors; the engine keeps a copy.  Entry (b, k, r) replaces ``row_lb[r]`` / ``row_ub[r]`` at node k of instance b
+        in the QP's rows and the merit's violation (solve, sqp, merit_terms, policy_step's solve); a value with |v| >= 1e5 is an
+        absent side.  The tests against check bounds (check_trajectory, check_guess, score_rollout, loop_post) do not read it.  None
+        clears it, and so does :meth:`set_horizon`.  While set, the calls that read it must come with the same B; the parallel policy
+        and :meth:`rollout` refuse it."""
+        self._set_instance(self.L.smpc_set_instance_row_bounds, 'set_instance_row_bounds', [None, None] if lo is None else [lo, hi],
+                           (self.N + 1, int(self.problem.desc.n_rows)))
+
     def set_instance_scene(self, geom=None):
         """A scene of its own for every instance (smpc_set_instance_scene): ``geom [B, n_rows, 8]`` -- per (instance, row) the
         world-fixed element's C[3], D[3], offset, 0, as ``OcpProblem.row_geometry`` / ``scene`` / ``jittered_scenes`` lay it out --

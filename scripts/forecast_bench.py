@@ -14,9 +14,15 @@
    32, the line (smpc_forecast_scene_fit) and degrees 0 and 2 (smpc_forecast_scene_poly) window by window.
 6. The closed loop on the turning tracks of 2, without observation noise (the controller sees the world) and with it (as 4): the arms
    true, cv, and the polynomial fit of degrees 1, 0 and 2 with windows 4, 8, 16, 32 -- lag against noise by window length and degree.
+7. Room for being wrong (profiles/row_bounds.txt): the closed loop of 4 with forecast='cv' under observation noise and
+   run_mpc(row_margin=(0, b)) for growth rates b of SMPC_MARGIN_GROWTH (default 0, 0.0005, 0.001, 0.002, 0.004 metres per node), one
+   run each: collisions with the true world, abort events and the mean closed-loop cost of the instances that did not collide.
+8. What the table costs a solve: smpc_solve_batch at B = 4096, N = 30 with a scene per instance set, without and with a row-bounds
+   table (the descriptor's own bounds in every entry: the same QPs), in alternation, SMPC_ROUNDS (default 5) rounds of 10 calls
+   between HIP events after 3 warm-up calls.
 A measurement tool, not a test; it reads nothing outside the repository.
 
-    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop]"""
+    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop|margin-loop|margin-solve]"""
 import os
 import sys
 
@@ -146,6 +152,75 @@ def loop_times(B, noisy=False, poly=False):
               f'conv {int(a[0, 1])}, collisions {int(a[0, 2])}, viable {int(a[0, 3])}, unconv {int(a[0, 4])}; B = {B}, N = {N}, {steps} steps')
 
 
+def margin_loop(B):
+    from safe_mpc_amd import controller as C
+    par, prob, net = bench.build_problem()
+    par.N = prob.N
+    steps = int(os.environ.get('SMPC_STEPS', '60'))
+    sigma = float(os.environ.get('SMPC_OBS_NOISE', '0.005'))
+    rates = [float(v) for v in os.environ.get('SMPC_MARGIN_GROWTH', '0,0.0005,0.001,0.002,0.004').split(',')]
+    probe = BatchedOcpSolver(prob, net)
+    x0 = bench.initial_states(probe, prob, B, 0)
+    probe.close()
+    N = prob.N
+    xg, ug = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((B, N, prob.nu))
+    ocp = C.OcpProblem(par, 'htwa', 'ext', N=N)
+    world = turning_scenes(ocp, B, steps + 1 + N, 0.3, 3.0, seed=0)
+    seen = observe_tracks(ocp, world, sigma, seed=0)
+    print(f"forecast='cv', observation noise sigma = {sigma}, turning tracks (sigma_v 0.3, sigma_a 3.0); B = {B}, N = {N}, {steps} steps")
+    for b in rates:
+        kw = {} if b == 0.0 else {'row_margin': (0.0, b)}      # (b = 0: the run without the argument)
+        out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, forecast='cv', observed=seen, score=True, **kw)
+        alive = np.ones(B, bool)
+        alive[out['collisions_idx']] = False
+        cost = out['score']['cost'][alive]
+        print(f"row_margin = (0, {b:g}): collisions with the true world {len(out['collisions_idx'])}, abort events {len(out['x_viable'])}, "
+              f"converged {len(out['conv_idx'])}, mean closed-loop cost of the {int(alive.sum())} others {np.nanmean(cost):.6g}", flush=True)
+
+
+def margin_solve_times(B):
+    import torch
+    par, prob, net = bench.build_problem()
+    s = BatchedOcpSolver(prob, net)
+    N, nr = prob.N, len(prob.rows)
+    device = torch.device('cuda', s.device)
+    dev = lambda a: torch.tensor(a, dtype=torch.float64, device=device)
+    x0 = bench.initial_states(s, prob, B, 0)
+    p = np.zeros((B, N + 1, 5))
+    p[:, :, :3], p[:, :, 3], p[:, :, 4] = prob.ee_ref, par.alpha, 1.0
+    args = [dev(x0), dev(np.repeat(x0[:, None, :], N + 1, axis=1)), dev(np.zeros((B, N, prob.nu))), dev(p)]
+    s.set_instance_scene(dev(turning_scenes(prob, B, 1, 0.3, 3.0, seed=0)[:, 0]))
+    lo = dev(np.ascontiguousarray(np.broadcast_to(prob.row_lb, (B, N + 1, nr))))
+    hi = dev(np.ascontiguousarray(np.broadcast_to(prob.row_ub, (B, N + 1, nr))))
+    rounds = int(os.environ.get('SMPC_ROUNDS', '5'))
+    stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
+    res = {False: [], True: []}
+    with torch.cuda.stream(stream):
+        out = s.solve(*args)
+        for r in range(rounds):
+            for table in (False, True):
+                s.set_instance_row_bounds(*((lo, hi) if table else (None, None)))
+                for _ in range(3):
+                    s.solve(*args, out=out)
+                ms = []
+                for _ in range(10):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(stream)
+                    s.solve(*args, out=out)
+                    b.record(stream)
+                    b.synchronize()
+                    ms.append(a.elapsed_time(b))
+                res[table].append(np.mean(ms))
+                print(f'round {r} table={table}: {np.mean(ms):.4f} ms per solve (min {np.min(ms):.4f}, max {np.max(ms):.4f})', flush=True)
+    for table in (False, True):
+        a = np.array(res[table])
+        print(f'smpc_solve_batch with a scene, row-bounds table {"set" if table else "not set"}: mean {a.mean():.4f} ms (rounds {a.min():.4f} .. '
+              f'{a.max():.4f}); B = {B}, N = {N}, {nr} rows, {rounds} rounds of 10 calls in alternation')
+    s.set_instance_row_bounds(None)
+    s.set_instance_scene(None)
+    s.close()
+
+
 def main(argv=None):
     what = (sys.argv[1:] if argv is None else argv) or ['kernel', 'loop']
     B = int(os.environ.get('SMPC_B', '4096'))
@@ -162,6 +237,10 @@ def main(argv=None):
     if 'poly-loop' in what:
         loop_times(B, poly=True)
         loop_times(B, noisy=True, poly=True)
+    if 'margin-loop' in what:
+        margin_loop(B)
+    if 'margin-solve' in what:
+        margin_solve_times(B)
     return 0
 
 

@@ -24,6 +24,9 @@ behind ``_w<M>`` for P other than 1.
 --scene-obs-noise SIGMA [--scene-obs-seed S] (needs --scene-forecast hold, cv or fit): the controller sees the world through a sensor --
 every obstacle's position in every column off by its own N(0, SIGMA^2) draw per axis (problem.observe_tracks, seed S, default 0), and
 the forecast is formed from that (run_mpc(observed=...)); the plant meets the true world.  Suffix ``_on<SIGMA>`` for SIGMA > 0.
+--row-margin A [--row-margin-growth B] (metres, metres per node; B needs A, default 0): obstacle inflation along the horizon -- node k of
+every solve leaves A + B k metres of extra room around the world-fixed obstacles (run_mpc(row_margin=(A, B)), DESIGN.md section 9q);
+the outcome tests keep the physical check bounds.  Suffix ``_rm<A>`` and, for B other than 0, ``_g<B>`` behind it.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -109,6 +112,12 @@ def main(argv=None):
         from safe_mpc_amd.problem import OcpProblem, observe_tracks
         fc_kw['observed'] = observe_tracks(OcpProblem(params, 'naive'), scenes, obs_noise, opt('--scene-obs-seed', 0, int))
         name_kw['obs_noise'] = obs_noise
+    if '--row-margin-growth' in raw and '--row-margin' not in raw:
+        raise SystemExit('--row-margin-growth needs --row-margin: there is no margin to grow')
+    if '--row-margin' in raw:
+        fc_kw['row_margin'] = name_kw['row_margin'] = (opt('--row-margin', 0.0, float), opt('--row-margin-growth', 0.0, float))
+        if cont_name == 'parallel':
+            raise SystemExit("--row-margin: the 'parallel' policy is not supported")
     cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
     if cmodel not in ('nominal', 'plant'):
         raise SystemExit(f'--controller-model {cmodel}: expected nominal or plant')
