@@ -14,6 +14,7 @@ import copy
 import heapq
 import os
 import pickle
+from collections import namedtuple
 
 import numpy as np
 
@@ -42,9 +43,8 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
     track = 'traj_track' if params.track_traj else ''
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
-            f"{'_cmplant' if controller_model == 'plant' else ''}{'' if forecast is None else '_fc' + forecast}"
-            f"{f'_w{int(forecast_window)}' if forecast == 'fit' else ''}"
-            f"{f'_d{int(forecast_degree)}' if forecast == 'fit' and int(forecast_degree) != 1 else ''}"
+            f"{'_cmplant' if controller_model == 'plant' else ''}"
+            f"{'' if forecast is None else _Forecast(forecast, forecast_window, forecast_degree).file_suffix()}"
             f"{f'_on{obs_noise}' if obs_noise > 0 else ''}"
             f"{'' if row_margin is None else f'_rm{float(row_margin[0])}' + (f'_g{float(row_margin[1])}' if float(row_margin[1]) != 0.0 else '')}"
             "_mpc.pkl")
@@ -310,6 +310,12 @@ def _sqp_on_device(ctrl, x0, max_iter, history, verbose, opts):
     return state['status'].cpu().numpy()
 
 
+def _require(solver, feature, method):
+    """the capability check of every per-instance feature: ValueError, naming the feature, unless ``solver`` has ``method``"""
+    if not hasattr(solver, method):
+        raise ValueError(f'{feature}: {type(solver).__name__} has no {method}')
+
+
 def _check_scenes(scenes, B, problem):
     """``scenes`` as a contiguous float64 array: [B, n_rows, SCENE_ROW] (problem.row_geometry's layout per instance), or a track
     [B, T, n_rows, SCENE_ROW] with T >= 1 time columns (problem.moving_scenes); ValueError otherwise"""
@@ -344,8 +350,7 @@ def _set_scene(solver, geom):
     solver's safe-set net has a context, the instances' contexts go on and off with the scenes: a track of T > 1 columns brings a
     context track of the same T (solver.set_instance_context_track), so that the network row of node k is asked
     about the scene its collision rows see."""
-    if not hasattr(solver, 'set_instance_scene'):
-        raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene')
+    _require(solver, 'scenes', 'set_instance_scene')
     select = _context_select(solver)
     if select is not None:
         from .problem import scene_context
@@ -357,8 +362,7 @@ def _set_scene(solver, geom):
         else:
             solver.set_instance_context(None if geom is None else scene_context(geom.reshape((geom.shape[0],) + geom.shape[-2:]), select))
     if geom is not None and geom.ndim == 4:
-        if not hasattr(solver, 'set_instance_scene_track'):
-            raise ValueError(f'scenes: {type(solver).__name__} has no set_instance_scene_track')
+        _require(solver, 'scenes', 'set_instance_scene_track')
         solver.set_instance_scene_track(geom)
     else:
         solver.set_instance_scene(geom)
@@ -376,30 +380,9 @@ def _clear_scene(solver):
         solver.set_scene_clock(None)
 
 
-def _check_models(models, B, noise, cont_name):
-    """run_mpc's ``models`` before anything is built: None, 'plant' (needs plant tables, so noise > 0) or a JOINT_DTYPE table
-    [B, nq]; not with the parallel policy.  Returns None, 'plant' or the contiguous table."""
-    if models is None:
-        return None
-    if cont_name == 'parallel':
-        raise ValueError("models: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
-                         "the engine refuses a model table there)")
-    if isinstance(models, str):
-        if models != 'plant':
-            raise ValueError(f"models: {models!r}: expected None, 'plant' or a joint table [{B}, nq]")
-        if not noise > 0:
-            raise ValueError("models='plant': the plant has a model of its own per instance only with noise > 0")
-        return models
-    models = np.ascontiguousarray(models)
-    if models.dtype != JOINT_DTYPE or models.ndim != 2 or models.shape[0] != B:
-        raise ValueError(f'models: expected a JOINT_DTYPE table [{B}, nq], got {models.dtype} {models.shape}')
-    return models
-
-
 def _set_models(solver, table):
     """the controller models [B, nq] of a batch onto the solver (None clears them)"""
-    if not hasattr(solver, 'set_instance_models'):
-        raise ValueError(f'models: {type(solver).__name__} has no set_instance_models')
+    _require(solver, 'models', 'set_instance_models')
     solver.set_instance_models(table)
 
 
@@ -597,8 +580,8 @@ def generate_guess(params, cont_name, n, make_controller=None, sqp_tol=1e-6, ver
         if models.dtype != JOINT_DTYPE or models.ndim != 2 or models.shape[0] != n:
             raise ValueError(f'models: expected a JOINT_DTYPE table [{n}, nq], got {models.dtype} {models.shape}')
     ctrl = make_controller(cont_name, n)
-    if models is not None and not hasattr(ctrl.ocp_solver, 'set_instance_models'):
-        raise ValueError(f'models: {type(ctrl.ocp_solver).__name__} has no set_instance_models')
+    if models is not None:
+        _require(ctrl.ocp_solver, 'models', 'set_instance_models')
     curves = traj is not None and np.ndim(traj) == 3
     if traj is not None:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1067,6 +1050,242 @@ def _masked_step(ctrl, x, active):
     return u, abort & active
 
 
+class _Forecast:
+    """What the controller forecasts the world with (run_mpc(forecast=, forecast_window=, forecast_degree=); DESIGN.md sections 9n-9p):
+    'hold', 'cv', 'true', or 'fit' -- a least-squares polynomial of ``degree`` through the last ``window`` columns seen -- and the one
+    place that tells the kinds apart, on the host path and the device path.  Degree 1 keeps the line fit's own statement and entry point."""
+
+    def __init__(self, kind, window=None, degree=None):
+        self.kind, self._fit = kind, kind == 'fit'
+        self.window, self.degree = int(window) if self._fit else None, 1 if degree is None else int(degree)
+        self._poly = self._fit and self.degree != 1
+
+    @classmethod
+    def checked(cls, kind, window, degree, scenes):
+        """run_mpc's three forecast arguments against its (checked) ``scenes``: the spec, None without a forecast, or ValueError"""
+        if kind is not None:
+            from .problem import FIT_MAX, FORECAST_MODES
+            if kind != 'fit' and kind not in FORECAST_MODES:
+                raise ValueError(f"forecast: {kind!r}: expected None, 'fit' or one of {sorted(FORECAST_MODES)}")
+            if kind == 'fit' and not (isinstance(window, (int, np.integer)) and 1 <= window <= FIT_MAX):
+                raise ValueError(f'forecast_window: {window!r}: a fit takes 1 to {FIT_MAX} columns')
+            if scenes is None or scenes.ndim != 4:
+                raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
+                                 + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
+        if degree is not None:
+            if kind != 'fit':
+                raise ValueError(f"forecast_degree: forecast={kind!r} has no degree: it goes with forecast='fit'")
+            if not (isinstance(degree, (int, np.integer)) and 0 <= degree <= 2):
+                raise ValueError(f'forecast_degree: {degree!r}: a polynomial fit has degree 0, 1 or 2')
+        return None if kind is None else cls(kind, window, degree)
+
+    def statement(self, world, observed, rows, t, N):
+        """the host path: the N + 1 scenes forecast at time t for the instances ``rows``, by the statement of the engine's entry point.
+        'hold', 'cv' and 'fit' (of any degree) are formed from what was seen, the observed track where the run has one; 'true' from the world"""
+        from .problem import fit_forecast_statement, forecast_statement, poly_forecast_statement
+        seen = world if observed is None or self.kind == 'true' else observed
+        if not self._fit:
+            return forecast_statement(seen[rows], t, N, self.kind)
+        if not self._poly:
+            return fit_forecast_statement(seen[rows], t, N, self.window)
+        return poly_forecast_statement(seen[rows], t, N, self.window, self.degree)
+
+    def enqueue(self, sv, select):
+        """the device path: one forecast from ``sv``'s world (and observed track) at its clock cell, into its scene slot"""
+        if self._poly:
+            sv.forecast_scene_poly(self.window, self.degree, select)
+        elif self._fit:
+            sv.forecast_scene_fit(self.window, select)
+        else:
+            sv.forecast_scene(self.kind, select)
+
+    def require(self, sv, observed):
+        """ValueError unless ``sv`` has the entry points :meth:`enqueue` calls (and takes an observed track, for a run with one)"""
+        for need, feature, method in ((True, 'forecast', 'forecast_scene'), (self._fit, 'forecast', 'forecast_scene_fit'),
+                                      (self._poly, 'forecast_degree', 'forecast_scene_poly'), (observed, 'observed', 'set_instance_observed_track')):
+            if need:
+                _require(sv, feature, method)
+
+    def result_keys(self, observed):
+        return {'forecast': self.kind, 'observed': bool(observed), **({'forecast_window': self.window} if self._fit else {}),
+                **({'forecast_degree': self.degree} if self._poly else {})}
+
+    def file_suffix(self):
+        return f"_fc{self.kind}{f'_w{self.window}' if self._fit else ''}{f'_d{self.degree}' if self._poly else ''}"
+
+
+class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_margin', defaults=(None,) * 5)):
+    """run_mpc's ``scenes``, ``models``, ``forecast*`` (a :class:`_Forecast`), ``observed`` and ``row_margin``, checked
+    (:func:`_check_world`): of the whole run, or of one group's instances (:meth:`rows`)"""
+
+    def rows(self, lo, hi):
+        cut = lambda a: a if a is None or isinstance(a, str) else a[lo:hi]
+        return self._replace(scenes=cut(self.scenes), models=cut(self.models), observed=cut(self.observed))
+
+
+def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models):
+    """run_mpc's arguments about the world of its B instances, before anything is built: the :class:`_RunWorld`, or ValueError"""
+    for name, given, thing in (('models', models, 'model table'), ('scenes', scenes, 'scene'), ('row_margin', row_margin, 'row-bounds table')):
+        if cont_name == 'parallel' and given is not None:
+            raise ValueError(f"{name}: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
+                             f"the engine refuses a {thing} there)")
+    if isinstance(models, str):
+        if models != 'plant':
+            raise ValueError(f"models: {models!r}: expected None, 'plant' or a joint table [{B}, nq]")
+        if not noise > 0:
+            raise ValueError("models='plant': the plant has a model of its own per instance only with noise > 0")
+    elif models is not None:
+        models = np.ascontiguousarray(models)
+        if models.dtype != JOINT_DTYPE or models.ndim != 2 or models.shape[0] != B:
+            raise ValueError(f'models: expected a JOINT_DTYPE table [{B}, nq], got {models.dtype} {models.shape}')
+    if scenes is not None:
+        scenes = np.ascontiguousarray(scenes, np.float64)
+        if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
+            raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
+    if row_margin is not None:
+        row_margin = tuple(float(v) for v in np.asarray(row_margin, float).reshape(-1))
+        if len(row_margin) != 2 or not all(np.isfinite(row_margin)):
+            raise ValueError(f'row_margin: expected (a, b), the margin a + b k metres at node k, got {row_margin}')
+    fc = _Forecast.checked(forecast, forecast_window, forecast_degree, scenes)
+    if observed is not None:
+        if fc is None or fc.kind == 'true':
+            raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
+        observed = np.ascontiguousarray(observed, np.float64)
+        if observed.shape != scenes.shape:
+            raise ValueError(f'observed: expected the world\'s shape {scenes.shape}, got {observed.shape}')
+    return _RunWorld(scenes, models, fc, observed, row_margin)
+
+
+def _joint_tensor(xp, table, B, nq):        # [B, nq] smpc_joint records as a float64 device tensor [B, nq, 29]
+    return xp.asarray(np.ascontiguousarray(table).view(np.float64).reshape(B, nq, -1), xp.f64)
+
+
+class _World:
+    """Everything ONE group of a run sets on its two solver handles beyond the OCP itself (``run``: the group's :class:`_RunWorld`;
+    run_mpc's docstring says what each argument means).  The controller's handle holds the group's scenes or track -- with a forecast
+    the track is the WORLD, which only the plant meets, and the scene slot holds what the controller forecasts at the head of every
+    step --, its row-bounds table and its models for the whole run; the backup's handle gets the aborting instances' rows of each, over
+    its own horizon, before each of its compact solves.  The loop's step counter is the scene clock of both handles."""
+
+    def __init__(self, run, ctrl, backup, B):
+        self._run, self._ctrl, self._backup, self._B, self._xp = run, ctrl, backup, B, ctrl.xp
+        self._sv, self._bsv, self.forecast, self.track = ctrl.ocp_solver, backup.ocp_solver, run.forecast, False
+        self.scenes = self.observed = self.row_bounds = self.models = self.clock = self.backup_clock = self._select = self._backup_select = None
+
+    def attach(self):
+        """what the run's arguments alone say: the scenes (without a forecast) and the row bounds onto the controller's handle"""
+        run, xp, ctrl, backup, B = self._run, self._xp, self._ctrl, self._backup, self._B
+        if run.scenes is not None:
+            self.scenes = xp.asarray(_check_scenes(run.scenes, B, ctrl.problem), xp.f64)
+            if run.observed is not None:
+                self.observed = xp.asarray(_check_scenes(run.observed, B, ctrl.problem), xp.f64)
+            self.track = self.scenes.ndim == 4
+            if self.forecast is None:
+                _set_scene(self._sv, self.scenes)
+            if self.track:
+                for sv in (self._sv, self._bsv):
+                    _require(sv, 'scenes', 'set_scene_clock')
+        if run.row_margin is not None:
+            from .problem import inflated_row_bounds
+            for sv in (self._sv, self._bsv):
+                _require(sv, 'row_margin', 'set_instance_row_bounds')
+            a, g = (float(v) for v in run.row_margin)
+            table = lambda c: tuple(xp.asarray(v, xp.f64) for v in inflated_row_bounds(c.problem, B, a + g * np.arange(c.N + 1)))
+            self._sv.set_instance_row_bounds(*table(ctrl))
+            self.row_bounds = table(backup)
+
+    def attach_loop(self, counter, plant):
+        """what needs the loop's own state: the clock cells of a track and the controller models.  ``counter``: the step counter of a
+        device loop, which IS the controller handle's scene clock (smpc_loop_post reads column j + 1, then advances it); its backup
+        handle solves on its own stream while the loop goes on, so that clock is a cell of its own, which receives the counter's value
+        at the abort event.  None on the host: one cell per handle, written before the calls of a step.  ``plant``: the tables the plant
+        steps with, which models='plant' hands to the controller -- on the device the very tensor.  A device loop with a forecast
+        sets the world (and what was observed of it) once: the engine's forecast at the head of every step reads it."""
+        xp, sv, bsv, dev, table = self._xp, self._sv, self._bsv, self._xp.on_device, self._run.models
+        if table is not None:
+            for s in (sv, bsv):
+                _require(s, 'models', 'set_instance_models')
+            self.models = plant if isinstance(table, str) else _joint_tensor(xp, table, self._B, self._ctrl.nq) if dev else table
+            if dev:                             # (the two loops hand the models over on either side of the clocks)
+                _set_models(sv, self.models)
+        if self.track:
+            self.clock, self.backup_clock = (counter, xp.step_index(0)) if dev else (_new_scene_clock(sv), _new_scene_clock(bsv))
+            sv.set_scene_clock(self.clock)
+            bsv.set_scene_clock(self.backup_clock)
+        if table is not None and not dev:
+            _set_models(sv, self.models)
+        if dev and self.forecast is not None:
+            for s in (sv, bsv):
+                self.forecast.require(s, self.observed is not None)
+            self._select, self._backup_select = _context_select(sv), _context_select(bsv)
+            sv.set_instance_world_track(self.scenes)
+            if self.observed is not None:       # (what HOLD, CV and the fit then read instead of the world)
+                sv.set_instance_observed_track(self.observed)
+
+    def _forecast_into(self, sv, select, rows, t, N):
+        """one forecast into ``sv``'s scene slot: on the device from its world (and observed track) at its clock cell; on the host the
+        statement at time ``t`` for the instances ``rows`` (with their context rows, _set_scene) and no clock -- node k reads column k"""
+        if self._xp.on_device:
+            return self.forecast.enqueue(sv, select)
+        sv.set_scene_clock(None)
+        _set_scene(sv, self.forecast.statement(self.scenes, self.observed, rows, t, N))
+
+    def head_of_step(self, t=None):
+        """what the controller plans in at the step that begins (``t``: the step, on the host): the scenes forecast at time t, read from
+        node 0 on; without a forecast node k of the step's solve and tests is formed at time t + k, by the clock"""
+        if self.forecast is not None:
+            self._forecast_into(self._sv, self._select, slice(None), t, self._ctrl.N)
+        elif not self._xp.on_device:
+            _write_scene_clock(self.clock, t)
+
+    def dress_backup(self, rows, t=None):
+        """the backup OCP of an abort event is solved in the scenes of the aborting instances ``rows`` (in the compact batch's order) --
+        with a forecast, in what the controller knows of their world at the event --, with their row bounds and with their models"""
+        sv = self._bsv
+        if self.scenes is not None and self.forecast is None:
+            _set_scene(sv, self.scenes[rows])
+        elif self.scenes is not None:
+            if self._xp.on_device:              # (the forecast reads them at the handle's own clock cell)
+                sv.set_instance_world_track(self.scenes[rows])
+                if self.observed is not None:
+                    sv.set_instance_observed_track(self.observed[rows])
+            self._forecast_into(sv, self._backup_select, rows, t, self._backup.N)
+        if self.row_bounds is not None:
+            sv.set_instance_row_bounds(self.row_bounds[0][rows], self.row_bounds[1][rows])
+        if self.models is not None:
+            _set_models(sv, self.models[rows])
+
+    def to_true_world(self):
+        """the plant lives, and the run is scored, in the TRUE world: with a forecast the track replaces the last forecast in the scene
+        slot of the controller's handle (with its context track where the net has one), read by the loop's clock again"""
+        if self.forecast is not None:
+            _set_scene(self._sv, self.scenes)
+            self._sv.set_scene_clock(self.clock)
+
+    def detach(self):
+        """both handles keep nothing behind the run, every call of which has been enqueued by now: no scene, context or clock, no world
+        nor what was observed of it, no row-bounds or model table, no curves (the controller hands those over again should it step)"""
+        sv, bsv = self._sv, self._bsv
+        if self.scenes is not None:
+            _clear_scene(sv)
+            _clear_scene(bsv)
+            if self.forecast is not None:
+                for s in (sv, bsv):
+                    if self.observed is not None and hasattr(s, 'set_instance_observed_track'):
+                        s.set_instance_observed_track(None)
+                    if hasattr(s, 'set_instance_world_track'):
+                        s.set_instance_world_track(None)
+        if self.row_bounds is not None:
+            sv.set_instance_row_bounds(None)
+            bsv.set_instance_row_bounds(None)
+        if self.models is not None:
+            _set_models(sv, None)
+            _set_models(bsv, None)
+        traj = getattr(self._ctrl, 'traj', None)
+        if traj is not None and traj.ndim == 3 and hasattr(sv, 'set_instance_curves'):
+            sv.set_instance_curves(None)
+
+
 class _Group:
     """The closed loop of ONE group of instances (global indices first .. first + B): the driver's safe-abort automaton around
     the controller's ``step``.  A step has two halves, ``part_a`` (PD abort tracking, controller step) and ``part_b`` (plant,
@@ -1076,46 +1295,17 @@ class _Group:
     numpy statement of the loop, :class:`_DeviceGroup` the same loop as engine calls."""
 
     def __init__(self, params, x_guess, u_guess, noise, control_noise, ctrl, backup, n_steps, first, callback, collect_times=False,
-                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None, forecast_degree=1, row_margin=None):
+                 scenes=None, models=None, forecast=None, forecast_window=None, observed=None, forecast_degree=1, row_margin=None,
+                 world=None):
         self._params, self._ctrl, self._backup, self._n_steps, self._first, self._callback = params, ctrl, backup, n_steps, first, callback
         B = x_guess.shape[0]
         xp = ctrl.xp
         self._xp, self._B = xp, B
-        # a scene per instance (run_mpc(scenes=...)): the controller's handle holds the group's [B, n_rows, 8]; the backup handle gets
-        # the rows of the aborting instances before each of its compact solves (_backup_scene).  A track [B, T, n_rows, 8] goes the
-        # same way; the loop's step counter is then the scene clock of both handles (the subclasses say where the cell lives)
-        # A forecast (run_mpc(forecast=...), DESIGN.md section 9n): the track is the WORLD, which only the plant meets; the scene slot
-        # of either handle holds what the controller forecasts at the head of every step (the subclasses say how), so the track
-        # itself does not go onto the scene slot until the run is scored.
-        # 'fit' forecasts by a line through the last forecast_window columns; with ``observed`` (the world's shape: what a sensor
-        # shows of it, DESIGN.md section 9o) 'hold', 'cv' and 'fit' are formed from that table instead of the world.
-        # forecast_degree other than 1 makes the fit a window mean (0) or a parabola (2), DESIGN.md section 9p.
-        self._scenes, self._track, self._forecast, self._window, self._observed = None, False, forecast, forecast_window, None
-        self._degree = int(forecast_degree)
-        if scenes is not None:
-            self._scenes = xp.asarray(_check_scenes(scenes, B, ctrl.problem), xp.f64)
-            if observed is not None:
-                self._observed = xp.asarray(_check_scenes(observed, B, ctrl.problem), xp.f64)
-            self._track = self._scenes.ndim == 4
-            if forecast is None:
-                _set_scene(ctrl.ocp_solver, self._scenes)
-            if self._track:
-                for sv in (ctrl.ocp_solver, backup.ocp_solver):
-                    if not hasattr(sv, 'set_scene_clock'):
-                        raise ValueError(f'scenes: {type(sv).__name__} has no set_scene_clock')
-        # row bounds that leave more room along the horizon (run_mpc(row_margin=(a, b)), DESIGN.md section 9q): d_k = a + b k metres at
-        # node k, the same for every instance.  The controller's handle gets its table once, here; the backup handle gets the rows of
-        # the aborting instances, over its own horizon, before each of its compact solves (_backup_row_bounds).
-        self._row_bounds = None
-        if row_margin is not None:
-            from .problem import inflated_row_bounds
-            for sv in (ctrl.ocp_solver, backup.ocp_solver):
-                if not hasattr(sv, 'set_instance_row_bounds'):
-                    raise ValueError(f'row_margin: {type(sv).__name__} has no set_instance_row_bounds')
-            a, g = (float(v) for v in row_margin)
-            lo, hi = inflated_row_bounds(ctrl.problem, B, a + g * np.arange(ctrl.N + 1))
-            ctrl.ocp_solver.set_instance_row_bounds(xp.asarray(lo, xp.f64), xp.asarray(hi, xp.f64))
-            self._row_bounds = tuple(xp.asarray(v, xp.f64) for v in inflated_row_bounds(backup.problem, B, a + g * np.arange(backup.N + 1)))
+        if world is None:           # (run_mpc hands over the group's _RunWorld; a caller of this class the single arguments)
+            world = _RunWorld(scenes, models, None if forecast is None else _Forecast(forecast, forecast_window, forecast_degree), observed,
+                              row_margin)
+        self._world = _World(world, ctrl, backup, B)
+        self._world.attach()
         # stats.append(controller.getTime()) of scripts/mpc.py:239: one row of the seven time_fields per step of this group's
         # controller (host: read when step() returns; device: _DeviceGroup._read_times)
         self._collect_times = bool(collect_times) and hasattr(ctrl.ocp_solver, 'timing_history')
@@ -1126,13 +1316,6 @@ class _Group:
         self._Nb = backup.N
         seeds = np.arange(first, first + B)
         self._joints_noisy = perturbed_joint_tables(params, nq, noise, seeds) if noise > 0 else None          # mpc.py:106-107
-        # a controller model per instance (run_mpc(models=...)): 'plant' or the group's rows of a table; the subclasses hand it to the
-        # handles once the tables are where the loop keeps them (_hand_over_models)
-        self._models_arg, self._models = models, None
-        if models is not None:
-            for sv in (ctrl.ocp_solver, backup.ocp_solver):
-                if not hasattr(sv, 'set_instance_models'):
-                    raise ValueError(f'models: {type(sv).__name__} has no set_instance_models')
         # model.reset_seed(i) is called at EVERY step (mpc.py:126): each instance sees the same torque-noise draw each step
         self._tau_noise = None
         if control_noise > 0:
@@ -1160,34 +1343,6 @@ class _Group:
         self.last_x, self.last_u = xp.full((B,), n_steps, xp.i64), xp.full((B,), n_steps - 1, xp.i64)
         self._abort_events = []
 
-    def _backup_scene(self, rows):
-        """the backup OCP of an abort event is solved in the scenes of the aborting instances: their geometry rows, gathered in the
-        order of the compact batch, onto the backup handle"""
-        if self._scenes is None:
-            return
-        if self._forecast is None:
-            _set_scene(self._backup.ocp_solver, self._scenes[rows])
-        else:       # (what the controller knows of these instances' world at the event, over the backup's own horizon)
-            self._backup_forecast(rows)
-
-    def _backup_row_bounds(self, rows):
-        """... and with the aborting instances' rows of the inflated row bounds, over the backup's own horizon"""
-        if self._row_bounds is not None:
-            self._backup.ocp_solver.set_instance_row_bounds(self._row_bounds[0][rows], self._row_bounds[1][rows])
-
-    def _hand_over_models(self, table=None):
-        """the group's controller models onto the controller's handle: ``table`` (the subclass's form of the rows it was given), or
-        with 'plant' the very tables -- on the device the very tensor -- the plant steps with"""
-        if self._models_arg is None:
-            return
-        self._models = self._joints_noisy if isinstance(self._models_arg, str) else table
-        _set_models(self._ctrl.ocp_solver, self._models)
-
-    def _backup_models(self, rows):
-        """... and the backup OCP of an abort event is solved with the models of the aborting instances, like its scenes"""
-        if self._models is not None:
-            _set_models(self._backup.ocp_solver, self._models[rows])
-
     def _progress(self, j):
         xp = self._xp
         if self._callback and j % 50 == 0:
@@ -1211,12 +1366,8 @@ class _Group:
     def results(self, score=False):
         xp, ctrl, params, B, n_steps = self._xp, self._ctrl, self._params, self._B, self._n_steps
         solver, pr = ctrl.ocp_solver, ctrl.problem
-        scored = None
-        if self._forecast is not None:
-            # the run is scored in the TRUE world: the track replaces the last forecast in the scene slot (with its context track
-            # where the net has one), read by the loop's clock again
-            _set_scene(solver, self._scenes)
-            solver.set_scene_clock(self._clock)
+        scored, world = None, self._world
+        world.to_true_world()
         if score:
             # the run's scores: on the device from the logs where they are (one enqueue on the group's stream, ahead of the wait
             # below), on the host by the statement; the safe-set score where the formulation has a safe-set row
@@ -1227,8 +1378,8 @@ class _Group:
             else:
                 scored = score_rollout_statement(solver, pr, params, self.x_log, self.u_log, self.last_x, self.last_u,
                                                  traj=None if traj is None else xp.host(traj), want_safe=want_safe,
-                                                 per_instance=self._scenes is not None,
-                                                 scene_clock=self._clock if self._track else None)
+                                                 per_instance=world.scenes is not None,
+                                                 scene_clock=world.clock if world.track else None)
         if xp.on_device:
             solver.sync()
         # convergence at the last step (mpc.py:273): the reference tests x_sim[-1], NaN for instances that broke
@@ -1244,24 +1395,9 @@ class _Group:
         if not self._quirks:
             conv &= xp.host(self.alive)        # (the reference tests x_sim[-1] even of an instance it has just recorded as failed)
         extra = {'score': _score_dict(xp.host(scored[0]), xp.host(scored[1]))} if score else {}
-        if self._scenes is not None:
-            extra['scenes'] = xp.host(self._scenes)
-            _clear_scene(solver)                   # (every engine call of the run has been enqueued with its scene by now)
-            _clear_scene(self._backup.ocp_solver)
-            if self._forecast is not None:         # (nor a world, nor what was observed of it)
-                for sv in (solver, self._backup.ocp_solver):
-                    if self._observed is not None and hasattr(sv, 'set_instance_observed_track'):
-                        sv.set_instance_observed_track(None)
-                    if hasattr(sv, 'set_instance_world_track'):
-                        sv.set_instance_world_track(None)
-        if self._row_bounds is not None:           # (nor a row-bounds table)
-            solver.set_instance_row_bounds(None)
-            self._backup.ocp_solver.set_instance_row_bounds(None)
-        if self._models is not None:               # (nor a model table)
-            _set_models(solver, None)
-            _set_models(self._backup.ocp_solver, None)
-        if getattr(ctrl, 'traj', None) is not None and ctrl.traj.ndim == 3 and hasattr(solver, 'set_instance_curves'):
-            solver.set_instance_curves(None)       # (nor curves: the controller hands them over again should it step once more)
+        if world.scenes is not None:
+            extra['scenes'] = xp.host(world.scenes)
+        world.detach()
         return dict(**extra, x=x_sim, u=u_sim, r_receding=np.transpose(xp.host(self.r_log), (1, 0))[:, :, None], conv=conv,
                     time_rows=np.array(self._time_rows, float).reshape(-1, len(TIME_FIELDS)), time_lost=self._time_lost,
                     collided=xp.host(self.collided), viable=xp.host(self.viable).astype(np.int64),
@@ -1281,14 +1417,7 @@ class _HostGroup(_Group):
         self._zeros_u = np.zeros((B, self._ctrl.nu))
         self._jt = 0                              # the step counter
         self._ever_aborted = False
-        # a scene track: the step counter as the scene clock, one cell per handle, written before the calls of a step
-        self._clock = self._backup_clock = None
-        if self._track:
-            self._clock = _new_scene_clock(self._ctrl.ocp_solver)
-            self._backup_clock = _new_scene_clock(self._backup.ocp_solver)
-            self._ctrl.ocp_solver.set_scene_clock(self._clock)
-            self._backup.ocp_solver.set_scene_clock(self._backup_clock)
-        self._hand_over_models(self._models_arg)
+        self._world.attach_loop(None, self._joints_noisy)
 
     # ---- first half: everything up to the controller's verdict ---------------------------------------------------------------
     def part_a(self):
@@ -1320,10 +1449,7 @@ class _HostGroup(_Group):
         stepping = self.alive & ~self.sa
         if hasattr(ctrl, 'r'):
             self.r_log[self._jt] = np.where(stepping, ctrl.r, -1)
-        if self._forecast is None:
-            _write_scene_clock(self._clock, self._jt)       # node k of this step's solve and tests: time j + k
-        else:                                               # ... in the scenes forecast at time j, read from node 0 on
-            self._forecast_onto(ctrl.ocp_solver, slice(None), self._jt, ctrl.N)
+        self._world.head_of_step(self._jt)
         # (until the first abort event every live instance steps: no snapshot / roll-back needed; dead instances are never
         #  read again, so they may step along)
         if self._ever_aborted:
@@ -1340,25 +1466,6 @@ class _HostGroup(_Group):
             self.sa = self.sa | again
             self.new_abort = self.new_abort & ~again
 
-    def _forecast_onto(self, sv, rows, t, N):
-        """the statement of smpc_forecast_scene / smpc_forecast_scene_fit / smpc_forecast_scene_poly: the N + 1 scenes forecast at
-        time t for the instances ``rows`` onto ``sv``'s scene slot (and their context rows, _set_scene), with no clock -- node k reads
-        column k.  'hold', 'cv' and 'fit' (of any degree) are formed from what was seen, the observed track where the run has one;
-        'true' from the world"""
-        from .problem import fit_forecast_statement, forecast_statement, poly_forecast_statement
-        seen = self._scenes if self._observed is None or self._forecast == 'true' else self._observed
-        sv.set_scene_clock(None)
-        if self._forecast != 'fit':
-            F = forecast_statement(seen[rows], t, N, self._forecast)
-        elif self._degree == 1:
-            F = fit_forecast_statement(seen[rows], t, N, self._window)
-        else:
-            F = poly_forecast_statement(seen[rows], t, N, self._window, self._degree)
-        _set_scene(sv, F)
-
-    def _backup_forecast(self, rows):
-        self._forecast_onto(self._backup.ocp_solver, rows, self._jt, self._Nb)
-
     # ---- the step's decision: abort events (mpc.py:161-190) ----------------------------------------------------------------------
     def handle_aborts(self):
         ctrl, backup, B, Nb = self._ctrl, self._backup, self._B, self._Nb
@@ -1370,10 +1477,8 @@ class _HostGroup(_Group):
         j, n_c = self._jt, len(rows)
         xv_c = ctrl.getLastViableState()[rows]
         xg_c = np.repeat(xv_c[:, None, :], Nb + 1, axis=1)
-        self._backup_scene(rows)
-        self._backup_row_bounds(rows)
-        self._backup_models(rows)
-        _write_scene_clock(self._backup_clock, j)
+        self._world.dress_backup(rows, j)
+        _write_scene_clock(self._world.backup_clock, j)
         xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(np.ascontiguousarray(xv_c), xg_c, np.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
         self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))
         ok_c = np.asarray(st_c) == 0
@@ -1402,10 +1507,8 @@ class _HostGroup(_Group):
         # outcome tests on the new state (mpc.py:246-264): one node per instance, so the engine's box + collision test
         # (model bounds widened by tol_x, rows against the check bounds) is exactly checkStateConstraints; the new state is
         # the state of time j + 1, which is where a scene track is read -- with a forecast the WORLD's track, not the controller's
-        if self._forecast is not None:
-            _set_scene(solver, self._scenes)
-            solver.set_scene_clock(self._clock)
-        _write_scene_clock(self._clock, j + 1)
+        self._world.to_true_world()
+        _write_scene_clock(self._world.clock, j + 1)
         okn = np.asarray(solver.check_trajectory(x_next[:, None, :]))
         self.x_log[j + 1] = x_next
         bad = self.alive & ~okn
@@ -1438,38 +1541,12 @@ class _DeviceGroup(_Group):
         super().__init__(*args, **kw)
         import torch
         xp, ctrl, B, nu = self._xp, self._ctrl, self._B, self._ctrl.nu
-        as_tensor = lambda t: xp.asarray(np.ascontiguousarray(t).view(np.float64).reshape(B, ctrl.nq, -1), xp.f64)
-        if self._joints_noisy is not None:            # [B, nq] smpc_joint records as a float64 tensor (29 doubles each)
-            self._joints_noisy = as_tensor(self._joints_noisy)
-        self._hand_over_models(None if self._models_arg is None or isinstance(self._models_arg, str) else as_tensor(self._models_arg))
+        if self._joints_noisy is not None:
+            self._joints_noisy = _joint_tensor(xp, self._joints_noisy, B, ctrl.nq)
         if self._tau_noise is not None:
             self._tau_noise = xp.asarray(self._tau_noise, xp.f64)
         self._jt = xp.step_index(0)               # the step counter, a device tensor: smpc_loop_post advances it, graphs replay it
-        # a scene track: the step counter IS the controller handle's scene clock (smpc_loop_post reads column j + 1 and then
-        # advances it).  The backup handle solves on its own stream while the loop goes on, so its clock is a cell of its own
-        # that receives the counter's value at the abort event, on the loop's stream (handle_aborts).
-        self._clock = self._backup_clock = None
-        if self._track:
-            self._clock, self._backup_clock = self._jt, xp.step_index(0)
-            ctrl.ocp_solver.set_scene_clock(self._clock)
-            self._backup.ocp_solver.set_scene_clock(self._backup_clock)
-        # a forecast: the world goes on once; smpc_forecast_scene at the head of every step (inside the captured half) fills the
-        # scene slot from it at the counter's value, and smpc_loop_post tests the plant's next state in the world
-        self._select = self._backup_select = None
-        if self._forecast is not None:
-            for sv in (ctrl.ocp_solver, self._backup.ocp_solver):
-                if not hasattr(sv, 'forecast_scene'):
-                    raise ValueError(f'forecast: {type(sv).__name__} has no forecast_scene')
-                if self._forecast == 'fit' and not hasattr(sv, 'forecast_scene_fit'):
-                    raise ValueError(f"forecast: {type(sv).__name__} has no forecast_scene_fit")
-                if self._forecast == 'fit' and self._degree != 1 and not hasattr(sv, 'forecast_scene_poly'):
-                    raise ValueError(f"forecast_degree: {type(sv).__name__} has no forecast_scene_poly")
-                if self._observed is not None and not hasattr(sv, 'set_instance_observed_track'):
-                    raise ValueError(f'observed: {type(sv).__name__} has no set_instance_observed_track')
-            self._select, self._backup_select = _context_select(ctrl.ocp_solver), _context_select(self._backup.ocp_solver)
-            ctrl.ocp_solver.set_instance_world_track(self._scenes)
-            if self._observed is not None:          # (what HOLD, CV and the fit then read instead of the world)
-                ctrl.ocp_solver.set_instance_observed_track(self._observed)
+        self._world.attach_loop(self._jt, self._joints_noisy)
         self._use_graphs = bool(use_graphs)
         self._graphs = {}                         # half -> captured graph
         self._u_other = xp.zeros((B, nu))
@@ -1489,8 +1566,7 @@ class _DeviceGroup(_Group):
 
     def part_a(self):
         ctrl, sv = self._ctrl, self._ctrl.ocp_solver
-        if self._forecast is not None:
-            self._enqueue_forecast(sv, self._select)
+        self._world.head_of_step()
         sv.loop_pre(self, getattr(ctrl, 'r', None), self._pending, self._u_other, self._stepping)
         ctrl.step_on_device(self.x_cur, self._stepping, self._u_other, u_out=self.u)
         if ctrl.can_abort:
@@ -1523,17 +1599,15 @@ class _DeviceGroup(_Group):
         n_c = len(rows)
         self._abort_events.append((rows + self._first, np.full(n_c, j), xv_c))      # (xv_c goes to the host in results())
         self._pending.copy_(self.new_abort)
-        if self._backup_clock is not None:
-            self._backup_clock.copy_(self._jt)               # (the previous event's solve has finished: _apply_inflight above)
+        if self._world.backup_clock is not None:
+            self._world.backup_clock.copy_(self._jt)         # (the previous event's solve has finished: _apply_inflight above)
         main = torch.cuda.current_stream()
         ev0 = torch.cuda.Event()
         ev0.record(main)
         with torch.cuda.stream(self._side):
             self._side.wait_event(ev0)
             xg_c = xp.repeat_nodes(xv_c, Nb + 1)
-            self._backup_scene(rows_b)
-            self._backup_row_bounds(rows_b)
-            self._backup_models(rows_b)
+            self._world.dress_backup(rows_b)
             xo_c, uo_c, st_c, _ = backup.ocp_solver.solve(xv_c, xg_c, xp.zeros((n_c, Nb, ctrl.nu)), backup.p[:n_c])
             ev = torch.cuda.Event()
             ev.record(self._side)
@@ -1542,24 +1616,6 @@ class _DeviceGroup(_Group):
         #  event recorded on the main stream after that.  torch's record_stream is not usable here -- on this ROCm build it
         #  faults on an ExternalStream.)
         self._inflight = (rows_b, xv_c, xo_c, uo_c, st_c, ev)
-
-    def _backup_forecast(self, rows):
-        """the aborting instances' world rows onto the backup handle and one forecast over ITS horizon, at its own clock cell (which
-        holds the counter's value at the event: handle_aborts)"""
-        sv = self._backup.ocp_solver
-        sv.set_instance_world_track(self._scenes[rows])
-        if self._observed is not None:
-            sv.set_instance_observed_track(self._observed[rows])
-        self._enqueue_forecast(sv, self._backup_select)
-
-    def _enqueue_forecast(self, sv, select):
-        """one forecast of the run's kind from ``sv``'s world (and observed track) at its clock cell, into its scene slot"""
-        if self._forecast == 'fit' and self._degree != 1:
-            sv.forecast_scene_poly(self._window, self._degree, select)
-        elif self._forecast == 'fit':
-            sv.forecast_scene_fit(self._window, select)
-        else:
-            sv.forecast_scene(self._forecast, select)
 
     def part_b(self):
         self._ctrl.ocp_solver.loop_post(self, self.u, self._joints_noisy, self._tau_noise)
@@ -1727,42 +1783,7 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     ``'row_margin'``.  Not with the parallel policy (ValueError).  None: the calls of a run without the argument, one for one."""
     import time
     B = x_guess.shape[0]
-    models = _check_models(models, B, noise, cont_name)
-    if scenes is not None:
-        if cont_name == 'parallel':
-            raise ValueError("scenes: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
-                             "the engine refuses a scene there)")
-        scenes = np.ascontiguousarray(scenes, np.float64)
-        if scenes.ndim not in (3, 4) or scenes.shape[0] != B:
-            raise ValueError(f'scenes: expected [{B}, n_rows, 8] or a track [{B}, T, n_rows, 8], got {scenes.shape}')
-    if row_margin is not None:
-        if cont_name == 'parallel':
-            raise ValueError("row_margin: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
-                             "the engine refuses a row-bounds table there)")
-        row_margin = tuple(float(v) for v in np.asarray(row_margin, float).reshape(-1))
-        if len(row_margin) != 2 or not all(np.isfinite(row_margin)):
-            raise ValueError(f'row_margin: expected (a, b), the margin a + b k metres at node k, got {row_margin}')
-    if forecast is not None:
-        from .problem import FIT_MAX, FORECAST_MODES
-        if forecast != 'fit' and forecast not in FORECAST_MODES:
-            raise ValueError(f"forecast: {forecast!r}: expected None, 'fit' or one of {sorted(FORECAST_MODES)}")
-        if forecast == 'fit' and not (isinstance(forecast_window, (int, np.integer)) and 1 <= forecast_window <= FIT_MAX):
-            raise ValueError(f'forecast_window: {forecast_window!r}: a fit takes 1 to {FIT_MAX} columns')
-        if scenes is None or scenes.ndim != 4:
-            raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
-                             + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
-    if forecast_degree is not None:
-        if forecast != 'fit':
-            raise ValueError(f"forecast_degree: forecast={forecast!r} has no degree: it goes with forecast='fit'")
-        if not (isinstance(forecast_degree, (int, np.integer)) and 0 <= forecast_degree <= 2):
-            raise ValueError(f'forecast_degree: {forecast_degree!r}: a polynomial fit has degree 0, 1 or 2')
-    degree = 1 if forecast_degree is None else int(forecast_degree)
-    if observed is not None:
-        if forecast is None or forecast == 'true':
-            raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
-        observed = np.ascontiguousarray(observed, np.float64)
-        if observed.shape != scenes.shape:
-            raise ValueError(f'observed: expected the world\'s shape {scenes.shape}, got {observed.shape}')
+    world = _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models)
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1784,28 +1805,22 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     gens, grps, streams = [], [], []
     for lo, hi in spans:
         ctrl = make_controller(cont_name, hi - lo)
-        if models is not None and not hasattr(ctrl.ocp_solver, 'set_instance_models'):
-            raise ValueError(f'models: {type(ctrl.ocp_solver).__name__} has no set_instance_models')
+        if world.models is not None:
+            _require(ctrl.ocp_solver, 'models', 'set_instance_models')
         backup = make_backup(hi - lo)
         _check_state_kind(ctrl, backup, on_device)
         if traj is not None:
             ctrl.setTrajectory(traj[lo:hi] if curves else traj)
         args = (params, x_guess[lo:hi], u_guess[lo:hi], noise, control_noise, ctrl, backup, n_steps, lo, callback, collect_times)
-        fit_kw = dict(forecast_window=int(forecast_window) if forecast == 'fit' else None, forecast_degree=degree,
-                      observed=None if observed is None else observed[lo:hi])
-        if row_margin is not None:          # (a run without it constructs its groups with the arguments of before)
-            fit_kw['row_margin'] = row_margin
         if on_device:
             import torch
             sv = ctrl.ocp_solver
             streams.append(torch.cuda.ExternalStream(sv.L.smpc_stream(sv.h), device=torch.device('cuda', sv.device)))
             with torch.cuda.stream(streams[-1]):
-                grp = _DeviceGroup(*args, scenes=None if scenes is None else scenes[lo:hi], use_graphs=graphs, forecast=forecast, **fit_kw,
-                                   models=models if models is None or isinstance(models, str) else models[lo:hi])
+                grp = _DeviceGroup(*args, use_graphs=graphs, world=world.rows(lo, hi))
         else:
             streams.append(None)
-            grp = _HostGroup(*args, scenes=None if scenes is None else scenes[lo:hi], forecast=forecast, **fit_kw,
-                             models=models if models is None or isinstance(models, str) else models[lo:hi])
+            grp = _HostGroup(*args, world=world.rows(lo, hi))
         grps.append(grp)
         gens.append(grp.run())
 
@@ -1885,15 +1900,10 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra['score'] = {k: np.concatenate([o['score'][k] for o in outs]) for k in outs[0]['score']}
     if scenes is not None:
         extra['scenes'] = np.concatenate([o['scenes'] for o in outs], axis=0)
-    if forecast is not None:
-        extra['forecast'] = forecast
-        extra['observed'] = observed is not None
-        if forecast == 'fit':
-            extra['forecast_window'] = int(forecast_window)
-            if degree != 1:
-                extra['forecast_degree'] = degree
-    if row_margin is not None:
-        extra['row_margin'] = row_margin
+    if world.forecast is not None:
+        extra.update(world.forecast.result_keys(observed is not None))
+    if world.row_margin is not None:
+        extra['row_margin'] = world.row_margin
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -230,6 +230,17 @@ class BatchedOcpSolver:
         evaluates collision rows uses it and must come with the same B; the parallel policy and :meth:`rollout` refuse it."""
         self._set_instance(self.L.smpc_set_instance_scene, 'set_instance_scene', [geom], (len(self.problem.rows), SCENE_ROW))
 
+    def _set_track(self, fn, name, geom):
+        """what the three track setters share: ``geom`` is None (clears the slot) or ``[B, T >= 1, n_rows, 8]``"""
+        T = 1
+        if geom is not None:
+            if geom.ndim != 4:
+                raise ValueError(f'{name}: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
+            T = int(geom.shape[1])
+            if T < 1:
+                raise ValueError(f'{name}: a track has at least one time column')
+        self._set_instance(fn, name, [geom], (T, len(self.problem.rows), SCENE_ROW), T)
+
     def set_instance_scene_track(self, geom=None):
         """Obstacles that move along the horizon (smpc_set_instance_scene_track): ``geom [B, T, n_rows, 8]``, one scene of
         :meth:`set_instance_scene`'s layout per (instance, time column) -- ``OcpProblem.scene_track`` / ``moving_scenes`` -- as a
@@ -237,31 +248,23 @@ class BatchedOcpSolver:
         formed in column ``clip(t + k, 0, T - 1)``, t = the scene clock (:meth:`set_scene_clock`; 0 without one); the table of
         include/smpc.h says it for every entry point.  A track and a scene are one slot: setting one replaces the other, and None
         (here or in ``set_instance_scene``) clears both."""
-        T = 1
-        if geom is not None:
-            if geom.ndim != 4:
-                raise ValueError(f'set_instance_scene_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
-            T = int(geom.shape[1])
-            if T < 1:
-                raise ValueError('set_instance_scene_track: a track has at least one time column')
-        self._set_instance(self.L.smpc_set_instance_scene_track, 'set_instance_scene_track', [geom],
-                           (T, len(self.problem.rows), SCENE_ROW), T)
+        self._set_track(self.L.smpc_set_instance_scene_track, 'set_instance_scene_track', geom)
 
     def set_instance_world_track(self, geom=None):
         """The WORLD of every instance (smpc_set_instance_world_track): ``geom [B, T, n_rows, 8]``, a scene
         track's layout, as a numpy array or a contiguous ROCm float64 tensor; the engine keeps a copy.  Only :meth:`forecast_scene`
         and the plant's outcome test of :meth:`loop_post` read it -- the controller plans in the scene slot, which a forecast
         fills.  None clears it, and with it a forecast in the scene slot and a context that the forecast wrote."""
-        T = 1
-        if geom is not None:
-            if geom.ndim != 4:
-                raise ValueError(f'set_instance_world_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
-            T = int(geom.shape[1])
-            if T < 1:
-                raise ValueError('set_instance_world_track: a track has at least one time column')
-        self._set_instance(self.L.smpc_set_instance_world_track, 'set_instance_world_track', [geom],
-                           (T, len(self.problem.rows), SCENE_ROW), T)
+        self._set_track(self.L.smpc_set_instance_world_track, 'set_instance_world_track', geom)
         self._world_B = 0 if geom is None else int(geom.shape[0])
+
+    def _forecast(self, fn, select, B, *ints):
+        """what the three forecast entry points share, for ``fn(h, B, *ints, n_sel, select)``.  Ordered like a device-path call wherever
+        torch is in play: the clock cell is the caller's to write on torch's stream, and a capture on torch's stream must see the launch"""
+        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
+        B = int(getattr(self, '_world_B', 0) if B is None else B)
+        with self._ordered('torch' in sys.modules):
+            self._chk(fn(self.h, B, *ints, len(sel), sel.ctypes.data if len(sel) else None))
 
     def forecast_scene(self, mode, select=None, B=None):
         """The horizon's N + 1 scenes as forecast from the world at the scene clock, into the scene slot (smpc_forecast_scene;
@@ -275,12 +278,7 @@ class BatchedOcpSolver:
             if mode not in FORECAST_MODES:
                 raise ValueError(f'forecast_scene: mode {mode!r}: expected one of {sorted(FORECAST_MODES)}')
             mode = FORECAST_MODES[mode]
-        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
-        B = int(getattr(self, '_world_B', 0) if B is None else B)
-        # (ordered like a device-path call wherever torch is in play: the clock cell is the caller's to write on torch's stream, and a
-        #  capture on torch's stream must see the launch)
-        with self._ordered('torch' in sys.modules):
-            self._chk(self.L.smpc_forecast_scene(self.h, B, int(mode), len(sel), sel.ctypes.data if len(sel) else None))
+        self._forecast(self.L.smpc_forecast_scene, select, B, int(mode))
 
     def set_instance_observed_track(self, geom=None):
         """What the controller OBSERVES of the world (smpc_set_instance_observed_track): ``geom [B, T, n_rows,
@@ -288,35 +286,21 @@ class BatchedOcpSolver:
         engine keeps a copy.  While it is set, :meth:`forecast_scene` ('hold', 'cv') and :meth:`forecast_scene_fit` read it instead
         of the world; 'true' and the plant's outcome test of :meth:`loop_post` keep reading the world.  None clears it, and so does
         clearing the world."""
-        T = 1
-        if geom is not None:
-            if geom.ndim != 4:
-                raise ValueError(f'set_instance_observed_track: expected [B, T, n_rows, {SCENE_ROW}], got {tuple(geom.shape)}')
-            T = int(geom.shape[1])
-            if T < 1:
-                raise ValueError('set_instance_observed_track: a track has at least one time column')
-        self._set_instance(self.L.smpc_set_instance_observed_track, 'set_instance_observed_track', [geom],
-                           (T, len(self.problem.rows), SCENE_ROW), T)
+        self._set_track(self.L.smpc_set_instance_observed_track, 'set_instance_observed_track', geom)
 
     def forecast_scene_fit(self, window, select=None, B=None):
         """The horizon's N + 1 scenes forecast by a least-squares line through the last ``window`` (1..``problem.FIT_MAX``) columns of
         what was seen -- the observed track, or the world without one -- at the scene clock, into the scene slot
         (smpc_forecast_scene_fit; ``problem.fit_forecast_statement`` is its definition).  Enqueue-only; ``select`` and ``B`` as for
         :meth:`forecast_scene`, and the slot is read from time 0 in the same way.  Window 1 is 'hold', window 2 is 'cv'."""
-        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
-        B = int(getattr(self, '_world_B', 0) if B is None else B)
-        with self._ordered('torch' in sys.modules):         # (as forecast_scene)
-            self._chk(self.L.smpc_forecast_scene_fit(self.h, B, int(window), len(sel), sel.ctypes.data if len(sel) else None))
+        self._forecast(self.L.smpc_forecast_scene_fit, select, B, int(window))
 
     def forecast_scene_poly(self, window, degree, select=None, B=None):
         """The horizon's N + 1 scenes forecast by a least-squares polynomial of degree 0, 1 or 2 through the last ``window``
         (1..``problem.FIT_MAX``) columns of what was seen, at the scene clock, into the scene slot (smpc_forecast_scene_poly;
         ``problem.poly_forecast_statement`` is its definition).  Enqueue-only; ``select`` and ``B`` as for :meth:`forecast_scene`.
         Degree 1 is :meth:`forecast_scene_fit`, degree 0 the window mean, degree 2 a constant-acceleration model."""
-        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
-        B = int(getattr(self, '_world_B', 0) if B is None else B)
-        with self._ordered('torch' in sys.modules):         # (as forecast_scene)
-            self._chk(self.L.smpc_forecast_scene_poly(self.h, B, int(window), int(degree), len(sel), sel.ctypes.data if len(sel) else None))
+        self._forecast(self.L.smpc_forecast_scene_poly, select, B, int(window), int(degree))
 
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on
