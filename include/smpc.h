@@ -393,6 +393,38 @@ int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int 
  * (ABI version unchanged: no existing entry point or structure changed) */
 int smpc_set_instance_row_bounds(smpc_handle* h, int B, const double* lo, const double* hi, int on_device);
 
+/* The row-bounds table formed ON THE DEVICE from the residuals of a fit: a prediction interval per instance, row and node (DESIGN.md
+ * section 9r).  Enqueue-only once the slot's buffer has its size.  Reads S ("what was seen": the observed track while one is set, else
+ * the world) and the scene clock exactly as smpc_forecast_scene_poly does -- t, col, m = min(window, max(t, 0) + 1),
+ * p = min(degree, m - 1), y_j = S[b][col(t - j)][r][s] and a, v, e are that call's, the same operations in the same order -- and is
+ * meant to follow a forecast with the same window and degree; it neither needs nor touches the scene slot.  For instance b and row r:
+ *   moving slots  SMPC_ROW_SEG_FIXEDSEG: 0..5;  SMPC_ROW_SEG_POINT, _POINT_POINT: 0..2;  SMPC_ROW_COORD: 6;  SMPC_ROW_SEG_SEG: none (d = 0)
+ *   nu = m - p - 1.   nu >= 1:  per moving slot, in increasing j:  f_j = a  |  a - j v  |  (a - j v) + (j (j + 1) / 2) e   (p = 0 | 1 | 2)
+ *                               res = y_j - f_j;   q = res res at j = 0,  q = q + res res afterwards;   rss = the largest q over the
+ *                               moving slots, a NaN winning;   s2 = rss / (double)nu,  raised to sigma_prior^2 where it is below it
+ *                               (a NaN stays)
+ *                     nu == 0:  s2 = sigma_prior^2  (nothing can be estimated)
+ *   h_k = sum_j c_kj^2  (increasing j from the j = 0 term),  c_kj = 1.0 / (double)m  |  u_j + k w_j  |  (ua_j + k uv_j) + (k (k - 1) / 2) ue_j
+ *         with the weights of smpc_forecast_scene_fit / _poly: no "+ 1" under the root, the true obstacle carries no noise
+ *   d_k = (base_a + base_b k) + (z sqrt(s2)) sqrt(h_k),   d_k = d_k <= d_max ? d_k : d_max       (a NaN in the window gives the cap)
+ * every product rounded before its sum.  The table is what smpc_set_instance_row_bounds would be handed for these margins: a plane row
+ * gets lb + d_k and ub - d_k, any other row (sqrt(lb) + d_k)^2, a side with |v| >= SMPC_INF stays absent, and where d_k == 0.0 the
+ * descriptor's own lb and ub.  It fills the slot of smpc_set_instance_row_bounds for B under that slot's rules: the same size is
+ * overwritten in place, so a captured [forecast; margin; solve] replays with the clock; smpc_set_horizon drops it;
+ * SMPC_POLICY_PARALLEL and smpc_rollout_batch keep refusing the slot.  A refused call changes nothing.
+ * SMPC_ESTATE: no world is set; the buffer would have to grow while the stream is being captured.
+ * SMPC_EINVAL: B is not the world's; an observed track of another shape than the world's; window outside 1..SMPC_FIT_MAX; degree
+ * outside 0..2; z, sigma_prior, base_a, base_b or d_max negative or not finite (the message names it); a d_max with which a plane
+ * row's two sides would cross, lb + d_max > ub - d_max (the message names the row); a descriptor without rows.
+ * (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_forecast_row_margin(smpc_handle* h, int B, int window, int degree, double z, double sigma_prior, double base_a, double base_b,
+                             double d_max);
+
+/* The row-bounds table as the slot holds it: lo and hi receive [B][N+1][n_rows] doubles each.  Stream-ordered with device pointers;
+ * with host pointers the call waits for the copy.  SMPC_ESTATE while no table is set, SMPC_EINVAL for another B than the table's or a
+ * NULL pointer.  What a test or a study reads the margins of a step with. */
+int smpc_get_instance_row_bounds(smpc_handle* h, int B, double* lo, double* hi, int on_device);
+
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle
  * keeps a copy like a scene (stream-ordered; with host pointers the call checks every entry for finiteness and waits for the

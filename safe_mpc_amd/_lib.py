@@ -23,7 +23,8 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_score_rollout', 'smpc_set_instance_scene', 'smpc_ik_batch', 'smpc_ray_update', 'smpc_set_instance_curves',
            'smpc_set_instance_scene_track', 'smpc_set_scene_clock', 'smpc_set_mlp_context', 'smpc_set_instance_context',
            'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene',
-           'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit', 'smpc_forecast_scene_poly', 'smpc_set_instance_row_bounds']
+           'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit', 'smpc_forecast_scene_poly', 'smpc_set_instance_row_bounds',
+           'smpc_forecast_row_margin', 'smpc_get_instance_row_bounds']
 
 
 class EngineError(RuntimeError):
@@ -145,6 +146,8 @@ def lib():
     L.smpc_set_instance_observed_track.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_forecast_scene_fit.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     L.smpc_forecast_scene_poly.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    L.smpc_forecast_row_margin.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5
+    L.smpc_get_instance_row_bounds.argtypes = [vp, C.c_int, dp, dp, C.c_int]
     L.smpc_set_instance_curves.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_solve_batch.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_eval_nodes.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int]

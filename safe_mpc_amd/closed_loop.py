@@ -31,12 +31,13 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
 
 
 def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None,
-                forecast_window=None, obs_noise=0.0, forecast_degree=1, row_margin=None):
+                forecast_window=None, obs_noise=0.0, forecast_degree=1, row_margin=None, row_margin_fit=None):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
     before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
     it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns, ``_d<p>`` behind that for ``forecast_degree = p`` other than 1
     (a polynomial fit, --forecast-degree); ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
     that; ``row_margin = (a, b)`` (--row-margin, run_mpc(row_margin=...)): ``_rm<a>`` behind that, and ``_g<b>`` for b other than 0;
+    ``row_margin_fit = (z, sigma_prior, d_max)`` (--row-margin-z, run_mpc(row_margin_fit=...)): ``_rmf<z>_p<sigma_prior>_c<d_max>`` behind that;
     the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
@@ -47,6 +48,7 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
             f"{'' if forecast is None else _Forecast(forecast, forecast_window, forecast_degree).file_suffix()}"
             f"{f'_on{obs_noise}' if obs_noise > 0 else ''}"
             f"{'' if row_margin is None else f'_rm{float(row_margin[0])}' + (f'_g{float(row_margin[1])}' if float(row_margin[1]) != 0.0 else '')}"
+            f"{'' if row_margin_fit is None else '_rmf{}_p{}_c{}'.format(*(float(v) for v in row_margin_fit))}"
             "_mpc.pkl")
 
 
@@ -1114,8 +1116,8 @@ class _Forecast:
         return f"_fc{self.kind}{f'_w{self.window}' if self._fit else ''}{f'_d{self.degree}' if self._poly else ''}"
 
 
-class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_margin', defaults=(None,) * 5)):
-    """run_mpc's ``scenes``, ``models``, ``forecast*`` (a :class:`_Forecast`), ``observed`` and ``row_margin``, checked
+class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_margin row_margin_fit', defaults=(None,) * 6)):
+    """run_mpc's ``scenes``, ``models``, ``forecast*`` (a :class:`_Forecast`), ``observed``, ``row_margin`` and ``row_margin_fit``, checked
     (:func:`_check_world`): of the whole run, or of one group's instances (:meth:`rows`)"""
 
     def rows(self, lo, hi):
@@ -1123,9 +1125,11 @@ class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_mar
         return self._replace(scenes=cut(self.scenes), models=cut(self.models), observed=cut(self.observed))
 
 
-def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models):
+def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models,
+                 row_margin_fit=None):
     """run_mpc's arguments about the world of its B instances, before anything is built: the :class:`_RunWorld`, or ValueError"""
-    for name, given, thing in (('models', models, 'model table'), ('scenes', scenes, 'scene'), ('row_margin', row_margin, 'row-bounds table')):
+    for name, given, thing in (('models', models, 'model table'), ('scenes', scenes, 'scene'), ('row_margin', row_margin, 'row-bounds table'),
+                               ('row_margin_fit', row_margin_fit, 'row-bounds table')):
         if cont_name == 'parallel' and given is not None:
             raise ValueError(f"{name}: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
                              f"the engine refuses a {thing} there)")
@@ -1147,13 +1151,19 @@ def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_win
         if len(row_margin) != 2 or not all(np.isfinite(row_margin)):
             raise ValueError(f'row_margin: expected (a, b), the margin a + b k metres at node k, got {row_margin}')
     fc = _Forecast.checked(forecast, forecast_window, forecast_degree, scenes)
+    if row_margin_fit is not None:
+        if forecast != 'fit':
+            raise ValueError(f"row_margin_fit: forecast={forecast!r} leaves no residuals to form a margin from: it goes with forecast='fit'")
+        row_margin_fit = tuple(float(v) for v in np.asarray(row_margin_fit, float).reshape(-1))
+        if len(row_margin_fit) != 3 or not all(np.isfinite(v) and v >= 0.0 for v in row_margin_fit):
+            raise ValueError(f'row_margin_fit: expected (z, sigma_prior, d_max), finite and not negative, got {row_margin_fit}')
     if observed is not None:
         if fc is None or fc.kind == 'true':
             raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
         observed = np.ascontiguousarray(observed, np.float64)
         if observed.shape != scenes.shape:
             raise ValueError(f'observed: expected the world\'s shape {scenes.shape}, got {observed.shape}')
-    return _RunWorld(scenes, models, fc, observed, row_margin)
+    return _RunWorld(scenes, models, fc, observed, row_margin, row_margin_fit)
 
 
 def _joint_tensor(xp, table, B, nq):        # [B, nq] smpc_joint records as a float64 device tensor [B, nq, 29]
@@ -1171,6 +1181,7 @@ class _World:
         self._run, self._ctrl, self._backup, self._B, self._xp = run, ctrl, backup, B, ctrl.xp
         self._sv, self._bsv, self.forecast, self.track = ctrl.ocp_solver, backup.ocp_solver, run.forecast, False
         self.scenes = self.observed = self.row_bounds = self.models = self.clock = self.backup_clock = self._select = self._backup_select = None
+        self.margin_fit = None      # (z, sigma_prior, base, d_max) of a margin formed from the fit's residuals at the head of every step
 
     def attach(self):
         """what the run's arguments alone say: the scenes (without a forecast) and the row bounds onto the controller's handle"""
@@ -1185,7 +1196,13 @@ class _World:
             if self.track:
                 for sv in (self._sv, self._bsv):
                     _require(sv, 'scenes', 'set_scene_clock')
-        if run.row_margin is not None:
+        if run.row_margin_fit is not None:
+            # the margin follows the fit, step by step; row_margin is its base, not a table of its own
+            z, prior, cap = run.row_margin_fit
+            self.margin_fit = (z, prior, (0.0, 0.0) if run.row_margin is None else tuple(float(v) for v in run.row_margin), cap)
+            for sv in (self._sv, self._bsv):
+                _require(sv, 'row_margin_fit', 'forecast_row_margin' if xp.on_device else 'set_instance_row_bounds')
+        elif run.row_margin is not None:
             from .problem import inflated_row_bounds
             for sv in (self._sv, self._bsv):
                 _require(sv, 'row_margin', 'set_instance_row_bounds')
@@ -1230,11 +1247,25 @@ class _World:
         sv.set_scene_clock(None)
         _set_scene(sv, self.forecast.statement(self.scenes, self.observed, rows, t, N))
 
+    def _margin_into(self, sv, prob, rows, t):
+        """the row-bounds table of ``sv`` from the residuals of the fit it has just forecast with: on the device one enqueued call at
+        its clock cell; on the host the statement at time ``t`` for the instances ``rows`` over ``prob``'s horizon, then the setter"""
+        z, prior, base, cap = self.margin_fit
+        fc = self.forecast
+        if self._xp.on_device:
+            return sv.forecast_row_margin(fc.window, fc.degree, z, prior, base, cap)
+        from .problem import fit_margin_statement, inflated_row_bounds
+        seen = self.scenes if self.observed is None else self.observed
+        d = fit_margin_statement(prob, seen[rows], t, fc.window, fc.degree, z, prior, base, cap)
+        sv.set_instance_row_bounds(*inflated_row_bounds(prob, d.shape[0], d))
+
     def head_of_step(self, t=None):
         """what the controller plans in at the step that begins (``t``: the step, on the host): the scenes forecast at time t, read from
         node 0 on; without a forecast node k of the step's solve and tests is formed at time t + k, by the clock"""
         if self.forecast is not None:
             self._forecast_into(self._sv, self._select, slice(None), t, self._ctrl.N)
+            if self.margin_fit is not None:
+                self._margin_into(self._sv, self._ctrl.problem, slice(None), t)
         elif not self._xp.on_device:
             _write_scene_clock(self.clock, t)
 
@@ -1250,6 +1281,8 @@ class _World:
                 if self.observed is not None:
                     sv.set_instance_observed_track(self.observed[rows])
             self._forecast_into(sv, self._backup_select, rows, t, self._backup.N)
+            if self.margin_fit is not None:
+                self._margin_into(sv, self._backup.problem, rows, t)
         if self.row_bounds is not None:
             sv.set_instance_row_bounds(self.row_bounds[0][rows], self.row_bounds[1][rows])
         if self.models is not None:
@@ -1275,7 +1308,7 @@ class _World:
                         s.set_instance_observed_track(None)
                     if hasattr(s, 'set_instance_world_track'):
                         s.set_instance_world_track(None)
-        if self.row_bounds is not None:
+        if self.row_bounds is not None or self.margin_fit is not None:
             sv.set_instance_row_bounds(None)
             bsv.set_instance_row_bounds(None)
         if self.models is not None:
@@ -1707,7 +1740,7 @@ def _check_state_kind(ctrl, backup, on_device):
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
             score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None,
-            forecast_degree=None, row_margin=None):
+            forecast_degree=None, row_margin=None, row_margin_fit=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1780,10 +1813,20 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     solver.set_instance_row_bounds), set once per group on the controller's handle before the loop, and on the backup handle, over its
     own horizon, for the aborting instances of an abort event.  The outcome tests and the scores keep the physical check bounds.  With
     or without ``scenes`` and ``forecast``; both handles are left without a table when the run ends and the result gains
-    ``'row_margin'``.  Not with the parallel policy (ValueError).  None: the calls of a run without the argument, one for one."""
+    ``'row_margin'``.  Not with the parallel policy (ValueError).  None: the calls of a run without the argument, one for one.
+    ``row_margin_fit`` ``(z, sigma_prior, d_max)``, only with ``forecast='fit'`` (ValueError otherwise): the
+    margin is formed at the head of every step from the residuals of the fit the step forecasts with -- node k leaves
+    ``d_k = a + b k + z s g_k`` metres, at most ``d_max``, per instance and row (``problem.fit_margin_statement``): s the residual
+    standard deviation of the window, at least ``sigma_prior``, g_k the growth of the forecast's error along the horizon, and
+    ``(a, b)`` the ``row_margin`` of the same call, (0, 0) without one -- which then is this margin's base and no table of its own.
+    On the device one smpc_forecast_row_margin behind the forecast inside the captured half of every step, and on the backup handle
+    behind its forecast at an abort event, over its own horizon; on the host the statement and solver.set_instance_row_bounds per
+    step.  Both handles end without a table and the result gains ``'row_margin_fit'``.  Not with the parallel policy (ValueError).
+    None: the calls of a run without the argument, one for one."""
     import time
     B = x_guess.shape[0]
-    world = _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models)
+    world = _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models,
+                         row_margin_fit)
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1904,6 +1947,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra.update(world.forecast.result_keys(observed is not None))
     if world.row_margin is not None:
         extra['row_margin'] = world.row_margin
+    if world.row_margin_fit is not None:
+        extra['row_margin_fit'] = world.row_margin_fit
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -1895,26 +1895,47 @@ int smpc_set_instance_observed_track(smpc_handle* h, int B, int64_t T, const dou
     return set_scene_table(h, h->seen, h->seen_T, "smpc_set_instance_observed_track", B, T, geom, on_device);
 }
 
+// What every entry point that reads S -- the three forecasts and smpc_forecast_row_margin -- asks of the world, of a fit's window and
+// degree, and of the observed track, in this order, with the caller's name in the message.
+static int check_forecast_world(smpc_handle* h, const char* who, int B) {
+    if (!h->world.B) return fail(h, SMPC_ESTATE, "%s: no world is set (smpc_set_instance_world_track)", who);
+    if (B != h->world.B)
+        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance world track was set for %d instances "
+                    "(smpc_set_instance_world_track: clear it or set one of this size)", who, B, h->world.B);
+    return SMPC_OK;
+}
+static int check_fit_shape(smpc_handle* h, const char* who, int window, int degree) {
+    if (window < 1 || window > SMPC_FIT_MAX)
+        return fail(h, SMPC_EINVAL, "%s: window %d: a fit takes 1 to SMPC_FIT_MAX = %d samples", who, window, SMPC_FIT_MAX);
+    if (degree < 0 || degree > 2)
+        return fail(h, SMPC_EINVAL, "%s: degree %d: a polynomial of degree 0, 1 or 2", who, degree);
+    return SMPC_OK;
+}
+static int check_forecast_observed(smpc_handle* h, const char* who) {
+    if (h->seen.B && (h->seen.B != h->world.B || h->seen_T != h->world_T))
+        return fail(h, SMPC_EINVAL, "%s: the instance observed track was set for %d instances and %lld columns, but the instance world "
+                    "track for %d instances and %lld columns (smpc_set_instance_observed_track: clear it or set one of the world's "
+                    "shape)", who, h->seen.B, (long long)h->seen_T, h->world.B, (long long)h->world_T);
+    return SMPC_OK;
+}
+// S as the fits read it: the observed track while one is set, else the world, at the scene clock (the window grows with the clock
+// even where T = 1 leaves one column to read)
+static SceneSrc fit_source(const smpc_handle* h) {
+    return SceneSrc{h->seen.B ? h->seen.d.p : h->world.d.p, h->scene_clock, h->world_T, 0};
+}
+
 // The one body of smpc_forecast_scene (fit = false: `what` is its mode), smpc_forecast_scene_fit (fit = true: `what` is its window,
 // degree 1) and smpc_forecast_scene_poly (fit = true with its degree); `who` names the entry point in every message.  S, "what was seen", is the observed track while one is set and the world
 // otherwise; SMPC_FORECAST_TRUE reads the world whatever was observed.
 static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit, int what, int n_sel, const int32_t* select,
                                int degree = 1) {
     const int mode = what, window = what;
-    if (!h->world.B) return fail(h, SMPC_ESTATE, "%s: no world is set (smpc_set_instance_world_track)", who);
-    if (B != h->world.B)
-        return fail(h, SMPC_EINVAL, "%s: batch size %d, but the instance world track was set for %d instances "
-                    "(smpc_set_instance_world_track: clear it or set one of this size)", who, B, h->world.B);
+    int rc;
+    if ((rc = check_forecast_world(h, who, B))) return rc;
     if (!fit && mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
         return fail(h, SMPC_EINVAL, "%s: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", who, mode);
-    if (fit && (window < 1 || window > SMPC_FIT_MAX))
-        return fail(h, SMPC_EINVAL, "%s: window %d: a fit takes 1 to SMPC_FIT_MAX = %d samples", who, window, SMPC_FIT_MAX);
-    if (fit && (degree < 0 || degree > 2))
-        return fail(h, SMPC_EINVAL, "%s: degree %d: a polynomial of degree 0, 1 or 2", who, degree);
-    if (h->seen.B && (h->seen.B != h->world.B || h->seen_T != h->world_T))
-        return fail(h, SMPC_EINVAL, "%s: the instance observed track was set for %d instances and %lld columns, but the instance world "
-                    "track for %d instances and %lld columns (smpc_set_instance_observed_track: clear it or set one of the world's "
-                    "shape)", who, h->seen.B, (long long)h->seen_T, h->world.B, (long long)h->world_T);
+    if (fit && (rc = check_fit_shape(h, who, window, degree))) return rc;
+    if ((rc = check_forecast_observed(h, who))) return rc;
     const Net& net = *h->net;
     const int nr = h->desc.n_rows, N = h->N, nc = net.n_ctx;
     if (n_sel < 0) return fail(h, SMPC_EINVAL, "%s: n_sel=%d", who, n_sel);
@@ -1942,7 +1963,6 @@ static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit,
     if ((scene_grows || ctx_grows) && capturing(h))
         return fail(h, SMPC_ESTATE, "%s: the %s must grow to %zu bytes while the stream is being captured: run one eager call of this size "
                     "first", who, scene_grows ? h->scene.noun : h->ctx.noun, scene_grows ? n * sizeof(double) : n_ctx_el * sizeof(float));
-    int rc;
     if (scene_grows) h->scene.clear();
     if ((rc = h->scene.room(h, n))) return rc;
     if (ctx_grows) h->ctx.clear();
@@ -1998,6 +2018,69 @@ int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int 
     if (!h) return SMPC_EINVAL;
     (void)hipSetDevice(h->device);
     return forecast_into_scene(h, "smpc_forecast_scene_poly", B, true, window, n_sel, select, degree);
+}
+
+// The row-bounds slot filled from what was seen: the margins of k_fit_margin as the table that
+// smpc_set_instance_row_bounds takes.  Reads S and the clock as smpc_forecast_scene_poly does; neither needs nor touches the scene slot.
+int smpc_forecast_row_margin(smpc_handle* h, int B, int window, int degree, double z, double sigma_prior, double base_a, double base_b,
+                             double d_max) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    const char* who = "smpc_forecast_row_margin";
+    const int nr = h->desc.n_rows, N = h->N;
+    // (first: a descriptor without rows takes no world either)
+    if (nr == 0) return fail(h, SMPC_EINVAL, "%s: the problem has no collision rows: there are no row bounds to set", who);
+    int rc;
+    if ((rc = check_forecast_world(h, who, B)) || (rc = check_fit_shape(h, who, window, degree)) || (rc = check_forecast_observed(h, who)))
+        return rc;
+    const struct { const char* name; double v; } args[] = {{"z", z}, {"sigma_prior", sigma_prior}, {"base_a", base_a}, {"base_b", base_b},
+                                                           {"d_max", d_max}};
+    for (const auto& a : args)
+        if (!(a.v >= 0.0 && a.v - a.v == 0.0))
+            return fail(h, SMPC_EINVAL, "%s: %s=%g: a finite number that is not negative", who, a.name, a.v);
+    MarginRows rows{};
+    for (int r = 0; r < nr; r++) {
+        const smpc_row& R = h->desc.rows[r];
+        if (R.kind == SMPC_ROW_COORD && fabs(R.lb) < SMPC_INF && fabs(R.ub) < SMPC_INF && R.lb + d_max > R.ub - d_max)
+            return fail(h, SMPC_EINVAL, "%s: row %d: d_max=%g makes its sides cross (%g > %g)", who, r, d_max, R.lb + d_max, R.ub - d_max);
+        rows.kind[r] = R.kind;
+        rows.lb[r] = R.lb;
+        rows.ub[r] = R.ub;
+        // (on the host: the very double problem.inflated_row_bounds squares; read only where the row is a squared distance with a lower side)
+        rows.sqrt_lb[r] = R.kind != SMPC_ROW_COORD && R.lb >= 0.0 ? sqrt(R.lb) : 0.0;
+    }
+    // room first, launch last: a call refused for growth under capture has changed nothing; a buffer that did grow lost its old
+    // content, so the slot is empty until the commit below
+    const size_t n = (size_t)B * (N + 1) * nr;
+    const bool grows = 2 * n * sizeof(double) > h->rowb.d.cap;
+    if (grows && capturing(h))
+        return fail(h, SMPC_ESTATE, "%s: the %s must grow to %zu bytes while the stream is being captured: run one eager call of this size "
+                    "first", who, h->rowb.noun, 2 * n * sizeof(double));
+    if (grows) h->rowb.clear();
+    if ((rc = h->rowb.room(h, 2 * n))) return rc;
+    const int n_piece = 4 * B * nr;     // four lanes to a record: see k_fit_margin
+    const MarginArgs ma{z, sigma_prior * sigma_prior, base_a, base_b, d_max};
+    hipLaunchKernelGGL(k_fit_margin, dim3((unsigned)(((size_t)n_piece + 63) / 64)), dim3(64), 0, h->stream, n_piece, nr, N, window, degree,
+                       fit_source(h), ma, rows, h->rowb.d.p, h->rowb.d.p + n);
+    HIPCHK(h, hipGetLastError());
+    h->rowb.commit(B);
+    return SMPC_OK;
+}
+
+int smpc_get_instance_row_bounds(smpc_handle* h, int B, double* lo, double* hi, int on_device) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    const char* who = "smpc_get_instance_row_bounds";
+    if (!lo || !hi) return fail(h, SMPC_EINVAL, "%s: lo and hi must both be given", who);
+    if (!h->rowb.B) return fail(h, SMPC_ESTATE, "%s: no %s is set (%s, smpc_forecast_row_margin)", who, h->rowb.noun, h->rowb.setter);
+    int rc;
+    if ((rc = h->rowb.guard(h, B, who))) return rc;
+    const size_t n = (size_t)B * (h->N + 1) * h->desc.n_rows;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(h, hipMemcpyAsync(lo, h->rowb.d.p, n * sizeof(double), kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hi, h->rowb.d.p + n, n * sizeof(double), kind, h->stream));
+    if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SMPC_OK;
 }
 
 // a scene that stands still: the track of one column

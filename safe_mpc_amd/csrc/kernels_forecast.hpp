@@ -262,6 +262,167 @@ __global__ __launch_bounds__(64) void k_scene_poly(int n_piece, int n_rows, int 
     }
 }
 
+// k_fit_margin: the row-bounds table [lo | hi], each [B][N+1][n_rows], from the residuals of the fit that k_scene_fit / k_scene_poly
+// forecast with -- the prediction interval of a least-squares polynomial per (instance, row, node); DESIGN.md section 9r.  With S, t,
+// col, m, p and y_j as in k_scene_poly and a, v, e that kernel's numbers for every slot (the same operations in the same order):
+//   nu = m - p - 1;   nu >= 1:  f_j = a | a - j v | (a - j v) + (j (j + 1) / 2) e   (p = 0 | 1 | 2),  res = y_j - f_j,
+//                               q = res res at j = 0, q = q + res res afterwards;  rss = the largest q over the row kind's moving slots,
+//                               a NaN winning;  s2 = rss / (double)nu, raised to var_prior where it is below it (a NaN stays)
+//                     nu == 0:  s2 = var_prior
+//   h_k = sum_j c_kj^2,  c_kj = 1 / m | u_j + k w_j | (ua_j + k uv_j) + (k (k - 1) / 2) ue_j,  in increasing j from the j = 0 term
+//   d_k = (base_a + base_b k) + (z sqrt(s2)) sqrt(h_k);   d_k = d_k <= d_max ? d_k : d_max      -- a NaN gives the cap
+// every product rounded before its sum (rounded_product): problem.fit_margin_statement operation for operation.  A row without a
+// world-fixed element (SEG_SEG) has d = 0.  The bounds are problem.inflated_row_bounds': a plane row lb + d and ub - d, any other
+// (sqrt(lb) + d)^2 with sqrt(lb) taken on the host, an absent side (|v| >= SMPC_INF) as it is, and the descriptor's own doubles where
+// d == 0.0.
+// One-wavefront blocks.  N + 1 <= 64, so lane k forms h_k and sqrt(h_k) once per block into N + 1 doubles of LDS: m and p come from
+// one clock cell, so the age loop has a scalar bound and the weights are uniform reads of the constant tables.  Then k_scene_poly's
+// mapping: four neighbouring lanes own the four 16-byte pieces of a record, FIT_AHEAD age loads in flight.  The first pass forms a, v,
+// e; the second re-reads the window (m <= 32 columns of 64 bytes, hot in L2) for the residuals.  The maximum over the record's slots
+// crosses its four lanes by two shuffles -- a maximum does not depend on order, so it keeps its bits -- and the four lanes then share
+// the nodes for the stores.  No atomics; nothing is shared between instances, so an instance's result depends neither on B nor on its
+// neighbours, and two calls give the same bits.
+struct MarginRows {
+    double lb[SMPC_MAX_ROWS], ub[SMPC_MAX_ROWS], sqrt_lb[SMPC_MAX_ROWS];
+    int32_t kind[SMPC_MAX_ROWS];
+};
+struct MarginArgs { double z, var_prior, base_a, base_b, d_max; };
+// a NaN wins: what np.maximum does
+__device__ __forceinline__ double max_nan_wins(double best, double x) { return (x > best || x != x) ? x : best; }
+__global__ __launch_bounds__(64) void k_fit_margin(int n_piece, int n_rows, int N, int window, int degree, SceneSrc seen, MarginArgs ma,
+                                                   MarginRows rows, double* __restrict__ lo, double* __restrict__ hi) {
+    __shared__ double g_lds[SMPC_MAX_N + 1];
+    const int64_t t = scene_time(seen);
+    const int64_t shown = (t < 0 ? 0 : t) + 1;
+    const int m = shown < window ? (int)shown : window;
+    const int p = degree < m - 1 ? degree : m - 1;
+    const int nu = m - p - 1;
+    const int row = m * (m - 1) / 2;
+    const double* __restrict__ ua = p == 2 ? POLY_WEIGHTS.ua + row : FIT_WEIGHTS.u + row;
+    const double* __restrict__ uv = p == 2 ? POLY_WEIGHTS.uv + row : FIT_WEIGHTS.w + row;
+    const double* __restrict__ ue = POLY_WEIGHTS.ue + row;
+    const double mean = POLY_WEIGHTS.mean[m];
+    {   // the growth along the horizon: lane k forms g_k
+        const int k = threadIdx.x;
+        const double kd = (double)k, kk = (double)(k * (k - 1) / 2);
+        double h = 0.0;
+        for (int j = 0; j < m; j++) {
+            double c = mean;
+            if (p == 1) c = ua[j] + rounded_product(kd, uv[j]);
+            if (p == 2) c = (ua[j] + rounded_product(kd, uv[j])) + rounded_product(kk, ue[j]);
+            const double cc = rounded_product(c, c);
+            h = j == 0 ? cc : h + cc;
+        }
+        if (k <= N) g_lds[k] = __builtin_sqrt(h);
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_piece) return;       // (n_piece is a multiple of four: the four lanes of a record leave together)
+    const int rec_i = i / (SMPC_SCENE_ROW / 2), q = i % (SMPC_SCENE_ROW / 2);
+    const int b = rec_i / n_rows, r = rec_i % n_rows;
+    const int kind = rows.kind[r];
+    // the record's moving slots (the ones set_scene_table validates) lie in [s_lo, s_hi); this lane holds slots 2q and 2q + 1
+    const int s_lo = kind == SMPC_ROW_COORD ? 6 : 0;
+    const int s_hi = kind == SMPC_ROW_SEG_FIXEDSEG ? 6 : (kind == SMPC_ROW_SEG_POINT || kind == SMPC_ROW_POINT_POINT ? 3 : (kind == SMPC_ROW_COORD ? 7 : 0));
+    double s2 = ma.var_prior;
+    if (nu >= 1 && s_hi > 0) {      // (scalar on nu; a record's four lanes agree on its kind)
+        const size_t piece = (size_t)r * SMPC_SCENE_ROW + 2 * q;
+        const auto sample = [&](int j) {
+            const int age = j < m ? j : m - 1;
+            return *static_cast<const ScenePiece*>(__builtin_assume_aligned(scene_block(seen, b, t - age, n_rows) + piece, 16));
+        };
+        ScenePiece a{0.0, 0.0}, v{0.0, 0.0}, e{0.0, 0.0};
+        for (int j0 = 0; j0 < m; j0 += FIT_AHEAD) {
+            ScenePiece y[FIT_AHEAD];
+#pragma unroll
+            for (int l = 0; l < FIT_AHEAD; l++) y[l] = sample(j0 + l);
+#pragma unroll
+            for (int l = 0; l < FIT_AHEAD; l++) {
+                const int j = j0 + l;
+                if (j >= m) break;
+                const double wa = p == 0 ? mean : ua[j];
+                const ScenePiece pa{rounded_product(wa, y[l].a), rounded_product(wa, y[l].b)};
+                if (j == 0) {
+                    a = pa;
+                } else {
+                    a.a = a.a + pa.a; a.b = a.b + pa.b;
+                }
+                if (p >= 1) {
+                    const ScenePiece pv{rounded_product(uv[j], y[l].a), rounded_product(uv[j], y[l].b)};
+                    if (j == 0) {
+                        v = pv;
+                    } else {
+                        v.a = v.a + pv.a; v.b = v.b + pv.b;
+                    }
+                }
+                if (p == 2) {
+                    const ScenePiece pe{rounded_product(ue[j], y[l].a), rounded_product(ue[j], y[l].b)};
+                    if (j == 0) {
+                        e = pe;
+                    } else {
+                        e.a = e.a + pe.a; e.b = e.b + pe.b;
+                    }
+                }
+            }
+        }
+        ScenePiece qq{0.0, 0.0};
+        for (int j0 = 0; j0 < m; j0 += FIT_AHEAD) {
+            ScenePiece y[FIT_AHEAD];
+#pragma unroll
+            for (int l = 0; l < FIT_AHEAD; l++) y[l] = sample(j0 + l);
+#pragma unroll
+            for (int l = 0; l < FIT_AHEAD; l++) {
+                const int j = j0 + l;
+                if (j >= m) break;
+                ScenePiece f = a;
+                if (p >= 1) {
+                    const double jd = (double)j;
+                    f.a = a.a - rounded_product(jd, v.a); f.b = a.b - rounded_product(jd, v.b);
+                }
+                if (p == 2) {
+                    const double tj = (double)(j * (j + 1) / 2);
+                    f.a = f.a + rounded_product(tj, e.a); f.b = f.b + rounded_product(tj, e.b);
+                }
+                const double ra = y[l].a - f.a, rb = y[l].b - f.b;
+                const ScenePiece rr{rounded_product(ra, ra), rounded_product(rb, rb)};
+                if (j == 0) {
+                    qq = rr;
+                } else {
+                    qq.a = qq.a + rr.a; qq.b = qq.b + rr.b;
+                }
+            }
+        }
+        double rss = 0.0;
+        if (2 * q >= s_lo && 2 * q < s_hi) rss = max_nan_wins(rss, qq.a);
+        if (2 * q + 1 >= s_lo && 2 * q + 1 < s_hi) rss = max_nan_wins(rss, qq.b);
+        rss = max_nan_wins(rss, __shfl_xor(rss, 1));
+        rss = max_nan_wins(rss, __shfl_xor(rss, 2));
+        const double var = rss / (double)nu;
+        s2 = (var > ma.var_prior || var != var) ? var : ma.var_prior;
+    }
+    const double zs = rounded_product(ma.z, __builtin_sqrt(s2));
+    const double lb = rows.lb[r], ub = rows.ub[r], root = rows.sqrt_lb[r];
+    const bool has_lb = __builtin_fabs(lb) < SMPC_INF, has_ub = __builtin_fabs(ub) < SMPC_INF;
+    const size_t at = (size_t)b * (size_t)(N + 1) * n_rows + r;
+    for (int k = q; k <= N; k += SMPC_SCENE_ROW / 2) {
+        double d = (ma.base_a + rounded_product(ma.base_b, (double)k)) + rounded_product(zs, g_lds[k]);
+        d = d <= ma.d_max ? d : ma.d_max;
+        if (s_hi == 0) d = 0.0;
+        double l = lb, u = ub;
+        if (d != 0.0) {
+            if (kind == SMPC_ROW_COORD) {
+                if (has_lb) l = lb + d;
+                if (has_ub) u = ub - d;
+            } else if (has_lb) {
+                const double w = root + d;
+                l = rounded_product(w, w);
+            }
+        }
+        lo[at + (size_t)k * n_rows] = l;
+        hi[at + (size_t)k * n_rows] = u;
+    }
+}
+
 // k_forecast_context: the context rows of a scene-aware safe-set network from the same F, one thread per number:
 //   ctx[b][k][i] = (float)((F[b][k][row_i][slot_i] - mean[i]) / std[i])       -- the expression of k_ctx_normalise
 // sel: which (row, slot) of the scene context number i is, by value like nm (at most MLP_KPAD pairs: no device block to keep, and a

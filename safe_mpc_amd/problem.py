@@ -731,3 +731,143 @@ def inflated_row_bounds(prob, B, margin):
         elif abs(r.lb) < INF:
             lo[:, :, i] = np.where(on, (np.sqrt(r.lb) + di) ** 2, r.lb)
     return lo, hi
+
+
+FIT_MARGIN_CAP = 0.05                                  # the default d_max of a fitted margin, metres
+
+# the slots of a scene record that move with the row's world-fixed element, by row kind: the ones smpc_set_instance_scene_track
+# validates (set_scene_table, engine.hip).  A robot-robot row has none.
+_MOVING_SLOTS = {ROW_SEG_FIXEDSEG: (0, 1, 2, 3, 4, 5), ROW_SEG_POINT: (0, 1, 2), ROW_POINT_POINT: (0, 1, 2), ROW_COORD: (6,),
+                 ROW_SEG_SEG: ()}
+
+
+def moving_slots(kind):
+    """The slots of a scene record that a row of ``kind`` reads of its world-fixed element: 0..5 for a fixed capsule, 0..2 for a
+    fixed point, 6 for a plane, none for a robot-robot row."""
+    return _MOVING_SLOTS[int(kind)]
+
+
+def margin_growth(m, degree, N):
+    """``h [N + 1]``: the sum of the squared weights with which a least-squares polynomial of degree ``p = min(degree, m - 1)``
+    through m samples forms its forecast k columns ahead, ``h_k = sum_j c_kj^2`` -- the variance of the forecast at node k in units
+    of the variance of one sample; ``g_k = sqrt(h_k)`` is the growth of a fitted margin along the horizon.
+    With ``poly_weights(m, p)``: ``c_kj = 1 / m`` (p = 0), ``u_j + k w_j`` (p = 1), ``(ua_j + k uv_j) + (k (k - 1) / 2) ue_j``
+    (p = 2); every product rounded before its sum, the sum in increasing j starting from the j = 0 term.  k_fit_margin repeats it
+    operation for operation."""
+    m, N = int(m), int(N)
+    p = min(int(degree), m - 1)
+    us = poly_weights(m, p)
+    k = np.arange(N + 1, dtype=float)
+    kk = np.arange(N + 1, dtype=float) * (np.arange(N + 1, dtype=float) - 1.0) / 2.0      # k (k - 1) / 2: small integers, exact
+    h = None
+    for j in range(m):
+        if p == 0:
+            c = np.full(N + 1, us[0][j])
+        elif p == 1:
+            c = us[0][j] + k * us[1][j]
+        else:
+            c = (us[0][j] + k * us[1][j]) + kk * us[2][j]
+        h = c * c if h is None else h + c * c
+    return h
+
+
+def _check_fit_margin(who, prob, window, degree, z, sigma_prior, base, d_max):
+    window, degree = int(window), int(degree)
+    if not 1 <= window <= FIT_MAX:
+        raise ValueError(f'{who}: window {window}: expected 1..{FIT_MAX}')
+    if not 0 <= degree <= 2:
+        raise ValueError(f'{who}: degree {degree}: expected 0, 1 or 2')
+    base = tuple(float(v) for v in np.asarray(base, float).reshape(-1))
+    if len(base) != 2:
+        raise ValueError(f'{who}: base {base}: expected (a, b), the margin a + b k metres at node k')
+    vals = {'z': float(z), 'sigma_prior': float(sigma_prior), 'base_a': base[0], 'base_b': base[1], 'd_max': float(d_max)}
+    for name, v in vals.items():
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f'{who}: {name}={v}: expected a finite number that is not negative')
+    for i, r in enumerate(prob.rows):
+        if r.kind == ROW_COORD and abs(r.lb) < INF and abs(r.ub) < INF and r.lb + vals['d_max'] > r.ub - vals['d_max']:
+            raise ValueError(f'{who}: row {i} ({prob.row_names[i]}): d_max={vals["d_max"]:g} makes its sides cross '
+                             f'({r.lb + vals["d_max"]:g} > {r.ub - vals["d_max"]:g})')
+    return window, degree, vals['z'], vals['sigma_prior'], base, vals['d_max']
+
+
+def fit_margin_statement(prob, seen, t, window, degree, z, sigma_prior=0.0, base=(0.0, 0.0), d_max=FIT_MARGIN_CAP):
+    """``d [B, N + 1, n_rows]``, metres: the margin a controller leaves around the world-fixed element of every collision row at
+    every node, formed from the residuals of the fit it forecasts with -- the prediction interval of a least-squares polynomial, the
+    numpy statement of smpc_forecast_row_margin and its readable definition.  ``inflated_row_bounds(prob, B,
+    d)`` turns it into the table the entry point writes.
+
+    ``seen``, ``t``, ``col``, ``m = min(window, max(t, 0) + 1)``, ``p = min(degree, m - 1)`` and ``y_j = S[col(t - j)]`` as in
+    :func:`poly_forecast_statement`, and ``a``, ``v``, ``e`` are that statement's numbers for every slot (p = 0: a; p = 1: a and the
+    step, here v; p = 2: a, v, e), formed by the same operations in the same order.
+
+    The residual variance.  ``nu = m - p - 1``.  With ``nu >= 1``, per slot in increasing j: ``f_j = a`` (p = 0), ``a - j v``
+    (p = 1), ``(a - j v) + T_j e`` with ``T_j = j (j + 1) / 2`` (p = 2) -- the fitted polynomial at age j --, ``res = y_j - f_j``,
+    ``q = res res`` at j = 0 and ``q = q + res res`` afterwards, every product rounded before its sum.  ``rss`` is the largest q
+    over the row's moving slots (:func:`moving_slots`), taken so that a NaN wins; ``s2 = rss / float(nu)``, raised to
+    ``var_prior = sigma_prior^2`` where it is below it (a NaN stays).  ``nu == 0``: nothing can be estimated, ``s2 = var_prior``.
+    ``s = sqrt(s2)``.
+
+    The growth.  ``g_k = sqrt(h_k)``, ``h = margin_growth(m, p, N)``: without a "+ 1" under the root, because the true obstacle
+    carries no noise -- what is bounded is the forecast's error against the truth.
+
+    The margin.  ``d_k = (base_a + base_b k) + (z s) g_k``, every product rounded; ``d_k = d_k if d_k <= d_max else d_max``, so a
+    NaN anywhere in a moving slot of the window gives the cap, never a NaN bound.  A row without a world-fixed element (``row_obstacle``
+    None, kind SEG_SEG) has d = 0 at every node.
+
+    The margin is per axis: the largest residual sum over the moving slots stands for the element's whole displacement, and the
+    distance to an obstacle that errs along three axes can exceed it by up to sqrt(3).  Taking the maximum, not the mean, over the
+    slots errs on the wide side of a per-axis interval.
+
+    ValueError: window outside 1..FIT_MAX, degree outside 0..2, a negative or non-finite z, sigma_prior, base or d_max, or a d_max
+    that makes a plane row's two sides cross (the message names the row)."""
+    S = np.asarray(seen, float)
+    nr = len(prob.rows)
+    if S.ndim != 4 or S.shape[2:] != (nr, SCENE_ROW):
+        raise ValueError(f'fit_margin_statement: expected a track [B, T, {nr}, {SCENE_ROW}], got {S.shape}')
+    window, degree, z, sigma_prior, (base_a, base_b), d_max = _check_fit_margin('fit_margin_statement', prob, window, degree, z,
+                                                                                 sigma_prior, base, d_max)
+    B, T, N = S.shape[0], S.shape[1], int(prob.N)
+    t = 0 if t is None else min(max(int(t), -2 ** 62), 2 ** 62)
+    m = min(window, max(t, 0) + 1)
+    p = min(degree, m - 1)
+    nu = m - p - 1
+    var_prior = sigma_prior * sigma_prior
+    s2 = np.full((B, nr), var_prior)
+    if nu >= 1:
+        us = poly_weights(m, p)
+        y = S[:, scene_column(t, T)]
+        acc = [u[0] * y for u in us]
+        for j in range(1, m):
+            y = S[:, scene_column(t - j, T)]
+            acc = [x + u[j] * y for x, u in zip(acc, us)]
+        q = None
+        for j in range(m):
+            y = S[:, scene_column(t - j, T)]
+            if p == 0:
+                f = acc[0]
+            elif p == 1:
+                f = acc[0] - float(j) * acc[1]
+            else:
+                f = (acc[0] - float(j) * acc[1]) + float(j * (j + 1) // 2) * acc[2]
+            res = y - f
+            q = res * res if q is None else q + res * res
+        for i, r in enumerate(prob.rows):
+            slots = moving_slots(r.kind)
+            if not slots:
+                continue
+            rss = np.zeros(B)
+            for s_ in slots:
+                rss = np.maximum(rss, q[:, i, s_])              # (a NaN wins)
+            v = rss / float(nu)
+            s2[:, i] = np.where((v > var_prior) | (v != v), v, var_prior)
+    s = np.sqrt(s2)
+    g = np.sqrt(margin_growth(m, p, N))
+    k = np.arange(N + 1, dtype=float)
+    with np.errstate(invalid='ignore'):
+        d = (base_a + base_b * k)[None, :, None] + (z * s)[:, None, :] * g[None, :, None]
+        d = np.where(d <= d_max, d, d_max)
+    for i, r in enumerate(prob.rows):
+        if not moving_slots(r.kind):
+            d[:, :, i] = 0.0
+    return d

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from .problem import FORECAST_MODES, JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem     # noqa: F401 (FORECAST_MODES: re-exported)
+from .problem import FIT_MARGIN_CAP, FORECAST_MODES, JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem     # noqa: F401 (FORECAST_MODES: re-exported)
 
 
 # columns of BatchedOcpSolver.score_rollout's two results (SMPC_SCORE_ND doubles, SMPC_SCORE_NI int32 of include/smpc.h)
@@ -188,6 +188,7 @@ class BatchedOcpSolver:
     def set_horizon(self, N):
         self._chk(self.L.smpc_set_horizon(self.h, int(N)))
         self.N = int(N)
+        self._rowb_B = 0            # (the engine drops the row-bounds table with the horizon)
 
     def set_stage_bounds(self, lo=None, hi=None):
         if lo is None:
@@ -222,6 +223,25 @@ class BatchedOcpSolver:
         and :meth:`rollout` refuse it."""
         self._set_instance(self.L.smpc_set_instance_row_bounds, 'set_instance_row_bounds', [None, None] if lo is None else [lo, hi],
                            (self.N + 1, int(self.problem.desc.n_rows)))
+        self._rowb_B = 0 if lo is None else int(lo.shape[0])
+
+    def get_instance_row_bounds(self, device=False, B=None):
+        """``(lo, hi)``, each ``[B, N+1, n_rows]``: the row-bounds table as the slot holds it (smpc_get_instance_row_bounds), whoever
+        filled it -- :meth:`set_instance_row_bounds` or :meth:`forecast_row_margin`.  numpy arrays (the call waits for the copy), or
+        ROCm tensors with ``device=True`` (stream-ordered).  ``B``: the table's batch size, the one this solver set it with unless
+        given.  The engine refuses while no table is set."""
+        B = int(getattr(self, '_rowb_B', 0) if B is None else B)
+        shape = (max(B, 1), self.N + 1, int(self.problem.desc.n_rows))
+        if device:
+            import torch
+            lo, hi = (torch.empty(shape, dtype=torch.float64, device=torch.device('cuda', self.device)) for _ in range(2))
+            with self._ordered(True):
+                self._chk(self.L.smpc_get_instance_row_bounds(self.h, max(B, 1), lo.data_ptr(), hi.data_ptr(), 1))
+            return lo, hi
+        lo, hi = np.empty(shape), np.empty(shape)
+        with self._ordered('torch' in sys.modules):
+            self._chk(self.L.smpc_get_instance_row_bounds(self.h, max(B, 1), lo.ctypes.data, hi.ctypes.data, 0))
+        return lo, hi
 
     def set_instance_scene(self, geom=None):
         """A scene of its own for every instance (smpc_set_instance_scene): ``geom [B, n_rows, 8]`` -- per (instance, row) the
@@ -301,6 +321,19 @@ class BatchedOcpSolver:
         ``problem.poly_forecast_statement`` is its definition).  Enqueue-only; ``select`` and ``B`` as for :meth:`forecast_scene`.
         Degree 1 is :meth:`forecast_scene_fit`, degree 0 the window mean, degree 2 a constant-acceleration model."""
         self._forecast(self.L.smpc_forecast_scene_poly, select, B, int(window), int(degree))
+
+    def forecast_row_margin(self, window, degree, z, sigma_prior=0.0, base=(0.0, 0.0), d_max=FIT_MARGIN_CAP, B=None):
+        """The row-bounds table formed on the device from the residuals of the fit (smpc_forecast_row_margin;
+        ``problem.fit_margin_statement`` is its definition): node k of every instance and row leaves
+        ``d_k = base[0] + base[1] k + z s g_k`` metres of room, at most ``d_max`` -- s the residual standard deviation of a polynomial
+        of ``degree`` through the last ``window`` columns seen (at least ``sigma_prior``), g_k the growth of its forecast's error along
+        the horizon.  Enqueue-only, read at the scene clock like :meth:`forecast_scene_poly`, which it is meant to follow with the
+        same window and degree; it fills the slot of :meth:`set_instance_row_bounds`.  ``B`` as for :meth:`forecast_scene`."""
+        a, b = (float(v) for v in base)
+        B = int(getattr(self, '_world_B', 0) if B is None else B)
+        with self._ordered('torch' in sys.modules):
+            self._chk(self.L.smpc_forecast_row_margin(self.h, B, int(window), int(degree), float(z), float(sigma_prior), a, b, float(d_max)))
+        self._rowb_B = B
 
     def set_scene_clock(self, clock=None):
         """The time of node 0 for a scene track (smpc_set_scene_clock): a ONE-element int64 ROCm tensor that the engine reads on

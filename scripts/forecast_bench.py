@@ -20,9 +20,16 @@
 8. What the table costs a solve: smpc_solve_batch at B = 4096, N = 30 with a scene per instance set, without and with a row-bounds
    table (the descriptor's own bounds in every entry: the same QPs), in alternation, SMPC_ROUNDS (default 5) rounds of 10 calls
    between HIP events after 3 warm-up calls.
+9. k_fit_margin alone beside the forecast kernel of the same fit (profiles/row_margin_fit.txt): the shapes and the observed track of
+   3, windows 4, 8, 16, 32 and degrees 1, 0, 2; per (window, degree) the forecast and smpc_forecast_row_margin in alternation,
+   SMPC_ROUNDS (default 3) rounds of 10 calls between HIP events after 3 warm-up calls.
+10. A margin that follows the fit: the closed loop of 7 with forecast='fit' (window SMPC_FIT_WINDOW, default 8; degree SMPC_FIT_DEGREE,
+   default 1) and run_mpc(row_margin_fit=(z, 0, SMPC_MARGIN_CAP)) for z of SMPC_MARGIN_Z (default 0, 1, 2, 3), next to the arms over b
+   of 7 on the CV forecast and on the same fit, all in one session, one run each.
 A measurement tool, not a test; it reads nothing outside the repository.
 
-    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop|margin-loop|margin-solve]"""
+    python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop|margin-loop|margin-solve|interval-kernel|
+                                      interval-loop]"""
 import os
 import sys
 
@@ -152,6 +159,83 @@ def loop_times(B, noisy=False, poly=False):
               f'conv {int(a[0, 1])}, collisions {int(a[0, 2])}, viable {int(a[0, 3])}, unconv {int(a[0, 4])}; B = {B}, N = {N}, {steps} steps')
 
 
+def interval_kernel_times(B):
+    import torch
+    par, prob, net = bench.build_problem()
+    s = BatchedOcpSolver(prob, net)
+    N, T, clock, nr = prob.N, 131, 50, len(prob.rows)
+    device = torch.device('cuda', s.device)
+    world = turning_scenes(prob, B, T, 0.3, 3.0, seed=0)
+    s.set_instance_world_track(torch.tensor(world, dtype=torch.float64, device=device))
+    s.set_instance_observed_track(torch.tensor(observe_tracks(prob, world, 0.005), dtype=torch.float64, device=device))
+    cell = torch.full((1,), clock, dtype=torch.int64, device=device)
+    s.set_scene_clock(cell)
+    stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
+    rounds = int(os.environ.get('SMPC_ROUNDS', '3'))
+    rec = B * nr * 64 / 1e6                                     # MB per column of the table that was seen
+    out_fc, out_mg = (N + 1) * rec, B * (N + 1) * nr * 16 / 1e6
+    with torch.cuda.stream(stream):
+        for m in (4, 8, 16, 32):
+            for p in (1, 0, 2):
+                calls = {'forecast': (lambda: s.forecast_scene_poly(m, p)), 'margin': (lambda: s.forecast_row_margin(m, p, 2.0))}
+                res = {k: [] for k in calls}
+                for r in range(rounds):
+                    for name, call in calls.items():
+                        for _ in range(3):
+                            call()
+                        for _ in range(10):
+                            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            a.record(stream)
+                            call()
+                            b.record(stream)
+                            b.synchronize()
+                            res[name].append(a.elapsed_time(b))
+                f, g = np.array(res['forecast']), np.array(res['margin'])
+                print(f'window {m:2d} degree {p}: forecast kernel mean {1e3 * f.mean():.1f} us (min {1e3 * f.min():.1f}, max {1e3 * f.max():.1f}), '
+                      f'reads {m * rec:.1f} MB, writes {out_fc:.1f} MB | k_fit_margin mean {1e3 * g.mean():.1f} us (min {1e3 * g.min():.1f}, max '
+                      f'{1e3 * g.max():.1f}), reads 2 x {m * rec:.1f} MB, writes {out_mg:.1f} MB; {rounds} rounds of 10 calls each in alternation; '
+                      f'B = {B}, N = {N}, {nr} rows, T = {T}, clock {clock}', flush=True)
+    s.set_instance_row_bounds(None)
+    s.set_instance_world_track(None)
+    s.set_scene_clock(None)
+    s.close()
+
+
+def interval_loop(B):
+    from safe_mpc_amd import controller as C
+    par, prob, net = bench.build_problem()
+    par.N = prob.N
+    steps = int(os.environ.get('SMPC_STEPS', '60'))
+    sigma = float(os.environ.get('SMPC_OBS_NOISE', '0.005'))
+    window, degree = int(os.environ.get('SMPC_FIT_WINDOW', '8')), int(os.environ.get('SMPC_FIT_DEGREE', '1'))
+    cap = float(os.environ.get('SMPC_MARGIN_CAP', '0.15'))
+    rates = [float(v) for v in os.environ.get('SMPC_MARGIN_GROWTH', '0,0.0005,0.001,0.002,0.004').split(',')]
+    zs = [float(v) for v in os.environ.get('SMPC_MARGIN_Z', '0,1,2,3').split(',')]
+    probe = BatchedOcpSolver(prob, net)
+    x0 = bench.initial_states(probe, prob, B, 0)
+    probe.close()
+    N = prob.N
+    xg, ug = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((B, N, prob.nu))
+    ocp = C.OcpProblem(par, 'htwa', 'ext', N=N)
+    world = turning_scenes(ocp, B, steps + 1 + N, 0.3, 3.0, seed=0)
+    seen = observe_tracks(ocp, world, sigma, seed=0)
+    fit = {'forecast': 'fit', 'forecast_window': window, 'forecast_degree': degree}
+    print(f'observation noise sigma = {sigma}, turning tracks (sigma_v 0.3, sigma_a 3.0); B = {B}, N = {N}, {steps} steps; the fit: window '
+          f'{window}, degree {degree}; cap of the fitted margin {cap} m')
+    arms = [(f"forecast='cv', row_margin = (0, {b:g})", {'forecast': 'cv', **({} if b == 0.0 else {'row_margin': (0.0, b)})}) for b in rates]
+    arms += [(f"forecast='fit', row_margin = (0, {b:g})", {**fit, 'row_margin': (0.0, b)}) for b in rates if b != 0.0]   # (b = 0 is z = 0 below)
+    arms += [(f"forecast='fit', row_margin_fit = ({z:g}, 0, {cap:g})", {**fit, 'row_margin_fit': (z, 0.0, cap)}) for z in zs]
+    for name, kw in arms:
+        tm = {}
+        out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, observed=seen, score=True, timing=tm, **kw)
+        alive = np.ones(B, bool)
+        alive[out['collisions_idx']] = False
+        cost = out['score']['cost'][alive]
+        print(f"{name}: collisions with the true world {len(out['collisions_idx'])}, abort events {len(out['x_viable'])}, converged "
+              f"{len(out['conv_idx'])}, mean closed-loop cost of the {int(alive.sum())} others {np.nanmean(cost):.6g}; "
+              f"{tm['ms_per_step']:.3f} ms per step", flush=True)
+
+
 def margin_loop(B):
     from safe_mpc_amd import controller as C
     par, prob, net = bench.build_problem()
@@ -241,6 +325,10 @@ def main(argv=None):
         margin_loop(B)
     if 'margin-solve' in what:
         margin_solve_times(B)
+    if 'interval-kernel' in what:
+        interval_kernel_times(B)
+    if 'interval-loop' in what:
+        interval_loop(B)
     return 0
 
 

@@ -27,6 +27,10 @@ the forecast is formed from that (run_mpc(observed=...)); the plant meets the tr
 --row-margin A [--row-margin-growth B] (metres, metres per node; B needs A, default 0): obstacle inflation along the horizon -- node k of
 every solve leaves A + B k metres of extra room around the world-fixed obstacles (run_mpc(row_margin=(A, B)), DESIGN.md section 9q);
 the outcome tests keep the physical check bounds.  Suffix ``_rm<A>`` and, for B other than 0, ``_g<B>`` behind it.
+--row-margin-z Z [--row-margin-prior S] [--row-margin-cap D] (needs --scene-forecast fit; S in metres, default 0; D in metres, default
+problem.FIT_MARGIN_CAP): the margin is formed every step from the residuals of the fit -- node k leaves A + B k + Z s g_k metres, at
+most D, per instance and row: s the residual standard deviation of the window, at least S, g_k the growth of the forecast's error
+(run_mpc(row_margin_fit=(Z, S, D))); --row-margin then gives its base.  Suffix ``_rmf<Z>_p<S>_c<D>``.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -118,6 +122,19 @@ def main(argv=None):
         fc_kw['row_margin'] = name_kw['row_margin'] = (opt('--row-margin', 0.0, float), opt('--row-margin-growth', 0.0, float))
         if cont_name == 'parallel':
             raise SystemExit("--row-margin: the 'parallel' policy is not supported")
+    for flag in ('--row-margin-prior', '--row-margin-cap'):
+        if flag in raw and '--row-margin-z' not in raw:
+            raise SystemExit(f'{flag} needs --row-margin-z: there is no fitted margin to bound')
+    if '--row-margin-z' in raw:
+        from safe_mpc_amd.problem import FIT_MARGIN_CAP
+        if forecast != 'fit':
+            raise SystemExit('--row-margin-z needs --scene-forecast fit: no other forecast leaves residuals')
+        if cont_name == 'parallel':
+            raise SystemExit("--row-margin-z: the 'parallel' policy is not supported")
+        fit = (opt('--row-margin-z', 0.0, float), opt('--row-margin-prior', 0.0, float), opt('--row-margin-cap', FIT_MARGIN_CAP, float))
+        if not all(0.0 <= v < float('inf') for v in fit):
+            raise SystemExit(f'--row-margin-z, --row-margin-prior, --row-margin-cap: {fit}: expected finite numbers that are not negative')
+        fc_kw['row_margin_fit'] = name_kw['row_margin_fit'] = fit
     cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
     if cmodel not in ('nominal', 'plant'):
         raise SystemExit(f'--controller-model {cmodel}: expected nominal or plant')
