@@ -211,10 +211,17 @@ def _step_real_receding(inst, numerics, x):
 # =========================================================================================================================
 # the driver's loop for ONE instance (scripts/mpc.py:118-287)
 # =========================================================================================================================
-def run_closed_loop(inst, numerics, x_guess, u_guess, n_steps, Nb, nq, on_step=None):
+def run_closed_loop(inst, numerics, x_guess, u_guess, n_steps, Nb, nq, on_step=None, step_fn=None, reference_quirks=True):
     """Returns a dict: x [n_steps+1][nx] and u [n_steps][nu] (NaN where the reference leaves its pre-filled NaN), the abort
     events [(step, x_viable)], r at every step the controller stepped (-1 otherwise), and what the outcome lists are built from
-    (collided: in collisions_idx; n_viable: times appended to viable_idx; conv: the test of mpc.py:273 on the last state)."""
+    (collided: in collisions_idx; n_viable: times appended to viable_idx; conv: the test of mpc.py:273 on the last state), and
+    the steps at which the rest test of mpc.py:138 was evaluated (rest_tests) and passed (resumes).
+
+    step_fn(inst, numerics, x) -> (u, abort) replaces the controller's ``step`` (default: this module's), so that a test can
+    drive the driver's automaton with a scripted controller.  reference_quirks = False is the product's switch of that name:
+    an abort raised on the step an instance resumes MPC opens an abort event like any other (see below)."""
+    if step_fn is None:
+        step_fn = step
     nx, nu = inst.nx, inst.nu
     kp, kd = 1.0, 1e2                                          # mpc.py:97
     x_sim = np.full((n_steps + 1, nx), np.nan)
@@ -229,20 +236,25 @@ def run_closed_loop(inst, numerics, x_guess, u_guess, n_steps, Nb, nq, on_step=N
     events = []
     collided = False
     n_viable = 0                                               # how often mpc.py:189 appended this instance to viable_idx
+    rest_tests, resumes = [], []
     has_r = inst.kind in ('receding', 'real_receding')
     for j in range(n_steps):
         if on_step is not None:
             on_step(j)
         x = x_sim[j]
+        event = False
         if sa_flag:                                            # mpc.py:130-146
             if ja < Nb:
                 u = np.array(u_abort[ja]) - (kp * (x[:nq] - x_abort[ja][:nq]) + kd * (x[nq:] - x_abort[ja][nq:]))
             else:
+                rest_tests.append(j)
                 if np.all(x[nq:] < 5e-3):
+                    resumes.append(j)
                     sa_flag = False
                     if has_r:
                         r_log[j] = inst.r
-                    u, sa_flag = step(inst, numerics, x)       # an abort raised HERE opens no new event: x_abort, ja are kept
+                    u, sa_flag = step_fn(inst, numerics, x)    # an abort raised HERE opens no new event: x_abort, ja are kept
+                    event = sa_flag and not reference_quirks   # (... unless the quirk is switched off: an event like any other)
                 else:
                     u = -(kp * (x[:nq] - x_abort[-1][:nq]) + 3e2 * (x[nq:] - x_abort[-1][nq:]))
             ja += 1
@@ -250,19 +262,20 @@ def run_closed_loop(inst, numerics, x_guess, u_guess, n_steps, Nb, nq, on_step=N
         else:                                                  # mpc.py:149-190
             if has_r:
                 r_log[j] = inst.r
-            u, sa_flag = step(inst, numerics, x)
+            u, sa_flag = step_fn(inst, numerics, x)
             u_log[j] = u
-            if sa_flag:
-                xv = np.array(inst.x_viable)
-                events.append((j, xv))
-                status, xa, ua = numerics.backup_solve(xv)
-                if status != 0:
-                    collided = True                            # mpc.py:186-190: lost at this step, nothing is integrated
-                    break
-                ja = 0
-                n_viable += 1
-                x_abort = [np.array(v, float) for v in xa]
-                u_abort = [np.array(v, float) for v in ua]
+            event = sa_flag
+        if event:
+            xv = np.array(inst.x_viable)
+            events.append((j, xv))
+            status, xa, ua = numerics.backup_solve(xv)
+            if status != 0:
+                collided = True                                # mpc.py:186-190: lost at this step, nothing is integrated
+                break
+            ja = 0
+            n_viable += 1
+            x_abort = [np.array(v, float) for v in xa]
+            u_abort = [np.array(v, float) for v in ua]
         x_next = np.array(numerics.plant(x, u), float)         # mpc.py:240
         x_sim[j + 1] = x_next
         if not numerics.check_state_bounds(x_next):            # mpc.py:246-257
@@ -273,7 +286,8 @@ def run_closed_loop(inst, numerics, x_guess, u_guess, n_steps, Nb, nq, on_step=N
             break
     last = x_sim[-1]
     conv = bool(not np.isnan(last).any() and numerics.converged(last))      # mpc.py:273 (a NaN norm compares false)
-    return {'x': x_sim, 'u': u_log, 'r': r_log, 'events': events, 'collided': collided, 'n_viable': n_viable, 'conv': conv}
+    return {'x': x_sim, 'u': u_log, 'r': r_log, 'events': events, 'collided': collided, 'n_viable': n_viable, 'conv': conv,
+            'rest_tests': rest_tests, 'resumes': resumes}
 
 
 def outcome_lists(results):
