@@ -425,6 +425,55 @@ int smpc_forecast_row_margin(smpc_handle* h, int B, int window, int degree, doub
  * NULL pointer.  What a test or a study reads the margins of a step with. */
 int smpc_get_instance_row_bounds(smpc_handle* h, int B, double* lo, double* hi, int on_device);
 
+/* Obstacle forecasts from a Kalman filter.  One filter per (instance, row) RECORD over all eight slots of a scene
+ * record with the record's gains; time is in columns.  The model: degree p in 0..2 (constant, constant velocity, constant acceleration;
+ * only components 0..p of a record are used), q >= 0 the process noise, r > 0 the sensor noise in metres, v0, a0 >= 0 the prior standard
+ * deviations of velocity and acceleration, beta in [0, 1] the rate of the innovation scale.
+ *   transition   pos' = (pos + vel) + 0.5 acc,  vel' = vel + acc,  acc' = acc;   Phi = ((1, 1, 1/2), (0, 1, 1), (0, 0, 1))
+ *   process      Q = q^2 G G',  G = (1) | (1/2, 1) | (1/6, 1/2, 1);  formed on the host as gq_i = q G_i, Q_ij = gq_i gq_j
+ * The state lives in CALLER-OWNED device memory, [B][n_rows][SMPC_KALMAN_REC] doubles (the engine keeps no filter state, as it keeps no
+ * policy or loop state), a record being  pos[8] | vel[8] | acc[8] | P00 P01 P02 P11 P12 P22 | s2 | n;  all zero means "nothing seen".
+ * A record is OBSERVED at a step when none of the moving slots of its row kind (smpc_forecast_row_margin lists them) holds a NaN in
+ * S[b][col(t)][r]; a SMPC_ROW_SEG_SEG row always is.
+ *   advance, n < 1    observed: pos = y, vel = acc = 0, P = diag(r^2, v0^2, a0^2), s2 = 1, n = 1;   unobserved: the record stays
+ *   advance, n >= 1   predict x- = Phi x, P- = Phi P Phi' + Q (first the rows of Phi P, then times Phi', then + Q);
+ *                     observed: S = P-00 + r^2, inv = 1.0 / S (the one division), K_i = P-0i inv; per slot nu = y - pos-, x_i = x-_i + K_i nu;
+ *                       P_ij = P-ij - K_i P-0j (i <= j); nis = the largest (nu nu) inv over the moving slots from 0, a NaN winning;
+ *                       s2 = s2 + beta (nis - s2), then 1 where it is below 1;  n = n + 1
+ *                     unobserved: x = x-, P = P-; s2 and n stay
+ *   forecast          p = 0: F[k] = pos (stored);  p = 1: F[0] = pos, F[k] = F[k-1] + vel;
+ *                     p = 2: v = vel + 0.5 acc, F[0] = pos, then F[k] = F[k-1] + v; v = v + acc
+ * every product rounded before its sum: problem.kalman_statement is the definition, and the kernel repeats it bit for bit. */
+#define SMPC_KALMAN_REC 32
+typedef struct {
+    int32_t degree, reserved;
+    double q, r, v0, a0, beta;
+} smpc_kalman_params;
+
+/* One step of the filter (advance != 0) and its forecast over the handle's horizon, written into the scene slot -- and the context slot
+ * with n_sel > 0 -- under every rule of smpc_forecast_scene: room first and launch last, growth under capture is SMPC_ESTATE with nothing
+ * changed, the slot then holds a forecast (read from time 0).  Enqueue-only, so [kalman; margin; solve] can be captured: a replay is
+ * one more advance.  state: DEVICE [B][n_rows][SMPC_KALMAN_REC], updated in place.
+ *   advance != 0   reads S (the observed track while one is set, else the world) at the scene clock: needs the world, B the world's
+ *                  and an observed track of the world's shape, as smpc_forecast_scene_fit does.
+ *   advance == 0   forecasts from the state as it is: reads no table, needs no world and takes any B > 0 -- what a second handle with
+ *                  another horizon calls on rows of the controller's state.
+ * SMPC_EINVAL, naming the argument: degree outside 0..2; r not finite or <= 0; q, v0 or a0 negative or not finite; beta outside [0, 1];
+ * par or state NULL; B <= 0; a descriptor without rows; n_sel / select as for smpc_forecast_scene.  A refused call changes nothing, the
+ * state included.  (ABI version unchanged: no existing entry point or structure changed) */
+int smpc_forecast_scene_kalman(smpc_handle* h, int B, const smpc_kalman_params* par, double* state, int advance, int n_sel,
+                               const int32_t* select);
+
+/* The row-bounds table from the filter's covariance: reads P and s2 of state (DEVICE [B][n_rows][SMPC_KALMAN_REC]) and nothing else --
+ * no world, no clock, not the scene slot.  Pi_0 = P, Pi_k = Phi Pi_{k-1} Phi' + Q, g_k = sqrt(Pi_k[0][0]) (no + r^2: the true obstacle
+ * carries no noise);  d_k = (base_a + base_b k) + (z sqrt(s2)) g_k,  d_k = d_k <= d_max ? d_k : d_max  (a NaN gives the cap);  d = 0 for
+ * a row without a moving slot.  The table is what smpc_forecast_row_margin writes for these d, and it fills the slot of
+ * smpc_set_instance_row_bounds under that slot's rules.  problem.kalman_margin_statement is the definition.
+ * SMPC_EINVAL: the model as above; z, base_a, base_b or d_max negative or not finite; a d_max with which a plane row's sides would
+ * cross; a descriptor without rows; B <= 0; par or state NULL.  SMPC_ESTATE: the buffer would have to grow under capture. */
+int smpc_kalman_row_margin(smpc_handle* h, int B, const smpc_kalman_params* par, const double* state, double z, double base_a,
+                           double base_b, double d_max);
+
 /* A reference curve of its own for every instance of the tracking task.  curves is [B][3][L] doubles: curves[b] has exactly the
  * layout of the shared table smpc_policy_state.traj / smpc_score_params.traj ([3][L], L = n_steps + 1 + N columns).  The handle
  * keeps a copy like a scene (stream-ordered; with host pointers the call checks every entry for finiteness and waits for the

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import subprocess
 
-from .problem import Joint, NodeEval, ProblemDesc
+from .problem import Joint, KalmanParams, NodeEval, ProblemDesc
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 # SMPC_HIP_LIB selects another build of the SAME engine (diagnostic builds of scripts/qp_phase_profile.py)
@@ -24,7 +24,7 @@ SYMBOLS = ['smpc_create', 'smpc_destroy', 'smpc_abi_version', 'smpc_last_error',
            'smpc_set_instance_scene_track', 'smpc_set_scene_clock', 'smpc_set_mlp_context', 'smpc_set_instance_context',
            'smpc_set_instance_models', 'smpc_set_instance_context_track', 'smpc_set_instance_world_track', 'smpc_forecast_scene',
            'smpc_set_instance_observed_track', 'smpc_forecast_scene_fit', 'smpc_forecast_scene_poly', 'smpc_set_instance_row_bounds',
-           'smpc_forecast_row_margin', 'smpc_get_instance_row_bounds']
+           'smpc_forecast_row_margin', 'smpc_get_instance_row_bounds', 'smpc_forecast_scene_kalman', 'smpc_kalman_row_margin']
 
 
 class EngineError(RuntimeError):
@@ -148,6 +148,9 @@ def lib():
     L.smpc_forecast_scene_poly.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
     L.smpc_forecast_row_margin.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5
     L.smpc_get_instance_row_bounds.argtypes = [vp, C.c_int, dp, dp, C.c_int]
+    if hasattr(L, 'smpc_forecast_scene_kalman'):      # (an older build named by SMPC_HIP_LIB: the solver's methods raise)
+        L.smpc_forecast_scene_kalman.argtypes = [vp, C.c_int, C.POINTER(KalmanParams), dp, C.c_int, C.c_int, dp]
+        L.smpc_kalman_row_margin.argtypes = [vp, C.c_int, C.POINTER(KalmanParams), dp] + [C.c_double] * 4
     L.smpc_set_instance_curves.argtypes = [vp, C.c_int, C.c_int64, dp, C.c_int]
     L.smpc_solve_batch.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.smpc_eval_nodes.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int]

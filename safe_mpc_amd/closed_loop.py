@@ -31,13 +31,17 @@ def guess_file(params, model_name, cont_name, horizon, use_net):
 
 
 def result_file(params, model_name, cont_name, horizon, use_net, noise, control_noise, jm, cm, controller_model='nominal', forecast=None,
-                forecast_window=None, obs_noise=0.0, forecast_degree=1, row_margin=None, row_margin_fit=None):
+                forecast_window=None, obs_noise=0.0, forecast_degree=1, row_margin=None, row_margin_fit=None, kalman=None,
+                row_margin_kalman=None, obs_dropout=None):
     """``controller_model='plant'`` (scripts/mpc.py --controller-model plant, run_mpc(models='plant')): the suffix ``_cmplant``
     before ``_mpc.pkl``; ``forecast`` (scripts/mpc.py --scene-forecast, run_mpc(forecast=...)): the suffix ``_fc<mode>`` behind
     it, ``_fcfit_w<m>`` for a fit over ``forecast_window = m`` columns, ``_d<p>`` behind that for ``forecast_degree = p`` other than 1
     (a polynomial fit, --forecast-degree); ``obs_noise = s > 0`` (--scene-obs-noise): ``_on<s>`` behind
     that; ``row_margin = (a, b)`` (--row-margin, run_mpc(row_margin=...)): ``_rm<a>`` behind that, and ``_g<b>`` for b other than 0;
     ``row_margin_fit = (z, sigma_prior, d_max)`` (--row-margin-z, run_mpc(row_margin_fit=...)): ``_rmf<z>_p<sigma_prior>_c<d_max>`` behind that;
+    ``forecast='kalman'`` with ``kalman = (q, r[, v0, a0, beta])`` (--scene-forecast kalman): ``_fckalman_d<p>_q<q>_r<r>_v<v0>_a<a0>_b<beta>``
+    in the forecast's place, ``obs_dropout = (p, len)`` (--scene-obs-dropout): ``_od<p>_l<len>`` behind ``_on``, and
+    ``row_margin_kalman = (z, d_max)`` (--row-margin-z with the filter): ``_rmk<z>_c<d_max>`` at the end;
     the defaults give the reference's name"""
     if controller_model not in ('nominal', 'plant'):
         raise ValueError(f"controller_model: {controller_model!r}: expected 'nominal' or 'plant'")
@@ -45,10 +49,12 @@ def result_file(params, model_name, cont_name, horizon, use_net, noise, control_
     return (f'{params.DATA_DIR}{model_name}_{cont_name}_use_net{use_net}_{horizon}hor_{int(params.alpha)}sm_{track}'
             f'noise_{noise}_control_noise{control_noise}_q_collision_margins_{jm}_{cm}'
             f"{'_cmplant' if controller_model == 'plant' else ''}"
-            f"{'' if forecast is None else _Forecast(forecast, forecast_window, forecast_degree).file_suffix()}"
+            f"{'' if forecast is None else _Forecast(forecast, forecast_window, forecast_degree, kalman).file_suffix()}"
             f"{f'_on{obs_noise}' if obs_noise > 0 else ''}"
+            f"{'' if obs_dropout is None else '_od{}_l{}'.format(*(float(v) for v in obs_dropout))}"
             f"{'' if row_margin is None else f'_rm{float(row_margin[0])}' + (f'_g{float(row_margin[1])}' if float(row_margin[1]) != 0.0 else '')}"
             f"{'' if row_margin_fit is None else '_rmf{}_p{}_c{}'.format(*(float(v) for v in row_margin_fit))}"
+            f"{'' if row_margin_kalman is None else '_rmk{}_c{}'.format(*(float(v) for v in row_margin_kalman))}"
             "_mpc.pkl")
 
 
@@ -1057,66 +1063,108 @@ class _Forecast:
     'hold', 'cv', 'true', or 'fit' -- a least-squares polynomial of ``degree`` through the last ``window`` columns seen -- and the one
     place that tells the kinds apart, on the host path and the device path.  Degree 1 keeps the line fit's own statement and entry point."""
 
-    def __init__(self, kind, window=None, degree=None):
-        self.kind, self._fit = kind, kind == 'fit'
+    def __init__(self, kind, window=None, degree=None, kalman=None):
+        self.kind, self._fit, self.is_kalman = kind, kind == 'fit', kind == 'kalman'
         self.window, self.degree = int(window) if self._fit else None, 1 if degree is None else int(degree)
         self._poly = self._fit and self.degree != 1
+        self.kalman = self.par = None       # (q, r, v0, a0, beta) as the result reports it, and the model as the entry points take it
+        if self.is_kalman:
+            from .problem import kalman_params
+            self.par = kalman_params(self.degree, *kalman, who='kalman')
+            self.kalman = tuple(float(getattr(self.par, k)) for k in ('q', 'r', 'v0', 'a0', 'beta'))
 
     @classmethod
-    def checked(cls, kind, window, degree, scenes):
-        """run_mpc's three forecast arguments against its (checked) ``scenes``: the spec, None without a forecast, or ValueError"""
+    def checked(cls, kind, window, degree, scenes, kalman=None):
+        """run_mpc's forecast arguments against its (checked) ``scenes``: the spec, None without a forecast, or ValueError"""
+        if kalman is not None and kind != 'kalman':
+            raise ValueError(f"kalman: forecast={kind!r} has no filter: it goes with forecast='kalman'")
         if kind is not None:
             from .problem import FIT_MAX, FORECAST_MODES
-            if kind != 'fit' and kind not in FORECAST_MODES:
-                raise ValueError(f"forecast: {kind!r}: expected None, 'fit' or one of {sorted(FORECAST_MODES)}")
+            if kind not in ('fit', 'kalman') and kind not in FORECAST_MODES:
+                raise ValueError(f"forecast: {kind!r}: expected None, 'fit' or one of {sorted(FORECAST_MODES)}, or 'kalman'")
+            if kind == 'kalman':
+                if kalman is None:
+                    raise ValueError("kalman: forecast='kalman' needs kalman=(q, r[, v0, a0, beta])")
+                kalman = tuple(np.asarray(kalman, float).reshape(-1))
+                if not 2 <= len(kalman) <= 5:
+                    raise ValueError(f'kalman: expected (q, r[, v0, a0, beta]), got {kalman}')
             if kind == 'fit' and not (isinstance(window, (int, np.integer)) and 1 <= window <= FIT_MAX):
                 raise ValueError(f'forecast_window: {window!r}: a fit takes 1 to {FIT_MAX} columns')
             if scenes is None or scenes.ndim != 4:
                 raise ValueError('forecast: needs a scene track (scenes [B, T, n_rows, 8]) to forecast from; '
                                  + ('no scenes were given' if scenes is None else 'standing scenes have nothing to predict'))
         if degree is not None:
-            if kind != 'fit':
-                raise ValueError(f"forecast_degree: forecast={kind!r} has no degree: it goes with forecast='fit'")
+            if kind not in ('fit', 'kalman'):
+                raise ValueError(f"forecast_degree: forecast={kind!r} has no degree: it goes with forecast='fit' or 'kalman'")
             if not (isinstance(degree, (int, np.integer)) and 0 <= degree <= 2):
                 raise ValueError(f'forecast_degree: {degree!r}: a polynomial fit has degree 0, 1 or 2')
-        return None if kind is None else cls(kind, window, degree)
+        return None if kind is None else cls(kind, window, degree, kalman)     # (a bad kalman tuple: kalman_params' ValueError)
 
-    def statement(self, world, observed, rows, t, N):
+    def statement(self, world, observed, rows, t, N, state=None, advance=True):
         """the host path: the N + 1 scenes forecast at time t for the instances ``rows``, by the statement of the engine's entry point.
-        'hold', 'cv' and 'fit' (of any degree) are formed from what was seen, the observed track where the run has one; 'true' from the world"""
+        'hold', 'cv', 'fit' (of any degree) and 'kalman' are formed from what was seen, the observed track where the run has one; 'true'
+        from the world.  'kalman': ``state`` is the filter state of the instances ``rows`` -- advanced IN PLACE by the column seen at
+        time t with ``advance``, only read without"""
         from .problem import fit_forecast_statement, forecast_statement, poly_forecast_statement
         seen = world if observed is None or self.kind == 'true' else observed
+        if self.is_kalman:
+            from .problem import kalman_statement, scene_column
+            y = seen[rows][:, scene_column(t, seen.shape[1])] if advance else None
+            new, F = kalman_statement(state, y, self._kinds, self.par, N, advance)
+            if advance:
+                state[...] = new
+            return F
         if not self._fit:
             return forecast_statement(seen[rows], t, N, self.kind)
         if not self._poly:
             return fit_forecast_statement(seen[rows], t, N, self.window)
         return poly_forecast_statement(seen[rows], t, N, self.window, self.degree)
 
-    def enqueue(self, sv, select):
-        """the device path: one forecast from ``sv``'s world (and observed track) at its clock cell, into its scene slot"""
-        if self._poly:
+    def enqueue(self, sv, select, state=None, advance=True):
+        """the device path: one forecast from ``sv``'s world (and observed track) at its clock cell, into its scene slot.  'kalman':
+        one step of the filter on the device tensor ``state`` first (``advance``), or the forecast from it as it is"""
+        if self.is_kalman:
+            sv.forecast_scene_kalman(self.par, state, advance, select)
+        elif self._poly:
             sv.forecast_scene_poly(self.window, self.degree, select)
         elif self._fit:
             sv.forecast_scene_fit(self.window, select)
         else:
             sv.forecast_scene(self.kind, select)
 
-    def require(self, sv, observed):
+    def margin_statement(self, prob, state, z, base, cap):
+        """the host path of a margin from the filter's covariance: d [B, N + 1, n_rows] for the records ``state``"""
+        from .problem import kalman_margin_statement
+        return kalman_margin_statement(prob, state, self.par, z, base, cap)
+
+    def enqueue_margin(self, sv, state, z, base, cap):
+        sv.kalman_row_margin(self.par, state, z, base, cap)
+
+    def bind(self, problem):
+        """the row kinds of the run's problem, which the filter's statement takes"""
+        self._kinds = [int(r.kind) for r in problem.rows]
+
+    def require(self, sv, observed, margin=False):
         """ValueError unless ``sv`` has the entry points :meth:`enqueue` calls (and takes an observed track, for a run with one)"""
         for need, feature, method in ((True, 'forecast', 'forecast_scene'), (self._fit, 'forecast', 'forecast_scene_fit'),
+                                      (self.is_kalman, 'forecast', 'forecast_scene_kalman'),
+                                      (self.is_kalman and margin, 'row_margin_kalman', 'kalman_row_margin'),
                                       (self._poly, 'forecast_degree', 'forecast_scene_poly'), (observed, 'observed', 'set_instance_observed_track')):
             if need:
                 _require(sv, feature, method)
 
     def result_keys(self, observed):
         return {'forecast': self.kind, 'observed': bool(observed), **({'forecast_window': self.window} if self._fit else {}),
-                **({'forecast_degree': self.degree} if self._poly else {})}
+                **({'forecast_degree': self.degree} if self._poly else {}),
+                **({'forecast_degree': self.degree, 'kalman': self.kalman} if self.is_kalman else {})}
 
     def file_suffix(self):
+        if self.is_kalman:
+            return '_fckalman_d{}_q{}_r{}_v{}_a{}_b{}'.format(self.degree, *self.kalman)
         return f"_fc{self.kind}{f'_w{self.window}' if self._fit else ''}{f'_d{self.degree}' if self._poly else ''}"
 
 
-class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_margin row_margin_fit', defaults=(None,) * 6)):
+class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_margin row_margin_fit row_margin_kalman', defaults=(None,) * 7)):
     """run_mpc's ``scenes``, ``models``, ``forecast*`` (a :class:`_Forecast`), ``observed``, ``row_margin`` and ``row_margin_fit``, checked
     (:func:`_check_world`): of the whole run, or of one group's instances (:meth:`rows`)"""
 
@@ -1126,10 +1174,11 @@ class _RunWorld(namedtuple('_RunWorld', 'scenes models forecast observed row_mar
 
 
 def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models,
-                 row_margin_fit=None):
+                 row_margin_fit=None, kalman=None, row_margin_kalman=None):
     """run_mpc's arguments about the world of its B instances, before anything is built: the :class:`_RunWorld`, or ValueError"""
     for name, given, thing in (('models', models, 'model table'), ('scenes', scenes, 'scene'), ('row_margin', row_margin, 'row-bounds table'),
-                               ('row_margin_fit', row_margin_fit, 'row-bounds table')):
+                               ('row_margin_fit', row_margin_fit, 'row-bounds table'), ('kalman', kalman, 'scene'),
+                               ('row_margin_kalman', row_margin_kalman, 'row-bounds table')):
         if cont_name == 'parallel' and given is not None:
             raise ValueError(f"{name}: the 'parallel' policy is not supported (its solver works on candidate slots, not instances, and "
                              f"the engine refuses a {thing} there)")
@@ -1150,7 +1199,14 @@ def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_win
         row_margin = tuple(float(v) for v in np.asarray(row_margin, float).reshape(-1))
         if len(row_margin) != 2 or not all(np.isfinite(row_margin)):
             raise ValueError(f'row_margin: expected (a, b), the margin a + b k metres at node k, got {row_margin}')
-    fc = _Forecast.checked(forecast, forecast_window, forecast_degree, scenes)
+    fc = _Forecast.checked(forecast, forecast_window, forecast_degree, scenes, kalman)
+    if row_margin_kalman is not None:
+        if forecast != 'kalman':
+            raise ValueError(f"row_margin_kalman: forecast={forecast!r} has no covariance to form a margin from: it goes with "
+                             f"forecast='kalman'")
+        row_margin_kalman = tuple(float(v) for v in np.asarray(row_margin_kalman, float).reshape(-1))
+        if len(row_margin_kalman) != 2 or not all(np.isfinite(v) and v >= 0.0 for v in row_margin_kalman):
+            raise ValueError(f'row_margin_kalman: expected (z, d_max), finite and not negative, got {row_margin_kalman}')
     if row_margin_fit is not None:
         if forecast != 'fit':
             raise ValueError(f"row_margin_fit: forecast={forecast!r} leaves no residuals to form a margin from: it goes with forecast='fit'")
@@ -1159,11 +1215,14 @@ def _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_win
             raise ValueError(f'row_margin_fit: expected (z, sigma_prior, d_max), finite and not negative, got {row_margin_fit}')
     if observed is not None:
         if fc is None or fc.kind == 'true':
-            raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv' or 'fit'")
+            raise ValueError(f"observed: forecast={forecast!r} does not read an observed track: it goes with 'hold', 'cv', 'fit' or 'kalman'")
         observed = np.ascontiguousarray(observed, np.float64)
         if observed.shape != scenes.shape:
             raise ValueError(f'observed: expected the world\'s shape {scenes.shape}, got {observed.shape}')
-    return _RunWorld(scenes, models, fc, observed, row_margin, row_margin_fit)
+        if not fc.is_kalman and np.isnan(observed).any():
+            raise ValueError(f"observed: a NaN (a sample that is missing): only forecast='kalman' skips one, forecast={forecast!r} would carry it "
+                             f"into the scenes")
+    return _RunWorld(scenes, models, fc, observed, row_margin, row_margin_fit, row_margin_kalman)
 
 
 def _joint_tensor(xp, table, B, nq):        # [B, nq] smpc_joint records as a float64 device tensor [B, nq, 29]
@@ -1182,6 +1241,9 @@ class _World:
         self._sv, self._bsv, self.forecast, self.track = ctrl.ocp_solver, backup.ocp_solver, run.forecast, False
         self.scenes = self.observed = self.row_bounds = self.models = self.clock = self.backup_clock = self._select = self._backup_select = None
         self.margin_fit = None      # (z, sigma_prior, base, d_max) of a margin formed from the fit's residuals at the head of every step
+        self.margin_kalman = None   # (z, base, d_max) of a margin formed from the filter's covariance there
+        self.kalman_state = None    # the filter state [B, n_rows, KALMAN_REC]: numpy on the host path, ONE device tensor on the device path
+        self._backup_state = None   # its rows of the last abort event, as the backup handle's calls read them
 
     def attach(self):
         """what the run's arguments alone say: the scenes (without a forecast) and the row bounds onto the controller's handle"""
@@ -1196,7 +1258,17 @@ class _World:
             if self.track:
                 for sv in (self._sv, self._bsv):
                     _require(sv, 'scenes', 'set_scene_clock')
-        if run.row_margin_fit is not None:
+        if self.forecast is not None and self.forecast.is_kalman:
+            from .problem import KALMAN_REC
+            self.forecast.bind(ctrl.problem)
+            self.kalman_state = xp.zeros((B, len(ctrl.problem.rows), KALMAN_REC))
+        if run.row_margin_kalman is not None:
+            # the margin follows the filter, step by step; row_margin is its base, as for row_margin_fit
+            z, cap = run.row_margin_kalman
+            self.margin_kalman = (z, (0.0, 0.0) if run.row_margin is None else tuple(float(v) for v in run.row_margin), cap)
+            for sv in (self._sv, self._bsv):
+                _require(sv, 'row_margin_kalman', 'kalman_row_margin' if xp.on_device else 'set_instance_row_bounds')
+        elif run.row_margin_fit is not None:
             # the margin follows the fit, step by step; row_margin is its base, not a table of its own
             z, prior, cap = run.row_margin_fit
             self.margin_fit = (z, prior, (0.0, 0.0) if run.row_margin is None else tuple(float(v) for v in run.row_margin), cap)
@@ -1233,7 +1305,7 @@ class _World:
             _set_models(sv, self.models)
         if dev and self.forecast is not None:
             for s in (sv, bsv):
-                self.forecast.require(s, self.observed is not None)
+                self.forecast.require(s, self.observed is not None and not (s is bsv and self.forecast.is_kalman), self.margin_kalman is not None)
             self._select, self._backup_select = _context_select(sv), _context_select(bsv)
             sv.set_instance_world_track(self.scenes)
             if self.observed is not None:       # (what HOLD, CV and the fit then read instead of the world)
@@ -1241,11 +1313,34 @@ class _World:
 
     def _forecast_into(self, sv, select, rows, t, N):
         """one forecast into ``sv``'s scene slot: on the device from its world (and observed track) at its clock cell; on the host the
-        statement at time ``t`` for the instances ``rows`` (with their context rows, _set_scene) and no clock -- node k reads column k"""
+        statement at time ``t`` for the instances ``rows`` (with their context rows, _set_scene) and no clock -- node k reads column k.
+        A filter advances on the controller's handle and is only read on the backup's, from the rows of the event"""
+        advance = sv is self._sv
+        state = self.kalman_state if advance else self._backup_state
         if self._xp.on_device:
-            return self.forecast.enqueue(sv, select)
+            return self.forecast.enqueue(sv, select, state, advance) if self.forecast.is_kalman else self.forecast.enqueue(sv, select)
         sv.set_scene_clock(None)
+        if self.forecast.is_kalman:
+            return _set_scene(sv, self.forecast.statement(self.scenes, self.observed, rows, t, N, state, advance))
         _set_scene(sv, self.forecast.statement(self.scenes, self.observed, rows, t, N))
+
+    def _kalman_margin_into(self, sv, prob):
+        """the row-bounds table of ``sv`` from the covariance of the filter it has just forecast with: on the device one enqueued call;
+        on the host the statement over ``prob``'s horizon, then the setter"""
+        z, base, cap = self.margin_kalman
+        state = self.kalman_state if sv is self._sv else self._backup_state
+        if self._xp.on_device:
+            return self.forecast.enqueue_margin(sv, state, z, base, cap)
+        from .problem import inflated_row_bounds
+        d = self.forecast.margin_statement(prob, state, z, base, cap)
+        sv.set_instance_row_bounds(*inflated_row_bounds(prob, d.shape[0], d))
+
+    def pick_backup_rows(self, rows):
+        """the filter's records of the aborting instances ``rows`` as they are now -- gathered where the state is written (a device
+        loop: on the loop's stream, before the event that the backup's stream waits for, because the next step's advance overwrites
+        the state in place); kept until the next event, when the previous one's solve has been waited for"""
+        if self.kalman_state is not None:
+            self._backup_state = self.kalman_state[rows]
 
     def _margin_into(self, sv, prob, rows, t):
         """the row-bounds table of ``sv`` from the residuals of the fit it has just forecast with: on the device one enqueued call at
@@ -1266,6 +1361,8 @@ class _World:
             self._forecast_into(self._sv, self._select, slice(None), t, self._ctrl.N)
             if self.margin_fit is not None:
                 self._margin_into(self._sv, self._ctrl.problem, slice(None), t)
+            if self.margin_kalman is not None:
+                self._kalman_margin_into(self._sv, self._ctrl.problem)
         elif not self._xp.on_device:
             _write_scene_clock(self.clock, t)
 
@@ -1276,13 +1373,18 @@ class _World:
         if self.scenes is not None and self.forecast is None:
             _set_scene(sv, self.scenes[rows])
         elif self.scenes is not None:
-            if self._xp.on_device:              # (the forecast reads them at the handle's own clock cell)
+            if self.forecast.is_kalman:         # (forecast from the event's records: no table is read, so no world goes on)
+                if not self._xp.on_device:
+                    self.pick_backup_rows(rows)
+            elif self._xp.on_device:            # (the forecast reads them at the handle's own clock cell)
                 sv.set_instance_world_track(self.scenes[rows])
                 if self.observed is not None:
                     sv.set_instance_observed_track(self.observed[rows])
             self._forecast_into(sv, self._backup_select, rows, t, self._backup.N)
             if self.margin_fit is not None:
                 self._margin_into(sv, self._backup.problem, rows, t)
+            if self.margin_kalman is not None:
+                self._kalman_margin_into(sv, self._backup.problem)
         if self.row_bounds is not None:
             sv.set_instance_row_bounds(self.row_bounds[0][rows], self.row_bounds[1][rows])
         if self.models is not None:
@@ -1308,7 +1410,7 @@ class _World:
                         s.set_instance_observed_track(None)
                     if hasattr(s, 'set_instance_world_track'):
                         s.set_instance_world_track(None)
-        if self.row_bounds is not None or self.margin_fit is not None:
+        if self.row_bounds is not None or self.margin_fit is not None or self.margin_kalman is not None:
             sv.set_instance_row_bounds(None)
             bsv.set_instance_row_bounds(None)
         if self.models is not None:
@@ -1634,6 +1736,7 @@ class _DeviceGroup(_Group):
         self._pending.copy_(self.new_abort)
         if self._world.backup_clock is not None:
             self._world.backup_clock.copy_(self._jt)         # (the previous event's solve has finished: _apply_inflight above)
+        self._world.pick_backup_rows(rows_b)                 # (a filter's records of the event: before ev0, like xv_c)
         main = torch.cuda.current_stream()
         ev0 = torch.cuda.Event()
         ev0.record(main)
@@ -1740,7 +1843,7 @@ def _check_state_kind(ctrl, backup, on_device):
 def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, make_controller=None, make_backup=None,
             n_steps=None, callback=False, on_device=False, device=0, timing=None, groups=None, graphs=True, collect_times=False,
             score=False, scenes=None, traj=None, models=None, forecast=None, forecast_window=8, observed=None,
-            forecast_degree=None, row_margin=None, row_margin_fit=None):
+            forecast_degree=None, row_margin=None, row_margin_fit=None, kalman=None, row_margin_kalman=None):
     """scripts/mpc.py:102-317 for all instances at once.  Returns the result dict the reference pickles (mpc.py:307-315).
 
     ``on_device=True``: the whole loop state -- the policy automaton of the controller, the safe-abort automaton of the driver
@@ -1822,11 +1925,23 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
     On the device one smpc_forecast_row_margin behind the forecast inside the captured half of every step, and on the backup handle
     behind its forecast at an abort event, over its own horizon; on the host the statement and solver.set_instance_row_bounds per
     step.  Both handles end without a table and the result gains ``'row_margin_fit'``.  Not with the parallel policy (ValueError).
-    None: the calls of a run without the argument, one for one."""
+    None: the calls of a run without the argument, one for one.
+    ``forecast='kalman'`` with ``kalman = (q, r[, v0, a0, beta])``: the controller forecasts with a Kalman filter
+    per (instance, row) -- ``forecast_degree`` 0, 1 (the default here) or 2 its model, q the process noise, r the sensor noise in
+    metres (``problem.kalman_params``, ``problem.kalman_statement``); ``forecast_window`` is not read.  One advancing forecast at the
+    head of every step, inside the captured half on the device; ``observed`` may hold NaN here, samples that are missing
+    (``problem.occlude_tracks``): the filter skips its update and its covariance grows.  The backup handle of an abort event forecasts
+    from the aborting instances' records as they are, over its own horizon, and is given no world.  The state is the run's: numpy on
+    the host path, one device tensor of a fixed address on the device path.
+    ``row_margin_kalman`` ``(z, d_max)``, only with ``forecast='kalman'``: the margin formed behind every such forecast from the
+    filter's predicted covariance (``problem.kalman_margin_statement``), ``row_margin`` its base as for ``row_margin_fit``.  The result
+    gains ``'kalman'`` (all five numbers), ``'forecast_degree'`` and ``'row_margin_kalman'``.  ValueError before anything is built:
+    the parallel policy, ``forecast='kalman'`` without ``kalman`` or either argument without it, ``row_margin_fit`` with it, a solver
+    without the calls."""
     import time
     B = x_guess.shape[0]
     world = _check_world(B, cont_name, noise, scenes, row_margin, forecast, forecast_window, forecast_degree, observed, models,
-                         row_margin_fit)
+                         row_margin_fit, kalman, row_margin_kalman)
     curves = traj is not None and np.ndim(traj) == 3
     if curves:
         traj = np.ascontiguousarray(traj, np.float64)
@@ -1949,6 +2064,8 @@ def run_mpc(params, cont_name, x_guess, u_guess, noise=0.0, control_noise=0.0, m
         extra['row_margin'] = world.row_margin
     if world.row_margin_fit is not None:
         extra['row_margin_fit'] = world.row_margin_fit
+    if world.row_margin_kalman is not None:
+        extra['row_margin_kalman'] = world.row_margin_kalman
     return {**extra, 'x': x_sim, 'u': np.concatenate([o['u'] for o in outs], axis=0),
             'r': np.full((B, n_steps, 1), np.nan), 'r_receding': np.concatenate([o['r_receding'] for o in outs], axis=0),
             'conv_idx': conv_idx, 'collisions_idx': coll_idx, 'unconv_idx': unconv_idx, 'viable_idx': viable_idx,

@@ -1927,15 +1927,21 @@ static SceneSrc fit_source(const smpc_handle* h) {
 // The one body of smpc_forecast_scene (fit = false: `what` is its mode), smpc_forecast_scene_fit (fit = true: `what` is its window,
 // degree 1) and smpc_forecast_scene_poly (fit = true with its degree); `who` names the entry point in every message.  S, "what was seen", is the observed track while one is set and the world
 // otherwise; SMPC_FORECAST_TRUE reads the world whatever was observed.
+// kal: smpc_forecast_scene_kalman's call (fit and what are not read then).  With advance it reads S as a fit does; without, it reads no
+// table, so it needs no world and takes any B.
+struct KalmanCall { KalmanArgs ka; double* state; bool advance; };
 static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit, int what, int n_sel, const int32_t* select,
-                               int degree = 1) {
+                               int degree = 1, const KalmanCall* kal = nullptr) {
     const int mode = what, window = what;
+    const bool reads_S = !kal || kal->advance;
     int rc;
-    if ((rc = check_forecast_world(h, who, B))) return rc;
-    if (!fit && mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
+    if (reads_S && (rc = check_forecast_world(h, who, B))) return rc;
+    if (!reads_S && B <= 0) return fail(h, SMPC_EINVAL, "%s: bad batch size %d", who, B);
+    if (!reads_S && h->desc.n_rows == 0) return fail(h, SMPC_EINVAL, "%s: the problem has no collision rows: there is no scene to forecast", who);
+    if (!kal && !fit && mode != SMPC_FORECAST_HOLD && mode != SMPC_FORECAST_CV && mode != SMPC_FORECAST_TRUE)
         return fail(h, SMPC_EINVAL, "%s: mode %d (SMPC_FORECAST_HOLD, _CV, _TRUE)", who, mode);
-    if (fit && (rc = check_fit_shape(h, who, window, degree))) return rc;
-    if ((rc = check_forecast_observed(h, who))) return rc;
+    if (!kal && fit && (rc = check_fit_shape(h, who, window, degree))) return rc;
+    if (reads_S && (rc = check_forecast_observed(h, who))) return rc;
     const Net& net = *h->net;
     const int nr = h->desc.n_rows, N = h->N, nc = net.n_ctx;
     if (n_sel < 0) return fail(h, SMPC_EINVAL, "%s: n_sel=%d", who, n_sel);
@@ -1975,18 +1981,29 @@ static int forecast_into_scene(smpc_handle* h, const char* who, int B, bool fit,
     // (one-wavefront blocks, as for every small kernel of the policy step: see check_nodes_dev)
     const dim3 grd((unsigned)((n_rec + 63) / 64)), blk(64);
     // (the fit and the polynomial last: a kernel's place in the code object follows its first mention, and the older ones keep theirs)
-    if (!fit && mode == SMPC_FORECAST_HOLD)
+    if (!kal && !fit && mode == SMPC_FORECAST_HOLD)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_HOLD>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
-    else if (!fit && mode == SMPC_FORECAST_CV)
+    else if (!kal && !fit && mode == SMPC_FORECAST_CV)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_CV>), grd, blk, 0, h->stream, n_rec, nr, N, seen, h->scene.d.p);
-    else if (!fit)
+    else if (!kal && !fit)
         hipLaunchKernelGGL((k_scene_forecast<SMPC_FORECAST_TRUE>), grd, blk, 0, h->stream, n_rec, nr, N, world, h->scene.d.p);
-    else if (degree == 1)       // four lanes to a record: see k_scene_fit
+    else if (!kal && degree == 1)       // four lanes to a record: see k_scene_fit
         hipLaunchKernelGGL(k_scene_fit, dim3((unsigned)((4 * (size_t)n_rec + 63) / 64)), blk, 0, h->stream, 4 * n_rec, nr, N, window, seen,
                            h->scene.d.p);
-    else                        // degrees 0 and 2: the same mapping
+    else if (!kal)                      // degrees 0 and 2: the same mapping
         hipLaunchKernelGGL(k_scene_poly, dim3((unsigned)((4 * (size_t)n_rec + 63) / 64)), blk, 0, h->stream, 4 * n_rec, nr, N, window, degree,
                            seen, h->scene.d.p);
+    else {                              // the filter: the same mapping again; the row kinds travel by value
+        KalmanKinds kinds{};
+        for (int r = 0; r < nr; r++) kinds.kind[r] = h->desc.rows[r].kind;
+        const dim3 grd4((unsigned)((4 * (size_t)n_rec + 63) / 64));
+        seen.clock = h->scene_clock;    // (the filter advances with the clock even where T = 1 leaves one column to read)
+        if (kal->advance)
+            hipLaunchKernelGGL((k_scene_kalman<true>), grd4, blk, 0, h->stream, 4 * n_rec, nr, N, kal->ka, kinds, seen, kal->state, h->scene.d.p);
+        else
+            hipLaunchKernelGGL((k_scene_kalman<false>), grd4, blk, 0, h->stream, 4 * n_rec, nr, N, kal->ka, kinds, SceneSrc{}, kal->state,
+                               h->scene.d.p);
+    }
     HIPCHK(h, hipGetLastError());
     h->scene.commit(B);
     h->scene_T = N + 1;
@@ -2020,6 +2037,32 @@ int smpc_forecast_scene_poly(smpc_handle* h, int B, int window, int degree, int 
     return forecast_into_scene(h, "smpc_forecast_scene_poly", B, true, window, n_sel, select, degree);
 }
 
+// What the two margin entry points (smpc_forecast_row_margin, smpc_kalman_row_margin) share: the descriptor's rows by value with the
+// crossing-sides check, and the slot's room for [lo | hi] of n doubles each.
+static int margin_rows(smpc_handle* h, const char* who, double d_max, MarginRows* rows) {
+    for (int r = 0; r < h->desc.n_rows; r++) {
+        const smpc_row& R = h->desc.rows[r];
+        if (R.kind == SMPC_ROW_COORD && fabs(R.lb) < SMPC_INF && fabs(R.ub) < SMPC_INF && R.lb + d_max > R.ub - d_max)
+            return fail(h, SMPC_EINVAL, "%s: row %d: d_max=%g makes its sides cross (%g > %g)", who, r, d_max, R.lb + d_max, R.ub - d_max);
+        rows->kind[r] = R.kind;
+        rows->lb[r] = R.lb;
+        rows->ub[r] = R.ub;
+        // (on the host: the very double problem.inflated_row_bounds squares; read only where the row is a squared distance with a lower side)
+        rows->sqrt_lb[r] = R.kind != SMPC_ROW_COORD && R.lb >= 0.0 ? sqrt(R.lb) : 0.0;
+    }
+    return SMPC_OK;
+}
+static int rowb_room_for_margin(smpc_handle* h, const char* who, size_t n) {
+    // room first, launch last: a call refused for growth under capture has changed nothing; a buffer that did grow lost its old
+    // content, so the slot is empty until the commit
+    const bool grows = 2 * n * sizeof(double) > h->rowb.d.cap;
+    if (grows && capturing(h))
+        return fail(h, SMPC_ESTATE, "%s: the %s must grow to %zu bytes while the stream is being captured: run one eager call of this size "
+                    "first", who, h->rowb.noun, 2 * n * sizeof(double));
+    if (grows) h->rowb.clear();
+    return h->rowb.room(h, 2 * n);
+}
+
 // The row-bounds slot filled from what was seen: the margins of k_fit_margin as the table that
 // smpc_set_instance_row_bounds takes.  Reads S and the clock as smpc_forecast_scene_poly does; neither needs nor touches the scene slot.
 int smpc_forecast_row_margin(smpc_handle* h, int B, int window, int degree, double z, double sigma_prior, double base_a, double base_b,
@@ -2039,29 +2082,76 @@ int smpc_forecast_row_margin(smpc_handle* h, int B, int window, int degree, doub
         if (!(a.v >= 0.0 && a.v - a.v == 0.0))
             return fail(h, SMPC_EINVAL, "%s: %s=%g: a finite number that is not negative", who, a.name, a.v);
     MarginRows rows{};
-    for (int r = 0; r < nr; r++) {
-        const smpc_row& R = h->desc.rows[r];
-        if (R.kind == SMPC_ROW_COORD && fabs(R.lb) < SMPC_INF && fabs(R.ub) < SMPC_INF && R.lb + d_max > R.ub - d_max)
-            return fail(h, SMPC_EINVAL, "%s: row %d: d_max=%g makes its sides cross (%g > %g)", who, r, d_max, R.lb + d_max, R.ub - d_max);
-        rows.kind[r] = R.kind;
-        rows.lb[r] = R.lb;
-        rows.ub[r] = R.ub;
-        // (on the host: the very double problem.inflated_row_bounds squares; read only where the row is a squared distance with a lower side)
-        rows.sqrt_lb[r] = R.kind != SMPC_ROW_COORD && R.lb >= 0.0 ? sqrt(R.lb) : 0.0;
-    }
-    // room first, launch last: a call refused for growth under capture has changed nothing; a buffer that did grow lost its old
-    // content, so the slot is empty until the commit below
+    if ((rc = margin_rows(h, who, d_max, &rows))) return rc;
     const size_t n = (size_t)B * (N + 1) * nr;
-    const bool grows = 2 * n * sizeof(double) > h->rowb.d.cap;
-    if (grows && capturing(h))
-        return fail(h, SMPC_ESTATE, "%s: the %s must grow to %zu bytes while the stream is being captured: run one eager call of this size "
-                    "first", who, h->rowb.noun, 2 * n * sizeof(double));
-    if (grows) h->rowb.clear();
-    if ((rc = h->rowb.room(h, 2 * n))) return rc;
+    if ((rc = rowb_room_for_margin(h, who, n))) return rc;
     const int n_piece = 4 * B * nr;     // four lanes to a record: see k_fit_margin
     const MarginArgs ma{z, sigma_prior * sigma_prior, base_a, base_b, d_max};
     hipLaunchKernelGGL(k_fit_margin, dim3((unsigned)(((size_t)n_piece + 63) / 64)), dim3(64), 0, h->stream, n_piece, nr, N, window, degree,
                        fit_source(h), ma, rows, h->rowb.d.p, h->rowb.d.p + n);
+    HIPCHK(h, hipGetLastError());
+    h->rowb.commit(B);
+    return SMPC_OK;
+}
+
+// What both filter entry points ask of the model, naming the argument; ka: the model as the kernels take it (problem.kalman_noise)
+static int check_kalman(smpc_handle* h, const char* who, const smpc_kalman_params* par, const double* state, KalmanArgs* ka) {
+    if (!par) return fail(h, SMPC_EINVAL, "%s: par == NULL", who);
+    if (!state) return fail(h, SMPC_EINVAL, "%s: state == NULL", who);
+    if (par->degree < 0 || par->degree > 2) return fail(h, SMPC_EINVAL, "%s: degree %d: a model of degree 0, 1 or 2", who, par->degree);
+    if (!(par->r > 0.0 && par->r - par->r == 0.0)) return fail(h, SMPC_EINVAL, "%s: r=%g: a finite number above zero", who, par->r);
+    const struct { const char* name; double v; } args[] = {{"q", par->q}, {"v0", par->v0}, {"a0", par->a0}};
+    for (const auto& a : args)
+        if (!(a.v >= 0.0 && a.v - a.v == 0.0))
+            return fail(h, SMPC_EINVAL, "%s: %s=%g: a finite number that is not negative", who, a.name, a.v);
+    if (!(par->beta >= 0.0 && par->beta <= 1.0)) return fail(h, SMPC_EINVAL, "%s: beta=%g: a number in [0, 1]", who, par->beta);
+    const int p = par->degree;
+    // (volatile: every product is one rounded multiplication, whatever the host compiler would like to fold or fuse)
+    volatile double gq[3] = {0.0, 0.0, 0.0};
+    if (p == 0) gq[0] = par->q;
+    if (p == 1) { gq[0] = par->q * 0.5; gq[1] = par->q; }
+    if (p == 2) { gq[0] = par->q * (1.0 / 6.0); gq[1] = par->q * 0.5; gq[2] = par->q; }
+    *ka = KalmanArgs{p, 0, gq[0] * gq[0], gq[0] * gq[1], gq[0] * gq[2], gq[1] * gq[1], gq[1] * gq[2], gq[2] * gq[2],
+                     par->r * par->r, par->v0 * par->v0, par->a0 * par->a0, par->beta};
+    return SMPC_OK;
+}
+
+int smpc_forecast_scene_kalman(smpc_handle* h, int B, const smpc_kalman_params* par, double* state, int advance, int n_sel,
+                               const int32_t* select) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    const char* who = "smpc_forecast_scene_kalman";
+    KalmanCall kal{{}, state, advance != 0};
+    int rc;
+    if ((rc = check_kalman(h, who, par, state, &kal.ka))) return rc;
+    return forecast_into_scene(h, who, B, false, 0, n_sel, select, 1, &kal);
+}
+
+// The row-bounds slot filled from the filter's covariance: k_kalman_margin's margins as the table that
+// smpc_set_instance_row_bounds takes.  Reads the state alone: no world, no clock, not the scene slot.
+int smpc_kalman_row_margin(smpc_handle* h, int B, const smpc_kalman_params* par, const double* state, double z, double base_a,
+                           double base_b, double d_max) {
+    if (!h) return SMPC_EINVAL;
+    (void)hipSetDevice(h->device);
+    const char* who = "smpc_kalman_row_margin";
+    const int nr = h->desc.n_rows, N = h->N;
+    if (nr == 0) return fail(h, SMPC_EINVAL, "%s: the problem has no collision rows: there are no row bounds to set", who);
+    if (B <= 0) return fail(h, SMPC_EINVAL, "%s: bad batch size %d", who, B);
+    KalmanArgs ka{};
+    int rc;
+    if ((rc = check_kalman(h, who, par, state, &ka))) return rc;
+    const struct { const char* name; double v; } args[] = {{"z", z}, {"base_a", base_a}, {"base_b", base_b}, {"d_max", d_max}};
+    for (const auto& a : args)
+        if (!(a.v >= 0.0 && a.v - a.v == 0.0))
+            return fail(h, SMPC_EINVAL, "%s: %s=%g: a finite number that is not negative", who, a.name, a.v);
+    MarginRows rows{};
+    if ((rc = margin_rows(h, who, d_max, &rows))) return rc;
+    const size_t n = (size_t)B * (N + 1) * nr;
+    if ((rc = rowb_room_for_margin(h, who, n))) return rc;
+    const int n_rec = B * nr;       // a thread to a record: see k_kalman_margin
+    const MarginArgs ma{z, 0.0, base_a, base_b, d_max};
+    hipLaunchKernelGGL(k_kalman_margin, dim3((unsigned)(((size_t)n_rec + 63) / 64)), dim3(64), 0, h->stream, n_rec, nr, N, ka, ma, rows, state,
+                       h->rowb.d.p, h->rowb.d.p + n);
     HIPCHK(h, hipGetLastError());
     h->rowb.commit(B);
     return SMPC_OK;

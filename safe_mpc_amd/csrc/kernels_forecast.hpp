@@ -439,4 +439,200 @@ __global__ __launch_bounds__(64) void k_forecast_context(long n, int n_ctx, int 
     out[i] = (float)((v - nm.mean[c]) / nm.std[c]);
 }
 
+// The obstacle filter: a Kalman filter per (instance, row) record over all eight slots with the record's gains.
+// The model by value: the degree p (0: constant, 1: constant velocity, 2: constant acceleration), Q = q^2 G G' as the six numbers the
+// host formed (problem.kalman_noise), r^2 and the prior variances.  Row kinds by value too: no device block to keep, and a captured
+// launch carries its own.
+struct KalmanArgs { int32_t degree, reserved; double q00, q01, q02, q11, q12, q22, r2, v02, a02, beta; };
+struct KalmanKinds { int32_t kind[SMPC_MAX_ROWS]; };
+struct KalmanCov { double p00, p01, p02, p11, p12, p22; };
+
+// Phi P Phi' + Q with Phi = ((1, 1, 1/2), (0, 1, 1), (0, 0, 1)) cut to p + 1 components: problem.kalman_predict_cov operation for
+// operation -- the rows of A = Phi P, then A Phi', then + Q; the entries of absent components pass through.  p is uniform.
+__device__ __forceinline__ KalmanCov kalman_predict_cov(int p, const KalmanCov& P, const KalmanArgs& ka) {
+    KalmanCov o = P;
+    if (p == 0) {
+        o.p00 = P.p00 + ka.q00;
+    } else if (p == 1) {
+        const double a00 = P.p00 + P.p01, a01 = P.p01 + P.p11;
+        o.p00 = (a00 + a01) + ka.q00;
+        o.p01 = a01 + ka.q01;
+        o.p11 = P.p11 + ka.q11;
+    } else {
+        const double a00 = (P.p00 + P.p01) + rounded_product(0.5, P.p02);
+        const double a01 = (P.p01 + P.p11) + rounded_product(0.5, P.p12);
+        const double a02 = (P.p02 + P.p12) + rounded_product(0.5, P.p22);
+        const double a11 = P.p11 + P.p12, a12 = P.p12 + P.p22;
+        o.p00 = ((a00 + a01) + rounded_product(0.5, a02)) + ka.q00;
+        o.p01 = (a01 + a02) + ka.q01;
+        o.p02 = a02 + ka.q02;
+        o.p11 = (a11 + a12) + ka.q11;
+        o.p12 = a12 + ka.q12;
+        o.p22 = P.p22 + ka.q22;
+    }
+    return o;
+}
+
+// the moving slots of a row kind lie in [lo, hi) (the ones set_scene_table validates); a robot-robot row has none
+__device__ __forceinline__ int moving_lo(int kind) { return kind == SMPC_ROW_COORD ? 6 : 0; }
+__device__ __forceinline__ int moving_hi(int kind) {
+    return kind == SMPC_ROW_SEG_FIXEDSEG ? 6 : (kind == SMPC_ROW_SEG_POINT || kind == SMPC_ROW_POINT_POINT ? 3 : (kind == SMPC_ROW_COORD ? 7 : 0));
+}
+
+// k_scene_kalman<ADVANCE>: one step of the filter on state [B][n_rows][SMPC_KALMAN_REC] (ADVANCE: reading y = S[b][col(t)][r], t the
+// scene clock's cell) and F [B][N+1][n_rows][SMPC_SCENE_ROW] from the state as it then is -- problem.kalman_statement operation for
+// operation, so the kernel equals it bit for bit.  A record is pos[8] | vel[8] | acc[8] | P00 P01 P02 P11 P12 P22 | s2 | n: four
+// 64-byte lines.  k_scene_poly's mapping and for its reasons: a thread owns ONE 16-byte piece of pos, vel and acc, four neighbouring
+// lanes a whole record, a wavefront's access 16 whole records; one-wavefront blocks.  Each of the four lanes reads the record's last
+// line and forms the six covariance numbers and the gains itself -- the same arithmetic on the same bits, cheaper than sending nine
+// doubles across lanes -- and lane 0 of the four stores them.  What does cross the four lanes, by two __shfl_xor each: "observed" (an
+// AND) and nis (a maximum), neither of which depends on order.  (n_piece is a multiple of four and a record's lanes agree on n and on
+// "observed": they take every branch together.)  ONE division per record and step; every product rounded before its sum.  p is
+// uniform, so the branches on it are scalar and the absent components cost no load, no store and no register.  Without ADVANCE no
+// table is read and `seen` is not touched.  Nothing is shared between records: no atomics, no LDS, and an instance's result depends
+// neither on B nor on its neighbours.
+template <bool ADVANCE>
+__global__ __launch_bounds__(64) void k_scene_kalman(int n_piece, int n_rows, int N, KalmanArgs ka, KalmanKinds kinds, SceneSrc seen,
+                                                     double* __restrict__ state, double* __restrict__ F) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_piece) return;
+    const int rec_i = i / (SMPC_SCENE_ROW / 2), q = i % (SMPC_SCENE_ROW / 2);
+    const int b = rec_i / n_rows, r = rec_i % n_rows;
+    const int p = ka.degree;
+    ScenePiece* st = static_cast<ScenePiece*>(__builtin_assume_aligned(state + (size_t)rec_i * SMPC_KALMAN_REC, 16));   // 16 pieces
+    const size_t piece = (size_t)r * SMPC_SCENE_ROW + 2 * q;
+    ScenePiece pos = st[q], vel{0.0, 0.0}, acc{0.0, 0.0};
+    if (p >= 1) vel = st[4 + q];
+    if (p == 2) acc = st[8 + q];
+    if constexpr (ADVANCE) {
+        const ScenePiece t0 = st[12], t1 = st[13], t2 = st[14], t3 = st[15];
+        const int64_t t = scene_time(seen);
+        const ScenePiece y = *static_cast<const ScenePiece*>(__builtin_assume_aligned(scene_block(seen, b, t, n_rows) + piece, 16));
+        const int kind = kinds.kind[r];
+        const int s_lo = moving_lo(kind), s_hi = moving_hi(kind);
+        const bool in_a = 2 * q >= s_lo && 2 * q < s_hi, in_b = 2 * q + 1 >= s_lo && 2 * q + 1 < s_hi;
+        int obs = !((in_a && y.a != y.a) || (in_b && y.b != y.b));
+        obs &= __shfl_xor(obs, 1);
+        obs &= __shfl_xor(obs, 2);
+        KalmanCov P{t0.a, t0.b, t1.a, t1.b, t2.a, t2.b};
+        double s2 = t3.a, n = t3.b;
+        bool changed = false, first = false;      // (first seen: the absent components are written too, as zero)
+        if (n >= 1.0) {
+            changed = true;
+            if (p == 2) {
+                pos.a = (pos.a + vel.a) + rounded_product(0.5, acc.a); pos.b = (pos.b + vel.b) + rounded_product(0.5, acc.b);
+                vel.a = vel.a + acc.a; vel.b = vel.b + acc.b;
+            } else if (p == 1) {
+                pos.a = pos.a + vel.a; pos.b = pos.b + vel.b;
+            }
+            P = kalman_predict_cov(p, P, ka);
+            if (obs) {
+                const double inv = 1.0 / (P.p00 + ka.r2);
+                const double k0 = rounded_product(P.p00, inv), k1 = rounded_product(P.p01, inv), k2 = rounded_product(P.p02, inv);
+                const ScenePiece nu{y.a - pos.a, y.b - pos.b};
+                pos.a = pos.a + rounded_product(k0, nu.a); pos.b = pos.b + rounded_product(k0, nu.b);
+                if (p >= 1) { vel.a = vel.a + rounded_product(k1, nu.a); vel.b = vel.b + rounded_product(k1, nu.b); }
+                if (p == 2) { acc.a = acc.a + rounded_product(k2, nu.a); acc.b = acc.b + rounded_product(k2, nu.b); }
+                const KalmanCov M = P;
+                P.p00 = M.p00 - rounded_product(k0, M.p00);
+                if (p >= 1) {
+                    P.p01 = M.p01 - rounded_product(k0, M.p01);
+                    P.p11 = M.p11 - rounded_product(k1, M.p01);
+                }
+                if (p == 2) {
+                    P.p02 = M.p02 - rounded_product(k0, M.p02);
+                    P.p12 = M.p12 - rounded_product(k1, M.p02);
+                    P.p22 = M.p22 - rounded_product(k2, M.p02);
+                }
+                double nis = 0.0;
+                if (in_a) nis = max_nan_wins(nis, rounded_product(rounded_product(nu.a, nu.a), inv));
+                if (in_b) nis = max_nan_wins(nis, rounded_product(rounded_product(nu.b, nu.b), inv));
+                nis = max_nan_wins(nis, __shfl_xor(nis, 1));
+                nis = max_nan_wins(nis, __shfl_xor(nis, 2));
+                s2 = s2 + rounded_product(ka.beta, nis - s2);
+                s2 = s2 < 1.0 ? 1.0 : s2;
+                n = n + 1.0;
+            }
+        } else if (obs) {
+            changed = first = true;
+            pos = y;
+            vel = ScenePiece{0.0, 0.0};
+            acc = ScenePiece{0.0, 0.0};
+            P = KalmanCov{ka.r2, 0.0, 0.0, p >= 1 ? ka.v02 : 0.0, 0.0, p == 2 ? ka.a02 : 0.0};
+            s2 = 1.0;
+            n = 1.0;
+        }
+        if (changed) {
+            st[q] = pos;
+            if (p >= 1 || first) st[4 + q] = vel;
+            if (p == 2 || first) st[8 + q] = acc;
+            if (q == 0) {
+                st[12] = ScenePiece{P.p00, P.p01};
+                st[13] = ScenePiece{P.p02, P.p11};
+                st[14] = ScenePiece{P.p12, P.p22};
+                st[15] = ScenePiece{s2, n};
+            }
+        }
+    }
+    ScenePiece* out = static_cast<ScenePiece*>(__builtin_assume_aligned(F + (size_t)b * (size_t)(N + 1) * n_rows * SMPC_SCENE_ROW + piece, 16));
+    const size_t step = (size_t)n_rows * (SMPC_SCENE_ROW / 2);      // in pieces
+    *out = pos;
+    if (p == 2) {
+        ScenePiece v{vel.a + rounded_product(0.5, acc.a), vel.b + rounded_product(0.5, acc.b)};
+        for (int k = 1; k <= N; k++) {
+            pos.a = pos.a + v.a; pos.b = pos.b + v.b;
+            v.a = v.a + acc.a; v.b = v.b + acc.b;
+            out[k * step] = pos;
+        }
+    } else if (p == 1) {
+        for (int k = 1; k <= N; k++) {
+            pos.a = pos.a + vel.a; pos.b = pos.b + vel.b;
+            out[k * step] = pos;
+        }
+    } else {
+        for (int k = 1; k <= N; k++) out[k * step] = pos;
+    }
+}
+
+// k_kalman_margin: the row-bounds table [lo | hi], each [B][N+1][n_rows], from the filter's own covariance -- problem.
+// kalman_margin_statement operation for operation.  It reads P and s2 of a record (its last 64-byte line) and nothing else: no table,
+// no clock.  Pi_0 = P, Pi_k = kalman_predict_cov(Pi_{k-1}), g_k = sqrt(Pi_k[0][0]); d_k = (base_a + base_b k) + (z sqrt(s2)) g_k,
+// d_k = d_k <= d_max ? d_k : d_max (a NaN gives the cap); d = 0 for a row without a moving slot; the bounds are k_fit_margin's, the
+// descriptor's own doubles where d == 0.0.  The walk along the horizon is a recurrence, so a thread owns a record and its N + 1 nodes:
+// at node k neighbouring threads store neighbouring rows.  One-wavefront blocks; no atomics, no LDS, nothing shared between records.
+__global__ __launch_bounds__(64) void k_kalman_margin(int n_rec, int n_rows, int N, KalmanArgs ka, MarginArgs ma, MarginRows rows,
+                                                      const double* __restrict__ state, double* __restrict__ lo, double* __restrict__ hi) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_rec) return;
+    const int b = i / n_rows, r = i % n_rows;
+    const int p = ka.degree;
+    const int kind = rows.kind[r];
+    const int s_hi = moving_hi(kind);
+    const ScenePiece* st = static_cast<const ScenePiece*>(__builtin_assume_aligned(state + (size_t)i * SMPC_KALMAN_REC, 16));
+    const ScenePiece t0 = st[12], t1 = st[13], t2 = st[14], t3 = st[15];
+    KalmanCov Pi{t0.a, t0.b, t1.a, t1.b, t2.a, t2.b};
+    const double zs = rounded_product(ma.z, __builtin_sqrt(t3.a));
+    const double lb = rows.lb[r], ub = rows.ub[r], root = rows.sqrt_lb[r];
+    const bool has_lb = __builtin_fabs(lb) < SMPC_INF, has_ub = __builtin_fabs(ub) < SMPC_INF;
+    const size_t at = (size_t)b * (size_t)(N + 1) * n_rows + r;
+    for (int k = 0; k <= N; k++) {
+        double d = (ma.base_a + rounded_product(ma.base_b, (double)k)) + rounded_product(zs, __builtin_sqrt(Pi.p00));
+        d = d <= ma.d_max ? d : ma.d_max;
+        if (s_hi == 0) d = 0.0;
+        double l = lb, u = ub;
+        if (d != 0.0) {
+            if (kind == SMPC_ROW_COORD) {
+                if (has_lb) l = lb + d;
+                if (has_ub) u = ub - d;
+            } else if (has_lb) {
+                const double w = root + d;
+                l = rounded_product(w, w);
+            }
+        }
+        lo[at + (size_t)k * n_rows] = l;
+        hi[at + (size_t)k * n_rows] = u;
+        Pi = kalman_predict_cov(p, Pi, ka);
+    }
+}
+
 }  // namespace smpc

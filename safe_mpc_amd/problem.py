@@ -871,3 +871,238 @@ def fit_margin_statement(prob, seen, t, window, degree, z, sigma_prior=0.0, base
         if not moving_slots(r.kind):
             d[:, :, i] = 0.0
     return d
+
+
+KALMAN_REC = 32                                        # SMPC_KALMAN_REC of include/smpc.h: doubles per (instance, row) filter record
+# the record's layout: pos[8] | vel[8] | acc[8] | P00 P01 P02 P11 P12 P22 | s2 | n
+KALMAN_POS, KALMAN_VEL, KALMAN_ACC, KALMAN_P, KALMAN_S2, KALMAN_N = 0, 8, 16, 24, 30, 31
+
+
+class KalmanParams(C.Structure):
+    """smpc_kalman_params (include/smpc.h): the model of one filter, shared by every record of a call"""
+    _fields_ = [('degree', C.c_int32), ('reserved', C.c_int32), ('q', C.c_double), ('r', C.c_double), ('v0', C.c_double),
+                ('a0', C.c_double), ('beta', C.c_double)]
+
+
+def kalman_params(degree, q, r, v0=None, a0=None, beta=0.0, who='kalman_params'):
+    """A checked :class:`KalmanParams`: ``degree`` 0..2 (constant, constant velocity, constant acceleration), ``q >= 0`` the process
+    noise, ``r > 0`` the sensor noise in metres, ``v0``, ``a0 >= 0`` the prior standard deviations of velocity and acceleration per
+    column (default: ``r`` each -- before anything moves, a step is as uncertain as one sample), ``beta`` in [0, 1] the rate at which
+    the innovation scale s2 follows the normalised innovation.  ValueError names the argument."""
+    if isinstance(degree, KalmanParams):      # (a record is checked again: its fields are the caller's to write)
+        par = degree
+        degree, q, r, v0, a0, beta = par.degree, par.q, par.r, par.v0, par.a0, par.beta
+    elif isinstance(degree, (tuple, list)):
+        return kalman_params(*degree, who=who)
+    degree = int(degree)
+    if not 0 <= degree <= 2:
+        raise ValueError(f'{who}: degree {degree}: expected 0, 1 or 2')
+    q, r, beta = float(q), float(r), float(beta)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f'{who}: r={r}: expected a finite number above zero')
+    v0, a0 = (r if v is None else float(v) for v in (v0, a0))
+    for name, v in (('q', q), ('v0', v0), ('a0', a0)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f'{who}: {name}={v}: expected a finite number that is not negative')
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f'{who}: beta={beta}: expected a number in [0, 1]')
+    return KalmanParams(degree, 0, q, r, v0, a0, beta)
+
+
+def kalman_noise(par):
+    """``(Q, r2, v02, a02)`` as the engine forms them on the host: ``Q = q^2 G G'`` with G = (1), (1/2, 1) or (1/6, 1/2, 1) as the six
+    numbers Q00 Q01 Q02 Q11 Q12 Q22 -- ``gq_i = q G_i`` rounded, ``Q_ij = gq_i gq_j`` rounded, zero where a component is absent --
+    and the three squares."""
+    p, q = int(par.degree), float(par.q)
+    G = ((1.0,), (0.5, 1.0), (1.0 / 6.0, 0.5, 1.0))[p]
+    gq = [q * g for g in G] + [0.0] * (2 - p)
+    Q = (gq[0] * gq[0], gq[0] * gq[1], gq[0] * gq[2], gq[1] * gq[1], gq[1] * gq[2], gq[2] * gq[2])
+    return Q, float(par.r) * float(par.r), float(par.v0) * float(par.v0), float(par.a0) * float(par.a0)
+
+
+def kalman_predict_cov(p, P, Q):
+    """``Phi P Phi' + Q`` for the six numbers ``P = (P00, P01, P02, P11, P12, P22)`` (floats or arrays) of a filter of degree p, with
+    Phi = ((1, 1, 1/2), (0, 1, 1), (0, 0, 1)) cut to p + 1 components, in THE order of operations (k_scene_kalman and k_kalman_margin
+    repeat it): first the rows of ``A = Phi P``, then ``A Phi'``, then ``+ Q``; entries of absent components pass through."""
+    P00, P01, P02, P11, P12, P22 = P
+    if p == 0:
+        return (P00 + Q[0], P01, P02, P11, P12, P22)
+    if p == 1:
+        A00 = P00 + P01
+        A01 = P01 + P11
+        return ((A00 + A01) + Q[0], A01 + Q[1], P02, P11 + Q[3], P12, P22)
+    A00 = (P00 + P01) + 0.5 * P02
+    A01 = (P01 + P11) + 0.5 * P12
+    A02 = (P02 + P12) + 0.5 * P22
+    A11 = P11 + P12
+    A12 = P12 + P22
+    return (((A00 + A01) + 0.5 * A02) + Q[0], (A01 + A02) + Q[1], A02 + Q[2], (A11 + A12) + Q[3], A12 + Q[4], P22 + Q[5])
+
+
+def new_kalman_state(B, n_rows):
+    """``[B, n_rows, KALMAN_REC]`` zeros: every record "nothing seen" """
+    return np.zeros((int(B), int(n_rows), KALMAN_REC))
+
+
+def kalman_statement(state, y, kinds, par, N, advance=True):
+    """``(state', F)``: one step of the obstacle filter and its forecast -- the numpy statement of smpc_forecast_scene_kalman and its
+    readable definition.  ``state [B, n_rows, KALMAN_REC]``: per (instance, row) record
+    ``pos[8] | vel[8] | acc[8] | P00 P01 P02 P11 P12 P22 | s2 | n`` (all zero: nothing seen); ``y [B, n_rows, SCENE_ROW]``: the column
+    of what was seen at the scene clock, ``S[:, col(t)]`` (not read with ``advance=False``; may be None then); ``kinds [n_rows]``: the
+    row kinds; ``par``: :func:`kalman_params`; ``F [B, N + 1, n_rows, SCENE_ROW]``.  Time is in columns.  All eight slots of a record
+    are filtered with the record's gains; only components 0..p of the state are used, the others are written as zero when a record
+    is first seen and otherwise neither read nor written.
+
+    A record is OBSERVED when none of its row kind's moving slots (:func:`moving_slots`) holds a NaN in y; a robot-robot row always is.
+
+    Advance, n < 1 (nothing seen).  Observed: ``pos = y``, ``vel = acc = 0``, ``P = diag(r^2, v0^2, a0^2)`` (an absent component: 0),
+    ``s2 = 1``, ``n = 1``.  Unobserved: the record stays.
+
+    Advance, n >= 1.  Predict: ``pos- = (pos + vel) + 0.5 acc``, ``vel- = vel + acc`` (without the absent terms),
+    ``P- = kalman_predict_cov(p, P, Q)``.  Observed: ``S = P-00 + r^2``, ``inv = 1.0 / S`` -- the ONE division --, ``K_i = P-0i inv``;
+    per slot ``nu = y - pos-``, ``x_i = x-_i + K_i nu``; ``P_ij = P-ij - K_i P-0j`` for i <= j; ``nis`` the largest ``(nu nu) inv``
+    over the moving slots from 0.0, a NaN winning; ``s2 = s2 + beta (nis - s2)``, then 1.0 where it is below 1.0; ``n = n + 1``.
+    Unobserved: ``x = x-``, ``P = P-``; s2 and n stay.  Every product is rounded before its sum.
+
+    Forecast, from the state after the advance.  p = 0: ``F[k] = pos`` for every k, stored.  p = 1: ``F[0] = pos``,
+    ``F[k] = F[k-1] + vel``.  p = 2: ``v = vel + 0.5 acc``, ``F[0] = pos``, then ``F[k] = F[k-1] + v; v = v + acc``, in that order."""
+    st = np.array(state, float)
+    if st.ndim != 3 or st.shape[2] != KALMAN_REC:
+        raise ValueError(f'kalman_statement: expected a state [B, n_rows, {KALMAN_REC}], got {st.shape}')
+    par = kalman_params(par, 0, 1, who='kalman_statement')
+    p, beta, N = int(par.degree), float(par.beta), int(N)
+    kinds = [int(k) for k in kinds]
+    B, nr = st.shape[:2]
+    if len(kinds) != nr:
+        raise ValueError(f'kalman_statement: {len(kinds)} row kinds for {nr} rows')
+    Q, r2, v02, a02 = kalman_noise(par)
+    pos, vel, acc = st[:, :, 0:8].copy(), st[:, :, 8:16].copy(), st[:, :, 16:24].copy()
+    if advance:
+        y = np.asarray(y, float)
+        if y.shape != (B, nr, SCENE_ROW):
+            raise ValueError(f'kalman_statement: expected y [{B}, {nr}, {SCENE_ROW}], got {y.shape}')
+        P = tuple(st[:, :, KALMAN_P + i].copy() for i in range(6))
+        s2, n = st[:, :, KALMAN_S2].copy(), st[:, :, KALMAN_N].copy()
+        obs = np.ones((B, nr), bool)
+        for i, kind in enumerate(kinds):
+            for s_ in moving_slots(kind):
+                obs[:, i] &= ~np.isnan(y[:, i, s_])
+        seen = n >= 1.0
+        with np.errstate(all='ignore'):
+            # predict
+            pos_m = pos if p == 0 else (pos + vel if p == 1 else (pos + vel) + 0.5 * acc)
+            vel_m = vel + acc if p == 2 else vel
+            Pm = kalman_predict_cov(p, P, Q)
+            # update
+            inv = 1.0 / (Pm[0] + r2)
+            K = (Pm[0] * inv, Pm[1] * inv, Pm[2] * inv)
+            nu = y - pos_m
+            pos_u = pos_m + K[0][:, :, None] * nu
+            vel_u = vel_m + K[1][:, :, None] * nu if p >= 1 else vel
+            acc_u = acc + K[2][:, :, None] * nu if p == 2 else acc
+            Pu = [Pm[0] - K[0] * Pm[0], Pm[1] - K[0] * Pm[1], Pm[2] - K[0] * Pm[2], Pm[3] - K[1] * Pm[1], Pm[4] - K[1] * Pm[2],
+                  Pm[5] - K[2] * Pm[2]]
+            used = (True, p >= 1, p == 2, p >= 1, p == 2, p == 2)
+            Pu = [u if on else m for u, m, on in zip(Pu, Pm, used)]
+            nis = np.zeros((B, nr))
+            for i, kind in enumerate(kinds):
+                for s_ in moving_slots(kind):
+                    nis[:, i] = np.maximum(nis[:, i], (nu[:, i, s_] * nu[:, i, s_]) * inv[:, i])       # (a NaN wins)
+            s2_u = s2 + beta * (nis - s2)
+            s2_u = np.where(s2_u < 1.0, 1.0, s2_u)
+        first, upd, pred = ~seen & obs, seen & obs, seen & ~obs
+        P0 = (r2, 0.0, 0.0, v02 if p >= 1 else 0.0, 0.0, a02 if p == 2 else 0.0)
+
+        def pick(old, init, predicted, updated):
+            sel = [x[:, :, None] if np.ndim(old) == 3 else x for x in (first, pred, upd)]
+            return np.where(sel[0], init, np.where(sel[1], predicted, np.where(sel[2], updated, old)))
+        pos, vel, acc = pick(pos, y, pos_m, pos_u), pick(vel, 0.0, vel_m, vel_u), pick(acc, 0.0, acc, acc_u)
+        P = tuple(pick(P[i], P0[i], Pm[i], Pu[i]) for i in range(6))
+        s2, n = pick(s2, 1.0, s2, s2_u), pick(n, 1.0, n, n + 1.0)
+        st[:, :, 0:8], st[:, :, 8:16], st[:, :, 16:24] = pos, vel, acc
+        for i in range(6):
+            st[:, :, KALMAN_P + i] = P[i]
+        st[:, :, KALMAN_S2], st[:, :, KALMAN_N] = s2, n
+    F = np.empty((B, N + 1, nr, SCENE_ROW))
+    F[:, 0] = pos
+    with np.errstate(all='ignore'):
+        v = vel + 0.5 * acc if p == 2 else vel
+        for k in range(1, N + 1):
+            if p == 0:
+                F[:, k] = pos
+                continue
+            F[:, k] = F[:, k - 1] + v
+            if p == 2:
+                v = v + acc
+    return st, F
+
+
+def kalman_margin_statement(prob, state, par, z, base=(0.0, 0.0), d_max=FIT_MARGIN_CAP):
+    """``d [B, N + 1, n_rows]``, metres: the margin around the world-fixed element of every collision row at every node from the
+    filter's own covariance -- the numpy statement of smpc_kalman_row_margin and its readable definition.
+    ``inflated_row_bounds(prob, B, d)`` turns it into the table the entry point writes.  It reads P and s2 of ``state [B, n_rows,
+    KALMAN_REC]`` and nothing else:
+
+    ``Pi_0 = P``, ``Pi_k = kalman_predict_cov(p, Pi_{k-1}, Q)``, ``g_k = sqrt(Pi_k[0][0])`` -- the predicted covariance grows along the
+    horizon because the obstacle may turn (Q), not only because the state is uncertain; no ``+ r^2``, the true obstacle carries no
+    noise (as in 9r).  ``d_k = (base_a + base_b k) + (z sqrt(s2)) g_k``, every product rounded; ``d_k = d_k if d_k <= d_max else
+    d_max``, so a NaN gives the cap.  A row without a moving slot (SEG_SEG) has d = 0.  A record that has seen nothing (all zero)
+    has P = 0 and s2 = 0: only the base and what Q adds along the horizon.
+
+    ValueError as :func:`fit_margin_statement`'s for z, base and d_max, and :func:`kalman_params`' for ``par``."""
+    st = np.asarray(state, float)
+    nr = len(prob.rows)
+    if st.ndim != 3 or st.shape[1:] != (nr, KALMAN_REC):
+        raise ValueError(f'kalman_margin_statement: expected a state [B, {nr}, {KALMAN_REC}], got {st.shape}')
+    par = kalman_params(par, 0, 1, who='kalman_margin_statement')
+    _, _, z, _, (base_a, base_b), d_max = _check_fit_margin('kalman_margin_statement', prob, 1, 0, z, 0.0, base, d_max)
+    p, N, B = int(par.degree), int(prob.N), st.shape[0]
+    Q = kalman_noise(par)[0]
+    Pi = tuple(st[:, :, KALMAN_P + i] for i in range(6))
+    d = np.empty((B, N + 1, nr))
+    with np.errstate(invalid='ignore'):
+        zs = z * np.sqrt(st[:, :, KALMAN_S2])
+        for k in range(N + 1):
+            dk = (base_a + base_b * float(k)) + zs * np.sqrt(Pi[0])
+            d[:, k] = np.where(dk <= d_max, dk, d_max)
+            Pi = kalman_predict_cov(p, Pi, Q)
+    for i, r in enumerate(prob.rows):
+        if not moving_slots(r.kind):
+            d[:, :, i] = 0.0
+    return d
+
+
+def occlude_tracks(prob, observed, p_start, mean_len, seed=0):
+    """``observed [B, T, n_rows, SCENE_ROW]`` with NaN bursts where a sensor loses sight of an obstacle: per (instance, obstacle),
+    walking the columns, a visible obstacle starts a burst with probability ``p_start`` and an occluded one comes back with
+    probability ``1 / mean_len`` (burst lengths are geometric with that mean; ``mean_len >= 1``).  A burst sets NaN in the moving
+    slots (:func:`moving_slots`) of every row the obstacle appears in, and nowhere else.  The draws come instance by instance, one
+    ``[T, obstacle]`` block of uniforms each, so instance b's do not depend on B; reproducible per seed; ``p_start = 0`` returns the
+    input's bits.  What run_mpc(observed=..., forecast='kalman') studies dropouts with."""
+    S = np.asarray(observed, float)
+    if S.ndim != 4 or S.shape[2:] != (len(prob.rows), SCENE_ROW):
+        raise ValueError(f'occlude_tracks: expected a track [B, T, {len(prob.rows)}, {SCENE_ROW}], got {S.shape}')
+    p_start, mean_len = float(p_start), float(mean_len)
+    if not 0.0 <= p_start <= 1.0:
+        raise ValueError(f'occlude_tracks: p_start={p_start}: expected a probability')
+    if not (np.isfinite(mean_len) and mean_len >= 1.0):
+        raise ValueError(f'occlude_tracks: mean_len={mean_len}: expected a finite number >= 1')
+    out = S.copy()
+    if p_start == 0.0:
+        return out
+    B, T = S.shape[:2]
+    names = sorted({n for n in prob.row_obstacle if n is not None})
+    rng = np.random.default_rng([int(seed), 4])
+    u = np.stack([rng.random((T, len(names))) for _ in range(B)]).reshape(B, T, len(names))
+    hidden = np.zeros((B, T, len(names)), bool)
+    now = np.zeros((B, len(names)), bool)
+    for j in range(T):
+        now = np.where(now, u[:, j] >= 1.0 / mean_len, u[:, j] < p_start)
+        hidden[:, j] = now
+    for i, (r, name) in enumerate(zip(prob.rows, prob.row_obstacle)):
+        if name is None:
+            continue
+        h = hidden[:, :, names.index(name)]
+        for s_ in moving_slots(r.kind):
+            out[:, :, i, s_] = np.where(h, np.nan, out[:, :, i, s_])
+    return out

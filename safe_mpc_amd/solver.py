@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from .problem import FIT_MARGIN_CAP, FORECAST_MODES, JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem     # noqa: F401 (FORECAST_MODES: re-exported)
+from .problem import FIT_MARGIN_CAP, FORECAST_MODES, KALMAN_REC, JOINT_DTYPE, NODE_EVAL_DTYPE, SCENE_ROW, OcpProblem     # noqa: F401 (FORECAST_MODES: re-exported)
 
 
 # columns of BatchedOcpSolver.score_rollout's two results (SMPC_SCORE_ND doubles, SMPC_SCORE_NI int32 of include/smpc.h)
@@ -333,6 +333,55 @@ class BatchedOcpSolver:
         B = int(getattr(self, '_world_B', 0) if B is None else B)
         with self._ordered('torch' in sys.modules):
             self._chk(self.L.smpc_forecast_row_margin(self.h, B, int(window), int(degree), float(z), float(sigma_prior), a, b, float(d_max)))
+        self._rowb_B = B
+
+    def new_kalman_state(self, B):
+        """``[B, n_rows, KALMAN_REC]`` zeros on this solver's device: the filter state of :meth:`forecast_scene_kalman`, every record
+        "nothing seen".  The caller owns it; the engine keeps no filter state."""
+        import torch
+        return torch.zeros((int(B), len(self.problem.rows), KALMAN_REC), dtype=torch.float64, device=torch.device('cuda', self.device))
+
+    def _kalman_args(self, name, par, state, B):
+        from .problem import kalman_params
+        import torch
+        par = kalman_params(par, 0, 1, who=name)
+        nr = len(self.problem.rows)
+        if not _is_torch(state) or state.dtype != torch.float64 or not state.is_cuda or not state.is_contiguous():
+            raise ValueError(f'{name}: state: expected a contiguous float64 tensor on the device (new_kalman_state)')
+        if state.device.index != self.device:
+            raise ValueError(f'{name}: state is on device {state.device.index}, the solver on {self.device}')
+        if state.ndim != 3 or tuple(state.shape[1:]) != (nr, KALMAN_REC) or (B is not None and int(B) != state.shape[0]):
+            raise ValueError(f'{name}: state of shape {tuple(state.shape)}: expected [{"B" if B is None else int(B)}, {nr}, {KALMAN_REC}]')
+        return par, int(state.shape[0])
+
+    def forecast_scene_kalman(self, par, state, advance=True, select=None, B=None):
+        """One step of the obstacle filter and its forecast over the horizon, into the scene slot (smpc_forecast_scene_kalman;
+        ``problem.kalman_statement`` is its definition, DESIGN.md section 9s).  ``par``: ``problem.kalman_params(degree, q, r, ...)``;
+        ``state``: the ROCm tensor of :meth:`new_kalman_state`, updated in place.  ``advance=True`` reads what was seen (the observed
+        track while one is set, else the world) at the scene clock and needs the world; a NaN in a moving slot leaves the record
+        unobserved: predict only.  ``advance=False`` forecasts from the state as it is: no table is read, no world is needed and any B
+        goes -- what a second solver with another horizon calls on rows of the first one's state.  Enqueue-only; ``select`` as for
+        :meth:`forecast_scene`; ``B``: the state's unless given."""
+        if not hasattr(self.L, 'smpc_forecast_scene_kalman'):
+            raise _lib.EngineError('forecast_scene_kalman: this build of the engine has no smpc_forecast_scene_kalman')
+        par, B = self._kalman_args('forecast_scene_kalman', par, state, B)
+        sel = np.ascontiguousarray([] if select is None else select, np.int32).reshape(-1, 2)
+        with self._ordered(True):
+            self._chk(self.L.smpc_forecast_scene_kalman(self.h, B, C.byref(par), state.data_ptr(), 1 if advance else 0, len(sel),
+                                                        sel.ctypes.data if len(sel) else None))
+
+    def kalman_row_margin(self, par, state, z, base=(0.0, 0.0), d_max=FIT_MARGIN_CAP, B=None):
+        """The row-bounds table formed on the device from the filter's covariance (smpc_kalman_row_margin;
+        ``problem.kalman_margin_statement`` is its definition): node k leaves ``d_k = base[0] + base[1] k + z sqrt(s2) g_k`` metres,
+        at most ``d_max`` -- g_k the predicted standard deviation of the position k columns ahead, s2 the innovation scale.  Reads
+        ``state`` alone; enqueue-only; fills the slot of :meth:`set_instance_row_bounds`.  Meant to follow
+        :meth:`forecast_scene_kalman` with the same ``par`` and ``state``."""
+        if not hasattr(self.L, 'smpc_kalman_row_margin'):
+            raise _lib.EngineError('kalman_row_margin: this build of the engine has no smpc_kalman_row_margin')
+        par, B = self._kalman_args('kalman_row_margin', par, state, B)
+        a, b = (float(v) for v in base)
+        with self._ordered(True):
+            self._chk(self.L.smpc_kalman_row_margin(self.h, B, C.byref(par), state.data_ptr(), float(z), a, b, float(d_max)))
         self._rowb_B = B
 
     def set_scene_clock(self, clock=None):

@@ -26,10 +26,18 @@
 10. A margin that follows the fit: the closed loop of 7 with forecast='fit' (window SMPC_FIT_WINDOW, default 8; degree SMPC_FIT_DEGREE,
    default 1) and run_mpc(row_margin_fit=(z, 0, SMPC_MARGIN_CAP)) for z of SMPC_MARGIN_Z (default 0, 1, 2, 3), next to the arms over b
    of 7 on the CV forecast and on the same fit, all in one session, one run each.
+11. k_scene_kalman + k_kalman_margin beside k_scene_poly + k_fit_margin at window 32 (profiles/scene_forecast_kalman.txt): the shapes
+   and the observed track of 3, degrees 1, 0, 2, the four calls in alternation, SMPC_ROUNDS (default 3) rounds of 10 calls between HIP
+   events after 3 warm-up calls.  The filter advances with every call (a state of B x rows x 256 bytes is read and written).
+12. The closed loop with the filter: the tracks of 4, with and without dropouts (problem.occlude_tracks, p SMPC_DROPOUT, default 0.05,
+   mean length SMPC_DROPOUT_LEN, default 4): forecast='fit' (window SMPC_FIT_WINDOW, degree SMPC_FIT_DEGREE, with and without
+   row_margin_fit z = 2; only without dropouts, a fit carries a NaN) against forecast='kalman' for q / r of SMPC_KALMAN_QR (default
+   0.03, 0.1, 0.3) with r = the sensor's sigma, with and without row_margin_kalman z = 2, SMPC_ROUNDS rounds in alternation: ms per
+   step, collisions of B and the mean closed-loop cost of the others.
 A measurement tool, not a test; it reads nothing outside the repository.
 
     python scripts/forecast_bench.py [kernel|loop|fit-kernel|fit-loop|poly-kernel|poly-loop|margin-loop|margin-solve|interval-kernel|
-                                      interval-loop]"""
+                                      interval-loop|kalman-kernel|kalman-loop]"""
 import os
 import sys
 
@@ -236,6 +244,93 @@ def interval_loop(B):
               f"{tm['ms_per_step']:.3f} ms per step", flush=True)
 
 
+def kalman_kernel_times(B):
+    import torch
+    from safe_mpc_amd.problem import kalman_params
+    par, prob, net = bench.build_problem()
+    s = BatchedOcpSolver(prob, net)
+    N, T, clock, nr = prob.N, 131, 50, len(prob.rows)
+    device = torch.device('cuda', s.device)
+    world = turning_scenes(prob, B, T, 0.3, 3.0, seed=0)
+    s.set_instance_world_track(torch.tensor(world, dtype=torch.float64, device=device))
+    s.set_instance_observed_track(torch.tensor(observe_tracks(prob, world, 0.005), dtype=torch.float64, device=device))
+    cell = torch.full((1,), clock, dtype=torch.int64, device=device)
+    s.set_scene_clock(cell)
+    stream = torch.cuda.ExternalStream(s.L.smpc_stream(s.h), device=device)
+    rounds = int(os.environ.get('SMPC_ROUNDS', '3'))
+    rec = B * nr * 64 / 1e6                                     # MB per column of the table that was seen
+    state = s.new_kalman_state(B)
+    with torch.cuda.stream(stream):
+        for p in (1, 0, 2):
+            kp = kalman_params(p, 0.0005, 0.005)
+            state.zero_()
+            calls = {'k_scene_poly w32': (lambda: s.forecast_scene_poly(32, p)), 'k_fit_margin w32': (lambda: s.forecast_row_margin(32, p, 2.0)),
+                     'k_scene_kalman': (lambda: s.forecast_scene_kalman(kp, state)), 'k_kalman_margin': (lambda: s.kalman_row_margin(kp, state, 2.0))}
+            res = {k: [] for k in calls}
+            for r in range(rounds):
+                for name, call in calls.items():
+                    for _ in range(3):
+                        call()
+                    for _ in range(10):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record(stream)
+                        call()
+                        b.record(stream)
+                        b.synchronize()
+                        res[name].append(a.elapsed_time(b))
+            line = ' | '.join(f'{k} mean {1e3 * np.mean(v):.1f} us (min {1e3 * np.min(v):.1f}, max {1e3 * np.max(v):.1f})' for k, v in res.items())
+            print(f'degree {p}: {line}; a column is {rec:.1f} MB, the state {4 * rec:.1f} MB, F {(N + 1) * rec:.1f} MB, a row-bounds table '
+                  f'{B * (N + 1) * nr * 16 / 1e6:.1f} MB; {rounds} rounds of 10 calls each in alternation; B = {B}, N = {N}, {nr} rows, T = {T}, '
+                  f'clock {clock}', flush=True)
+    s.set_instance_row_bounds(None)
+    s.set_instance_world_track(None)
+    s.set_scene_clock(None)
+    s.close()
+
+
+def kalman_loop(B):
+    from safe_mpc_amd import controller as C
+    from safe_mpc_amd.problem import occlude_tracks
+    par, prob, net = bench.build_problem()
+    par.N = prob.N
+    steps, rounds = int(os.environ.get('SMPC_STEPS', '60')), int(os.environ.get('SMPC_ROUNDS', '1'))
+    sigma = float(os.environ.get('SMPC_OBS_NOISE', '0.005'))
+    window, degree = int(os.environ.get('SMPC_FIT_WINDOW', '8')), int(os.environ.get('SMPC_FIT_DEGREE', '1'))
+    cap = float(os.environ.get('SMPC_MARGIN_CAP', '0.15'))
+    drop = (float(os.environ.get('SMPC_DROPOUT', '0.05')), float(os.environ.get('SMPC_DROPOUT_LEN', '4')))
+    ratios = [float(v) for v in os.environ.get('SMPC_KALMAN_QR', '0.03,0.1,0.3').split(',')]
+    probe = BatchedOcpSolver(prob, net)
+    x0 = bench.initial_states(probe, prob, B, 0)
+    probe.close()
+    N = prob.N
+    xg, ug = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((B, N, prob.nu))
+    ocp = C.OcpProblem(par, 'htwa', 'ext', N=N)
+    world = turning_scenes(ocp, B, steps + 1 + N, 0.3, 3.0, seed=0)
+    seen = observe_tracks(ocp, world, sigma, seed=0)
+    lost = occlude_tracks(ocp, seen, drop[0], drop[1], seed=0)
+    lost[:, 0] = seen[:, 0]                                     # (every obstacle is seen once before it can be lost)
+    print(f'observation noise sigma = {sigma}, turning tracks (sigma_v 0.3, sigma_a 3.0); B = {B}, N = {N}, {steps} steps; the fit: window '
+          f'{window}, degree {degree}; cap of the margins {cap} m; dropouts p = {drop[0]}, mean length {drop[1]}: '
+          f'{100 * np.isnan(lost[:, :, 0, 0]).mean():.1f} % of row 0\'s samples lost')
+    fit = {'forecast': 'fit', 'forecast_window': window, 'forecast_degree': degree, 'observed': seen}
+    arms = [("forecast='fit'", fit), (f"forecast='fit', row_margin_fit = (2, 0, {cap:g})", {**fit, 'row_margin_fit': (2.0, 0.0, cap)})]
+    for obs, tag in ((seen, ''), (lost, ' with dropouts')):
+        for ratio in ratios:
+            kal = {'forecast': 'kalman', 'forecast_degree': degree, 'kalman': (ratio * sigma, sigma, sigma, sigma, 0.1), 'observed': obs}
+            arms += [(f"forecast='kalman' q/r = {ratio:g}{tag}", kal),
+                     (f"forecast='kalman' q/r = {ratio:g}{tag}, row_margin_kalman = (2, {cap:g})", {**kal, 'row_margin_kalman': (2.0, cap)})]
+    for r in range(rounds):
+        for name, kw in arms:
+            tm = {}
+            out = cl.run_mpc(par, 'htwa', xg, ug, n_steps=steps, on_device=True, scenes=world, score=True, timing=tm, **kw)
+            alive = np.ones(B, bool)
+            alive[out['collisions_idx']] = False
+            cost = out['score']['cost'][alive]
+            print(f"round {r} {name}: collisions with the true world {len(out['collisions_idx'])}, abort events {len(out['x_viable'])}, converged "
+                  f"{len(out['conv_idx'])}, mean closed-loop cost of the {int(alive.sum())} others {np.nanmean(cost):.6g}; "
+                  f"{tm['ms_per_step']:.3f} ms per step", flush=True)
+
+
 def margin_loop(B):
     from safe_mpc_amd import controller as C
     par, prob, net = bench.build_problem()
@@ -329,6 +424,10 @@ def main(argv=None):
         interval_kernel_times(B)
     if 'interval-loop' in what:
         interval_loop(B)
+    if 'kalman-kernel' in what:
+        kalman_kernel_times(B)
+    if 'kalman-loop' in what:
+        kalman_loop(B)
     return 0
 
 

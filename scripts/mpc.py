@@ -31,6 +31,15 @@ the outcome tests keep the physical check bounds.  Suffix ``_rm<A>`` and, for B 
 problem.FIT_MARGIN_CAP): the margin is formed every step from the residuals of the fit -- node k leaves A + B k + Z s g_k metres, at
 most D, per instance and row: s the residual standard deviation of the window, at least S, g_k the growth of the forecast's error
 (run_mpc(row_margin_fit=(Z, S, D))); --row-margin then gives its base.  Suffix ``_rmf<Z>_p<S>_c<D>``.
+--scene-forecast kalman [--forecast-degree P] --kalman-q Q --kalman-r R [--kalman-prior V0 A0] [--kalman-beta B]: the forecast is a
+Kalman filter per (instance, row) -- P = 0, 1 (the default here) or 2 its model, Q the process noise, R the sensor noise in metres, V0 and
+A0 the prior standard deviations of velocity and acceleration per column (default R each), B in [0, 1] the rate of the innovation scale
+(default 0) -- run_mpc(forecast='kalman', kalman=(Q, R, V0, A0, B)), DESIGN.md section 9s.  Suffix ``_fckalman_d<P>_q<Q>_r<R>_v<V0>_a<A0>_b<B>``.
+--scene-obs-dropout P [--scene-obs-dropout-len L] (needs --scene-forecast kalman): the sensor loses sight of an obstacle -- per (instance,
+obstacle) a visible one starts a burst of missing samples with probability P per column, of mean length L columns (default 4;
+problem.occlude_tracks, seed --scene-obs-seed); the filter skips its update there.  Suffix ``_od<P>_l<L>`` behind ``_on``.
+--row-margin-z Z [--row-margin-cap D] with --scene-forecast kalman: the margin is formed every step from the filter's predicted covariance
+(run_mpc(row_margin_kalman=(Z, D))); --row-margin gives its base; --row-margin-prior does not apply.  Suffix ``_rmk<Z>_c<D>``.
 --track 8|circle (or ``track_traj: true`` in config.yaml, which means the "8"): the trajectory-tracking task -- the controller follows
 tracking.tracking_trajectory's curve for n_steps_tracking steps, from the warm starts guess_acados.py --track wrote.
 --track-jitter SIGMA [--track-scale-jitter S] [--track-seed S] (only with a tracking run): every instance follows a curve of its own --
@@ -76,23 +85,50 @@ def main(argv=None):
             scenes = jittered_scenes(OcpProblem(params, 'naive'), x_guess.shape[0], float(raw[raw.index('--scene-jitter') + 1]), seed)
     opt = lambda flag, default, cast: cast(raw[raw.index(flag) + 1]) if flag in raw else default
     forecast = opt('--scene-forecast', None, str)
-    if forecast is not None and forecast not in ('hold', 'cv', 'true', 'fit'):
-        raise SystemExit(f'--scene-forecast {forecast}: expected hold, cv or true, or fit')
+    if forecast is not None and forecast not in ('hold', 'cv', 'true', 'fit', 'kalman'):
+        raise SystemExit(f'--scene-forecast {forecast}: expected hold, cv or true, or fit, or kalman')
     window, obs_noise = opt('--forecast-window', 8, int), opt('--scene-obs-noise', 0.0, float)
     if '--forecast-window' in raw and forecast != 'fit':
         raise SystemExit('--forecast-window needs --scene-forecast fit: no other forecast has a window')
     if forecast == 'fit' and not 1 <= window <= 32:
         raise SystemExit(f'--forecast-window {window}: expected 1..32')
     degree = opt('--forecast-degree', 1, int)
-    if '--forecast-degree' in raw and forecast != 'fit':
-        raise SystemExit('--forecast-degree needs --scene-forecast fit: no other forecast has a degree')
+    if '--forecast-degree' in raw and forecast not in ('fit', 'kalman'):
+        raise SystemExit('--forecast-degree needs --scene-forecast fit or kalman: no other forecast has a degree')
     if not 0 <= degree <= 2:
         raise SystemExit(f'--forecast-degree {degree}: expected 0, 1 or 2')
     for flag in ('--scene-obs-noise', '--scene-obs-seed'):
-        if flag in raw and forecast not in ('hold', 'cv', 'fit'):
-            raise SystemExit(f'{flag} needs --scene-forecast hold, cv or fit: nothing else reads what was observed')
+        if flag in raw and forecast not in ('hold', 'cv', 'fit', 'kalman'):
+            raise SystemExit(f'{flag} needs --scene-forecast hold, cv or fit, or kalman: nothing else reads what was observed')
     if obs_noise < 0:
         raise SystemExit(f'--scene-obs-noise {obs_noise}: a standard deviation is not negative')
+    for flag in ('--kalman-q', '--kalman-r', '--kalman-prior', '--kalman-beta', '--scene-obs-dropout', '--scene-obs-dropout-len'):
+        if flag in raw and forecast != 'kalman':
+            raise SystemExit(f'{flag} needs --scene-forecast kalman: no other forecast has a filter or skips a missing sample')
+    kalman = dropout = None
+    if forecast == 'kalman':
+        for flag in ('--kalman-q', '--kalman-r'):
+            if flag not in raw:
+                raise SystemExit(f'--scene-forecast kalman needs {flag}: the filter has no default noise')
+        try:
+            q, r = opt('--kalman-q', 0.0, float), opt('--kalman-r', 0.0, float)
+            v0, a0 = ((float(raw[raw.index('--kalman-prior') + 1]), float(raw[raw.index('--kalman-prior') + 2]))
+                      if '--kalman-prior' in raw else (r, r))
+        except (ValueError, IndexError):
+            raise SystemExit('--kalman-q Q, --kalman-r R, --kalman-prior V0 A0: expected numbers')
+        kalman = (q, r, v0, a0, opt('--kalman-beta', 0.0, float))
+        from safe_mpc_amd.problem import kalman_params
+        try:
+            kalman_params(degree, *kalman, who='--kalman')
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if '--scene-obs-dropout-len' in raw and '--scene-obs-dropout' not in raw:
+            raise SystemExit('--scene-obs-dropout-len needs --scene-obs-dropout: there is no burst to size')
+        if '--scene-obs-dropout' in raw:
+            dropout = (opt('--scene-obs-dropout', 0.0, float), opt('--scene-obs-dropout-len', 4.0, float))
+            if not (0.0 <= dropout[0] <= 1.0 and 1.0 <= dropout[1] < float('inf')):
+                raise SystemExit(f'--scene-obs-dropout {dropout[0]} --scene-obs-dropout-len {dropout[1]}: expected a probability and a mean '
+                                 f'length of at least one column')
     for flag in ('--scene-forecast', '--scene-accel'):
         if flag in raw and '--scene-velocity' not in raw:
             raise SystemExit(f'{flag} needs --scene-velocity: there is no track to forecast or to turn')
@@ -110,12 +146,19 @@ def main(argv=None):
     fc_kw, name_kw = ({} if forecast is None else {'forecast': forecast}), ({} if forecast is None else {'forecast': forecast})
     if forecast == 'fit':
         fc_kw['forecast_window'] = name_kw['forecast_window'] = window
-    if degree != 1:             # (degree 1 is the fit of before: its call and its file name)
+    if degree != 1 or forecast == 'kalman':     # (degree 1 is the fit of before: its call and its file name)
         fc_kw['forecast_degree'] = name_kw['forecast_degree'] = degree
+    if kalman is not None:
+        fc_kw['kalman'] = name_kw['kalman'] = kalman
     if '--scene-obs-noise' in raw:
         from safe_mpc_amd.problem import OcpProblem, observe_tracks
         fc_kw['observed'] = observe_tracks(OcpProblem(params, 'naive'), scenes, obs_noise, opt('--scene-obs-seed', 0, int))
         name_kw['obs_noise'] = obs_noise
+    if dropout is not None:
+        from safe_mpc_amd.problem import OcpProblem, occlude_tracks
+        fc_kw['observed'] = occlude_tracks(OcpProblem(params, 'naive'), fc_kw.get('observed', scenes), dropout[0], dropout[1],
+                                           opt('--scene-obs-seed', 0, int))
+        name_kw['obs_dropout'] = dropout
     if '--row-margin-growth' in raw and '--row-margin' not in raw:
         raise SystemExit('--row-margin-growth needs --row-margin: there is no margin to grow')
     if '--row-margin' in raw:
@@ -127,14 +170,19 @@ def main(argv=None):
             raise SystemExit(f'{flag} needs --row-margin-z: there is no fitted margin to bound')
     if '--row-margin-z' in raw:
         from safe_mpc_amd.problem import FIT_MARGIN_CAP
-        if forecast != 'fit':
-            raise SystemExit('--row-margin-z needs --scene-forecast fit: no other forecast leaves residuals')
+        if forecast not in ('fit', 'kalman'):
+            raise SystemExit('--row-margin-z needs --scene-forecast fit or kalman: no other forecast leaves residuals or a covariance')
         if cont_name == 'parallel':
             raise SystemExit("--row-margin-z: the 'parallel' policy is not supported")
+        if forecast == 'kalman' and '--row-margin-prior' in raw:
+            raise SystemExit("--row-margin-prior goes with --scene-forecast fit: the filter's floor is its own sensor noise, --kalman-r")
         fit = (opt('--row-margin-z', 0.0, float), opt('--row-margin-prior', 0.0, float), opt('--row-margin-cap', FIT_MARGIN_CAP, float))
         if not all(0.0 <= v < float('inf') for v in fit):
             raise SystemExit(f'--row-margin-z, --row-margin-prior, --row-margin-cap: {fit}: expected finite numbers that are not negative')
-        fc_kw['row_margin_fit'] = name_kw['row_margin_fit'] = fit
+        if forecast == 'kalman':
+            fc_kw['row_margin_kalman'] = name_kw['row_margin_kalman'] = (fit[0], fit[2])
+        else:
+            fc_kw['row_margin_fit'] = name_kw['row_margin_fit'] = fit
     cmodel = raw[raw.index('--controller-model') + 1] if '--controller-model' in raw else 'nominal'
     if cmodel not in ('nominal', 'plant'):
         raise SystemExit(f'--controller-model {cmodel}: expected nominal or plant')
